@@ -12,7 +12,9 @@ device and resident in HBM, 1,000,000 synthetic read pairs (2 x 150 bp, opposite
 With N > 1 every rank maps its own shard of pairs against its own replica of the index (weak scaling, no collective on
 the data path).  `--workload ecoli` is configs[1] (single-ended), `--workload chr21` configs[2].
 
-Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement" for how each field is obtained.
+Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement" for how each field is obtained.  A plain run sets up, warms up, times
+--steps steps and reports; --full adds the CPU baseline, the parity sample against the CPU oracle, the PCIe-inclusive streaming
+region and the "default" read set.  --dump-outputs DIR writes a fixed sample of the last timed step's results as DIR/<name>.npy.
 """
 import argparse
 import ctypes as C
@@ -77,6 +79,15 @@ def log(msg):
 T0 = time.perf_counter()
 
 
+def in_threads(fn, items):
+    """[fn(x) for x in items] on up to 16 host threads, in item order.  The generators below draw every chromosome's share from a
+    seed of its own and spend their time in numpy calls that release the GIL, so this is the serial loop's result, sooner."""
+    import concurrent.futures as cf
+    items = list(items)
+    with cf.ThreadPoolExecutor(max(1, min(len(items), usable_cores(), 16))) as ex:
+        return list(ex.map(fn, items))
+
+
 def shared_reference(name, lens, repeat_frac, local_rank, world_local):
     """The synthetic chromosomes.  With several ranks on a node, local rank 0 generates them once into /dev/shm and the
     others map that file (a 3 Gbp reference per rank would be 8 x the host memory and 8 x the time)."""
@@ -85,7 +96,8 @@ def shared_reference(name, lens, repeat_frac, local_rank, world_local):
     def generate():
         fam = max(50, 2000 // len(lens))
         lead = LEAD_N.get(name, [0] * len(lens))
-        return [W.make_reference(n, seed=38 + i, repeat_frac=repeat_frac, families=fam, lead_n=lead[i]) for i, n in enumerate(lens)]
+        return in_threads(lambda i: W.make_reference(lens[i], seed=38 + i, repeat_frac=repeat_frac, families=fam, lead_n=lead[i]),
+                          range(len(lens)))
     if world_local <= 1:
         return generate(), None
     total = sum(n + 2 * W.START_PAD for n in lens)
@@ -131,20 +143,18 @@ def make_batch(chroms, n_reads, paired, seed, read_set="mutated", lead=None, wit
     lens = np.array([len(c) for c in chroms], np.float64)
     share = np.floor(units * lens / lens.sum()).astype(np.int64)
     share[0] += units - share.sum()
-    parts, tparts = [], []
     pf, hard = (0.5, 0.03) if read_set == "mutated" else (1.0, 0.0)
-    for i, (c, m) in enumerate(zip(chroms, share)):
-        if m <= 0:
-            continue
+
+    def one(i):
+        c, m = chroms[i], int(share[i])
         lo = lead[i] if lead else 0
         if paired:
-            rd, t = W.make_pairs(c, int(m), read_len=L, seed=seed + 7 * i, del_model=DEL_MODEL, perfect_frac=pf, hard_frac=hard, lo=lo)
-            parts.append(rd.reshape(-1, 2 * L))
-            tparts.append(np.stack([np.full(int(m), i + 1, np.int64), t["start1"], t["strand1"], t["start2"], t["strand2"]], axis=1))
-        else:
-            rd, _, t = W.make_reads_and_jobs(c, int(m), read_len=L, seed=seed + 7 * i, del_model=DEL_MODEL, perfect_frac=pf, lo=lo)
-            parts.append(rd.reshape(-1, L))
-            tparts.append(np.stack([np.full(int(m), i + 1, np.int64), t["start"], np.zeros(int(m), np.int64)], axis=1))
+            rd, t = W.make_pairs(c, m, read_len=L, seed=seed + 7 * i, del_model=DEL_MODEL, perfect_frac=pf, hard_frac=hard, lo=lo)
+            return rd.reshape(-1, 2 * L), np.stack([np.full(m, i + 1, np.int64), t["start1"], t["strand1"], t["start2"], t["strand2"]], axis=1)
+        rd, _, t = W.make_reads_and_jobs(c, m, read_len=L, seed=seed + 7 * i, del_model=DEL_MODEL, perfect_frac=pf, lo=lo)
+        return rd.reshape(-1, L), np.stack([np.full(m, i + 1, np.int64), t["start"], np.zeros(m, np.int64)], axis=1)
+    done = in_threads(one, [i for i in range(len(chroms)) if share[i] > 0])
+    parts, tparts = [p for p, _ in done], [t for _, t in done]
     allp = np.concatenate(parts)
     perm = np.random.Generator(np.random.PCG64(seed)).permutation(len(allp))      # mix the chromosomes within the batch
     reads = np.ascontiguousarray(allp[perm]).reshape(-1)
@@ -205,6 +215,53 @@ def parity_sample(mp, out, oi, reads, L, paired, offsets, key_scores, count):
     good = [i for i in range(count) if out["nsites"][i] >= 0 or out["nsites"][i] == -3]
     bad = compare(out, orc, count, paired, reads_range=good)
     return {"checked_reads": count, "mismatches": len(bad), "overflowed_in_sample": len(over), "first": bad[:3]}
+
+
+DUMP_BYTES_MAX = 64 << 20
+DUMP_SEED = 7
+DUMP_READS = 65536                 # per-read results: a seeded sample of this many reads
+DUMP_SITE_ENTRIES = 262144         # site lists: the batch's first DUMP_SITE_ENTRIES / max_sites reads (the batch is a seeded shuffle)
+
+
+def dump_site_reads(max_sites):
+    return max(1, DUMP_SITE_ENTRIES // max_sites)
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy; at most DUMP_BYTES_MAX bytes in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        raise SystemExit("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_BYTES_MAX))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def _crc32_rows(blob, offs, lens):
+    import zlib
+    return np.array([zlib.crc32(blob[int(o):int(o) + int(n)].tobytes()) if n > 0 else 0 for o, n in zip(offs, lens)], np.float64)
+
+
+def mapper_outputs(out, max_sites):
+    """What a caller of the mapped step receives (Mapper.fetch), as float64 arrays: nsites of a seeded sample of the reads; the site
+    lists of the batch's first reads, slots past a read's count zeroed; with the final stage, the final records of the same sample and
+    the CRC-32 of each one's match string.  Log positions (match_job, match_off) follow the order in which concurrent fills took their
+    log slots, so they are left out."""
+    from tests.mapper_check import FINAL_FIELDS, SITE_FIELDS
+    ns = out["nsites"]
+    pick = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(len(ns), size=min(len(ns), DUMP_READS), replace=False))
+    d = {"nsites": ns[pick].astype(np.float64)}
+    sites = out["sites"][:dump_site_reads(max_sites)]
+    keep = np.arange(sites.shape[1])[None, :] < np.maximum(ns[:len(sites)], 0)[:, None]
+    for f in SITE_FIELDS:
+        d["site_" + f] = np.where(keep, sites[f], 0).astype(np.float64)
+    if "final" in out:
+        rec = out["final"][pick]
+        for f in FINAL_FIELDS:
+            d["final_" + f] = rec[f].astype(np.float64)
+        d["final_match_crc32"] = _crc32_rows(out["final_match"], rec["match_off"], rec["match_len"])
+    return d
 
 
 _HIP = None
@@ -369,6 +426,10 @@ def pacbio_dp_main(args):
         kms += ctx.last_kernel_ms3()[1]
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        d = {f: res[f].astype(np.float64) for f in ("result", "status", "iterations", "score", "score_len", "match_len")}
+        d["match_crc32"] = _crc32_rows(match.reshape(-1), np.arange(n) * stride, res["match_len"])
+        write_outputs(args.dump_outputs, d)
     cells = int(res["iterations"].sum())
     swept = float((jobs["read_len"].astype(np.int64) * (jobs["refEndLoc"] - jobs["refStartLoc"] + 1)).sum())
     kms /= args.steps
@@ -488,6 +549,8 @@ def pacbio_main(args):
     st = mp.stats()
     ms = {key: v / max(1, args.steps) for key, v in acc.items()}
     out = mp.fetch(with_match=args.parity_sample > 0 and rank == 0)
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, mapper_outputs(out, args.max_sites))
     parity = None
     if rank == 0 and args.parity_sample > 0:
         from tests.mapper_check import compare
@@ -590,7 +653,7 @@ def _first_library_call(dev_index):
     return time.perf_counter() - t
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -600,12 +663,29 @@ def main():
     ap.add_argument("--reads", type=int, default=2000000, help="reads per GPU per step (pairs x 2 in the paired workloads)")
     ap.add_argument("--k", type=int, default=13)
     ap.add_argument("--max-sites", type=int, default=32)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--parity-sample", type=int, default=600)
-    ap.add_argument("--stream-steps", type=int, default=10, help="steps of the PCIe-inclusive streaming region (0 = skip it)")
-    ap.add_argument("--default-set-steps", type=int, default=3, help="steps timed on the 'default' (unmutated) read set after the main region (0 = skip)")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run the CPU baseline, the parity sample against the CPU oracle, the PCIe-inclusive "
+                         "streaming region and the 'default' read set (a plain run sets up, warms up, times --steps and reports)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--parity-sample", type=int, default=None, help="reads checked against the CPU oracle (default 600 with --full, else 0)")
+    ap.add_argument("--stream-steps", type=int, default=None,
+                    help="steps of the PCIe-inclusive streaming region (default 10 with --full, else 0 = skip it)")
+    ap.add_argument("--default-set-steps", type=int, default=None,
+                    help="steps timed on the 'default' (unmutated) read set after the main region (default 3 with --full, else 0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (a fixed sample, float64) as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    args.no_cpu_baseline = args.no_cpu_baseline or not args.full
+    for name, full_default in (("parity_sample", 600), ("stream_steps", 10), ("default_set_steps", 3)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else 0)
+    return args
 
+
+def main():
+    args = parse_args()
     if args.workload == "pacbio_dp":
         if args.gpus != 1 or "WORLD_SIZE" in os.environ:
             raise SystemExit("--workload pacbio_dp is a one-GPU DP benchmark")
@@ -704,6 +784,18 @@ def main():
     # ---- outside the timed region: checks and bookkeeping
     st = mp.stats()
     ms = {key: v / max(1, args.steps) for key, v in acc.items()}
+    # the last timed step's results.  A read's site list is max_sites x 128 B (8 GB for the default batch): with the final stage, whose
+    # records say what was mapped, only the rows the parity sample and the dump look at are copied to the host
+    want_match = args.parity_sample > 0 and rank == 0
+    dumping = rank == 0 and args.dump_outputs
+    if mp.cfg.finalStage:
+        out = mp.fetch(with_match=want_match, rows=max(args.parity_sample, dump_site_reads(args.max_sites) if dumping else 0))
+        out["final"], out["final_match"] = mp.final(with_match=want_match or dumping)
+    else:
+        out = mp.fetch(with_match=want_match)
+    if dumping:
+        write_outputs(args.dump_outputs, mapper_outputs(out, args.max_sites))
+    log("outputs fetched")
     stream_res = None
     if args.stream_steps > 0:
         # the PCIe-inclusive rate: distinct batches, uploads and downloads inside the timed region (reported beside `value`)
@@ -718,21 +810,20 @@ def main():
         if dist is not None:
             s_el = D.max_over_ranks(s_el, dist, red_dev)
         stream_res = (s_el, s_up, s_down) if s_el != float("inf") else None
-        mp.step()                                                # the parity sample below looks at batch `reads` again
         log("streaming region done")
-    out = mp.fetch(with_match=args.parity_sample > 0 and rank == 0)
     nsites = out["nsites"]
-    top = out["sites"][:, 0]
     minScore = int(np.float32(0.56) * np.float32(70 + 149 * 100))
-    mapped = int(((nsites > 0) & (top["slowScore"] >= minScore)).sum())
     cells = int(out["results"]["iterations"].sum() + out["gresults"]["iterations"].sum())
     tier = out.get("overflow")
     if tier is not None:                                    # reads the overflow tier mapped (nsites == -3 in the main list)
-        mapped += int(((tier["nsites"] > 0) & (tier["sites"][:, 0]["slowScore"] >= minScore)).sum())
         cells += int(tier["results"]["iterations"].sum() + tier["gresults"]["iterations"].sum())
     fin = out.get("final")
     final_info = None
-    if fin is not None:                                     # the final records: what BBMap would print
+    if fin is None:
+        mapped = int(((nsites > 0) & (out["sites"][:, 0]["slowScore"] >= minScore)).sum())
+        if tier is not None:
+            mapped += int(((tier["nsites"] > 0) & (tier["sites"][:, 0]["slowScore"] >= minScore)).sum())
+    else:                                                   # the final records: what BBMap would print
         mapped = int((fin["mapped"] > 0).sum())
         final_info = {"mapped": mapped, "paired": int((fin["paired"] > 0).sum()), "ambiguous": int((fin["ambiguous"] > 0).sum()),
                       "perfect": int((fin["perfect"] > 0).sum()), "rescued": int(((fin["mapped"] > 0) & (fin["rescued"] > 0)).sum()),
