@@ -58,6 +58,12 @@ struct Settings {
     int ptsMatch, ptsMatch2, ptsSub, ptsSub2, ptsSub3, impDelta, clearzone1e;
     int msaMaxColumns;          // columns of the reference's MSA instance (realign_new's padding rules read msa.maxColumns)
     int finalStage;
+    // the final stage's use of the aligner class: POINTS_SUBR, the insertion tiers of calcInsScore (INS, INS2 up to length 5, INS3 up
+    // to 20, INS4 beyond) and the deletion tiers of calcDelScore (DEL, DEL2 / DEL3 / DEL4 / DEL5 at the same limits, GAP per 128)
+    int ptsSubR, ptsIns, ptsIns2, ptsIns3, ptsIns4, ptsDel, ptsDel2, ptsDel3, ptsDel4, ptsDel5, ptsGap;
+    // the mapping thread's tail (final_begin_kernel / final_end_kernel): 0 = BBMapThread's, 1 = BBMapThreadPacBio's; its clearzones
+    // CLEARZONEP / CLEARZONE1 / 1b / 1c = (int)(CLEARZONE_RATIO* x POINTS_MATCH2), CLEARZONE_LIMIT1e (BBMapThread only)
+    int finalPolicy, czP, cz1, cz1b, cz1c, czLimit1e;
 };
 
 struct SlowState {      // scoreSlow's loop state of one read
@@ -1181,8 +1187,21 @@ static int create_impl(bbidx_ctx *index, const bbmap_config *cfg, bbmap_ctx *par
     else { S.ptsMatch = 70; S.ptsMatch2 = 100; S.ptsSub = -127; S.ptsSub2 = -51; S.ptsSub3 = -25; S.impDelta = -495; }          // min(-472, -395 - 100)
     S.clearzone1e = 2 * S.ptsMatch2 - S.ptsMatch - S.ptsSub + 1;
     S.msaMaxColumns = cfg->msaMaxColumns;
-    if (cfg->finalStage && pacbio) return bail(mfail(BBMAP_E_ARG, "bbmap_create: the final alignment stage follows BBMapThread (BBIDX_PROFILE_BBMAP) only; set finalStage = 0 for BBIDX_PROFILE_PACBIO"));
+    // MultiStateAligner9PacBio.java:2375-2407 / MultiStateAligner11tsJNI.c:18-98
+    if (pacbio) { S.ptsSubR = -157; S.ptsIns = -205; S.ptsIns2 = -42; S.ptsIns3 = -23; S.ptsIns4 = -8; S.ptsDel = -292; S.ptsDel2 = -37; S.ptsDel3 = -17; S.ptsDel4 = -2; }
+    else { S.ptsSubR = -147; S.ptsIns = -395; S.ptsIns2 = -39; S.ptsIns3 = -23; S.ptsIns4 = -8; S.ptsDel = -472; S.ptsDel2 = -33; S.ptsDel3 = -9; S.ptsDel4 = -1; }
+    S.ptsDel5 = -1; S.ptsGap = -2;
+    // finalStage: 0 off, 1 the profile's own mapping thread (BBMapThread / BBMapThreadPacBio), 2 BBMapThread's whatever the profile
+    // (the parity seam: the oracle restates that tail only, oracle/mapper_oracle.c:758)
+    if (pacbio && (cfg->finalStage < 0 || cfg->finalStage > 2)) return bail(mfail(BBMAP_E_ARG, "bbmap_create: finalStage must be 0, 1 or 2"));
     S.finalStage = cfg->finalStage ? 1 : 0;
+    S.finalPolicy = (pacbio && cfg->finalStage == 1) ? 1 : 0;
+    {   // BBMapThreadPacBio.java:38-41, :112-115; BBMapThread.java:38-44
+        const float rP = S.finalPolicy ? 1.5f : 1.6f, r1 = S.finalPolicy ? 2.2f : 2.0f, r1b = S.finalPolicy ? 2.8f : 2.6f, r1c = S.finalPolicy ? 4.8f : 4.6f;
+        const float m2 = (float)S.ptsMatch2;
+        S.czP = (int)(rP * m2); S.cz1 = (int)(r1 * m2); S.cz1b = (int)(r1b * m2); S.cz1c = (int)(r1c * m2);
+        S.czLimit1e = 40;
+    }
     // BBMap.java:434: `if(paired){BBIndex.QUIT_AFTER_TWO_PERFECTS=false;}` -- a static of the index class in the reference, so the
     // borrowed index context is switched the same way (and back for a single-ended mapper)
     index->dev.p.quitAfterTwoPerfects = cfg->paired ? 0 : 1;

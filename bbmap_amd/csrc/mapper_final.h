@@ -14,7 +14,9 @@
 //                           :2097-2164 canPair, :2499-2609 calcTipScorePenalty / applyScorePenalty
 //   Tools                   current/align2/Tools.java:913-930 countTopScores, :986-1003 removeLowQualitySitesUnpaired
 // Configuration: bbmap.sh defaults (ambiguous=best, KILL_BAD_PAIRS / LOCAL_ALIGN / PRINT_SECONDARY_ALIGNMENTS / STRICT_MAX_INDEL off,
-// no identity / edit filters).
+// no identity / edit filters).  mapPacBio: the aligner's points come from Settings (MultiStateAligner9PacBio.java:2375-2407), and
+// Settings.finalPolicy = 1 selects BBMapThreadPacBio's tail (current/align2/BBMapThreadPacBio.java:497-670, :1088-1290) in the
+// begin / end kernels: its clearzone steps, no CLEARZONE1e block, the fixed CLEARZONE3; the state machine is shared.
 //
 // Shape on the device.  genMatchString is a per-read SEQUENCE of DP calls whose windows and minimum scores follow from the results
 // before them (realign_new: up to four fills, called up to twice per site with a tail recursion of its own), so -- as in scoreSlow --
@@ -106,18 +108,18 @@ __device__ int f_sub_score(const Settings &S, int len) {
     if (len > 1) score += (len - 1) * S.ptsSub2;
     return score;
 }
-__device__ int f_ins_score(int len) {                       // POINTS_INS_ARRAY_C[len]: -395, then -39 (x4), -23 (x15), -8
+__device__ int f_ins_score(const Settings &S, int len) {     // POINTS_INS_ARRAY_C[len] / calcInsScore: INS, then INS2 (x4), INS3 (x15), INS4
     if (len <= 0) return 0;
-    return -395 + imin(len - 1, 4) * -39 + imin(imax(len - 5, 0), 15) * -23 + imax(len - 20, 0) * -8;
+    return S.ptsIns + imin(len - 1, 4) * S.ptsIns2 + imin(imax(len - 5, 0), 15) * S.ptsIns3 + imax(len - 20, 0) * S.ptsIns4;
 }
-__device__ int f_del_score(int len) {
+__device__ int f_del_score(const Settings &S, int len) {     // calcDelScore(len, true)
     if (len <= 0) return 0;
-    int score = -472;
-    if (len > MINGAP) { const int rem = len % GAPLEN, div = (len - GAPBUFFER2) / GAPLEN; score += div * -2; len = rem + GAPBUFFER2; }
-    if (len > 80) { score += ((len - 80 + 3) / 4) * -1; len = 80; }
-    if (len > 20) { score += (len - 20) * -1; len = 20; }
-    if (len > 5) { score += (len - 5) * -9; len = 5; }
-    if (len > 1) score += (len - 1) * -33;
+    int score = S.ptsDel;
+    if (len > MINGAP) { const int rem = len % GAPLEN, div = (len - GAPBUFFER2) / GAPLEN; score += div * S.ptsGap; len = rem + GAPBUFFER2; }
+    if (len > 80) { score += ((len - 80 + 3) / 4) * S.ptsDel5; len = 80; }
+    if (len > 20) { score += (len - 20) * S.ptsDel4; len = 20; }
+    if (len > 5) { score += (len - 5) * S.ptsDel3; len = 5; }
+    if (len > 1) score += (len - 1) * S.ptsDel2;
     return score;
 }
 __device__ int msa_score_mode(const Settings &S, uint8_t mode, int current, uint8_t prevMode, int prevStreak) {
@@ -125,11 +127,11 @@ __device__ int msa_score_mode(const Settings &S, uint8_t mode, int current, uint
     if (mode == 'S') {
         int s = f_sub_score(S, current);
         if (prevMode == 'N' || prevMode == 'R') s += S.ptsSub2 - S.ptsSub;
-        else if (prevMode == 'm' && prevStreak < 2) s += -20;                   // POINTS_SUBR - POINTS_SUB
+        else if (prevMode == 'm' && prevStreak < 2) s += S.ptsSubR - S.ptsSub;
         return s;
     }
-    if (mode == 'D') return f_del_score(current);
-    if (mode == 'I' || mode == 'X' || mode == 'Y') return f_ins_score(current);
+    if (mode == 'D') return f_del_score(S, current);
+    if (mode == 'I' || mode == 'X' || mode == 'Y') return f_ins_score(S, current);
     return 0;
 }
 __device__ int msa_score_match(const Settings &S, const uint8_t *match, int n) {          // MSA.score(match) :488-558
@@ -466,10 +468,17 @@ __device__ int merge_duplicate_sites_exact(Site *s, int n) {
     return condense(s, n, dead);
 }
 
-__device__ int clearzone_single(const Settings &S, bool perfect, int score, int maxSw) {       // BBMapThread.java:508-525
+// the clearzone of the single-ended flow.  BBMapThread (:508-525) interpolates between its cutoffs SCALE x maxSw - FLAT;
+// BBMapThreadPacBio (:499-503, cutoffs :53-54) steps at (int)(maxSw x 0.92f) and (int)(maxSw x 0.82f)
+__device__ int clearzone_single(const Settings &S, bool perfect, int score, int maxSw) {
     const int M2 = S.ptsMatch2;
-    const int CZ1 = (int)__fmul_rn(2.0f, (float)M2), CZ1b = (int)__fmul_rn(2.6f, (float)M2), CZ1c = (int)__fmul_rn(4.6f, (float)M2), CZP = (int)__fmul_rn(1.6f, (float)M2);
-    if (perfect) return CZP;
+    const int CZ1 = S.cz1, CZ1b = S.cz1b, CZ1c = S.cz1c;
+    if (perfect) return S.czP;
+    if (S.finalPolicy == 1) {
+        if (score >= (int)__fmul_rn((float)maxSw, 0.92f)) return CZ1;
+        if (score >= (int)__fmul_rn((float)maxSw, 0.82f)) return CZ1b;
+        return CZ1c;
+    }
     const float cz1blimit = __fsub_rn(__fmul_rn((float)maxSw, 0.97f), __fmul_rn(12.f, (float)M2));
     const float cz1climit = __fsub_rn(__fmul_rn((float)maxSw, 0.92f), __fmul_rn(26.f, (float)M2));
     if ((float)score > cz1blimit)
@@ -478,13 +487,18 @@ __device__ int clearzone_single(const Settings &S, bool perfect, int score, int 
         return (int)__fdiv_rn(__fadd_rn(__fmul_rn(__fsub_rn(cz1blimit, (float)score), (float)CZ1c), __fmul_rn(__fsub_rn((float)score, cz1climit), (float)CZ1b)), __fsub_rn(cz1blimit, cz1climit));
     return CZ1c;
 }
-__device__ int clearzone_paired(const Settings &S, bool perfect, int score, int maxSw) {        // :1158-1160
+// the paired flow's: BBMapThread :1158-1160 (cutoffs SCALE x maxSw - FLAT), BBMapThreadPacBio :1094-1096 (plain CUTOFF products)
+__device__ int clearzone_paired(const Settings &S, bool perfect, int score, int maxSw) {
     const int M2 = S.ptsMatch2;
-    const int CZ1 = (int)__fmul_rn(2.0f, (float)M2), CZ1b = (int)__fmul_rn(2.6f, (float)M2), CZ1c = (int)__fmul_rn(4.6f, (float)M2), CZP = (int)__fmul_rn(1.6f, (float)M2);
-    if (perfect) return CZP;
-    if (score >= (int)__fsub_rn(__fmul_rn((float)maxSw, 0.97f), __fmul_rn(12.f, (float)M2))) return CZ1;
-    if (score >= (int)__fsub_rn(__fmul_rn((float)maxSw, 0.92f), __fmul_rn(26.f, (float)M2))) return CZ1b;
-    return CZ1c;
+    if (perfect) return S.czP;
+    if (S.finalPolicy == 1) {
+        if (score >= (int)__fmul_rn((float)maxSw, 0.92f)) return S.cz1;
+        if (score >= (int)__fmul_rn((float)maxSw, 0.82f)) return S.cz1b;
+        return S.cz1c;
+    }
+    if (score >= (int)__fsub_rn(__fmul_rn((float)maxSw, 0.97f), __fmul_rn(12.f, (float)M2))) return S.cz1;
+    if (score >= (int)__fsub_rn(__fmul_rn((float)maxSw, 0.92f), __fmul_rn(26.f, (float)M2))) return S.cz1b;
+    return S.cz1c;
 }
 
 // pairSiteScoresFinal(r, r2, trim = true, setScore = true, ...) (AbstractMapThread.java:1919-2095)
@@ -594,9 +608,9 @@ __global__ __launch_bounds__(128) void final_begin_kernel(const Dev D) {
             const int score = s[0].score;
             const int clearzone = clearzone_single(S, f.perfect, score, maxSw);
             int numBest = count_top_scores(s, n, clearzone);
-            if (numBest > 1) f.ambiguous = 1;
-            else {
-                const int lim = (f.perfect ? 160 : (score + S.clearzone1e >= maxSw ? 80 : 40)) + 1;       // CLEARZONE_LIMIT1e = 40
+            if (numBest > 1) f.ambiguous = 1;                                   // processAmbiguous(.., save_xy = false) returns true (:1424-1425)
+            else if (S.finalPolicy == 0) {                                      // BBMapThread's CLEARZONE1e block (BBMapThreadPacBio has none)
+                const int lim = (f.perfect ? (int)__fmul_rn(4.f, (float)S.czLimit1e) : (score + S.clearzone1e >= maxSw ? 2 * S.czLimit1e : S.czLimit1e)) + 1;
                 if (n > lim && clearzone < S.clearzone1e) { numBest = count_top_scores(s, n, S.clearzone1e); if (numBest > lim) f.ambiguous = 1; }
             }
         }
@@ -1016,12 +1030,12 @@ __device__ void to_local_alignment(const Dev &D, FinalRead &f, Site *s, int &n, 
             } else if (mode == 'S') {
                 score += f_sub_score(S, current);
                 if (prevMode == 'N' || prevMode == 'R') score += S.ptsSub2 - S.ptsSub;
-                else if (prevMode == 'm' && prevStreak < 2) score += -20;
+                else if (prevMode == 'm' && prevStreak < 2) score += S.ptsSubR - S.ptsSub;
                 cpos += current; rpos += current;
-            } else if (mode == 'D') { score += f_del_score(current); rpos += current; }
-            else if (mode == 'I') { score += f_ins_score(current); cpos += current; }
+            } else if (mode == 'D') { score += f_del_score(S, current); rpos += current; }
+            else if (mode == 'I') { score += f_ins_score(S, current); cpos += current; }
             else if (mode == 'C') { cpos += current; rpos += current; }
-            else if (mode == 'X' || mode == 'Y') { score += f_ins_score(current); cpos += current; rpos += current; }
+            else if (mode == 'X' || mode == 'Y') { score += f_ins_score(S, current); cpos += current; rpos += current; }
             else if (mode == 'N' || mode == 'R') { cpos += current; rpos += current; }
             if (atEnd) break;
             prevMode = mode; prevStreak = current; mode = match[mpos]; current = 1;
@@ -1123,7 +1137,11 @@ __global__ __launch_bounds__(128) void final_end_kernel(const Dev D) {
         if (n > 0) site_set_match(s[0], f.match, f.matchLen);
         if (n > 0 && f.mapScore <= 0) { f.mapScore = 0; f.mapped = 0; n = 0; }                   // :633-641
         if (f.mapScore <= 0 && n > 0) r_clear_mapping(f, n);                                     // :647-657
-        if (n > 0 && !f.ambiguous && S.clearzone3 > 0) {                                         // :668-682
+        if (S.finalPolicy == 1) {                                               // BBMapThreadPacBio.java:633-641: the fixed CLEARZONE3
+            if ((S.clearzone3 > S.cz1 || S.clearzone3 > S.czP) && apply_clearzone3(f, s, n, L, S.clearzone3, __fdiv_rn(1.f, (float)S.clearzone3))) {
+                if (f.mapScore < (int)__fmul_rn((float)maxSw, S.minRatio)) f.ambiguous = 1;
+            }
+        } else if (n > 0 && !f.ambiguous && S.clearzone3 > 0) {                                  // BBMapThread :668-682
             const float q = __fdiv_rn((float)maxSw, (float)f.mapScore);
             const float cz3v2 = __fmul_rn((float)S.clearzone3, 1.25f < q ? 1.25f : q);
             if (apply_clearzone3(f, s, n, L, (int)cz3v2, __fdiv_rn(1.f, cz3v2))) {

@@ -125,7 +125,8 @@ class Mapper:
     def from_records(cls, di, recs, bases, base_scores, keyinfo, paired=False, device=0, max_sites=32, profile=0, **cfg_kw):
         """The general form: reads of any lengths with their own keys, as bbkeys_make_batch (bbmap_amd.keys.make_batch) lays them
         out -- recs (READ_DTYPE), the bases blob, base scores at the same offsets, keyinfo.  profile: 0 = bbmap.sh's classes,
-        1 = mapPacBio.sh's (BBIDX_PROFILE_*; must be the index's)."""
+        1 = mapPacBio.sh's (BBIDX_PROFILE_*; must be the index's).  cfg_kw sets bbmap_config fields, e.g. finalStage = 1 for
+        mapPacBio's final records (off by default for that profile; 2 = BBMapThread's tail, for parity tests)."""
         self = cls.__new__(cls)
         self.L = _lib.load()
         _bind(self.L)

@@ -520,7 +520,12 @@ typedef struct bbmap_config {
     int32_t finalStage;            /* 1 (default, BBIDX_PROFILE_BBMAP): the whole of processRead / processReadPair -- after rescue the final
                                     * pairing, the ambiguity policy, genMatchString -> genMatchStringForSite -> realign_new (the fills that
                                     * produce the printed start / stop / score and the match string), clipping and the score penalties;
-                                    * 0: stop after the rescue stage (the site lists as scoreSlow and rescue leave them) */
+                                    * 0: stop after the rescue stage (the site lists as scoreSlow and rescue leave them).
+                                    * BBIDX_PROFILE_PACBIO defaults to 0: the stage is opt-in there.  1 runs it with the profile's own
+                                    * mapping thread, BBMapThreadPacBio.java:497-670 / :1088-1290 (its clearzone steps, no CLEARZONE1e
+                                    * block, the fixed CLEARZONE3) and MultiStateAligner9PacBio's points.
+                                    * 2: the stage with BBMapThread's tail whatever the profile (the profile's aligner points).  Exists
+                                    * for parity tests: the CPU oracle restates BBMapThread's tail only. */
     int32_t reserved[4];           /* [0] != 0: strictly one fill per read and round (no fills ahead of time; for tests)
                                     * [1] overflow tier: reads it can hold per batch (0 = 4096, < 0 = no tier)
                                     * [2] overflow tier: its max_sites (0 = 1024)
@@ -555,7 +560,8 @@ typedef struct bbmap_output {      /* device pointers, valid until the next bbma
     const bbmsa_gaps *ggaps;
     /* the final alignment stage (cfg.finalStage): one record per read and the pool its match strings live in.  A site that was given a
      * match string of its own refers to it in the same pool: sites[].reserved[0] = byte offset / 4 + 1 (0 = none),
-     * reserved[1] & 0xffff = its length.  NULL / 0 when the stage is off. */
+     * reserved[1] & 0x7fffffff = its length (bit 31 is reserved and 0 on output; expanded gaps and long reads make strings longer than
+     * 65,535 bytes).  NULL / 0 when the stage is off. */
     const bbmap_final *final;
     const uint8_t *final_match;
     int64_t final_match_bytes;     /* bytes of the pool in use */

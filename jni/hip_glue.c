@@ -9,7 +9,7 @@
  *        replaces, batched: MSA.fillAndScoreLimited + traceback per site (current/align2/MSA.java:103-134, BBMapThread.java:309, :345)
  *   align2.BBIndexHIP                 build / destroy / setMaxReadLen / findBatch       -> bbidx_*
  *        replaces, batched: AbstractIndex.findAdvanced per read (current/align2/AbstractIndex.java:83, AbstractMapThread.java:736)
- *   align2.BBMapHIP                   create / destroy / mapBatch                       -> bbmap_*
+ *   align2.BBMapHIP                   create / destroy / mapBatch / getFinal            -> bbmap_*
  *        replaces, batched: BBMapThread.processRead / processReadPair up to the end of rescue (current/align2/BBMapThread.java:389-490,
  *        :943-1098)
  *   all three                         lastError                                         -> bbmap_last_error
@@ -187,15 +187,19 @@ JNIEXPORT void JNICALL Java_align2_BBIndexHIP_findBatch(JNIEnv *env, jclass cls,
 
 /* ------------------------------------------------------------------ align2.BBMapHIP */
 
-/* (JIZIII)J -- the profile's defaults (bbmap.sh / mapPacBio.sh) with the batch geometry filled in */
+/* (JIZIII)J -- the profile's defaults (bbmap.sh / mapPacBio.sh) with the batch geometry filled in.  profile: BBIDX_PROFILE_* in bits 0-7;
+ * bits 8-15 = bbmap_config.finalStage + 1 when the caller chooses the final stage (0: the profile's default -- on for bbmap.sh, off for
+ * mapPacBio.sh), so that BBMapHIP can ask for the PacBio final stage without another native */
 JNIEXPORT jlong JNICALL Java_align2_BBMapHIP_create(JNIEnv *env, jclass cls, jlong index, jint profile, jboolean paired, jint maxReads,
                                                     jint maxReadLen, jint maxSites) {
     (void)cls;
     bbmap_config cfg;
-    int rc = bbmap_default_config_profile(profile, &cfg);
+    const int stage = (profile >> 8) & 0xFF;
+    int rc = bbmap_default_config_profile((profile & ~0xFFFF) ? -1 : (profile & 0xFF), &cfg);      /* (bits 16-31: refused) */
     bbmap_ctx *ctx = NULL;
     if (rc == BBMAP_OK) {
         cfg.paired = paired ? 1 : 0; cfg.max_reads = maxReads; cfg.max_read_len = maxReadLen; cfg.max_sites = maxSites;
+        if (stage) cfg.finalStage = stage - 1;
         rc = bbmap_create((bbidx_ctx *)(intptr_t)index, &cfg, &ctx);
     }
     if (rc != BBMAP_OK) { throw_runtime(env, "bbmap_create", rc); return 0; }

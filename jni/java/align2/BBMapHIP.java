@@ -13,6 +13,7 @@ import java.nio.ByteOrder;
  * slowScore/pairedScore, hits, perfect/semiperfect, rescued, gaps); the Java side continues with statistics and output.
  *
  * paired: reads 2p and 2p+1 are mates.  Defaults are bbmap.sh's or mapPacBio.sh's (BBMap.setDefaults / BBMapPacBio.setDefaults).
+ * For mapPacBio.sh the final stage is opt-in (the finalStage argument; BBMapThreadPacBio's tail with finalStage = 1).
  */
 public final class BBMapHIP implements AutoCloseable {
 
@@ -35,8 +36,18 @@ public final class BBMapHIP implements AutoCloseable {
 	public final int maxReads;
 
 	public BBMapHIP(BBIndexHIP index_, boolean paired_, int maxReads_, int maxReadLen, int maxSites) {
+		this(index_, paired_, maxReads_, maxReadLen, maxSites, -1);
+	}
+
+	/**
+	 * finalStage: -1 = the profile's default (on for bbmap.sh; off for mapPacBio.sh, where the stage is opt-in), 0 = off (site lists
+	 * only), 1 = the final stage with the profile's own mapping thread -- BBMapThreadPacBio.processRead / processReadPair's tail for
+	 * mapPacBio.sh, so that {@link #finalRecord} serves it --, 2 = BBMapThread's tail whatever the profile (parity tests).
+	 */
+	public BBMapHIP(BBIndexHIP index_, boolean paired_, int maxReads_, int maxReadLen, int maxSites, int finalStage) {
 		index = index_; paired = paired_; maxReads = maxReads_;
-		ctx = create(index.ctx, index.profile, paired, maxReads, maxReadLen, maxSites);
+		if (finalStage < -1 || finalStage > 2) { throw new IllegalArgumentException("finalStage must be -1, 0, 1 or 2"); }
+		ctx = create(index.ctx, index.profile | ((finalStage + 1) << 8), paired, maxReads, maxReadLen, maxSites);
 		nsites = buf(4 * maxReads); offsets = buf(8 * (maxReads + 1));
 		sitesCap = 8 * maxReads; sites = buf(sitesCap * MSITE_BYTES);
 	}
