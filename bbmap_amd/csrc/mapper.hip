@@ -36,6 +36,7 @@ void bbmsa_use_narrow(bbmsa_ctx *c, bool on);          // msa_host.hip (internal
 int bbmsa_wait_first_pass(bbmsa_ctx *c, void *waiter);
 void bbmsa_sort_by_width(bbmsa_ctx *c, bool on);
 int bbmsa_set_latency_jobs(bbmsa_ctx *c, int64_t n);
+int bbmsa_last_route_flags(const bbmsa_ctx *c);        // bit 0 narrow kernel ran, bit 1 width-sorted first pass
 
 namespace bbmapper {
 
@@ -1070,6 +1071,8 @@ struct bbmap_ctx {
     void *d_packTmp; size_t packTmpBytes;     // bbmap_pack_sites_device's scan scratch (allocated on first use)
     bbmap_ctx *tier;
     bool ownsMsa;
+    long long narrowMinJobs;        // plain-context launches with at least this many fills run the narrow kernel (BBMAP_NARROW_MIN_JOBS)
+    bool sortWide;                  // the second context hands its fills on widest first (BBMAP_SORT_WIDE=0 switches it off)
     int *d_tierUnits; bbidx_read *d_tierReads; int *d_tierReadIds;
     long long tierReads;            // reads the tier mapped in the last batch
     // The tier's pass runs beside the main pass (its reads are known once begin_kernel has run): its own stream, driven by its
@@ -1247,6 +1250,8 @@ static int create_impl(bbidx_ctx *index, const bbmap_config *cfg, bbmap_ctx *par
     }
     const long long n = cfg->max_reads;
     const int cap = cfg->max_sites;
+    c->narrowMinJobs = getenv("BBMAP_NARROW_MIN_JOBS") ? atoll(getenv("BBMAP_NARROW_MIN_JOBS")) : 32768;
+    c->sortWide = !(getenv("BBMAP_SORT_WIDE") && atoi(getenv("BBMAP_SORT_WIDE")) == 0);      // (experiments: 0 switches the width order off)
     if (!pacbio) {
         // launches of a few hundred fills (the late rounds of scoreSlow and of the final stage) are one wavefront's latency: they take
         // the 64-lane geometry, whose step is the shorter chain (msa_ctx.h; 236 -> 231 ms per step for the second context alone)
@@ -1390,12 +1395,11 @@ static int run_fills(bbmap_ctx *c, hipStream_t stream, const uint8_t *bases, lon
     // The one-job-per-lane narrow kernel runs in front of the wavefront kernel on the same stream and is a ~1.5 ms dependent chain
     // however few jobs there are: worth it only for the big first rounds of scoreSlow (163 k of 459 k fills finish there in 4.8 ms
     // on the bench workload).  The final stage's fills never fit its band (see msa_ctx.h), nor do the second context's wide windows.
-    static const long long narrowMin = getenv("BBMAP_NARROW_MIN_JOBS") ? atoll(getenv("BBMAP_NARROW_MIN_JOBS")) : 32768;
-    static const bool sortWide = !(getenv("BBMAP_SORT_WIDE") && atoi(getenv("BBMAP_SORT_WIDE")) == 0);      // (experiments: 0 switches the width order off)
-    bbmsa_use_narrow(c->msa, !finalStage && nNew >= narrowMin);
+    bbmsa_use_narrow(c->msa, !finalStage && nNew >= c->narrowMinJobs);
     // (not the first context's: its windows span 162..256 columns, and sorted its pass ends 4 ms earlier -- leaving the second
     // context's latency-bound wide pass to finish on its own: final stage 79.6 -> 85.5 ms)
-    if (c->msaGapped != c->msa) { bbmsa_use_narrow(c->msaGapped, false); bbmsa_sort_by_width(c->msaGapped, sortWide); }
+    bbmsa_sort_by_width(c->msa, false);
+    if (c->msaGapped != c->msa) { bbmsa_use_narrow(c->msaGapped, false); bbmsa_sort_by_width(c->msaGapped, c->sortWide); }
     // the second context's launches first, on their own stream: its blocks take their share of the CUs and the plain context's
     // persistent blocks fill the rest (and the slots the others free)
     hipStream_t gs = (c->dpStream && nNew > 0) ? c->dpStream : stream;
@@ -1408,6 +1412,11 @@ static int run_fills(bbmap_ctx *c, hipStream_t stream, const uint8_t *bases, lon
     if (nNew > 0)
         MTRY(bbmsa_align_batch_device(c->msa, stream, nNew, c->d_jobs + jobBase, bases, c->refsBase, c->d_results + jobBase,
                                       c->d_match + jobBase * c->matchStride, c->matchStride));
+    // which routes the launches took (host flags of the DP contexts, no device read-back)
+    const int r1 = nNew > 0 ? bbmsa_last_route_flags(c->msa) : 0;
+    const int r2 = gNew > 0 ? bbmsa_last_route_flags(c->msaGapped) : 0;
+    c->stats.dp_narrow_launches += (r1 & 1) + (r2 & 1);
+    c->stats.dp_sorted_launches += ((r1 >> 1) & 1) + ((r2 >> 1) & 1);
     if (gNew > 0 && gs != stream) MHIP(hipStreamWaitEvent(stream, c->evJoin, 0));
     return BBMAP_OK;
 }
@@ -1696,6 +1705,7 @@ static int tier_finish(bbmap_ctx *c, hipStream_t stream) {
     st.fills += ts.fills; st.gapped_fills += ts.gapped_fills; st.refills += ts.refills; st.rescue_scans += ts.rescue_scans;
     st.rescue_fills += ts.rescue_fills; st.fills_dropped += ts.fills_dropped;
     st.final_fills += ts.final_fills; st.final_local += ts.final_local;
+    st.dp_narrow_launches += ts.dp_narrow_launches; st.dp_sorted_launches += ts.dp_sorted_launches;
     if (getenv("BBMAP_TIER_DEBUG"))
         fprintf(stderr, "[bbmap tier] reads %lld: probe %.2f begin %.2f score %.2f slow %.2f (rounds %lld) finish %.2f rescue %.2f total %.2f\n",
                 tn, ts.ms_probe, ts.ms_begin, ts.ms_score, ts.ms_slow, (long long)ts.rounds, ts.ms_finish, ts.ms_rescue, ts.ms_total);

@@ -30,6 +30,8 @@ struct bbmsa_ctx {
     int narrowBlocks, narrowSlack;     // 0 blocks = disabled
     bool narrowOff;                    // switched off by the caller for launches whose jobs it cannot take (bbmsa_use_narrow)
     bool narrowUsed;                   // whether the last launch ran it
+    bool lastSorted, lastLatency, lastIndirect;   // the last launch's route (bbmsa_last_route): width-sorted first pass, latency route,
+                                                  // job count read on the device
     // widest windows first (bbmsa_sort_by_width): two jobs share a wavefront and step together, so a 600-column job beside a
     // 200-column one idles half the wave for 400 steps; in width order neighbours are alike, and the longest jobs do not end up last
     bool sortByWidth;
@@ -72,11 +74,19 @@ int bbmsa_wait_first_pass(bbmsa_ctx *c, void *waiter);
 // front of the first pass); results are indexed by job as always.  The mapper asks for it on its second context, whose windows
 // span 170..640+ columns.
 void bbmsa_sort_by_width(bbmsa_ctx *c, bool on);
+// BBMSA_SORT_BY_WIDTH=1 in the environment switches it on for every context bbmsa_create makes (default 0; a caller that sets it,
+// like the mapper, overrides it per context).
 // Launches of at most n jobs skip the first pass and run in the wide pass's geometry (64 lanes x ceil(rows / 64) rows per lane, one job
 // per block): with few jobs a launch costs one wavefront's dependent chain, and three rows per lane make a step ~450 instructions
 // instead of ~740.  Measured on the mapper's late rounds (a few hundred fills each): 236.0 -> 230.9 ms per step for the second
 // context alone.  0 = off (the default of a context).
 int bbmsa_set_latency_jobs(bbmsa_ctx *c, int64_t n);
+// BBMSA_LATENCY_JOBS=n in the environment applies bbmsa_set_latency_jobs(c, n) to every 11ts context bbmsa_create makes (default 0;
+// the mapper overrides it per context with BBMAP_LATENCY_JOBS).
+// The route of the last launch as host flags, for callers that count launches without a device read-back:
+// bit 0 narrow kernel ran, bit 1 width-sorted first pass, bit 2 latency route (no first pass).  bbmsa_last_route has the counters too.
+enum { BBMSA_ROUTE_NARROW = 1, BBMSA_ROUTE_SORTED = 2, BBMSA_ROUTE_LATENCY = 4 };
+int bbmsa_last_route_flags(const bbmsa_ctx *c);
 
 // msa_legacy.hip: persistent buffers, stream and the call combiner of a BBMSA_LEGACY_ONLY context (c->d_matrix / d_limits exist)
 int bbmsa_legacy_create(bbmsa_ctx *c);

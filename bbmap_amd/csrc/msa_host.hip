@@ -288,6 +288,9 @@ extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
         c->narrowBlocks = c->numCUs * perCU;
         HIP_TRY(hipMalloc(&c->d_narrowDir, (size_t)c->narrowBlocks * (size_t)(cfg->maxRows + 1) * 64 * 8));
     }
+    // route switches of the environment (msa_ctx.h): defaults off, as the functions they mirror leave a context
+    c->sortByWidth = env_int("BBMSA_SORT_BY_WIDTH", 0) != 0;
+    { const int lat = env_int("BBMSA_LATENCY_JOBS", 0); if (lat > 0) { const int rc = bbmsa_set_latency_jobs(c, lat); if (rc != BBMAP_OK) return rc; } }
     for (int i = 0; i < 4; i++) HIP_TRY(hipEventCreate(&c->ev[i]));
     guard.c = nullptr;
     *out = c;
@@ -353,6 +356,7 @@ int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t
             c->slowCap = n_jobs;
         }
         HIP_TRY(hipMemsetAsync(c->d_counters, 0, 64, stream));
+        c->narrowUsed = false; c->lastSorted = false; c->lastLatency = false; c->lastIndirect = n_jobs_dev != nullptr;
         HIP_TRY(hipEventRecord(c->ev[0], stream));
         HIP_TRY(hipEventRecord(c->ev[3], stream));
         bbmsa::StripParams sp;
@@ -444,6 +448,7 @@ int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t
     // pass's geometry (64 lanes x 3 rows, one job per block) has the shorter chain per step (3 rows instead of 5: ~450 instead of
     // ~740 instructions), so such launches go to it directly (bbmsa_set_latency_jobs; the mapper's late rounds hold a few hundred fills).
     const bool latency = c->wideBlocks > 0 && !n_jobs_dev && !useNarrow && n_jobs <= c->latencyJobs;
+    c->lastSorted = sortJobs; c->lastLatency = latency; c->lastIndirect = n_jobs_dev != nullptr;
     const int jobsPerBlock = 4 * (64 / c->G);
     long long blocks = (n_jobs + jobsPerBlock - 1) / jobsPerBlock;
     if (blocks > c->blocks) blocks = c->blocks;
@@ -529,6 +534,23 @@ extern "C" int bbmsa_last_counts(bbmsa_ctx *c, int64_t *counts4) {
     HIP_TRY(hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
     counts4[0] = h[5]; counts4[1] = h[6]; counts4[2] = c->narrowUsed ? h[4] : 0; counts4[3] = c->wideBlocks > 0 ? h[7] : h[1];
     if (getenv("BBMAP_DP_COUNTS") && c->wideBlocks > 0) fprintf(stderr, "   (first pass handed %u jobs to the wide pass)\n", h[1]);
+    return BBMAP_OK;
+}
+
+int bbmsa_last_route_flags(const bbmsa_ctx *c) {
+    if (!c || !c->timed) return 0;
+    return (c->narrowUsed ? BBMSA_ROUTE_NARROW : 0) | (c->lastSorted ? BBMSA_ROUTE_SORTED : 0) | (c->lastLatency ? BBMSA_ROUTE_LATENCY : 0);
+}
+
+extern "C" int bbmsa_last_route(bbmsa_ctx *c, int64_t *route8) {
+    if (!c || !c->timed || !route8) return fail(BBMAP_E_ARG, "bbmsa_last_route: nothing launched yet");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipEventSynchronize(c->ev[2]));
+    unsigned h[16];
+    HIP_TRY(hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
+    const bool wide = c->scheme == BBMSA_SCHEME_11TS && c->wideBlocks > 0;
+    route8[0] = c->narrowUsed; route8[1] = c->lastSorted; route8[2] = c->lastLatency; route8[3] = wide; route8[4] = c->lastIndirect;
+    route8[5] = h[1]; route8[6] = wide ? h[7] : 0; route8[7] = c->narrowUsed ? h[5] : 0;
     return BBMAP_OK;
 }
 

@@ -46,7 +46,7 @@ class bbmap_stats(C.Structure):
                                          "ms_dp_narrow", "ms_dp_wave", "ms_dp_generic", "ms_dp_gapped", "ms_quick_rescue")] + \
                [("probe_stats", C.c_int64 * 5), ("reads_reprobed", C.c_int64), ("ms_overflow", C.c_float), ("log_growths", C.c_float),
                 ("ms_dp_wave_max", C.c_float), ("ms_final", C.c_float), ("final_fills", C.c_int64), ("final_rounds", C.c_int64),
-                ("final_local", C.c_int64)]
+                ("final_local", C.c_int64), ("dp_narrow_launches", C.c_int64), ("dp_sorted_launches", C.c_int64)]
 
 
 class bbmap_overflow_output(C.Structure):

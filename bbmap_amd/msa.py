@@ -130,6 +130,39 @@ class MSAContext:
                                              C.c_void_p(match_ptr) if match_ptr else None, match_stride)
         _lib.check(rc, "bbmsa_align_batch_device")
 
+    def align_batch_device_indirect(self, n_jobs_ptr, max_jobs, jobs_ptr, reads_ptr, refs_ptr, results_ptr, match_ptr=0,
+                                    match_stride=0, stream=0):
+        """align_batch_device with the job count in device memory (a uint32 at n_jobs_ptr, read when the kernels start):
+        min(count, max_jobs) jobs run, and max_jobs is the capacity of jobs / results / match."""
+        rc = self.L.bbmsa_align_batch_device_indirect(self.h, C.c_void_p(stream), C.c_void_p(n_jobs_ptr), max_jobs,
+                                                      C.c_void_p(jobs_ptr), C.c_void_p(reads_ptr), C.c_void_p(refs_ptr),
+                                                      C.c_void_p(results_ptr),
+                                                      C.c_void_p(match_ptr) if match_ptr else None, match_stride)
+        _lib.check(rc, "bbmsa_align_batch_device_indirect")
+
+    def align_gapped_batch_device(self, n_jobs, jobs_ptr, gaps_ptr, reads_ptr, refs_ptr, results_ptr, match_ptr=0,
+                                  match_stride=0, stream=0):
+        rc = self.L.bbmsa_align_gapped_batch_device(self.h, C.c_void_p(stream), n_jobs, C.c_void_p(jobs_ptr), C.c_void_p(gaps_ptr),
+                                                    C.c_void_p(reads_ptr), C.c_void_p(refs_ptr), C.c_void_p(results_ptr),
+                                                    C.c_void_p(match_ptr) if match_ptr else None, match_stride)
+        _lib.check(rc, "bbmsa_align_gapped_batch_device")
+
+    def align_gapped_batch_device_indirect(self, n_jobs_ptr, max_jobs, jobs_ptr, gaps_ptr, reads_ptr, refs_ptr, results_ptr,
+                                           match_ptr=0, match_stride=0, stream=0):
+        """align_gapped_batch_device with the job count in device memory (see align_batch_device_indirect)."""
+        rc = self.L.bbmsa_align_gapped_batch_device_indirect(self.h, C.c_void_p(stream), C.c_void_p(n_jobs_ptr), max_jobs,
+                                                             C.c_void_p(jobs_ptr), C.c_void_p(gaps_ptr), C.c_void_p(reads_ptr),
+                                                             C.c_void_p(refs_ptr), C.c_void_p(results_ptr),
+                                                             C.c_void_p(match_ptr) if match_ptr else None, match_stride)
+        _lib.check(rc, "bbmsa_align_gapped_batch_device_indirect")
+
+    def last_route(self):
+        """The route of the last launch sequence (bbmsa_last_route): host flags recorded at launch and the device counters."""
+        r = (C.c_int64 * 8)()
+        _lib.check(self.L.bbmsa_last_route(self.h, r), "bbmsa_last_route")
+        return {"narrow": bool(r[0]), "sorted": bool(r[1]), "latency": bool(r[2]), "wide_pass": bool(r[3]), "indirect": bool(r[4]),
+                "first_handed_on": r[5], "wide_handed_on": r[6], "narrow_finished": r[7]}
+
     def last_counts(self):
         """{narrow: finished by the one-job-per-lane kernel, narrow_left: its candidates handed on, wave: jobs of the
         wavefront kernel, generic: jobs of the generic kernel} for the last launch sequence."""

@@ -201,6 +201,12 @@ int bbmsa_last_kernel_ms3(bbmsa_ctx *ctx, float *ms3);
  * per lane, a band of diagonals in registers), candidates it handed on because their window left the band, jobs given
  * to the wavefront kernel in total, jobs the wavefront kernel handed to the generic kernel}. */
 int bbmsa_last_counts(bbmsa_ctx *ctx, int64_t *counts4);
+/* The route the last launch sequence took (host flags recorded at launch, then the device counters):
+ * route8 = {narrow-window kernel ran (0/1), first pass in descending window width (0/1), latency route: no first pass, the
+ * wide pass took every job (0/1), the context has a wide pass (0/1), job count read on the device (an _indirect entry, 0/1),
+ * jobs the first pass handed on (9PacBio: the strip kernel to the generic kernel), jobs the wide pass handed to the generic
+ * kernel, jobs the narrow-window kernel finished}.  Waits for the launch sequence to finish. */
+int bbmsa_last_route(bbmsa_ctx *ctx, int64_t *route8);
 
 /* =====================================================================================
  * BandedAligner (unit-cost edit distance in a diagonal band)
@@ -583,6 +589,8 @@ typedef struct bbmap_stats {
                                     * ms_dp_wave is the sum over all rounds and rescue passes */
     float ms_final;                /* the final alignment stage (included in ms_total) */
     int64_t final_fills, final_rounds, final_local;   /* its fills, rounds, reads that went through toLocalAlignment */
+    int64_t dp_narrow_launches;    /* DP launches that ran the narrow-window kernel (bbmsa_last_route: route8[0]) */
+    int64_t dp_sorted_launches;    /* DP launches whose first pass took the jobs widest first (route8[1]) */
 } bbmap_stats;
 
 typedef struct bbmap_ctx bbmap_ctx;

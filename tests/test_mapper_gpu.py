@@ -39,19 +39,53 @@ def _run(ref, reads, L, k, paired, max_sites=32, cap=64, **cfg):
     return out, orc, st, n
 
 
-def test_single_ended_matches_oracle():
+# The DP routes the mapper's launches take.  "latency": the defaults -- launches of up to 4,096 fills go straight to the 64-lane
+# geometry, and the narrow kernel only runs for launches of 32,768 fills or more, so at test sizes nearly every launch takes the
+# latency route.  "throughput": what the benchmark's big launches take -- the narrow kernel in front of the first pass in the plain
+# context, the width-sorted first pass in the second.
+DP_ROUTES = {"latency": {}, "throughput": {"BBMAP_LATENCY_JOBS": "0", "BBMAP_NARROW_MIN_JOBS": "1"}}
+
+
+def _set_route(monkeypatch, route):
+    for k_ in ("BBMAP_LATENCY_JOBS", "BBMAP_NARROW_MIN_JOBS", "BBMAP_SORT_WIDE"):
+        monkeypatch.delenv(k_, raising=False)
+    for k_, v in DP_ROUTES[route].items():
+        monkeypatch.setenv(k_, v)
+
+
+def _single_ended(monkeypatch, route, n_reads=3000, **workload):
+    _set_route(monkeypatch, route)
     L, k = 150, 12
     ref = W.make_reference(300000, seed=5, pad=2000, repeat_frac=0.15)
-    reads, _, _ = W.make_reads_and_jobs(ref, 3000, read_len=L, seed=9, pad=2000, long_del_frac=0.3, hard_frac=0.05)
+    workload = dict(dict(long_del_frac=0.3, hard_frac=0.05), **workload)
+    reads, _, _ = W.make_reads_and_jobs(ref, n_reads, read_len=L, seed=9, pad=2000, **workload)
     out, orc, st, n = _run(ref, reads, L, k, paired=False)
     assert st["reads_overflowed"] == 0
     bad = compare(out, orc, n, paired=False)
     assert not bad, "\n".join(bad[:20])
     assert st["fills"] > 0.1 * n and st["gapped_fills"] > 0        # the workload reaches both fill logs
     assert st["rounds"] >= 2                                         # and some reads need more than one fill
+    return st
 
 
-def test_paired_matches_oracle_with_rescue():
+def test_single_ended_matches_oracle(monkeypatch):
+    st = _single_ended(monkeypatch, "latency")
+    assert st["dp_narrow_launches"] == 0 and st["dp_sorted_launches"] == 0, st
+
+
+def test_single_ended_matches_oracle_on_the_throughput_route(monkeypatch):
+    st = _single_ended(monkeypatch, "throughput")
+    assert st["dp_narrow_launches"] > 0, st                          # the route really ran
+
+
+def test_single_ended_long_deletions_take_the_width_sorted_pass(monkeypatch):
+    """The throughput route with enough long deletions that the second context's launches reach the sort's 256-fill floor."""
+    st = _single_ended(monkeypatch, "throughput", n_reads=6000, perfect_frac=0.2, long_del_frac=1.0)
+    assert st["dp_narrow_launches"] > 0 and st["dp_sorted_launches"] > 0, st
+
+
+def _paired(monkeypatch, route):
+    _set_route(monkeypatch, route)
     L, k = 150, 12
     ref = W.make_reference(300000, seed=6, pad=2000, repeat_frac=0.15)
     reads, truth = W.make_pairs(ref, 2000, read_len=L, seed=4, pad=2000, hard_frac=0.08)
@@ -66,6 +100,18 @@ def test_paired_matches_oracle_with_rescue():
     top = out["sites"][:, 0]
     ok1 = (out["nsites"][0::2] > 0) & (np.abs(top["start"][0::2] - truth["start1"]) <= 40) & (top["strand"][0::2] == truth["strand1"])
     assert ok1.mean() > 0.97
+    return st
+
+
+def test_paired_matches_oracle_with_rescue(monkeypatch):
+    st = _paired(monkeypatch, "latency")
+    assert st["dp_narrow_launches"] == 0 and st["dp_sorted_launches"] == 0, st
+
+
+def test_paired_matches_oracle_with_rescue_on_the_throughput_route(monkeypatch):
+    st = _paired(monkeypatch, "throughput")
+    assert st["dp_narrow_launches"] > 0, st                          # the route really ran
+    print("throughput route: %d narrow launches, %d width-sorted launches" % (st["dp_narrow_launches"], st["dp_sorted_launches"]))
 
 
 def test_paired_without_tip_search_and_trimming():

@@ -9,7 +9,7 @@ import pytest
 from bbmap_amd import msa as M
 from oracle.oracle import OracleMSA
 from tests.problems import rand_seq
-from tests.test_msa_gpu import oracle_align
+from tests.msa_check import oracle_align
 
 pytestmark = pytest.mark.gpu
 
