@@ -234,6 +234,7 @@ extern "C" int bbidx_build_profile(int32_t device, int32_t profile, int32_t k, i
         if (!c) { bbmap_set_error("bbidx_build: out of memory"); return BBMAP_E_NOMEM; }
         c->device = device; c->kernelKind = BBIDX_KERNEL_AUTO; c->blocks = prop.multiProcessorCount * 8;
         c->totalSites = 0; c->maxReadLen = BBIDX_MAX_READ_LEN;
+        c->maxGroups = bbidx_env_max_groups();
         memset(&c->dev, 0, sizeof c->dev);
         const int nblocks = (nchroms >> chromBits) + 1;
         const int cpb = 1 << chromBits, shift = 31 - chromBits, lowMask = cpb - 1;

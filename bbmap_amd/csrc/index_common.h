@@ -118,5 +118,6 @@ __device__ inline int subArr(int t) { return t > 5 ? -25 : (t > 1 ? -51 : -127);
 
 }  // namespace bbidx
 
-// launcher of the wave kernel (index_probe_wave.hip)
-int bbidx_launch_wave(const bbidx::Params &P, hipStream_t stream, bool longLists, int maxReadLen);
+// launcher of the wave kernel (index_probe_wave.hip); maxGroups > 0 clamps the grid; the grid and whether the short-read
+// instantiation ran go to *groups / *shortReads
+int bbidx_launch_wave(const bbidx::Params &P, hipStream_t stream, bool longLists, int maxReadLen, int maxGroups, long long *groups, bool *shortReads);

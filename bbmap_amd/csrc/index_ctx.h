@@ -19,6 +19,10 @@ struct bbidx_launch {
     bool timed = false;
     int *d_longWs = nullptr;       // allocated at the first launch of the long-read kernel (index_probe_long.hip)
     int longBlocks = 0;
+    // what the last launch ran, as the host chose it (bbidx_last_launch; 0 for a kernel that did not run): wave-kernel groups,
+    // long-list variant, short-read instantiation, lane-kernel groups, long-kernel groups, the long kernel's maxLen / maxKeys
+    long long waveGroups = 0, lastLaneGroups = 0, lastLongGroups = 0;
+    int waveLongLists = 0, waveShort = 0, longMaxLen = 0, longMaxKeys = 0;
 };
 
 struct bbidx_ctx {
@@ -30,7 +34,11 @@ struct bbidx_ctx {
     int kernelKind;       // BBIDX_KERNEL_*
     long long totalSites; // list entries over all blocks (picks the wave kernel's long-list variant)
     int maxReadLen;       // bbidx_set_max_read_len: picks the wave kernel's LDS sizing (default BBIDX_MAX_READ_LEN)
+    int maxGroups;        // BBIDX_MAX_GROUPS at creation: every probe launch's grid is clamped to it (0 = no cap; tests run many reads per wave)
 };
+
+// BBIDX_MAX_GROUPS, read once per context (bbidx_create / bbidx_build): unset or 0 = no cap
+int bbidx_env_max_groups();
 
 int bbidx_launch_init(bbidx_ctx *c, bbidx_launch *ls);
 void bbidx_launch_free(bbidx_launch *ls);
@@ -48,4 +56,5 @@ int bbidx_finish_create(bbidx_ctx *c, const std::vector<const int *> &starts, co
 // index_probe_long.hip: one read per wavefront for reads of up to 6016 bases with up to 2047 keys (either profile)
 long long bbidx_long_workspace_ints_per_block();
 int bbidx_long_blocks(int profile);
-int bbidx_launch_long(const bbidx::Params &P, hipStream_t stream, int profile, int *ws, int blocks);
+// maxGroups > 0 clamps the grid; the grid and the layout's maxLen / maxKeys go to ls (bbidx_last_launch)
+int bbidx_launch_long(const bbidx::Params &P, hipStream_t stream, int profile, int *ws, int blocks, int maxGroups, bbidx_launch *ls);

@@ -763,6 +763,12 @@ void bbidx_launch_free(bbidx_launch *ls) {
     *ls = bbidx_launch();
 }
 
+int bbidx_env_max_groups() {
+    const char *ev = getenv("BBIDX_MAX_GROUPS");
+    const int v = ev && *ev ? atoi(ev) : 0;
+    return v > 0 ? v : 0;
+}
+
 extern "C" int bbidx_create(int32_t device, const bbidx_index_desc *d, bbidx_ctx **out) {
     if (!d || !out) return ifail(BBMAP_E_ARG, "bbidx_create: null argument");
     *out = nullptr;
@@ -786,6 +792,7 @@ extern "C" int bbidx_create(int32_t device, const bbidx_index_desc *d, bbidx_ctx
     c->kernelKind = BBIDX_KERNEL_AUTO;
     c->blocks = prop.multiProcessorCount * 8;
     c->totalSites = 0; c->maxReadLen = BBIDX_MAX_READ_LEN;
+    c->maxGroups = bbidx_env_max_groups();
     for (int b = 0; b < d->nblocks; b++) c->totalSites += (long long)d->numSites[b];
     const size_t keyspace = (size_t)1 << (2 * p.k);
     int rc = BBMAP_OK;
@@ -850,6 +857,9 @@ int bbidx_find_batch_device_with(bbidx_ctx *c, bbidx_launch *ls, void *stream_, 
     P.rcOut = bases_rc_out;
     long long blocks = (n + 63) / 64;
     if (blocks > c->blocks) blocks = c->blocks;
+    if (c->maxGroups > 0 && blocks > c->maxGroups) blocks = c->maxGroups;
+    ls->waveGroups = ls->lastLaneGroups = ls->lastLongGroups = 0;
+    ls->waveLongLists = ls->waveShort = ls->longMaxLen = ls->longMaxKeys = 0;
     IHIP(hipEventRecord(ls->ev[0], stream));
     if (c->dev.p.profile == BBIDX_PROFILE_PACBIO || c->kernelKind == BBIDX_KERNEL_LONG) {
         // mapPacBio's reads (thousands of bases, hundreds of keys), or the long-read kernel asked for by name
@@ -859,7 +869,8 @@ int bbidx_find_batch_device_with(bbidx_ctx *c, bbidx_launch *ls, void *stream_, 
             if (ls->longBlocks < 1) return ifail(BBMAP_E_HIP, "bbidx_find_batch_device: the long-read kernel does not fit this device");
             IHIP(hipMalloc(&ls->d_longWs, (size_t)ls->longBlocks * (size_t)bbidx_long_workspace_ints_per_block() * 4));
         }
-        const int rc = bbidx_launch_long(P, stream, c->dev.p.profile == BBIDX_PROFILE_PACBIO ? 1 : 0, ls->d_longWs, ls->longBlocks);
+        const int rc = bbidx_launch_long(P, stream, c->dev.p.profile == BBIDX_PROFILE_PACBIO ? 1 : 0, ls->d_longWs, ls->longBlocks,
+                                         c->maxGroups, ls);
         if (rc != BBMAP_OK) return rc;
         IHIP(hipEventRecord(ls->ev[1], stream));
         ls->timed = true;
@@ -871,12 +882,15 @@ int bbidx_find_batch_device_with(bbidx_ctx *c, bbidx_launch *ls, void *stream_, 
         // below that (small genomes) the plain variant, which is a few per cent faster there
         bool longLists = c->totalSites * 2 >= (1LL << (2 * c->dev.p.k)) * (long long)c->dev.nblocks;
         if (const char *ev = getenv("BBIDX_LONG_LISTS")) { if (*ev) longLists = atoi(ev) != 0; }      // tests force either variant
-        const int rc = bbidx_launch_wave(P, stream, longLists, c->maxReadLen);
+        bool shortReads = false;
+        const int rc = bbidx_launch_wave(P, stream, longLists, c->maxReadLen, c->maxGroups, &ls->waveGroups, &shortReads);
         if (rc != BBMAP_OK) return rc;
+        ls->waveLongLists = longLists ? 1 : 0; ls->waveShort = shortReads ? 1 : 0;
         P.onlyPending = 1;
     }
     hipLaunchKernelGGL(bbidx::probe_kernel, dim3((unsigned)blocks), dim3(64), 0, stream, P);
     IHIP(hipGetLastError());
+    ls->lastLaneGroups = blocks;
     IHIP(hipEventRecord(ls->ev[1], stream));
     ls->timed = true;
     return BBMAP_OK;
@@ -947,6 +961,22 @@ int bbidx_last_stats_with(bbidx_ctx *c, bbidx_launch *ls, int64_t *stats5, float
         for (int j = 0; j < 5; j++) stats5[j] = 0;
         for (int s = 0; s < bbidx::STAT_SHARDS; s++) for (int j = 0; j < 5; j++) stats5[j] += (int64_t)h[(size_t)s * 8 + j];
     }
+    return BBMAP_OK;
+}
+
+// What the last bbidx_find_batch_device launch ran (waits for it): launch8 = {wave-kernel groups, long-list variant (0/1),
+// short-read instantiation (0/1), reads the wave kernel left to the per-lane kernel (queue[1]), per-lane kernel groups,
+// long-read kernel groups, the long kernel's maxLen, its maxKeys}; 0 for a kernel that did not run.
+extern "C" int bbidx_last_launch(bbidx_ctx *c, int64_t *launch8) {
+    if (!c || !launch8) return ifail(BBMAP_E_ARG, "bbidx_last_launch: null argument");
+    bbidx_launch *ls = &c->own;
+    if (!ls->timed) return ifail(BBMAP_E_ARG, "bbidx_last_launch: nothing launched yet");
+    IHIP(hipSetDevice(c->device));
+    IHIP(hipEventSynchronize(ls->ev[1]));
+    unsigned int pending = 0;
+    if (ls->waveGroups > 0) IHIP(hipMemcpy(&pending, ls->d_queue + 1, sizeof pending, hipMemcpyDeviceToHost));
+    launch8[0] = ls->waveGroups; launch8[1] = ls->waveLongLists; launch8[2] = ls->waveShort; launch8[3] = pending;
+    launch8[4] = ls->lastLaneGroups; launch8[5] = ls->lastLongGroups; launch8[6] = ls->longMaxLen; launch8[7] = ls->longMaxKeys;
     return BBMAP_OK;
 }
 

@@ -31,6 +31,7 @@
 
 #include "bbmap_amd.h"
 #include "index_common.h"
+#include "index_ctx.h"
 #include "wave_prims.h"
 
 void bbmap_set_error(const char *msg);
@@ -1212,7 +1213,7 @@ static int long_cus(int profile) {                     // of the CURRENT device 
 // blocks the workspace has to be sized for: the most any launch uses
 int bbidx_long_blocks(int profile) { return long_cus(profile) * LONG_MAX_BLOCKS_PER_CU; }
 
-int bbidx_launch_long(const bbidx::Params &P, hipStream_t stream, int profile, int *ws, int blocks) {
+int bbidx_launch_long(const bbidx::Params &P, hipStream_t stream, int profile, int *ws, int blocks, int maxGroups, bbidx_launch *ls) {
     static thread_local char msg[256];
     // the batch's maxima size the LDS layout, and with it the number of resident wavefronts (one host round trip; the kernel runs
     // for milliseconds per read)
@@ -1240,7 +1241,9 @@ int bbidx_launch_long(const bbidx::Params &P, hipStream_t stream, int profile, i
     long long nb = (long long)(cus > 0 ? cus : 256) * per;
     if (nb > blocks) nb = blocks;
     if (nb > P.nreads) nb = P.nreads;
+    if (maxGroups > 0 && nb > maxGroups) nb = maxGroups;
     if (nb < 1) nb = 1;
+    ls->lastLongGroups = nb; ls->longMaxLen = Q.maxLen; ls->longMaxKeys = Q.maxKeys;
     if (profile) hipLaunchKernelGGL(bbidxl::probe_long_kernel<bbidxl::ProfPacBio>, dim3((unsigned)nb), dim3(64), lds, stream, Q);
     else hipLaunchKernelGGL(bbidxl::probe_long_kernel<bbidxl::ProfBBMap>, dim3((unsigned)nb), dim3(64), lds, stream, Q);
     const hipError_t e = hipGetLastError();

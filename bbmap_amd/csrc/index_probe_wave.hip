@@ -1630,7 +1630,8 @@ template <bool LONG, int WLEN> __global__ __launch_bounds__(64 * WAVES_PER_BLOCK
 
 }  // namespace bbidxw
 
-int bbidx_launch_wave(const bbidx::Params &P, hipStream_t stream, bool longLists, int maxReadLen) {
+int bbidx_launch_wave(const bbidx::Params &P, hipStream_t stream, bool longLists, int maxReadLen, int maxGroups, long long *groups,
+                      bool *shortReadsOut) {
     using namespace bbidxw;
     const bool shortReads = maxReadLen <= WSHORTLEN;
     // as many blocks as fit the device at once; they pull reads from a queue (Params.queue[2])
@@ -1648,6 +1649,8 @@ int bbidx_launch_wave(const bbidx::Params &P, hipStream_t stream, bool longLists
     }
     long long blocks = (P.nreads + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     if (blocks > (long long)numCUs * perCU[variant]) blocks = (long long)numCUs * perCU[variant];
+    if (maxGroups > 0 && blocks > maxGroups) blocks = maxGroups;
+    *groups = blocks; *shortReadsOut = shortReads;
     const dim3 g((unsigned)blocks), b(64 * WAVES_PER_BLOCK);
     if (longLists) {
         if (shortReads) hipLaunchKernelGGL((probe_wave_kernel<true, WSHORTLEN>), g, b, 0, stream, P);

@@ -354,6 +354,8 @@ class DeviceIndex:
         L.bbidx_get_params.restype = C.c_int
         L.bbidx_export_block.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.bbidx_export_block.restype = C.c_int
+        L.bbidx_last_launch.argtypes = [C.c_void_p, C.c_void_p]
+        L.bbidx_last_launch.restype = C.c_int
 
     def __init__(self, host, device=0):
         self.L = _lib.load()
@@ -409,9 +411,8 @@ class DeviceIndex:
         except Exception:
             pass
 
-    def find_batch(self, reads, max_sites=32):
-        """reads: list of (basesP, baseScoresP, keyScoresP, offsets).  Returns list of lists of site dicts
-        (None where the probe reported an overflow / unsupported read)."""
+    @staticmethod
+    def _pack(reads):
         bases, bscores, keyinfo = bytearray(), bytearray(), []
         recs = np.zeros(len(reads), READ_DTYPE)
         for i, (b, bs, ks, of) in enumerate(reads):
@@ -422,13 +423,12 @@ class DeviceIndex:
         bases_a = np.frombuffer(bytes(bases) or b"\0", np.uint8)
         bs_a = np.frombuffer(bytes(bscores) or b"\0", np.int8)
         ki = np.array(keyinfo or [0], np.int32)
-        sites = np.zeros((len(reads), max_sites), SITE_DTYPE)
-        ns = np.zeros(len(reads), np.int32)
-        rc = self.L.bbidx_find_batch(self.h, len(reads), recs.ctypes.data, bases_a.ctypes.data, bs_a.ctypes.data,
-                                     len(bases), ki.ctypes.data, len(keyinfo), sites.ctypes.data, max_sites, ns.ctypes.data)
-        _lib.check(rc, "bbidx_find_batch")
+        return recs, bases_a, bs_a, ki, len(bases), len(keyinfo)
+
+    @staticmethod
+    def _unpack(sites, ns):
         out = []
-        for i in range(len(reads)):
+        for i in range(len(ns)):
             if ns[i] < 0:
                 out.append(None)
                 continue
@@ -437,3 +437,44 @@ class DeviceIndex:
                              semiperfect=int(s["semiperfect"]), gaps=s["gaps"][:s["ngaps"]].tolist())
                         for s in sites[i, :ns[i]]])
         return out
+
+    def find_batch(self, reads, max_sites=32, codes=False):
+        """reads: list of (basesP, baseScoresP, keyScoresP, offsets).  Returns list of lists of site dicts
+        (None where the probe reported an overflow / unsupported read); with codes=True also the raw nsites array
+        (-1 = overflow, -2 = declined), as (lists, nsites)."""
+        recs, bases_a, bs_a, ki, nbases, nki = self._pack(reads)
+        sites = np.zeros((len(reads), max_sites), SITE_DTYPE)
+        ns = np.zeros(len(reads), np.int32)
+        rc = self.L.bbidx_find_batch(self.h, len(reads), recs.ctypes.data, bases_a.ctypes.data, bs_a.ctypes.data,
+                                     nbases, ki.ctypes.data, nki, sites.ctypes.data, max_sites, ns.ctypes.data)
+        _lib.check(rc, "bbidx_find_batch")
+        out = self._unpack(sites, ns)
+        return (out, ns) if codes else out
+
+    def find_batch_rc(self, reads, max_sites=32, sentinel=0xA5, slack=64):
+        """bbidx_find_batch_device_rc on device copies of the batch, with a bases_rc_out buffer filled with `sentinel` (the
+        bases' layout plus `slack` bytes behind it).  Returns (lists, nsites, rc buffer as a host uint8 array)."""
+        import torch
+        recs, bases_a, bs_a, ki, nbases, nki = self._pack(reads)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
+        d_recs, d_bases, d_bs, d_ki = t(recs), t(bases_a), t(bs_a), t(ki)
+        d_sites = torch.zeros(len(reads) * max_sites * SITE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_ns = torch.zeros(len(reads), dtype=torch.int32, device=dev)
+        d_rc = torch.full((max(nbases, 1) + slack,), sentinel, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        rc = self.L.bbidx_find_batch_device_rc(self.h, None, len(reads), d_recs.data_ptr(), d_bases.data_ptr(), d_bs.data_ptr(),
+                                               d_ki.data_ptr(), d_sites.data_ptr(), max_sites, d_ns.data_ptr(), d_rc.data_ptr())
+        _lib.check(rc, "bbidx_find_batch_device_rc")
+        torch.cuda.synchronize()
+        ns = d_ns.cpu().numpy()
+        sites = d_sites.cpu().numpy().view(SITE_DTYPE).reshape(len(reads), max_sites)
+        return self._unpack(sites, ns), ns, d_rc.cpu().numpy()
+
+    def last_launch(self):
+        """bbidx_last_launch: what the last probe launch ran, as a dict (0 for a kernel that did not run)."""
+        v = np.zeros(8, np.int64)
+        _lib.check(self.L.bbidx_last_launch(self.h, v.ctypes.data), "bbidx_last_launch")
+        return dict(zip(("wave_groups", "long_lists", "short_reads", "pending", "lane_groups", "long_groups", "max_len", "max_keys"),
+                        (int(x) for x in v)))
+

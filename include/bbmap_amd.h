@@ -340,15 +340,24 @@ enum { BBIDX_PACBIO_MAX_KEYS = 2047, BBIDX_PACBIO_MAX_READ_LEN = 6016 };   /* BB
 typedef struct bbidx_ctx bbidx_ctx;
 int bbidx_create(int32_t device, const bbidx_index_desc *desc, bbidx_ctx **out);
 void bbidx_destroy(bbidx_ctx *ctx);
-/* Device-resident batch.  sites: n_reads x max_sites records; nsites[i] = sites found for read i, or -1 when
- * max_sites was too small, -2 when the read exceeds BBIDX_MAX_KEYS / BBIDX_MAX_READ_LEN. */
+/* Device-resident batch.  sites: n_reads x max_sites records; nsites[i] = sites found for read i (0 also for a read
+ * shorter than k or without keys), -1 when max_sites was too small, or -2 when the probe declines the read:
+ *  - for its size: more than BBIDX_MAX_KEYS keys or BBIDX_MAX_READ_LEN bases (BBIDX_PROFILE_BBMAP, kernels AUTO and LANE),
+ *    more than BBIDX_PACBIO_MAX_KEYS keys or BBIDX_PACBIO_MAX_READ_LEN bases (BBIDX_PROFILE_PACBIO, and the LONG kernel on
+ *    either profile);
+ *  - the long-read kernel only: key offsets that are not ascending (a later key starts before an earlier one);
+ *  - every kernel: the chromosomes minChrom..maxChrom lie in more than 32 index blocks (the prescan keeps 64 strand
+ *    cycles): with minChrom 1, more than 32 chromosomes at chromBits 0, or 32 << chromBits or more at chromBits >= 1. */
 int bbidx_find_batch_device(bbidx_ctx *ctx, void *stream, int64_t n_reads, const bbidx_read *reads,
                             const uint8_t *bases, const int8_t *baseScores, const int32_t *keyinfo,
                             bbidx_site *sites, int32_t max_sites, int32_t *nsites);
 /* The same, and every probed read's reverse complement (AminoAcid.reverseComplementBases, which the mapper computes once
  * per read as basesM, current/align2/AbstractMapThread.java:643-655) is written to bases_rc_out at the read's offset: the
- * kernel has it in LDS anyway, which saves the separate bbpipe_revcomp_device pass.  Reads without a usable key (nsites 0
- * because len < k or no keys, or -2) are not written. */
+ * kernel has it in LDS anyway, which saves the separate bbpipe_revcomp_device pass.  Every read with nsites >= -1 and at
+ * least k bases and one key is written.  Left untouched: reads shorter than k or without keys, and reads declined (-2) for
+ * their size.  A read declined for its key order or for the 32-block limit may or may not have been written (the kernels
+ * write the reverse complement before those checks); where it is, it is the correct one.  No byte outside the reads'
+ * [bases_off, bases_off + len) ranges is written. */
 int bbidx_find_batch_device_rc(bbidx_ctx *ctx, void *stream, int64_t n_reads, const bbidx_read *reads,
                                const uint8_t *bases, const int8_t *baseScores, const int32_t *keyinfo,
                                bbidx_site *sites, int32_t max_sites, int32_t *nsites, uint8_t *bases_rc_out);
@@ -361,6 +370,12 @@ int bbidx_find_batch(bbidx_ctx *ctx, int64_t n_reads, const bbidx_read *reads,
  * stream has been synchronised.  stats5 = {list entries consumed by the prescan, by the walk, extendScore calls,
  * reference bytes compared, site records written}. */
 int bbidx_last_stats(bbidx_ctx *ctx, int64_t *stats5, float *kernel_ms);
+/* What the last bbidx_find_batch_device launch ran, as the host chose it (waits for the launch): launch8 = {wave-kernel
+ * groups, long-list variant (0/1), short-read instantiation (0/1), reads the wave kernel left to the per-lane kernel,
+ * per-lane kernel groups, long-read kernel groups, the long kernel's LDS layout maxLen, its maxKeys}; 0 for a kernel that
+ * did not run.  The environment variable BBIDX_MAX_GROUPS (read when a context is created; unset or 0 = no cap) clamps
+ * every probe launch's grid, the mapper's included, so that each wavefront or lane probes many reads in turn. */
+int bbidx_last_launch(bbidx_ctx *ctx, int64_t *launch8);
 
 /* Index construction on the device: align2.IndexMaker4 (current/align2/IndexMaker4.java:303-421: count -> prefix sum ->
  * fill, lists in genome order) + BBIndex.analyzeIndex (current/align2/BBIndex.java:101-191: COUNTS, clumpy keys, length

@@ -108,6 +108,13 @@ def test_paired_matches_oracle_with_rescue(monkeypatch):
     assert st["dp_narrow_launches"] == 0 and st["dp_sorted_launches"] == 0, st
 
 
+def test_paired_matches_oracle_with_rescue_at_two_probe_groups(monkeypatch):
+    """BBIDX_MAX_GROUPS = 2: the mapper's probe runs on two wave-kernel groups and two per-lane groups, so every wave and lane
+    probes many reads in turn; nothing may change."""
+    monkeypatch.setenv("BBIDX_MAX_GROUPS", "2")
+    _paired(monkeypatch, "latency")
+
+
 def test_paired_matches_oracle_with_rescue_on_the_throughput_route(monkeypatch):
     st = _paired(monkeypatch, "throughput")
     assert st["dp_narrow_launches"] > 0, st                          # the route really ran

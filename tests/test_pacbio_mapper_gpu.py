@@ -31,6 +31,16 @@ def _run(chroms, pieces, msa_rows, msa_cols, threads=4, max_sites=32):
 
 
 def test_pacbio_pieces_match_the_oracle():
+    _pieces_match_the_oracle()
+
+
+def test_pacbio_pieces_match_the_oracle_at_two_probe_groups(monkeypatch):
+    """BBIDX_MAX_GROUPS = 2: two long-kernel wavefronts probe all 55 pieces in turn; nothing may change."""
+    monkeypatch.setenv("BBIDX_MAX_GROUPS", "2")
+    _pieces_match_the_oracle()
+
+
+def _pieces_match_the_oracle():
     chroms = [W.make_reference(300000, seed=81, pad=3000, repeat_frac=0.1, families=60), W.make_reference(200000, seed=82, pad=3000)]
     pieces, truth = W.make_pacbio_pieces(chroms, 48, seed=3, min_len=300, max_len=2600, pad=3000, junk_frac=0.1)
     # a few nearly clean pieces (perfect / semiperfect handling) and one shorter than k
