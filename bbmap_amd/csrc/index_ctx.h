@@ -6,6 +6,7 @@
 
 #include "bbmap_amd.h"
 #include "index_common.h"
+#include "scaffold.h"
 
 // What ONE probe launch writes besides its outputs: the persistent waves' work queue, the work counters, the two timing events and
 // the long-read kernel's per-wave workspace.  The index itself (bbidx_ctx::dev) is read-only once built, so any number of launches
@@ -35,6 +36,12 @@ struct bbidx_ctx {
     long long totalSites; // list entries over all blocks (picks the wave kernel's long-list variant)
     int maxReadLen;       // bbidx_set_max_read_len: picks the wave kernel's LDS sizing (default BBIDX_MAX_READ_LEN)
     int maxGroups;        // BBIDX_MAX_GROUPS at creation: every probe launch's grid is clamped to it (0 = no cap; tests run many reads per wave)
+    // bbidx_set_scaffolds (scaffold_table.hip): the scaffold table every mapper over this index reads from its next batch on.
+    // scaf.off == nullptr: no table.  scafFilter: some chromosome holds two or more scaffolds (else isSingleScaffold is true everywhere
+    // and the mapper's filter stays off).  scafBuf owns off / loc / len.
+    bbscaf::Table scaf = {};
+    bool scafFilter = false;
+    void *scafBuf = nullptr;
 };
 
 // BBIDX_MAX_GROUPS, read once per context (bbidx_create / bbidx_build): unset or 0 = no cap

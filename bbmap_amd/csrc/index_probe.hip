@@ -821,6 +821,7 @@ extern "C" void bbidx_destroy(bbidx_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     for (void *p : c->allocs) (void)hipFree(p);
+    if (c->scafBuf) (void)hipFree(c->scafBuf);
     bbidx_launch_free(&c->own);
     delete c;
 }

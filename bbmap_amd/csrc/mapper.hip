@@ -30,6 +30,7 @@
 
 #include "bbmap_amd.h"
 #include "index_ctx.h"
+#include "scaffold.h"
 
 void bbmap_set_error(const char *msg);
 void bbmsa_use_narrow(bbmsa_ctx *c, bool on);          // msa_host.hip (internal, see msa_ctx.h)
@@ -113,7 +114,8 @@ struct Dev {
     struct FinalRead *fin; bbmap_final *finalOut;
     uint8_t *pool; long long poolUnits;         // match strings: bump-allocated in 4-byte units, counters[20] = units in use
     const uint8_t *match, *gmatch; int matchStride, gmatchStride;
-                                // counters: [20] pool units handed out (beyond the capacity once a request failed), [21] units in use when the first
+    bbscaf::Table scaf;         // the index's scaffold table when it has a chromosome of two or more scaffolds, else off == nullptr
+                                // counters: [9] sites quickMap's tail removed for spanning two scaffolds, [20] pool units handed out (beyond the capacity once a request failed), [21] units in use when the first
                                 // request failed, [22] requests that failed, [24] reads that need toLocalAlignment, [25] pool units those may take
 };
 
@@ -481,8 +483,10 @@ __device__ int remove_low_quality_paired(Site *s, int n, int maxSw, float multSi
 }
 
 // ---------------------------------------------------------------------------------------------- stage 1: begin
-// quickMap's tail for one read: probe records -> SiteScores, removeOutOfBounds (AbstractMapThread.java:2444-2476)
-__device__ int load_sites(const Dev &D, long long r, Site *s) {
+// quickMap's tail for one read: probe records -> SiteScores, removeOutOfBounds (AbstractMapThread.java:2444-2476).  SCAF: a scaffold
+// table is set, and a site that spans two scaffolds goes too (the SAM_OUT branch, Data.isSingleScaffold); `dropped` counts those.
+template <bool SCAF>
+__device__ int load_sites_t(const Dev &D, long long r, Site *s, int &dropped) {
     const int ns = D.pnsites[r];
     if (ns < 0) return -1;                                 // the probe ran out of room (or declined the read): reported, not mapped
     const bbidx_site *ps = D.psites + r * (long long)D.maxSites;
@@ -498,10 +502,23 @@ __device__ int load_sites(const Dev &D, long long r, Site *s) {
         ss.match_job = -1; ss.reserved[0] = ss.reserved[1] = 0;
         const int mx = D.chromArrLen[ss.chrom] - 1;
         if (ss.start < 0 || ss.stop > mx) continue;
+        if (SCAF && !bbscaf::is_single_scaffold(D.scaf, ss.chrom, ss.start, ss.stop)) { dropped++; continue; }
         if (calc_gref_len(ss) >= D.S.expLimit) { set_stop(ss, ss.start + imin(len + 40, D.S.expLimit)); if (ss.ngaps) fix_gaps(ss); }
         s[n++] = ss;
     }
     return n;
+}
+// (a uniform branch on the kernel argument: without a table the instantiation is the plain removeOutOfBounds)
+__device__ inline int load_sites(const Dev &D, long long r, Site *s, int &dropped) {
+    return D.scaf.off ? load_sites_t<true>(D, r, s, dropped) : load_sites_t<false>(D, r, s, dropped);
+}
+// One atomic per wavefront for a per-lane count (any set of active lanes; the lanes of `m` are active, so the shuffles read live values).
+__device__ inline void wave_add(unsigned *ctr, int v) {
+    const unsigned long long m = __ballot(v != 0);
+    if (!m) return;
+    unsigned tot = 0;
+    for (unsigned long long b = m; b; b &= b - 1) tot += (unsigned)__shfl(v, __builtin_ctzll(b));
+    if ((int)(threadIdx.x & 63) == __builtin_ctzll(m)) atomicAdd(ctr, tot);
 }
 
 // pairSiteScoresInitial (BBMapThread.java:736-940); REQUIRE_CORRECT_STRANDS_PAIRS = true, SAME_STRAND_PAIRS = false
@@ -558,12 +575,14 @@ __global__ __launch_bounds__(128) void begin_kernel(const Dev D) {
         if (2 * u + 1 >= D.nreads) return;
         const long long r1 = 2 * u, r2 = r1 + 1;
         Site *s1 = D.ms + r1 * D.cap, *s2 = D.ms + r2 * D.cap;
-        int n1 = load_sites(D, r1, s1), n2 = load_sites(D, r2, s2);
+        int drop1 = 0, drop2 = 0;
+        int n1 = load_sites(D, r1, s1, drop1), n2 = load_sites(D, r2, s2, drop2);
         if (n1 < 0 || n2 < 0) {                            // one mate's probe overflowed: the pair is reported, not mapped
             atomicAdd(&D.counters[3], (unsigned)((n1 < 0) + (n2 < 0)));
             D.mcount[r1] = n1 < 0 ? -1 : -2; D.mcount[r2] = n2 < 0 ? -1 : -2;
-            return;
+            return;                                        // (the overflow tier maps the pair again and counts its removals there)
         }
+        if (D.scaf.off) wave_add(&D.counters[9], drop1 + drop2);
         const int len1 = D.reads[r1].len, len2 = D.reads[r2].len;
         pair_initial(D.S, s1, n1, s2, n2, len1, len2);
         if (D.S.trimList) {
@@ -580,8 +599,10 @@ __global__ __launch_bounds__(128) void begin_kernel(const Dev D) {
     } else {
         if (u >= D.nreads) return;
         Site *s = D.ms + u * D.cap;
-        int n = load_sites(D, u, s);
+        int drop = 0;
+        int n = load_sites(D, u, s, drop);
         if (n < 0) { atomicAdd(&D.counters[3], 1u); D.mcount[u] = -1; return; }
+        if (D.scaf.off) wave_add(&D.counters[9], drop);
         if (D.S.trimList && n > 1) {
             sort_sites<false>(s, n);
             trim_list(s, n, false, max_quality(D.S, D.reads[u].len), true, MIN_TRIM_SINGLE, D.S.maxTrimSitesToRetain);
@@ -1036,6 +1057,124 @@ __global__ __launch_bounds__(256) void pack_sites_kernel(const Site *ms, const i
 
 struct ToLL { __host__ __device__ long long operator()(int x) const { return (long long)x; } };
 
+// ---------------------------------------------------------------------------------------------- scaffold coordinates (on demand)
+// SamLine's coordinate block (current/stream/SamLine.java:120-187) over the final records, bbmap_get_scaffold_records.  One
+// wavefront per read, or per pair (the mates unpair each other); every value below is wave-uniform.
+struct ScafMate { int mapped, single, gscaf, a1, b1, scaflen, pos0, pos1; };
+
+__device__ ScafMate scaf_mate(const bbscaf::Table &T, const bbmap_final &f, const uint8_t *m) {
+    const int lane = threadIdx.x & 63;
+    ScafMate o;
+    o.mapped = f.mapped != 0; o.single = 1; o.gscaf = -1; o.a1 = o.b1 = o.scaflen = o.pos0 = o.pos1 = 0;
+    const int chrom = f.chrom;
+    if (!o.mapped || chrom < 1 || chrom > T.nchroms) { o.mapped = 0; return o; }
+    const int start = f.start, stop = f.stop;
+    const int b = T.off[chrom], n = T.off[chrom + 1] - b;
+    const int *a = T.loc + b;
+    if (n >= 2) {                                           // Data.isSingleScaffold (Data.java:1112-1140)
+        const int scaf = bbscaf::wave_last_at_or_below(a, n, start + T.pad);
+        if (scaf != n - 1) {
+            const int lowerBound = a[scaf] - T.pad, upperBound = a[scaf + 1];
+            o.single = !(stop < lowerBound || start > upperBound) && stop < upperBound;
+        }
+    }
+    if (!o.single) { o.mapped = 0; return o; }              // :134-140 / :154-160: r.setMapped(false)
+    const int idx = n < 2 ? 0 : bbscaf::wave_last_at_or_below(a, n, (start + stop) / 2 + T.pad / 2);    // Data.scaffoldIndex
+    o.gscaf = b + idx; o.scaflen = T.len[b + idx];
+    o.a1 = start - a[idx];                                  // scaffoldRelativeLoc
+    o.b1 = o.a1 - start + stop;
+    // the match string is in long format (one symbol per column, no digits), 64 symbols per ballot
+    const int ml = f.match_len > 0 ? f.match_len : 0;
+    int clip = 0, tclip = 0, clippedIndels = 0;
+    if (ml > 0 && m[0] == 'C') {                            // countLeadingClip (:924-945)
+        for (int base = 0; base < ml; base += 64) {
+            const int i = base + lane;
+            const unsigned long long x = __ballot(i < ml && m[i] != 'C');
+            if (x) { clip += __builtin_ctzll(x); break; }
+            clip += min(64, ml - base);
+        }
+    }
+    for (int end = ml; end > 0; end -= 64) {                // countTrailingClip (:959-972)
+        const int i = end - 1 - lane;
+        const unsigned long long x = __ballot(i >= 0 && m[i] != 'C');
+        if (x) { tclip += __builtin_ctzll(x); break; }
+        tclip += min(64, end);
+    }
+    if (o.a1 < 0) {                                         // countLeadingIndels (:975-996): walk until rloc reaches 0
+        int rloc = o.a1, dels = 0, inss = 0;
+        for (int base = 0; base < ml && rloc < 0; base += 64) {
+            const int i = base + lane;
+            const bool v = i < ml;
+            const uint8_t ch = v ? m[i] : 0;
+            const unsigned long long adv = __ballot(v && ch != 'I');             // symbols that move rloc
+            const bool inc = v && __popcll(adv & ((1ull << lane) - 1)) < -rloc;  // rloc < 0 still holds when the loop reaches it
+            dels += __popcll(__ballot(inc && ch == 'D'));
+            inss += __popcll(__ballot(inc && ch == 'I'));
+            rloc += __popcll(__ballot(inc && ch != 'I'));
+        }
+        clippedIndels = dels - inss;
+    }
+    // countTrailingIndels(b1, scaflen, match) (:999-1020) returns 0 whenever b1 >= 0, and for b1 < 0 its loop condition
+    // rloc >= rlen is false at once: it is 0 for every record.
+    o.pos0 = (o.a1 + 1) + clip + clippedIndels;
+    o.pos1 = (o.b1 + 1) - tclip;
+    if (o.pos1 > o.scaflen) o.pos1 = o.scaflen;
+    if (o.pos0 < 1) o.pos0 = 1;
+    return o;
+}
+
+__device__ inline void put_scafrec(bbmap_scafrec *out, const ScafMate &q, int paired, int sameScaf) {
+    bbmap_scafrec w;
+    w.scaffold = q.mapped ? q.gscaf : -1;
+    w.start = q.a1; w.stop = q.b1; w.pos = q.pos0; w.end = q.pos1; w.scaflen = q.scaflen;
+    const int inbounds = q.mapped && q.a1 >= 0 && q.b1 < q.scaflen;         // :267-268
+    w.flags = (q.mapped ? BBMAP_SCAF_MAPPED : 0) | (paired ? BBMAP_SCAF_PAIRED : 0) | (inbounds ? BBMAP_SCAF_INBOUNDS : 0) |
+              (sameScaf ? BBMAP_SCAF_SAME_SCAFFOLD : 0);
+    w.reserved = 0;
+    *out = w;
+}
+
+// a read the overflow tier mapped takes the tier's record (as bbmap_get_final does)
+__device__ inline const bbmap_final *scaf_source(const bbmap_final *fin, const uint8_t *pool, const bbmap_final *tfin, const uint8_t *tpool,
+                                                 const int *tierIdx, long long r, const uint8_t *&m) {
+    const bbmap_final *f = fin + r;
+    const uint8_t *pl = pool;
+    if (tierIdx && f->nsites == BBMAP_NSITES_IN_TIER && tierIdx[r] >= 0) { f = tfin + tierIdx[r]; pl = tpool; }
+    m = f->match_len > 0 ? pl + f->match_off : nullptr;
+    return f;
+}
+
+__global__ __launch_bounds__(256) void scaffold_coords_kernel(const bbscaf::Table T, const bbmap_final *fin, const uint8_t *pool,
+                                                              const bbmap_final *tfin, const uint8_t *tpool, const int *tierIdx,
+                                                              long long units, int paired, bbmap_scafrec *out) {
+    const long long u = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (u >= units) return;
+    const bool lead = (threadIdx.x & 63) == 0;
+    if (!paired) {
+        const uint8_t *m;
+        const bbmap_final *f = scaf_source(fin, pool, tfin, tpool, tierIdx, u, m);
+        const ScafMate q = scaf_mate(T, *f, m);
+        if (lead) put_scafrec(out + u, q, f->paired != 0, 0);
+        return;
+    }
+    const uint8_t *m1, *m2;
+    const bbmap_final *f1 = scaf_source(fin, pool, tfin, tpool, tierIdx, 2 * u, m1);
+    const bbmap_final *f2 = scaf_source(fin, pool, tfin, tpool, tierIdx, 2 * u + 1, m2);
+    const ScafMate q1 = scaf_mate(T, *f1, m1), q2 = scaf_mate(T, *f2, m2);
+    const bool both = q1.single && q2.single;               // a mate that spans two scaffolds unpairs the other (:137-138, :157-158)
+    const int same = q1.mapped && q2.mapped && q1.gscaf == q2.gscaf;       // sameScaf (:160): idx1 == idx2 on the same chromosome
+    if (lead) {
+        put_scafrec(out + 2 * u, q1, both && f1->paired != 0, same);
+        put_scafrec(out + 2 * u + 1, q2, both && f2->paired != 0, same);
+    }
+}
+__global__ __launch_bounds__(256) void tier_index_kernel(const int *ids, long long n, long long nreads, int *tierIdx) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int r = ids[i];
+    if (r >= 0 && r < nreads) tierIdx[r] = (int)i;
+}
+
 }  // namespace bbmapper
 
 // ================================================================================================= host side
@@ -1087,6 +1226,9 @@ struct bbmap_ctx {
     struct BatchArgs { int64_t n_reads; const bbidx_read *reads; uint8_t *bases; int64_t minus_delta; const int8_t *baseScores; const int32_t *keyinfo; } batch;
     // bbmap_map_batch (host buffers in, packed site lists out): device copies the context keeps between calls, grown on demand
     struct HostIO { void *p[7]; size_t cap[7]; } hio;      // reads, bases (both strands), base scores, keyinfo, counts, offsets, packed
+    // bbmap_get_scaffold_records: its output (max_reads records) and the read -> overflow-tier record map, allocated on first use
+    bbmap_scafrec *d_scafRec = nullptr;
+    int *d_scafTier = nullptr;
 };
 
 static thread_local char g_merr[320];
@@ -1521,6 +1663,7 @@ static void fill_dev(bbmap_ctx *c, bbmapper::Dev &D, int64_t n_reads, const bbid
     D.jobs = c->d_jobs; D.jinfo = c->d_jinfo; D.results = c->d_results; D.jobCap = c->jobCap;
     D.gjobs = c->d_gjobs; D.ggaps = c->d_ggaps; D.ginfo = c->d_ginfo; D.gresults = c->d_gresults; D.gjobCap = c->gjobCap;
     D.rjobs = c->d_rjobs; D.rinfo = c->d_rinfo; D.rres = c->d_rres; D.pres = c->d_pres; D.rescCap = c->rescCap; D.rsite = c->d_rsite;
+    if (c->index->scafFilter) D.scaf = c->index->scaf;
 }
 
 // one context's pass over `n_reads` read records
@@ -1635,6 +1778,7 @@ static int map_records(bbmap_ctx *c, hipStream_t stream, int64_t n_reads, const 
     bbmap_stats &st = c->stats;
     st.reads_overflowed = c->h_counters[3]; st.reads_without_site = c->h_counters[5];
     st.fills = c->nJobs; st.gapped_fills = c->nGapped; st.refills = c->h_counters[6]; st.rescue_fills = c->h_counters[7]; st.fills_dropped = c->h_counters[8];
+    st.sites_cross_scaffold = c->h_counters[9];
     (void)hipEventElapsedTime(&st.ms_probe, c->ev[0], c->ev[1]);
     (void)hipEventElapsedTime(&st.ms_begin, c->ev[1], c->ev[2]);
     (void)hipEventElapsedTime(&st.ms_score, c->ev[2], c->ev[3]);
@@ -1706,6 +1850,7 @@ static int tier_finish(bbmap_ctx *c, hipStream_t stream) {
     st.rescue_fills += ts.rescue_fills; st.fills_dropped += ts.fills_dropped;
     st.final_fills += ts.final_fills; st.final_local += ts.final_local;
     st.dp_narrow_launches += ts.dp_narrow_launches; st.dp_sorted_launches += ts.dp_sorted_launches;
+    st.sites_cross_scaffold += ts.sites_cross_scaffold;
     if (getenv("BBMAP_TIER_DEBUG"))
         fprintf(stderr, "[bbmap tier] reads %lld: probe %.2f begin %.2f score %.2f slow %.2f (rounds %lld) finish %.2f rescue %.2f total %.2f\n",
                 tn, ts.ms_probe, ts.ms_begin, ts.ms_score, ts.ms_slow, (long long)ts.rounds, ts.ms_finish, ts.ms_rescue, ts.ms_total);
@@ -1976,6 +2121,35 @@ extern "C" int bbmap_get_final(bbmap_ctx *c, int64_t n_reads, bbmap_final *out, 
         f.match_off = used; used += f.match_len;
     }
     if (match_bytes) *match_bytes = used;
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_get_scaffold_records(bbmap_ctx *c, void *stream_, const bbmap_scafrec **out) {
+    if (!c || !out) return mfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: null argument");
+    if (!c->S.finalStage) return mfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: the context runs without the final stage (bbmap_config.finalStage)");
+    if (!c->ran) return mfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: no batch has been mapped yet");
+    const bbscaf::Table T = c->index->scaf;
+    if (!T.off) return mfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: the index has no scaffold table (bbidx_set_scaffolds)");
+    MHIP(hipSetDevice(c->cfg.device));
+    hipStream_t stream = (hipStream_t)stream_;
+    const long long n = c->stats.reads;
+    if (!c->d_scafRec) {
+        MTRY(dalloc(c, &c->d_scafRec, (size_t)c->cfg.max_reads));
+        MTRY(dalloc(c, &c->d_scafTier, (size_t)c->cfg.max_reads));
+    }
+    const int *tierIdx = nullptr; const bbmap_final *tfin = nullptr; const uint8_t *tpool = nullptr;
+    if (c->tier && c->tierReads > 0 && c->tier->ran && n > 0) {
+        MHIP(hipMemsetAsync(c->d_scafTier, 0xff, (size_t)n * 4, stream));
+        hipLaunchKernelGGL(bbmapper::tier_index_kernel, dim3((unsigned)((c->tierReads + 255) / 256)), dim3(256), 0, stream, c->d_tierReadIds,
+                           c->tierReads, n, c->d_scafTier);
+        tierIdx = c->d_scafTier; tfin = c->tier->d_final; tpool = c->tier->d_pool;
+    }
+    const long long units = c->cfg.paired ? n / 2 : n;
+    if (units > 0)
+        hipLaunchKernelGGL(bbmapper::scaffold_coords_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, stream, T, c->d_final, c->d_pool,
+                           tfin, tpool, tierIdx, units, c->cfg.paired, c->d_scafRec);
+    MHIP(hipGetLastError());
+    *out = c->d_scafRec;
     return BBMAP_OK;
 }
 

@@ -394,6 +394,27 @@ class DeviceIndex:
         long-read kernel: up to 6016 bases and 2047 keys per read; what a PROFILE_PACBIO index always runs)."""
         _lib.check(self.L.bbidx_set_kernel(self.h, {"auto": 0, "lane": 1, "long": 2}[kind]), "bbidx_set_kernel")
 
+    def set_scaffolds(self, packed):
+        """bbidx_set_scaffolds: the scaffold table of a bbmap_amd.reference.Packed (or anything with per-chromosome `locs`,
+        `lengths`, optional `names` and `inter_scaffold_padding`); None clears it.  Every Mapper over this index uses it from its
+        next step on."""
+        L = self.L
+        L.bbidx_set_scaffolds.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+        L.bbidx_set_scaffolds.restype = C.c_int
+        if packed is None:
+            _lib.check(L.bbidx_set_scaffolds(self.h, self.host.nchroms, None, None, None, 0), "bbidx_set_scaffolds")
+            self.scaffold_names = None
+            return
+        locs = [np.ascontiguousarray(a, np.int32) for a in packed.locs]
+        lens = [np.ascontiguousarray(a, np.int32) for a in packed.lengths]
+        counts = np.array([0] + [len(a) for a in locs], np.int32)
+        lp = (C.c_void_p * (len(locs) + 1))(*([0] + [a.ctypes.data if len(a) else 0 for a in locs]))
+        ln = (C.c_void_p * (len(lens) + 1))(*([0] + [a.ctypes.data if len(a) else 0 for a in lens]))
+        _lib.check(L.bbidx_set_scaffolds(self.h, len(locs), counts.ctypes.data, lp, ln, int(packed.inter_scaffold_padding)),
+                   "bbidx_set_scaffolds")
+        names = getattr(packed, "names", None)
+        self.scaffold_names = [n for ns in names for n in ns] if names is not None else None
+
     def set_max_read_len(self, max_len):
         """Sizing hint for the wavefront kernel (reads of at most 160 bases: 8 waves per SIMD instead of 6)."""
         self.L.bbidx_set_max_read_len.argtypes = [C.c_void_p, C.c_int32]

@@ -18,7 +18,11 @@ JOBINFO_DTYPE = np.dtype([("read", "<i4"), ("seq", "<i4"), ("kind", "<i4"), ("si
 FINAL_DTYPE = np.dtype([("mapped", "<i4"), ("chrom", "<i4"), ("strand", "<i4"), ("start", "<i4"), ("stop", "<i4"), ("mapScore", "<i4"),
                         ("paired", "<i4"), ("ambiguous", "<i4"), ("perfect", "<i4"), ("rescued", "<i4"), ("match_len", "<i4"),
                         ("nsites", "<i4"), ("match_off", "<i8"), ("reserved", "<i4", (2,))])
-assert MSITE_DTYPE.itemsize == 128 and FINAL_DTYPE.itemsize == 64
+# bbmap_scafrec: SamLine's scaffold coordinates of a final record (bbmap_get_scaffold_records); flags = SCAF_* bits
+SCAFREC_DTYPE = np.dtype([("scaffold", "<i4"), ("start", "<i4"), ("stop", "<i4"), ("pos", "<i4"), ("end", "<i4"), ("scaflen", "<i4"),
+                          ("flags", "<i4"), ("reserved", "<i4")])
+SCAF_MAPPED, SCAF_PAIRED, SCAF_INBOUNDS, SCAF_SAME_SCAFFOLD = 1, 2, 4, 8
+assert MSITE_DTYPE.itemsize == 128 and FINAL_DTYPE.itemsize == 64 and SCAFREC_DTYPE.itemsize == 32
 GAPPED_BIT = 1 << 30
 
 
@@ -46,7 +50,8 @@ class bbmap_stats(C.Structure):
                                          "ms_dp_narrow", "ms_dp_wave", "ms_dp_generic", "ms_dp_gapped", "ms_quick_rescue")] + \
                [("probe_stats", C.c_int64 * 5), ("reads_reprobed", C.c_int64), ("ms_overflow", C.c_float), ("log_growths", C.c_float),
                 ("ms_dp_wave_max", C.c_float), ("ms_final", C.c_float), ("final_fills", C.c_int64), ("final_rounds", C.c_int64),
-                ("final_local", C.c_int64), ("dp_narrow_launches", C.c_int64), ("dp_sorted_launches", C.c_int64)]
+                ("final_local", C.c_int64), ("dp_narrow_launches", C.c_int64), ("dp_sorted_launches", C.c_int64),
+                ("sites_cross_scaffold", C.c_int64)]
 
 
 class bbmap_overflow_output(C.Structure):
@@ -76,6 +81,8 @@ def _bind(L):
     L.bbmap_get_final.restype = C.c_int
     L.bbmap_set_average_pair_dist.argtypes = [C.c_void_p, C.c_int32]
     L.bbmap_set_average_pair_dist.restype = C.c_int
+    L.bbmap_get_scaffold_records.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.bbmap_get_scaffold_records.restype = C.c_int
     for f in ("bbmap_default_config", "bbmap_create", "bbmap_map_batch_device", "bbmap_get_output", "bbmap_last_stats",
               "bbmap_get_overflow_output"):
         getattr(L, f).restype = C.c_int
@@ -223,6 +230,17 @@ class Mapper:
         self.L.bbmap_final_batch_device.restype = C.c_int
         _lib.check(self.L.bbmap_final_batch_device(self.h, C.c_void_p(stream), self.n, self.reads.data_ptr(), self.bases.data_ptr(),
                                                    self.total_bytes, d_sites.data_ptr(), d_ns.data_ptr()), "bbmap_final_batch_device")
+
+    def scaffold_records(self):
+        """bbmap_get_scaffold_records: SamLine's scaffold coordinates of the last step's final records, overflow tier included.
+        Returns (SCAFREC_DTYPE[n], names): names[i] = the name of scaffold i (global number) as the index's table was set from
+        DeviceIndex.set_scaffolds (None when the table was set without names)."""
+        p = C.c_void_p()
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(self.L.bbmap_get_scaffold_records(self.h, C.c_void_p(stream), C.byref(p)), "bbmap_get_scaffold_records")
+        torch.cuda.current_stream().synchronize()
+        recs = _copy(p.value, self.n * SCAFREC_DTYPE.itemsize, self.dev).view(SCAFREC_DTYPE)
+        return recs, getattr(self.di, "scaffold_names", None)
 
     def set_average_pair_dist(self, v):
         _lib.check(self.L.bbmap_set_average_pair_dist(self.h, int(v)), "bbmap_set_average_pair_dist")

@@ -408,6 +408,24 @@ int bbidx_set_kernel(bbidx_ctx *ctx, int32_t kind);
  * instead of 6; reads longer than announced are still answered (by the per-lane kernel). */
 int bbidx_set_max_read_len(bbidx_ctx *ctx, int32_t max_len);
 
+/* Scaffold boundaries inside the chromosome arrays: Data.scaffoldLocs / scaffoldLengths / interScaffoldPadding (current/dna/Data.java),
+ * as FastaToChromArrays2 packs FASTA records into chromosome arrays (current/dna/FastaToChromArrays2.java:432-524; Python:
+ * bbmap_amd.reference.pack).  counts, locs and lengths have nchroms + 1 entries indexed by chromosome number (entry 0 unused, as in
+ * bbidx_build's chromArr); chromosome c holds counts[c] scaffolds, starting at locs[c][i] (0-based, strictly ascending) with lengths
+ * lengths[c][i].  nchroms must be the index's.  The table is copied to the device (CSR; a scaffold's global number, 0-based in FASTA
+ * order, is its position in the concatenation of the chromosomes' lists) and belongs to the index context: every mapper that borrows
+ * the index, its overflow tier included, uses it from its next batch on (do not call this while a batch runs).
+ *   - counts == NULL clears the table.  A table whose chromosomes each hold one scaffold keeps the filter off (Data.isSingleScaffold
+ *     is true when `array.length<2`): mapping is what it is without a table, and bbmap_get_scaffold_records still works.
+ *   - With a chromosome of two or more scaffolds, quickMap's tail drops every probe site that spans two scaffolds, as
+ *     removeOutOfBounds does when SAM is written (current/align2/AbstractMapThread.java:2444-2476); bbmap_stats.sites_cross_scaffold
+ *     counts them.  Rescue and tip-deletion sites are not filtered (nor are they in the reference).
+ *   - BBMAP_E_ARG, with the previous table left in force: nchroms other than the index's, a chromosome without scaffolds, a NULL row,
+ *     starts that do not ascend strictly from 0, a length < 1 or a scaffold that reaches past its chromosome array (chromArrLen), or
+ *     inter_scaffold_padding <= 0 while some chromosome holds two or more scaffolds. */
+int bbidx_set_scaffolds(bbidx_ctx *ctx, int32_t nchroms, const int32_t *counts, const int32_t *const *locs,
+                        const int32_t *const *lengths, int32_t inter_scaffold_padding);
+
 /* =====================================================================================
  * The probe's per-read inputs, host side: AbstractMapThread.quickMap up to its findAdvanced call
  *   (current/align2/AbstractMapThread.java:642-728): key error probabilities from the qualities (QualityTools.makeKeyProbs,
@@ -480,8 +498,10 @@ int bbpipe_quick_rescue_device(void *stream, int64_t n_jobs, const bbresc_job *j
  *                        TranslateColorspaceRead.java:229-653: up to three fillLimited and one fillUnlimited per call, again in rounds),
  *                        fixXY / clipTipIndels / toLocalAlignment, applyClearzone3 and the tip penalty -> bbmap_final per read
  *   Not carried over: per-thread adaptive state of the Java mapper (DYNAMIC_INSERT_LENGTH: the caller feeds averagePairDist, see
- *   bbmap_set_average_pair_dist; the "mating is not working" skip of rescue()), scaffold boundaries inside a chromosome, the
- *   non-default output policies (ambiguous=toss/random/all, secondary alignments, identity / edit filters, local alignment).
+ *   bbmap_set_average_pair_dist; the "mating is not working" skip of rescue()), the non-default output policies (ambiguous=toss/
+ *   random/all, secondary alignments, identity / edit filters, local alignment).
+ *   Scaffolds: with a table set (bbidx_set_scaffolds) quickMap's tail drops sites that span two scaffolds, and
+ *   bbmap_get_scaffold_records gives SamLine's scaffold coordinates; the SAM writer itself (CIGAR, MD) stays with the host.
  *   Added product: every successful fill also returns its traceback string (as the quickmatch=t branch obtains it,
  *   BBMapThread.java:345, without fixXY / clipTipIndels); site state follows the default (quickmatch=f) flow.
  * ===================================================================================== */
@@ -606,6 +626,9 @@ typedef struct bbmap_stats {
     int64_t final_fills, final_rounds, final_local;   /* its fills, rounds, reads that went through toLocalAlignment */
     int64_t dp_narrow_launches;    /* DP launches that ran the narrow-window kernel (bbmsa_last_route: route8[0]) */
     int64_t dp_sorted_launches;    /* DP launches whose first pass took the jobs widest first (route8[1]) */
+    int64_t sites_cross_scaffold;  /* probe sites quickMap's tail removed for spanning two scaffolds (bbidx_set_scaffolds; 0 without a
+                                    * table).  The overflow tier's pass adds its own: a pair one of whose mates overflowed the probe is
+                                    * counted there only; a read the tier maps again because rescue outgrew its list counts in both. */
 } bbmap_stats;
 
 typedef struct bbmap_ctx bbmap_ctx;
@@ -665,6 +688,26 @@ int bbmap_get_overflow_output(bbmap_ctx *ctx, bbmap_overflow_output *out);
  * *match_bytes = bytes the strings take; strings that do not fit match_cap are not written (call again with a larger buffer).
  * match_out may be NULL (records only).  BBMAP_E_ARG when the context runs without the final stage. */
 int bbmap_get_final(bbmap_ctx *ctx, int64_t n_reads, bbmap_final *out, uint8_t *match_out, int64_t match_cap, int64_t *match_bytes);
+/* SamLine's coordinate block (current/stream/SamLine.java:120-187, :267-268) for every final record of the last batch, overflow tier
+ * included: which scaffold a read landed on and where.  A record that still spans two scaffolds (Data.isSingleScaffold) is unmapped and
+ * its mate unpaired, as SamLine does.  Unmapped after that rule: scaffold = -1 and every coordinate 0. */
+enum { BBMAP_SCAF_MAPPED = 1,          /* mapped after the single-scaffold rule */
+       BBMAP_SCAF_PAIRED = 2,          /* paired after it */
+       BBMAP_SCAF_INBOUNDS = 4,        /* inbounds: mapped, start >= 0 and stop < scaflen */
+       BBMAP_SCAF_SAME_SCAFFOLD = 8 }; /* sameScaf: both mates mapped on the same scaffold */
+typedef struct bbmap_scafrec {
+    int32_t scaffold;              /* global scaffold number (0-based, FASTA order; see bbidx_set_scaffolds) */
+    int32_t start, stop;           /* a1 / b1: the record's start / stop relative to the scaffold's start (0-based; may lie in the pad) */
+    int32_t pos, end;              /* pos0 / pos1: 1-based, leading / trailing clips and clipped leading indels removed, pos >= 1,
+                                    * end <= scaflen */
+    int32_t scaflen;
+    int32_t flags;                 /* BBMAP_SCAF_* */
+    int32_t reserved;
+} bbmap_scafrec;                   /* 32 bytes */
+/* Runs the coordinate kernel over the last batch's final records, enqueued on `stream`: *out = a device array of n_reads records
+ * (read order), valid once the stream has reached it and until the next batch.  Uses the index's scaffold table as it is now (set it
+ * before the batch).  BBMAP_E_ARG when the context runs without the final stage or the index has no scaffold table. */
+int bbmap_get_scaffold_records(bbmap_ctx *ctx, void *stream, const bbmap_scafrec **out);
 int bbmap_last_stats(bbmap_ctx *ctx, bbmap_stats *out);
 /* The last batch's site lists without their empty slots, for a host that copies them back: counts (n_reads + 1 ints), offsets
  * (n_reads + 1 int64: exclusive prefix sums, offsets[n_reads] = total) and packed (packed_cap records) are device buffers of the
