@@ -24,6 +24,7 @@ EXPORTS = [
     "bbidx_build_profile", "bbkeys_default_config", "bbkeys_make", "bbkeys_make_batch", "bbmap_default_config_profile",
     "bbmap_get_final", "bbmap_set_average_pair_dist", "bbmap_final_batch_device",
     "bbidx_set_scaffolds", "bbmap_get_scaffold_records",
+    "bbmap_get_sam_records", "bbmap_get_sam",
 ]
 
 

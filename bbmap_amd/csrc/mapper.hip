@@ -30,6 +30,7 @@
 
 #include "bbmap_amd.h"
 #include "index_ctx.h"
+#include "sam_records.h"
 #include "scaffold.h"
 
 void bbmap_set_error(const char *msg);
@@ -1229,6 +1230,15 @@ struct bbmap_ctx {
     // bbmap_get_scaffold_records: its output (max_reads records) and the read -> overflow-tier record map, allocated on first use
     bbmap_scafrec *d_scafRec = nullptr;
     int *d_scafTier = nullptr;
+    // bbmap_get_sam_records: records, per-read byte counts and their prefix sums, the MAPQ table (allocated on first use), the
+    // scan's scratch and the text blob (grown on demand)
+    bbmap_samrec *d_samRec = nullptr;
+    int *d_samCounts = nullptr;
+    long long *d_samOffsets = nullptr;
+    float *d_mapqMax = nullptr;
+    void *d_samTmp = nullptr; size_t samTmpBytes = 0;
+    uint8_t *d_samText = nullptr; size_t samTextCap = 0;
+    long long samTextBytes = 0;
 };
 
 static thread_local char g_merr[320];
@@ -1273,6 +1283,8 @@ extern "C" void bbmap_destroy(bbmap_ctx *c) {
     if (c->tier) bbmap_destroy(c->tier);
     bbidx_launch_free(&c->probeLs);
     if (c->d_packTmp) (void)hipFree(c->d_packTmp);
+    if (c->d_samTmp) (void)hipFree(c->d_samTmp);
+    if (c->d_samText) (void)hipFree(c->d_samText);
     for (int i = 0; i < 7; i++) if (c->hio.p[i]) (void)hipFree(c->hio.p[i]);
     if (c->hostStream) (void)hipStreamDestroy(c->hostStream);
     if (c->tierStream) (void)hipStreamDestroy(c->tierStream);
@@ -1912,6 +1924,7 @@ extern "C" int bbmap_final_batch_device(bbmap_ctx *c, void *stream_, int64_t n_r
     if (c->tier) c->tier->ran = false;
     memset(&c->stats, 0, sizeof c->stats);
     c->stats.reads = n_reads;
+    c->batch = {n_reads, reads, bases, minus_delta, nullptr, nullptr};
     MHIP(hipMemsetAsync(c->d_counters, 0, 64 * 4, stream));
     MHIP(hipMemsetAsync(c->d_slow, 0, sizeof(bbmapper::SlowState) * (size_t)n_reads, stream));      // fills are numbered from 0
     MHIP(hipMemcpyAsync(c->d_ms, sites, sizeof(bbmap_msite) * (size_t)n_reads * (size_t)c->cfg.max_sites, hipMemcpyDeviceToDevice, stream));
@@ -2150,6 +2163,76 @@ extern "C" int bbmap_get_scaffold_records(bbmap_ctx *c, void *stream_, const bbm
                            tfin, tpool, tierIdx, units, c->cfg.paired, c->d_scafRec);
     MHIP(hipGetLastError());
     *out = c->d_scafRec;
+    return BBMAP_OK;
+}
+
+// SamLine's remaining fields for the last batch (sam_records.hip): the coordinate kernel, the sizing pass, a device-wide exclusive scan
+// of the per-read byte counts, the emit pass.  The blob's size comes back once between the scan and the emit pass (it sizes the blob).
+extern "C" int bbmap_get_sam_records(bbmap_ctx *c, void *stream_, int32_t flags, const bbmap_samrec **recs, const uint8_t **text,
+                                     int64_t *text_bytes) {
+    if (!c || !recs || !text) return mfail(BBMAP_E_ARG, "bbmap_get_sam_records: null argument");
+    if (flags & ~(BBMAP_SAM_CIGAR13 | BBMAP_SAM_MD)) return mfail(BBMAP_E_ARG, "bbmap_get_sam_records: unknown flag bits");
+    const bbmap_scafrec *scaf = nullptr;
+    MTRY(bbmap_get_scaffold_records(c, stream_, &scaf));    // its error cases are this call's: no final stage, no batch, no scaffold table
+    if (!c->batch.reads || !c->batch.bases || c->batch.n_reads != c->stats.reads)
+        return mfail(BBMAP_E_ARG, "bbmap_get_sam_records: the context does not hold the last batch's reads");
+    hipStream_t stream = (hipStream_t)stream_;
+    const long long n = c->stats.reads;
+    const int maxLen = c->cfg.max_read_len;
+    if (!c->d_samRec) {
+        MTRY(dalloc(c, &c->d_samRec, (size_t)c->cfg.max_reads));
+        MTRY(dalloc(c, &c->d_samCounts, (size_t)c->cfg.max_reads + 1));
+        MTRY(dalloc(c, &c->d_samOffsets, (size_t)c->cfg.max_reads + 1));
+        MTRY(dalloc(c, &c->d_mapqMax, (size_t)maxLen + 1));
+        std::vector<float> table((size_t)maxLen + 1);
+        bbsam::fill_mapq_max(table.data(), maxLen);
+        MHIP(hipMemcpy(c->d_mapqMax, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    bbsam::Args a;
+    a.fin = c->d_final; a.pool = c->d_pool; a.tfin = nullptr; a.tpool = nullptr; a.tierIdx = nullptr;
+    if (c->tier && c->tierReads > 0 && c->tier->ran && n > 0) { a.tierIdx = c->d_scafTier; a.tfin = c->tier->d_final; a.tpool = c->tier->d_pool; }
+    a.scaf = scaf; a.reads = c->batch.reads; a.bases = c->batch.bases;
+    a.chromArr = c->d_chromArr; a.chromArrLen = c->d_chromArrLen;
+    a.mapqMax = c->d_mapqMax; a.mapqMaxLen = maxLen;
+    a.n = n; a.paired = c->cfg.paired; a.flags = flags;
+    size_t need = 0;
+    auto wide = hipcub::TransformInputIterator<long long, bbmapper::ToLL, const int *>((const int *)c->d_samCounts, bbmapper::ToLL());
+    MHIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, wide, c->d_samOffsets, (int)(n + 1), stream));
+    if (need > c->samTmpBytes) {
+        if (c->d_samTmp) { MHIP(hipStreamSynchronize(stream)); (void)hipFree(c->d_samTmp); c->d_samTmp = nullptr; c->samTmpBytes = 0; }
+        MHIP(hipMalloc(&c->d_samTmp, need));
+        c->samTmpBytes = need;
+    }
+    MHIP(bbsam::launch_size(a, c->d_samRec, c->d_samCounts, stream));
+    MHIP(hipMemsetAsync(c->d_samCounts + n, 0, 4, stream));                 // n + 1 entries, so that offsets[n] is the total
+    MHIP(hipcub::DeviceScan::ExclusiveSum(c->d_samTmp, need, wide, c->d_samOffsets, (int)(n + 1), stream));
+    long long total = 0;
+    MHIP(hipMemcpyAsync(&total, c->d_samOffsets + n, 8, hipMemcpyDeviceToHost, stream));
+    MHIP(hipStreamSynchronize(stream));
+    if ((size_t)total > c->samTextCap) {
+        if (c->d_samText) { (void)hipFree(c->d_samText); c->d_samText = nullptr; c->samTextCap = 0; }
+        const size_t cap = (size_t)total + (size_t)total / 4 + 256;
+        MHIP(hipMalloc((void **)&c->d_samText, cap));
+        c->samTextCap = cap;
+    }
+    MHIP(bbsam::launch_emit(a, c->d_samRec, c->d_samOffsets, c->d_samText, stream));
+    c->samTextBytes = total;
+    *recs = c->d_samRec; *text = c->d_samText;
+    if (text_bytes) *text_bytes = total;
+    return BBMAP_OK;
+}
+
+// Host form: the records and the blob as they are on the device (packed in read order already), two copies.
+extern "C" int bbmap_get_sam(bbmap_ctx *c, int64_t n_reads, int32_t flags, bbmap_samrec *out, uint8_t *text_out, int64_t text_cap,
+                             int64_t *text_bytes) {
+    if (!c || !out) return mfail(BBMAP_E_ARG, "bbmap_get_sam: null argument");
+    if (!c->ran || n_reads != c->stats.reads) return mfail(BBMAP_E_ARG, "bbmap_get_sam: n_reads is not the last batch's");
+    if (text_cap < 0 || (text_cap > 0 && !text_out)) return mfail(BBMAP_E_ARG, "bbmap_get_sam: bad text buffer");
+    const bbmap_samrec *recs = nullptr; const uint8_t *text = nullptr; int64_t total = 0;
+    MTRY(bbmap_get_sam_records(c, nullptr, flags, &recs, &text, &total));
+    if (n_reads > 0) MHIP(hipMemcpy(out, recs, (size_t)n_reads * sizeof(bbmap_samrec), hipMemcpyDeviceToHost));    // (waits for the null stream)
+    if (text_out && total > 0 && total <= text_cap) MHIP(hipMemcpy(text_out, text, (size_t)total, hipMemcpyDeviceToHost));
+    if (text_bytes) *text_bytes = total;
     return BBMAP_OK;
 }
 

@@ -22,7 +22,14 @@ FINAL_DTYPE = np.dtype([("mapped", "<i4"), ("chrom", "<i4"), ("strand", "<i4"), 
 SCAFREC_DTYPE = np.dtype([("scaffold", "<i4"), ("start", "<i4"), ("stop", "<i4"), ("pos", "<i4"), ("end", "<i4"), ("scaflen", "<i4"),
                           ("flags", "<i4"), ("reserved", "<i4")])
 SCAF_MAPPED, SCAF_PAIRED, SCAF_INBOUNDS, SCAF_SAME_SCAFFOLD = 1, 2, 4, 8
-assert MSITE_DTYPE.itemsize == 128 and FINAL_DTYPE.itemsize == 64 and SCAFREC_DTYPE.itemsize == 32
+# bbmap_samrec: the fields of a SAM line (bbmap_get_sam_records); rname / rnext = global scaffold numbers (-1 `*`, rnext -2 `=`),
+# nm / am -1 = no tag, cigar_len / md_len 0 = none, offsets into the text blob
+SAMREC_DTYPE = np.dtype([("flag", "<i4"), ("mapq", "<i4"), ("rname", "<i4"), ("rnext", "<i4"), ("pos", "<i4"), ("pnext", "<i4"),
+                         ("tlen", "<i4"), ("nm", "<i4"), ("am", "<i4"), ("tags", "<i4"), ("cigar_off", "<i8"), ("cigar_len", "<i4"),
+                         ("md_len", "<i4"), ("md_off", "<i8")])
+SAM_CIGAR13, SAM_MD = 1, 2
+SAM_TAG_XT = 1
+assert MSITE_DTYPE.itemsize == 128 and FINAL_DTYPE.itemsize == 64 and SCAFREC_DTYPE.itemsize == 32 and SAMREC_DTYPE.itemsize == 64
 GAPPED_BIT = 1 << 30
 
 
@@ -83,6 +90,10 @@ def _bind(L):
     L.bbmap_set_average_pair_dist.restype = C.c_int
     L.bbmap_get_scaffold_records.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
     L.bbmap_get_scaffold_records.restype = C.c_int
+    L.bbmap_get_sam_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.bbmap_get_sam_records.restype = C.c_int
+    L.bbmap_get_sam.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    L.bbmap_get_sam.restype = C.c_int
     for f in ("bbmap_default_config", "bbmap_create", "bbmap_map_batch_device", "bbmap_get_output", "bbmap_last_stats",
               "bbmap_get_overflow_output"):
         getattr(L, f).restype = C.c_int
@@ -241,6 +252,27 @@ class Mapper:
         torch.cuda.current_stream().synchronize()
         recs = _copy(p.value, self.n * SCAFREC_DTYPE.itemsize, self.dev).view(SCAFREC_DTYPE)
         return recs, getattr(self.di, "scaffold_names", None)
+
+    def sam_records(self, flags=0):
+        """bbmap_get_sam_records: SamLine's fields for the last step's final records, overflow tier included, built on the device.
+        flags: SAM_CIGAR13 | SAM_MD.  Returns (SAMREC_DTYPE[n], text uint8[]): read r's CIGAR is text[cigar_off : + cigar_len], its MD
+        value text[md_off : + md_len] (bbmap_amd.sam formats lines from them)."""
+        p, t, nb = C.c_void_p(), C.c_void_p(), C.c_int64(0)
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(self.L.bbmap_get_sam_records(self.h, C.c_void_p(stream), int(flags), C.byref(p), C.byref(t), C.byref(nb)),
+                   "bbmap_get_sam_records")
+        torch.cuda.current_stream().synchronize()
+        recs = _copy(p.value, self.n * SAMREC_DTYPE.itemsize, self.dev).view(SAMREC_DTYPE)
+        return recs, _copy(t.value, nb.value, self.dev)
+
+    def sam_records_host(self, flags=0):
+        """bbmap_get_sam: the same through the host-buffer form (records first, then the blob once its size is known)."""
+        recs = np.zeros(self.n, SAMREC_DTYPE)
+        nb = C.c_int64(0)
+        _lib.check(self.L.bbmap_get_sam(self.h, self.n, int(flags), recs.ctypes.data, None, 0, C.byref(nb)), "bbmap_get_sam")
+        text = np.zeros(max(1, nb.value), np.uint8)
+        _lib.check(self.L.bbmap_get_sam(self.h, self.n, int(flags), recs.ctypes.data, text.ctypes.data, text.size, C.byref(nb)), "bbmap_get_sam")
+        return recs, text[:nb.value]
 
     def set_average_pair_dist(self, v):
         _lib.check(self.L.bbmap_set_average_pair_dist(self.h, int(v)), "bbmap_set_average_pair_dist")

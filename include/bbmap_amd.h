@@ -501,7 +501,8 @@ int bbpipe_quick_rescue_device(void *stream, int64_t n_jobs, const bbresc_job *j
  *   bbmap_set_average_pair_dist; the "mating is not working" skip of rescue()), the non-default output policies (ambiguous=toss/
  *   random/all, secondary alignments, identity / edit filters, local alignment).
  *   Scaffolds: with a table set (bbidx_set_scaffolds) quickMap's tail drops sites that span two scaffolds, and
- *   bbmap_get_scaffold_records gives SamLine's scaffold coordinates; the SAM writer itself (CIGAR, MD) stays with the host.
+ *   bbmap_get_scaffold_records gives SamLine's scaffold coordinates, and bbmap_get_sam_records the rest of SamLine's constructor
+ *   (FLAG, POS / PNEXT / TLEN, MAPQ, CIGAR, NM, AM, MD); names, SEQ / QUAL text and file I/O stay with the host.
  *   Added product: every successful fill also returns its traceback string (as the quickmatch=t branch obtains it,
  *   BBMapThread.java:345, without fixXY / clipTipIndels); site state follows the default (quickmatch=f) flow.
  * ===================================================================================== */
@@ -708,6 +709,42 @@ typedef struct bbmap_scafrec {
  * (read order), valid once the stream has reached it and until the next batch.  Uses the index's scaffold table as it is now (set it
  * before the batch).  BBMAP_E_ARG when the context runs without the final stage or the index has no scaffold table. */
 int bbmap_get_scaffold_records(bbmap_ctx *ctx, void *stream, const bbmap_scafrec **out);
+/* The fields of a SAM line for every final record of the last batch: the rest of stream.SamLine's constructor
+ * (current/stream/SamLine.java:82-413) behind the coordinate block above -- makeFlag (:2134-2151), the POS / PNEXT / TLEN table and its
+ * sign rule (:220-253, :349-354), RNAME / RNEXT (:164, :315), toMapq (:1703-1722), the CIGAR (toCigar14 :679-750, toCigar13 :600-663 and
+ * the `len=` / `lenM` shortcut :269-301), the default tags XT:A:R / NM / AM (makeOptionalTags :1481-1549) and MD (makeMdTag :1361-1445).
+ * Fixed at the reference's defaults, not configurable: SOFT_CLIP = true, PENALIZE_AMBIG = true, INTRON_LIMIT = Integer.MAX_VALUE (no
+ * `N` operator, no dropped deletion), MAKE_NM_TAG and MAKE_AM_TAG on, every other tag off; primary alignments only.
+ * Strings live in one text blob, packed in read order without gaps: per read its CIGAR, then its MD value (without "MD:Z:"). */
+enum { BBMAP_SAM_CIGAR13 = 1,          /* SamLine.VERSION <= 1.3: M instead of = and X (default: 1.4) */
+       BBMAP_SAM_MD = 2 };             /* MAKE_MD_TAG (off by default, as in the reference) */
+enum { BBMAP_SAM_TAG_XT = 1 };         /* bbmap_samrec.tags bit 0: XT:A:R */
+typedef struct bbmap_samrec {
+    int32_t flag, mapq;
+    int32_t rname;                 /* global scaffold number; -1 = `*` */
+    int32_t rnext;                 /* global scaffold number; -1 = `*`, -2 = `=` */
+    int32_t pos, pnext, tlen;
+    int32_t nm;                    /* -1 = no NM tag */
+    int32_t am;                    /* -1 = no AM tag */
+    int32_t tags;                  /* BBMAP_SAM_TAG_* */
+    int64_t cigar_off;             /* byte offset in the text blob */
+    int32_t cigar_len;             /* 0 = `*` */
+    int32_t md_len;                /* 0 = no MD tag */
+    int64_t md_off;
+} bbmap_samrec;                    /* 64 bytes */
+/* Runs bbmap_get_scaffold_records and then the SAM kernels (sizing pass, device-wide scan, emit pass) on `stream`: *recs = a device
+ * array of n_reads records (read order), *text = the blob; both valid once the stream has reached them and until the next batch.
+ * *text_bytes = the blob's size (may be NULL); the call waits for the stream once, between the scan and the emit pass, because that size
+ * is also what the blob is allocated by.  The batch's own reads and bases are the ones the context remembers from bbmap_map_batch_device
+ * / bbmap_final_batch_device (they must still be in place): the read length enters MAPQ, AM and the shortcut CIGAR, and MD compares
+ * an `N` column's read base with the reference.  BBMAP_E_ARG as bbmap_get_scaffold_records (no final stage, no batch, no scaffold
+ * table; a table of one scaffold per chromosome is fine), or unknown flag bits. */
+int bbmap_get_sam_records(bbmap_ctx *ctx, void *stream, int32_t flags, const bbmap_samrec **recs, const uint8_t **text,
+                          int64_t *text_bytes);
+/* Host form, mirroring bbmap_get_final: out[n_reads] and the blob (text_out may be NULL: records only).  *text_bytes = bytes the blob
+ * takes; when it does not fit text_cap nothing of it is written (call again with a larger buffer).  Two copies, no re-packing. */
+int bbmap_get_sam(bbmap_ctx *ctx, int64_t n_reads, int32_t flags, bbmap_samrec *out, uint8_t *text_out, int64_t text_cap,
+                  int64_t *text_bytes);
 int bbmap_last_stats(bbmap_ctx *ctx, bbmap_stats *out);
 /* The last batch's site lists without their empty slots, for a host that copies them back: counts (n_reads + 1 ints), offsets
  * (n_reads + 1 int64: exclusive prefix sums, offsets[n_reads] = total) and packed (packed_cap records) are device buffers of the
