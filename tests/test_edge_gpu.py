@@ -78,20 +78,74 @@ def test_rescue_edges():
     assert quick_rescue_batch([(ref[1000:1100], 1, 1000, 0, True, 1000, 2)], [ref])[0]["start"] == 1000
 
 
+def _complement_table():
+    """AminoAcid.baseToComplementExtended restated: the reference's pairs (it pairs S with W), both cases, U -> A, five symbols
+    that stay, and its fill of -1 (0xFF as a byte) everywhere else.  Java's table has 128 entries and an index of 128 or more
+    would throw there; the project answers 0xFF for those too."""
+    t = np.full(256, 0xFF, np.uint8)
+    for a, b in ("AT", "CG", "MK", "RY", "SW", "VB", "HD", "NN", "XX"):
+        for x, y in ((a, b), (b, a)):
+            t[ord(x)], t[ord(x.lower())] = ord(y), ord(y.lower())
+    t[ord("U")], t[ord("u")] = ord("A"), ord("a")
+    for c in "? -*.":
+        t[ord(c)] = ord(c)
+    assert int((t[:128] != 0xFF).sum()) == 16 * 2 + 2 + 5
+    return t
+
+
 def test_revcomp_kernel():
+    """bbpipe_revcomp_device against the complement table restated above, over every byte value.  Bytes of 128 and above map
+    to 0xFF: that is the project's own answer, the Java would throw.  Lengths around the 64-lane stride, 1, 3, 4, 5 and 11 reads
+    per launch (four waves per block), unaligned offsets, and canaries around every read of the output blob."""
     import torch
     from bbmap_amd.index import READ_DTYPE
     L = _lib.load()
     rng = np.random.default_rng(5)
-    lens = [150, 1, 77, 600, 64, 65]
-    reads = np.concatenate([rng.choice(list(b"ACGTNacgtnRYKM-"), n).astype(np.uint8) for n in lens])
-    recs = np.zeros(len(lens), READ_DTYPE)
-    recs["bases_off"] = np.cumsum([0] + lens[:-1]); recs["len"] = lens
+    table = _complement_table()
+    all_lens = [0, 1, 2, 63, 64, 65, 127, 128, 129, 1000, 6019]
+    cases = [[n] for n in all_lens] + [all_lens[:3], all_lens[3:7], all_lens[6:], all_lens[::-1]]
+    assert sorted({len(c) for c in cases}) == [1, 3, 4, 5, 11]
     dev = torch.device("cuda", 0)
-    t_in = torch.from_numpy(reads).to(dev); t_out = torch.zeros_like(t_in)
+    CANARY = 0xC3                                                           # not a value the table produces
+    assert CANARY not in table.tolist()
+    residues = set()
+    for ci, lens in enumerate(cases):
+        offs, pos = [], 0
+        for i, n in enumerate(lens):
+            pos += 1 + (5 * i + 3 * ci) % 13                                # canary bytes in front of every read
+            offs.append(pos)
+            pos += n
+        total = pos + 37                                                    # and after the last one
+        blob = np.full(total, CANARY, np.uint8)
+        inside = np.zeros(total, bool)
+        for off, n in zip(offs, lens):
+            rd = rng.integers(0, 256, n).astype(np.uint8)
+            if n >= 256:
+                rd[:256] = rng.permutation(256)                             # every byte value, whatever the draw
+            blob[off:off + n] = rd
+            inside[off:off + n] = True
+            residues.add(off % 16)
+        recs = np.zeros(len(lens), READ_DTYPE)
+        recs["bases_off"] = offs; recs["len"] = lens
+        t_in = torch.from_numpy(blob).to(dev)
+        t_out = torch.full((total,), CANARY, dtype=torch.uint8, device=dev)
+        t_recs = torch.from_numpy(recs.view(np.uint8).reshape(-1).copy()).to(dev)
+        _lib.check(L.bbpipe_revcomp_device(None, len(lens), t_recs.data_ptr(), t_in.data_ptr(), t_out.data_ptr()), "bbpipe_revcomp_device")
+        out = t_out.cpu().numpy()
+        for off, n in zip(offs, lens):
+            assert (out[off:off + n] == table[blob[off:off + n][::-1]]).all(), (lens, off, n)
+        assert (out[~inside] == CANARY).all(), lens                          # between the reads and after the last
+        assert (t_in.cpu().numpy() == blob).all()
+    assert len(residues) >= 12                                              # read offsets are not aligned to anything
+    # byte values 0..255 one by one, in a read of their own
+    blob = np.arange(256, dtype=np.uint8)
+    recs = np.zeros(1, READ_DTYPE)
+    recs["bases_off"] = 0; recs["len"] = 256
+    t_in = torch.from_numpy(blob).to(dev); t_out = torch.zeros_like(t_in)
     t_recs = torch.from_numpy(recs.view(np.uint8).reshape(-1).copy()).to(dev)
-    _lib.check(L.bbpipe_revcomp_device(None, len(lens), t_recs.data_ptr(), t_in.data_ptr(), t_out.data_ptr()), "bbpipe_revcomp_device")
-    comp = {ord(a): ord(b) for a, b in zip("ACGTNacgtnRYKM-", "TGCANtgcanYRMK-")}
-    out = t_out.cpu().numpy()
-    for off, n in zip(recs["bases_off"], lens):
-        assert out[off:off + n].tolist() == [comp[b] for b in reads[off:off + n][::-1]]
+    _lib.check(L.bbpipe_revcomp_device(None, 1, t_recs.data_ptr(), t_in.data_ptr(), t_out.data_ptr()), "bbpipe_revcomp_device")
+    out = t_out.cpu().numpy()[::-1]
+    assert out.tolist() == table.tolist()
+    assert (out[128:] == 0xFF).all()
+    comp = {ord(a): ord(b) for a, b in zip("ACGTNacgtnRYKM-", "TGCANtgcanYRMK-")}      # the pairs this test began with
+    assert all(out[a] == b for a, b in comp.items())
