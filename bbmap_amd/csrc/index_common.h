@@ -1,5 +1,5 @@
-// Shared by the two index-probe kernels (index_probe.hip: one read per lane, any shape;
-// index_probe_wave.hip: one read per wavefront, state in registers + LDS).
+// Types and constants shared by the index build, the host contexts and the three index-probe kernels (what only the kernels share
+// is in index_probe_shared.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -92,29 +92,6 @@ struct Codec {
     __device__ inline int siteOf(int number) const { return number & siteMask; }
     __device__ inline int baseChrom(int chrom) const { return max(0, chrom & highMask); }
 };
-
-__device__ inline int calcApproxHitsCutoff(const bbidx_params &p, int keys, int hits, int currentCutoff, bool perfect) {
-    const int reduction = min(max(hits / p.hitReductionDiv, p.maxHitsReduction2), max(p.maximumMaxHitsReduction, keys / 8));
-    int r = max(p.minApproxHitsToKeep, max(currentCutoff, hits - reduction));
-    if (perfect) r = max(r, keys);
-    return r;
-}
-
-// MultiStateAligner11tsJNI.calcAffineScore helpers, in plain points
-__device__ inline int calcDelScoreApprox(int len) {      // MultiStateAligner11tsJNI.java:1347-1376 with approximateGaps
-    if (len <= 0) return 0;
-    int score = -472;
-    if (len > MINGAP) { const int rem = len % 128, div = (len - 128) / 128; score += div * -2; len = rem + 128; }
-    if (len > 80) { score += ((len - 80 + 3) / 4) * -1; len = 80; }
-    if (len > 20) { score += (len - 20) * -1; len = 20; }
-    if (len > 5) { score += (len - 5) * -9; len = 5; }
-    if (len > 1) score += (len - 1) * -33;
-    return score;
-}
-__device__ inline int insCum(int n) {                    // POINTS_INS_ARRAY_C[n], n in 1..5
-    return -395 + (n > 1 ? (n - 1) * -39 : 0);
-}
-__device__ inline int subArr(int t) { return t > 5 ? -25 : (t > 1 ? -51 : -127); }   // POINTS_SUB_ARRAY[t]
 
 }  // namespace bbidx
 

@@ -11,13 +11,14 @@
 // (QuadHeap) only ever exposes its minimum under the total order (site, column), so it is replaced by a scan
 // over the list heads with the same tie-break.
 //
-// Functions follow, in this order, current/align2/BBIndex.java: calcApproxHitsCutoff :3267-3294, maxScoreZ
+// Functions follow, in this order, current/align2/BBIndex.java: maxScoreZ
 // :2948-2964, maxQuickScore :2473-2487, scoreZ2 :2882-2914, scoreLeft/Right :2967-3035, quickScore :2490-2511
 // (+ AbstractIndex.scoreY, AbstractIndex.java:52-78), findMaxQscore2 :2294-2450, extendScore :2558-2833
 // (+ MultiStateAligner11tsJNI.calcAffineScore :871-1027), makeGapArray :2837-2878, SiteScore.setPerfect
 // (current/stream/SiteScore.java:239-292), slowWalk3 :1219-1706, trimExcessHitListsByGreedy :266-350
-// (+ Solver.valueOfElement/findWorstGreedy, current/align2/Solver.java:46-151), find :403-639,
-// prescanAllBlocks :642-741.
+// (+ Solver.findWorstGreedy, current/align2/Solver.java:46-95), find :403-639, prescanAllBlocks :642-741.
+// calcApproxHitsCutoff, calcAffineScore's gap scores, adjustSite, overlap and Solver.valueOfElement are the single copies of
+// index_probe_shared.h, with BBIndex's constants (ProfBBMap).
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -27,9 +28,7 @@
 #include <vector>
 
 #include "bbmap_amd.h"
-#include "index_common.h"
-
-void bbmap_set_error(const char *msg);   // msa_host.hip
+#include "index_probe_shared.h"
 
 namespace bbidx {
 
@@ -102,11 +101,6 @@ __device__ int quickScore(const Walker &w, const int *locs, const int *keyScores
     return x + Y_MULT * (offsets[rightIndex] - offsets[centerIndex]);
 }
 
-__device__ inline int adjustSite(const Walker &w, int a, int offset, int baseChrom) {
-    if ((a & w.c.siteMask) >= offset) return a - offset;
-    const int ch = w.c.chromOf(a, baseChrom), st = w.c.siteOf(a);
-    return w.c.toNumber(max(st - offset, 0), ch);
-}
 __device__ void listsInit(const Walker &w, Lists &L, int block, const int *starts, const int *stops, const int *offsets,
                           const int *keyScores, int n, int baseChrom) {
     L.n = 0; L.sites = w.ix->sites[block];
@@ -114,7 +108,7 @@ __device__ void listsInit(const Walker &w, Lists &L, int block, const int *start
         if (starts[i] < 0) continue;
         const int j = L.n++;
         L.row[j] = starts[i]; L.stop[j] = stops[i]; L.offs[j] = offsets[i]; L.kscore[j] = keyScores[i];
-        L.value[j] = adjustSite(w, L.sites[starts[i]], offsets[i], baseChrom);
+        L.value[j] = adjustSite(w.c, L.sites[starts[i]], offsets[i], baseChrom);
         L.live[j] = true;
     }
     L.nlive = L.n;
@@ -158,7 +152,7 @@ __device__ void findMaxQscore2(const Walker &w, Lists &L, int baseChrom, int pre
             if (col < 0 || L.value[col] != site) break;
             w.cPrescan++;
             const int row = L.row[col] + 1;
-            if (row < L.stop[col]) { L.row[col] = row; L.value[col] = adjustSite(w, L.sites[row], L.offs[col], baseChrom); }
+            if (row < L.stop[col]) { L.row[col] = row; L.value[col] = adjustSite(w.c, L.sites[row], L.offs[col], baseChrom); }
             else {
                 L.live[col] = false; L.nlive--;
                 if (perfectOnly || L.nlive < approxHitsCutoff) { outQ = topQscore; outHits = maxHits; return; }
@@ -179,16 +173,16 @@ __device__ int calcAffineScore(const int *locArray, int n, const Strand &rd, int
             else if (loc == lastLoc || lastLoc < 0) { maxContig = max(maxContig, contig); contig = 1; score += 70 + rd.bscore(i); }
             else if (loc < lastLoc) {
                 maxContig = max(maxContig, contig); contig = 0;
-                score += 70 + rd.bscore(i) + calcDelScoreApprox(lastLoc - loc + 1);
+                score += 70 + rd.bscore(i) + calcDelScoreApprox<ProfBBMap>(lastLoc - loc + 1);
                 timeInMode = 1;
             } else {
                 maxContig = max(maxContig, contig); contig = 0;
-                score += 70 + rd.bscore(i) + insCum(min(loc - lastLoc, 5));
+                score += 70 + rd.bscore(i) + insCum<ProfBBMap>(min(loc - lastLoc, 5));
                 timeInMode = 1;
             }
             lastLoc = loc;
         } else if (loc == -1) {
-            if (lastValue < 0 && timeInMode > 0) { timeInMode++; score += subArr(timeInMode); }
+            if (lastValue < 0 && timeInMode > 0) { timeInMode++; score += subArr<ProfBBMap>(timeInMode); }
             else { score += -127; timeInMode = 1; }
         } else { timeInMode = 0; }
         lastValue = loc;
@@ -284,7 +278,6 @@ __device__ void setPerfect(const DevIndex &ix, bbidx_site &ss, const Strand &rd)
     perfect = perfect && semiperfect && (N == 0);
     ss.perfect = perfect; ss.semiperfect = semiperfect;
 }
-__device__ inline bool overlap(int a1, int b1, int a2, int b2) { return a2 <= b1 && b2 >= a1; }
 
 struct SiteList { bbidx_site *v; int n, cap; bool overflow; };
 
@@ -304,7 +297,7 @@ __device__ void slowWalk3(const Walker &w, Lists &L, int *locArray, int block, c
     int cutoff = max(minScore, (int)(currentTopScore * DYN_SCORE));
     int qcutoff = max(bestScores[2], minQuickScore);
     int bestqscore = bestScores[3], maxHits = bestScores[1], perfectsFound = bestScores[5];
-    int approxHitsCutoff = calcApproxHitsCutoff(p, numKeys, maxHits, p.minApproxHitsToKeep, currentTopScore >= maxScore);
+    int approxHitsCutoff = calcApproxHitsCutoff<ProfBBMap>(p, numKeys, maxHits, p.minApproxHitsToKeep, currentTopScore >= maxScore);
     if (approxHitsCutoff > numHits) return;
     const bool shortCircuit = allBasesCovered && numKeys == numHits && filter_by_qscore;
     if (currentTopScore >= maxScore) qcutoff = max(qcutoff, (int)(mqs * DYN_QSCORE_PERFECT));
@@ -343,14 +336,14 @@ __device__ void slowWalk3(const Walker &w, Lists &L, int *locArray, int block, c
                 }
                 if (score == maxScore) {
                     qcutoff = max(qcutoff, (int)(mqs * DYN_QSCORE_PERFECT));
-                    approxHitsCutoff = calcApproxHitsCutoff(p, numKeys, maxHits, p.minApproxHitsToKeep, true);
+                    approxHitsCutoff = calcApproxHitsCutoff<ProfBBMap>(p, numKeys, maxHits, p.minApproxHitsToKeep, true);
                 }
                 if (score >= cutoff) { qcutoff = max(qcutoff, (int)(qscore * DYN_QSCORE)); bestqscore = max(qscore, bestqscore); }
             }
             if (score >= cutoff) {
                 if (score > currentTopScore) {
                     maxHits = max(approxHits, maxHits);
-                    approxHitsCutoff = calcApproxHitsCutoff(p, numKeys, maxHits, approxHitsCutoff, currentTopScore >= maxScore);
+                    approxHitsCutoff = calcApproxHitsCutoff<ProfBBMap>(p, numKeys, maxHits, approxHitsCutoff, currentTopScore >= maxScore);
                     cutoff = max(cutoff, (int)(score * DYN_SCORE));
                     if (score >= maxScore) cutoff = max(cutoff, (int)(score * 0.95f));
                     currentTopScore = score;
@@ -433,7 +426,7 @@ __device__ void slowWalk3(const Walker &w, Lists &L, int *locArray, int block, c
             if (col < 0 || L.value[col] != site) break;
             w.cWalk++;
             const int row = L.row[col] + 1;
-            if (row < L.stop[col]) { L.row[col] = row; L.value[col] = adjustSite(w, L.sites[row], L.offs[col], baseChrom); }
+            if (row < L.stop[col]) { L.row[col] = row; L.value[col] = adjustSite(w.c, L.sites[row], L.offs[col], baseChrom); }
             else {
                 L.live[col] = false; L.nlive--;
                 if (L.nlive < approxHitsCutoff) { finished = true; break; }
@@ -447,31 +440,6 @@ __device__ void slowWalk3(const Walker &w, Lists &L, int *locArray, int block, c
     bestScores[3] = max(bestScores[3], bestqscore);
     bestScores[4] = mqs;
     bestScores[5] = perfectsFound;
-}
-
-__device__ long long valueOfElement(const int *offsets, int noffsets, const int *lengths, float keyWeight, int chunk,
-                                    const int *lists, int numlists, int index, long long pointsPerSite) {
-    const long long PPL = 30000, PPB1 = 6000, BONUS_END = 40000, WIDTH = 5500, SPACING = -30;
-    if (numlists < 1) return 0;
-    const int prospect = lists[index];
-    if (lengths[prospect] == 0) return -999999;
-    long long valuep = PPL + (PPL * 2 / numlists) + ((PPL * 10) / lengths[prospect]);
-    const long long valuem = pointsPerSite * lengths[prospect];
-    if (prospect == 0 || prospect == noffsets - 1) valuep += BONUS_END;
-    if (numlists == 1) { valuep += (WIDTH + PPB1) * chunk; return ((long long)__fmul_rn((float)valuep, keyWeight)) + valuem; }
-    const int first = lists[0], last = lists[numlists - 1];
-    const int offL = (prospect == first ? -1 : offsets[lists[index - 1]]);
-    const int offP = offsets[prospect];
-    const int offR = (prospect == last ? offsets[noffsets - 1] + 1 : offsets[lists[index + 1]]);
-    const int oldL = offP - offL, oldR = offR - offP, newS = offR - offL;
-    valuep += (long long)((oldL * oldL + oldR * oldR) - (newS * newS)) * SPACING;
-    int uniquelyCovered;
-    if (prospect == first) uniquelyCovered = offR - offP;
-    else if (prospect == last) uniquelyCovered = offP - offL;
-    else { const int b = offR - (offL + chunk); uniquelyCovered = b > 0 ? b : 0; }
-    if (prospect == first || prospect == last) valuep += (PPB1 + WIDTH) * uniquelyCovered;
-    else valuep += PPB1 * uniquelyCovered;
-    return ((long long)__fmul_rn((float)valuep, keyWeight)) + valuem;
 }
 
 __device__ int trimByGreedy(const DevIndex &ix, const int *offsets, const int *keyScores, int n, int maxHitLists, int *keys,
@@ -646,10 +614,10 @@ __global__ __launch_bounds__(64) void probe_kernel(const Params P) {
             if (bestScores[1] < p.minApproxHitsToKeep) dead = true;
             else if ((float)bestScores[3] < __fmul_rn((float)mqs, MIN_QSCORE_MULT2)) dead = true;
             else if (bestScores[3] >= mqs && pretend) {
-                hitsCutoff = calcApproxHitsCutoff(p, n, bestScores[1], p.minApproxHitsToKeep, true);
+                hitsCutoff = calcApproxHitsCutoff<ProfBBMap>(p, n, bestScores[1], p.minApproxHitsToKeep, true);
                 qscoreCutoff = max(qscoreCutoff, (int)(bestScores[3] * DYN_QSCORE_PERFECT));
             } else {
-                hitsCutoff = calcApproxHitsCutoff(p, n, bestScores[1], p.minApproxHitsToKeep, false);
+                hitsCutoff = calcApproxHitsCutoff<ProfBBMap>(p, n, bestScores[1], p.minApproxHitsToKeep, false);
                 qscoreCutoff = max(qscoreCutoff, (int)(bestScores[3] * PRESCAN_QSCORE_THRESH));
             }
         }

@@ -21,7 +21,9 @@
 //
 // Functions follow current/align2/BBIndexPacBio.java (= BBIndex.java minus camelWalk3): find :394-615, trimExcessHitListsByGreedy
 // :267-349 (+ Solver.java:46-151), prescanAllBlocks :618-711, findMaxQscore2 (BBIndex.java:2294-2450), slowWalk3 :1200-1680,
-// quickScore / scoreLeft / scoreRight / scoreZ2 / maxQuickScore, extendScore, makeGapArray, calcApproxHitsCutoff :2562-2585.
+// quickScore / scoreLeft / scoreRight / scoreZ2 / maxQuickScore, extendScore.  The two profiles' constants, calcApproxHitsCutoff
+// :2562-2585, calcAffineScore, makeGapArray, setPerfect and slowWalk3's site bookkeeping are index_probe_shared.h's, here over the
+// 16-bit location array (Loc16).
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -30,11 +32,8 @@
 #include <cstdio>
 
 #include "bbmap_amd.h"
-#include "index_common.h"
 #include "index_ctx.h"
-#include "wave_prims.h"
-
-void bbmap_set_error(const char *msg);
+#include "index_probe_shared.h"
 
 namespace bbidxl {
 using namespace bbidx;
@@ -46,25 +45,6 @@ constexpr int LMAX = BBIDX_PACBIO_MAX_READ_LEN;
 constexpr int WS_ARRAYS = 12;               // per-wave workspace: WS_ARRAYS x KMAX ints
 constexpr int DEADV = -(1 << 30);           // value of an unused column: outside every window
 typedef const int __attribute__((address_space(1))) *GlobalIntsT;   // global_load instead of flat_load
-
-struct ProfBBMap {      // BBIndex.java:3168-3305 ; MultiStateAligner11tsJNI.java:871-1027, jni/MultiStateAligner11tsJNI.c:18-98
-    static constexpr int Z_MULT = 20, SMALL_LIST = 20, MIN_LISTS_RETAIN = 6, INDEL_MULT = 20, PERFECT_RED = 0;
-    static constexpr float HIT_FRACTION = 0.85f, MIN_SCORE_MULT = 0.15f, MIN_QSCORE_MULT = 0.025f, MIN_QSCORE_MULT2 = 0.1f, DYN_SCORE = 0.84f;
-    static constexpr int RELAX1 = 4, RELAX2 = 3, RELAX3 = 3, RELAX4 = 2;
-    __device__ static inline int indelPenalty(int bkhs) { return bkhs / 2 - 1; }
-    static constexpr int MATCH = 70, MATCH2 = 100, SUB = -127, SUB2 = -51, SUB3 = -25;
-    static constexpr int INS = -395, INS2 = -39, DEL = -472, DEL2 = -33, DEL3 = -9, DEL4 = -1, DEL5 = -1, GAP = -2;
-    static constexpr int INS_DIF_PLUS = 0;              // POINTS_INS_ARRAY_C[min(loc - lastLoc, 5)]
-};
-struct ProfPacBio {     // BBIndexPacBio.java:2461-2596 ; MultiStateAligner9PacBio.java:2375-2407, :1681-1870
-    static constexpr int Z_MULT = 25, SMALL_LIST = 80, MIN_LISTS_RETAIN = 12, INDEL_MULT = 25, PERFECT_RED = 2;
-    static constexpr float HIT_FRACTION = 0.97f, MIN_SCORE_MULT = 0.02f, MIN_QSCORE_MULT = 0.005f, MIN_QSCORE_MULT2 = 0.005f, DYN_SCORE = 0.64f;
-    static constexpr int RELAX1 = 20, RELAX2 = 18, RELAX3 = 16, RELAX4 = 14;
-    __device__ static inline int indelPenalty(int bkhs) { return bkhs / 8 - 1; }
-    static constexpr int MATCH = 90, MATCH2 = 100, SUB = -137, SUB2 = -49, SUB3 = -25;
-    static constexpr int INS = -205, INS2 = -42, DEL = -292, DEL2 = -37, DEL3 = -17, DEL4 = -2, DEL5 = -1, GAP = -2;
-    static constexpr int INS_DIF_PLUS = 1;              // dif = min(loc - lastLoc + 1, 5), :1729
-};
 
 // debug build (-DBBIDXL_TIMERS): the five work counters become cycle counts (in units of 1024 cycles) of
 // {refillAll, popSite without its refills, quick scores, minHead + countWindow, everything else of the walk loops}
@@ -129,6 +109,11 @@ struct U {
 // many wavefronts a CU holds.
 __device__ __forceinline__ int ld_loc(const Lds &S, const U &u, int i) { const int r = S.loc[i]; return r >= 0xFFFE ? r - 0x10000 : r + u.locBase; }
 __device__ __forceinline__ void st_loc(const Lds &S, const U &u, int i, int v) { S.loc[i] = (unsigned short)(v < 0 ? v + 0x10000 : v - u.locBase); }
+struct Loc16 {               // this location array for the shared templates (index_probe_shared.h)
+    __device__ static __forceinline__ int ld(const U &u, const Lds &S, int i) { return ld_loc(S, u, i); }
+    __device__ static __forceinline__ void st(const U &u, const Lds &S, int i, int v) { st_loc(S, u, i, v); }
+    __device__ static __forceinline__ int &ngaps(const Lds &S) { return *S.ngapsP; }
+};
 
 // The lists of one (block, strand) cycle.  The heap stand-in works on registers: lane `lane` keeps the value, cursor and end of its
 // lists 64 j + lane in v[j] (every loop over j is fully unrolled, so the array never leaves the register file).
@@ -142,22 +127,10 @@ struct Lists {
     GlobalIntsT sites;
 };
 
-template <class PF> __device__ __forceinline__ int calcApproxHitsCutoffP(const bbidx_params &p, int keys, int hits, int currentCutoff, bool perfect) {
-    const int reduction = min(max(hits / p.hitReductionDiv, p.maxHitsReduction2), max(p.maximumMaxHitsReduction, keys / 8));
-    int r = max(p.minApproxHitsToKeep, max(currentCutoff, hits - reduction));
-    if (perfect) r = max(r, keys - PF::PERFECT_RED);
-    return r;
-}
-
 // cross-lane exchange through the workspace (HBM / L2): writes of one phase are visible to every lane's reads of the next
 __device__ __forceinline__ void wsfence() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-}
-
-__device__ __forceinline__ int adjustSite(const U &u, int a, int offset, int baseChrom) {
-    const int below = u.c.toNumber(0, u.c.chromOf(a, baseChrom));
-    return (a & u.c.siteMask) >= offset ? a - offset : below;
 }
 
 // ---------------------------------------------------------------------------------------------- heap stand-ins
@@ -218,7 +191,7 @@ __device__ __forceinline__ void refillAll(const U &u, Lds &S, Lists &L, int base
                 L.rowW[l] = row;
                 const int avail = stop - row - 1;
 #pragma unroll
-                for (int t = 0; t < NB; t++) S.nb[t][l] = adjustSite(u, L.sites[min(row + 1 + t, stop - 1)], off, baseChrom);
+                for (int t = 0; t < NB; t++) S.nb[t][l] = adjustSite(u.c, L.sites[min(row + 1 + t, stop - 1)], off, baseChrom);
                 S.st[l] = (uint8_t)((min(avail, NB) << 2) | (avail <= NB ? 0x80 : 0));
             }
         }
@@ -354,71 +327,7 @@ template <class PF> __device__ __forceinline__ int quickScoreL(const U &u, const
     return x + Y_MULT * ((int)S.off[right] - (int)S.off[centerIndex]);
 }
 
-// ---------------------------------------------------------------------------------------------- location-array scores
-template <class PF> __device__ __forceinline__ int delApprox(int len) {       // calcDelScore(len, approximateGaps = true)
-    if (len <= 0) return 0;
-    int score = PF::DEL;
-    if (len > MINGAP) { const int rem = len % 128, div = (len - 128) / 128; score += div * PF::GAP; len = rem + 128; }
-    if (len > 80) { score += ((len - 80 + 3) / 4) * PF::DEL5; len = 80; }
-    if (len > 20) { score += (len - 20) * PF::DEL4; len = 20; }
-    if (len > 5) { score += (len - 5) * PF::DEL3; len = 5; }
-    if (len > 1) score += (len - 1) * PF::DEL2;
-    return score;
-}
-template <class PF> __device__ __forceinline__ int insShort(int n) { return PF::INS + (n > 1 ? (n - 1) * PF::INS2 : 0); }     // n in 1..5
-template <class PF> __device__ __forceinline__ int subRun(int t) { return t > 5 ? PF::SUB3 : (t > 1 ? PF::SUB2 : PF::SUB); }
-
-// calcAffineScore(locArray, baseScores, bases[, minContig]) over the LDS location array, 64 bases per step (the sequential state is
-// recovered from ballot masks exactly as in index_probe_wave.hip's calcAffineScoreW)
-template <class PF> __device__ __forceinline__ int calcAffineScoreL(const U &u, const Lds &S, int strand, int minContig) {
-    const int blen = u.blen, lane = u.lane;
-    int score = 0, carryLastLoc = -3, carryRun = 0, carryContig = 0, maxContig = 0;
-    for (int base = 0; base < blen; base += 64) {
-        const int p = base + lane;
-        const bool valid = p < blen;
-        const int loc = valid ? ld_loc(S, u, p) : 0;
-        const int prev = (valid && p > 0) ? ld_loc(S, u, p - 1) : -1;
-        const bool pos = valid && loc > 0, neg1 = valid && loc == -1;
-        const u64 posM = __ballot(pos), n1M = __ballot(neg1);
-        const u64 lt = lt_mask(lane);
-        const u64 mlo = posM & lt;
-        const int lastLoc = mlo ? ld_loc(S, u, base + hibit(mlo)) : carryLastLoc;
-        int c = 0, ev = 0;                                   // ev: 1 equal, 2 restart, 3 indel
-        if (pos) {
-            const int bs = S.bsc[strand ? blen - 1 - p : p];
-            if (loc == prev) { c = PF::MATCH2 + bs; ev = 1; }
-            else if (loc == lastLoc || lastLoc < 0) { c = PF::MATCH + bs; ev = 2; }
-            else if (loc < lastLoc) { c = PF::MATCH + bs + delApprox<PF>(lastLoc - loc + 1); ev = 3; }
-            else { c = PF::MATCH + bs + insShort<PF>(min(loc - lastLoc + PF::INS_DIF_PLUS, 5)); ev = 3; }
-        } else if (neg1) {
-            const u64 nb = ~n1M & lt;
-            const int t = nb ? lane - hibit(nb) : lane + 1 + carryRun;
-            c = subRun<PF>(t);
-        }
-        score += wsum(c);
-        if (minContig > 1) {
-            const u64 EM = __ballot(ev == 1), SM = __ballot(ev == 2), IM = __ballot(ev == 3), RM = SM | IM;
-            int cval = 0;
-            if (ev == 1) {
-                const u64 rlo = RM & lt;
-                if (rlo) { const int r = hibit(rlo); cval = popc(EM & lt & gt_mask(r)) + 1 + (int)((SM >> r) & 1); }
-                else cval = popc(EM & lt) + 1 + carryContig;
-            } else if (ev == 2) cval = 1;
-            maxContig = max(maxContig, wmax(cval));
-            const u64 all = EM | RM;
-            if (all) carryContig = rl(cval, hibit(all));
-        }
-        if (posM) carryLastLoc = rl(loc, hibit(posM));
-        const int last = min(63, blen - 1 - base);
-        if ((n1M >> last) & 1) {
-            const u64 nbAll = ~n1M & (lt_mask(last) | (1ull << last));
-            carryRun = nbAll ? last - hibit(nbAll) : last + 1 + carryRun;
-        } else carryRun = 0;
-    }
-    if (minContig > 1 && maxContig < minContig) score = min(score, -50 * blen);
-    return score;
-}
-
+// ---------------------------------------------------------------------------------------------- extendScore
 // BBIndex.extendScore :2558-2833 (BBIndexPacBio.java:1907-2100): the columns in range are walked in column order, 64 at a time
 template <class PF> __device__ __forceinline__ int extendScoreL(U &u, Lds &S, const Lists &L, int strand, int chrom, int centerVal) {
     const bbidx_params &p = u.ix->p;
@@ -510,80 +419,8 @@ template <class PF> __device__ __forceinline__ int extendScoreL(U &u, Lds &S, co
     }
     for (int i = lane; i < blen; i += 64) if (rb[i] == 'N') st_loc(S, u, i, -2);
     wsync();
-    return uni(calcAffineScoreL<PF>(u, S, strand, p.kfilter));
+    return uni(calcAffineScore<PF, Loc16>(u, S, strand, p.kfilter));
 }
-
-// BBIndex.makeGapArray :2837-2878 -- rare (a site spanning more than MINGAP + read length); one lane walks LDS
-__device__ __forceinline__ int makeGapArrayL(const U &u, Lds &S, int minLoc, int minGap) {
-    if (u.lane == 0) {
-        // (the array is rewritten in place as the reference does; positions plus base indices still fit the 16-bit offsets)
-        auto LA = [&](int i) -> int { return ld_loc(S, u, i); };
-        auto SET = [&](int i, int v) { st_loc(S, u, i, v); };
-        const int n = u.blen;
-        int gaps = 0; bool doSort = false;
-        if (LA(0) < 0) SET(0, minLoc);
-        for (int i = 1; i < n; i++) {
-            if (LA(i) < 0) SET(i, LA(i - 1) + 1); else SET(i, LA(i) + i);
-            if (LA(i) < LA(i - 1)) doSort = true;
-        }
-        if (doSort) {
-            for (int i = 1; i < n; i++) { const int v = LA(i); int j = i - 1; while (j >= 0 && LA(j) > v) { SET(j + 1, LA(j)); j--; } SET(j + 1, v); }
-        }
-        for (int i = 1; i < n; i++) if (LA(i) - LA(i - 1) > minGap) gaps++;
-        int len = 0;
-        if (gaps >= 1) {
-            len = 2 + gaps * 2;
-            if (len > BBIDX_MAX_GAPS) len = -1;
-            else {
-                S.gaps[0] = LA(0); S.gaps[len - 1] = LA(n - 1);
-                for (int i = 1, j = 1; i < n; i++) if (LA(i) - LA(i - 1) > minGap) { S.gaps[j] = LA(i - 1); S.gaps[j + 1] = LA(i); j += 2; }
-            }
-        }
-        *S.ngapsP = len;
-    }
-    wsync();
-    return __builtin_amdgcn_readfirstlane(*S.ngapsP);
-}
-
-// SiteScore.setPerfect (current/stream/SiteScore.java:239-292), order-independent form as in index_probe_wave.hip
-__device__ __forceinline__ void setPerfectL(const U &u, const Lds &S, int chrom, int strand, int start, int stop, int &perfectOut, int &semiOut) {
-    const int blen = u.blen;
-    perfectOut = 0; semiOut = 0;
-    if (blen != stop - start + 1) return;
-    const uint8_t *ref = u.ix->chromArr[chrom];
-    const int reflen = u.ix->chromArrLen[chrom];
-    const uint8_t *rb = S.base[strand];
-    bool perfect = true;
-    int refloc = start, readloc = 0, N = 0;
-    const int mx = min(stop, reflen - 1), nlimit = blen / 2;
-    if (start < 0) { N -= start; readloc -= start; refloc -= start; perfect = false; }
-    if (stop >= reflen) { N += (stop - reflen + 1); perfect = false; }
-    if (N > nlimit) return;
-    bool anyHard = false, anyCN = false, anyBad = false;
-    const int total = uni(mx - refloc + 1);
-    for (int j0 = 0; j0 < total; j0 += 64) {
-        const bool in = j0 + u.lane < total;
-        const int j = in ? j0 + u.lane : total - 1;
-        const int c = rb[readloc + j], r = ref[refloc + j];
-        const bool bad = in && (c != r || c == 'N'), hard = bad && r != 'N', cn = bad && c == 'N';
-        const u64 badM = __ballot(bad);
-        if (badM) {
-            anyBad = true;
-            if (__ballot(hard)) { anyHard = true; break; }
-            if (__ballot(cn)) anyCN = true;
-            N += popc(badM);
-            if (N > nlimit) break;
-        }
-    }
-    if (anyHard || N > nlimit) return;
-    const bool semi = !anyCN;
-    semiOut = semi ? 1 : 0;
-    perfectOut = (perfect && !anyBad && semi && N == 0) ? 1 : 0;
-}
-__device__ __forceinline__ bool overlap(int a1, int b1, int a2, int b2) { return a2 <= b1 && b2 >= a1; }
-
-struct SiteOut { bbidx_site *v; int n, cap; bool overflow; };
-struct PrevSite { int idx, chrom, strand, start, stop, score, perfect, semiperfect, ngaps; };
 
 // ---------------------------------------------------------------------------------------------- findMaxQscore2
 // BBIndex.findMaxQscore2 :2294-2450 (earlyExit = true, as prescanAllBlocks calls it)
@@ -630,26 +467,12 @@ template <class PF> __device__ __forceinline__ void slowWalk3L(U &u, Lds &S, Lis
     const int baseChrom = u.c.baseChrom(baseChrom_);
     const int numHits = L.n;
     const bool filter_by_qscore = numKeys >= 5;
-    const int minScore = (int)(PF::MIN_SCORE_MULT * maxScore);
-    const int minQuickScore = (int)(PF::MIN_QSCORE_MULT * mqs);
-    int currentTopScore = bestScores[0];
-    int cutoff = max(minScore, (int)(currentTopScore * PF::DYN_SCORE));
-    int qcutoff = max(bestScores[2], minQuickScore);
-    int bestqscore = bestScores[3], maxHits = bestScores[1], perfectsFound = bestScores[5];
-    int approxHitsCutoff = calcApproxHitsCutoffP<PF>(p, numKeys, maxHits, p.minApproxHitsToKeep, currentTopScore >= maxScore);
-    if (approxHitsCutoff > numHits) return;
+    WalkState w{ssl};
+    if (!walkBegin<PF>(w, p, bestScores, numKeys, numHits, mqs, maxScore)) return;
     const bool shortCircuit = allBasesCovered && numKeys == numHits && filter_by_qscore;
-    if (currentTopScore >= maxScore) qcutoff = max(qcutoff, (int)(mqs * DYN_QSCORE_PERFECT));
-
-    PrevSite pv; pv.idx = -1; pv.chrom = pv.strand = pv.start = pv.stop = pv.score = pv.perfect = pv.semiperfect = pv.ngaps = 0;
-    bool finished = false;
     int lastSite = INT_MIN;
-    while (L.nlive > 0 && !finished) {
-        approxHitsCutoff = uni(approxHitsCutoff); cutoff = uni(cutoff); qcutoff = uni(qcutoff); currentTopScore = uni(currentTopScore);
-        maxHits = uni(maxHits); perfectsFound = uni(perfectsFound); bestqscore = uni(bestqscore); L.nlive = uni(L.nlive);
-        pv.idx = uni(pv.idx); pv.chrom = uni(pv.chrom); pv.strand = uni(pv.strand); pv.start = uni(pv.start); pv.stop = uni(pv.stop);
-        pv.score = uni(pv.score); pv.perfect = uni(pv.perfect); pv.semiperfect = uni(pv.semiperfect); pv.ngaps = uni(pv.ngaps);
-        ssl.n = uni(ssl.n); ssl.overflow = uni(ssl.overflow); u.cWalk = uni(u.cWalk); u.cExtend = uni(u.cExtend); u.cRefBytes = uni(u.cRefBytes);
+    while (L.nlive > 0 && !w.finished) {
+        w.reuni(); L.nlive = uni(L.nlive); u.cWalk = uni(u.cWalk); u.cExtend = uni(u.cExtend); u.cRefBytes = uni(u.cRefBytes);
         lastSite = uni(lastSite);
         int site, centerIndex, maxNearbySite = 0, best, second;
         int approxHits = 0;
@@ -657,13 +480,13 @@ template <class PF> __device__ __forceinline__ void slowWalk3L(U &u, Lds &S, Lis
         const bool fresh = site != lastSite;                    // a site is looked at once, with every list that sits on it still there
         lastSite = site;
         if (fresh) { LT_BEGIN(u); approxHits = countWindow(u, S, L, site - p.maxIndel, site + p.maxIndel2, site, centerIndex, best, second, maxNearbySite); LT_END(u, 3); }
-        if (fresh && approxHits >= approxHitsCutoff) {
+        if (fresh && approxHits >= w.approxHitsCutoff) {
             int score;
-            int qscore = filter_by_qscore ? quickScoreL<PF>(u, S, L, centerIndex, site, approxHits) : qcutoff;
+            int qscore = filter_by_qscore ? quickScoreL<PF>(u, S, L, centerIndex, site, approxHits) : w.qcutoff;
             qscore += scoreZ2L<PF>(u, S, L, site, approxHits);
             int mapStart = site, mapStop = maxNearbySite;
             bool locArrayValid = false;
-            if (qscore < qcutoff) score = -1;
+            if (qscore < w.qcutoff) score = -1;
             else {
                 const int chrom = u.c.chromOf(site, baseChrom);
                 if (shortCircuit && qscore == mqs) score = maxScore;
@@ -678,149 +501,20 @@ template <class PF> __device__ __forceinline__ void slowWalk3L(U &u, Lds &S, Lis
                     mapStop = u.c.toNumber(mx, chrom);
                 }
                 if (score == maxScore) {
-                    qcutoff = max(qcutoff, (int)(mqs * DYN_QSCORE_PERFECT));
-                    approxHitsCutoff = calcApproxHitsCutoffP<PF>(p, numKeys, maxHits, p.minApproxHitsToKeep, true);
+                    w.qcutoff = max(w.qcutoff, (int)(mqs * DYN_QSCORE_PERFECT));
+                    w.approxHitsCutoff = calcApproxHitsCutoff<PF>(p, numKeys, w.maxHits, p.minApproxHitsToKeep, true);
                 }
-                if (score >= cutoff) { qcutoff = max(qcutoff, (int)(qscore * DYN_QSCORE)); bestqscore = max(qscore, bestqscore); }
+                if (score >= w.cutoff) { w.qcutoff = max(w.qcutoff, (int)(qscore * DYN_QSCORE)); w.bestqscore = max(qscore, w.bestqscore); }
             }
-            if (score >= cutoff) {
-                if (score > currentTopScore) {
-                    maxHits = max(approxHits, maxHits);
-                    approxHitsCutoff = calcApproxHitsCutoffP<PF>(p, numKeys, maxHits, approxHitsCutoff, currentTopScore >= maxScore);
-                    cutoff = max(cutoff, (int)(score * PF::DYN_SCORE));
-                    if (score >= maxScore) cutoff = max(cutoff, (int)(score * 0.95f));
-                    currentTopScore = score;
-                }
-                const int chrom = u.c.chromOf(mapStart, baseChrom);
-                const int site2 = u.c.siteOf(mapStart);
-                const int site3 = u.c.siteOf(mapStop) + blen - 1;
-                int ngaps = 0;
-                if (site3 - site2 >= MINGAP + blen && locArrayValid) {
-                    ngaps = makeGapArrayL(u, S, site2, MINGAP);
-                    if (ngaps < 0) ngaps = 0;
-                    if (ngaps > 0) {
-                        if (lane == 0) { S.gaps[0] = min(S.gaps[0], site2); S.gaps[ngaps - 1] = max(S.gaps[ngaps - 1], site3); }
-                        wsync();
-                    }
-                }
-                ngaps = uni(ngaps);
-                const bool perfect1 = (score == maxScore && fullyDefined);
-                const bool inbounds = (site2 >= 0 && site3 < u.ix->chromLengths[chrom]);
-                const bool havePrev = pv.idx >= 0;
-                bool makeNew = false, withGaps = false;
-                int wb = 0;
-                if (inbounds && ngaps == 0 && havePrev && pv.chrom == chrom && pv.strand == strand && overlap(pv.start, pv.stop, site2, site3)) {
-                    const int betterScore = max(score, pv.score);
-                    const int minStart = min(pv.start, site2), maxStop = max(pv.stop, site3);
-                    const bool perfect2 = (pv.score == maxScore && fullyDefined);
-                    const bool shortEnough = (maxStop - minStart < 2 * blen);
-                    bbidx_site *pd = &ssl.v[pv.idx];
-                    if (pv.start == site2 && pv.stop == site3) {
-                        pv.score = betterScore;
-                        pv.perfect = (pv.perfect || perfect1 || perfect2) ? 1 : 0;
-                        if (pv.perfect) pv.semiperfect = 1;
-                        wb = 1;
-                    } else if (shortEnough && pv.start == site2 && !pv.semiperfect) {
-                        if (perfect2) { }
-                        else if (perfect1) {
-                            pv.stop = site3;
-                            if (!pv.perfect) perfectsFound++;
-                            pv.perfect = pv.semiperfect = 1;
-                        } else {
-                            pv.stop = maxStop;
-                            setPerfectL(u, S, pv.chrom, pv.strand, pv.start, pv.stop, pv.perfect, pv.semiperfect);
-                        }
-                        pv.score = betterScore;
-                        wb = 2;
-                    } else if (shortEnough && pv.stop == site3 && !pv.semiperfect) {
-                        if (perfect2) { }
-                        else if (perfect1) {
-                            pv.start = site2;
-                            if (!pv.perfect) perfectsFound++;
-                            pv.perfect = pv.semiperfect = 1;
-                        } else {
-                            pv.start = minStart;
-                            setPerfectL(u, S, pv.chrom, pv.strand, pv.start, pv.stop, pv.perfect, pv.semiperfect);
-                        }
-                        pv.score = betterScore;
-                        wb = 3;
-                    } else makeNew = true;
-                    wb = uni(wb);
-                    if (wb && lane == 0) {
-                        if (wb == 2) { pd->stop = pv.stop; if (pv.ngaps) pd->gaps[pv.ngaps - 1] = pv.stop; }
-                        if (wb == 3) { pd->start = pv.start; if (pv.ngaps) pd->gaps[0] = pv.start; }
-                        pd->perfect = pv.perfect; pd->semiperfect = pv.semiperfect; pd->score = pv.score;
-                    }
-                } else if (inbounds) { makeNew = true; withGaps = true; }
-                pv.chrom = uni(pv.chrom); pv.strand = uni(pv.strand); pv.start = uni(pv.start); pv.stop = uni(pv.stop);
-                pv.score = uni(pv.score); pv.perfect = uni(pv.perfect); pv.semiperfect = uni(pv.semiperfect); perfectsFound = uni(perfectsFound);
-                if (uni(makeNew)) {
-                    int sp = perfect1 ? 1 : 0, ssemi = sp;
-                    if (!perfect1) setPerfectL(u, S, chrom, strand, site2, site3, sp, ssemi);
-                    sp = uni(sp); ssemi = uni(ssemi);
-                    const int sg = withGaps ? ngaps : 0;
-                    if (ssl.n >= ssl.cap) { ssl.overflow = true; finished = true; }
-                    else {
-                        int wv = 0;
-                        switch (lane) {
-                            case 0: wv = chrom; break; case 1: wv = strand; break; case 2: wv = site2; break; case 3: wv = site3; break;
-                            case 4: wv = approxHits; break; case 5: wv = score; break; case 6: wv = sp; break; case 7: wv = ssemi; break;
-                            case 8: wv = sg; break;
-                            default: wv = (lane < 9 + sg) ? S.gaps[lane - 9] : 0; break;
-                        }
-                        if (lane < 25) ((int *)&ssl.v[ssl.n])[lane] = wv;
-                        const int idx = ssl.n++;
-                        bool stopNow = false;
-                        if (sp) {
-                            if (!havePrev || !pv.perfect || !(pv.chrom == chrom && pv.strand == strand && overlap(site2, site3, pv.start, pv.stop))) {
-                                perfectsFound++;
-                                if (p.quitAfterTwoPerfects && perfectsFound >= 2) stopNow = true;
-                            }
-                        }
-                        pv.idx = idx; pv.chrom = chrom; pv.strand = strand; pv.start = site2; pv.stop = site3; pv.score = score;
-                        pv.perfect = sp; pv.semiperfect = ssemi; pv.ngaps = sg;
-                        if (stopNow) finished = true;
-                    }
-                }
-            }
+            recordSite<PF, Loc16>(u, S, w, numKeys, baseChrom, strand, approxHits, score, mapStart, mapStop, locArrayValid, maxScore, fullyDefined);
         }
-        if (uni(finished)) break;
-        if (popOne(u, S, L, site, centerIndex, approxHitsCutoff, false, baseChrom, u.cWalk)) break;
+        if (uni(w.finished)) break;
+        if (popOne(u, S, L, site, centerIndex, w.approxHitsCutoff, false, baseChrom, u.cWalk)) break;
     }
-    bestScores[0] = max(bestScores[0], currentTopScore);
-    bestScores[1] = max(bestScores[1], maxHits);
-    bestScores[2] = max(bestScores[2], qcutoff);
-    bestScores[3] = max(bestScores[3], bestqscore);
-    bestScores[4] = mqs;
-    bestScores[5] = perfectsFound;
+    walkEnd(w, bestScores, mqs);
 }
 
 // ---------------------------------------------------------------------------------------------- greedy trim
-// Solver.valueOfElement (current/align2/Solver.java:97-151)
-__device__ __forceinline__ long long valueOfElement(const int *offsets, int noffsets, const int *lengths, float keyWeight, int chunk,
-                                                    const int *lists, int numlists, int index, long long pointsPerSite) {
-    const long long PPL = 30000, PPB1 = 6000, BONUS_END = 40000, WIDTH = 5500, SPACING = -30;
-    if (numlists < 1) return 0;
-    const int prospect = lists[index];
-    if (lengths[prospect] == 0) return -999999;
-    long long valuep = PPL + (PPL * 2 / numlists) + ((PPL * 10) / lengths[prospect]);
-    const long long valuem = pointsPerSite * lengths[prospect];
-    if (prospect == 0 || prospect == noffsets - 1) valuep += BONUS_END;
-    if (numlists == 1) { valuep += (WIDTH + PPB1) * chunk; return ((long long)__fmul_rn((float)valuep, keyWeight)) + valuem; }
-    const int first = lists[0], last = lists[numlists - 1];
-    const int offL = (prospect == first ? -1 : offsets[lists[index - 1]]);
-    const int offP = offsets[prospect];
-    const int offR = (prospect == last ? offsets[noffsets - 1] + 1 : offsets[lists[index + 1]]);
-    const int oldL = offP - offL, oldR = offR - offP, newS = offR - offL;
-    valuep += (long long)((oldL * oldL + oldR * oldR) - (newS * newS)) * SPACING;
-    int uniquelyCovered;
-    if (prospect == first) uniquelyCovered = offR - offP;
-    else if (prospect == last) uniquelyCovered = offP - offL;
-    else { const int b = offR - (offL + chunk); uniquelyCovered = b > 0 ? b : 0; }
-    if (prospect == first || prospect == last) valuep += (PPB1 + WIDTH) * uniquelyCovered;
-    else valuep += PPB1 * uniquelyCovered;
-    return ((long long)__fmul_rn((float)valuep, keyWeight)) + valuem;
-}
 __device__ __forceinline__ long long rl64(long long v, int l) {
     return (long long)(((u64)(unsigned)rl((int)(v >> 32), l) << 32) | (unsigned)rl((int)v, l));
 }
@@ -915,8 +609,6 @@ __device__ __forceinline__ int compactKeys(const U &u, int *keyW, int *offW, int
     wsfence();
     return m;
 }
-
-__device__ inline int base_num_fast(int b) { return base_num(b); }
 
 template <class PF> __global__ __launch_bounds__(64) void probe_long_kernel(const LongParams Q) {
     extern __shared__ __align__(16) unsigned char ldsRaw[];
@@ -1081,7 +773,7 @@ template <class PF> __global__ __launch_bounds__(64) void probe_long_kernel(cons
                         const int d = nh + popc(M & lt_mask(lane));
                         L.rowW[d] = start; L.stopW[d] = start + len;
                         S.off[d] = (short)off; S.ksc[d] = (short)ksc;
-                        S.val[d] = adjustSite(u, first, off, baseChrom);
+                        S.val[d] = adjustSite(u.c, first, off, baseChrom);
                         S.st[d] = 0;
                     }
                     nh += popc(M);
@@ -1126,10 +818,10 @@ template <class PF> __global__ __launch_bounds__(64) void probe_long_kernel(cons
                 if (bestScores[1] < p.minApproxHitsToKeep) dead = true;
                 else if ((float)bestScores[3] < __fmul_rn((float)mqs, PF::MIN_QSCORE_MULT2)) dead = true;
                 else if (bestScores[3] >= mqs && pretend) {
-                    hitsCutoff = calcApproxHitsCutoffP<PF>(p, n, bestScores[1], p.minApproxHitsToKeep, true);
+                    hitsCutoff = calcApproxHitsCutoff<PF>(p, n, bestScores[1], p.minApproxHitsToKeep, true);
                     qscoreCutoff = max(qscoreCutoff, (int)(bestScores[3] * DYN_QSCORE_PERFECT));
                 } else {
-                    hitsCutoff = calcApproxHitsCutoffP<PF>(p, n, bestScores[1], p.minApproxHitsToKeep, false);
+                    hitsCutoff = calcApproxHitsCutoff<PF>(p, n, bestScores[1], p.minApproxHitsToKeep, false);
                     qscoreCutoff = max(qscoreCutoff, (int)(bestScores[3] * PRESCAN_QSCORE_THRESH));
                 }
             }

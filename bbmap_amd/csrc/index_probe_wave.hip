@@ -20,17 +20,16 @@
 // per-lane kernel afterwards.  Four instantiations: <long lists?, LDS read capacity 160 | 400> (see bbidx_launch_wave).
 //
 // Functions follow current/align2/BBIndex.java exactly as index_probe.hip does (same citations); the two kernels and
-// the CPU oracle are compared SiteScore by SiteScore in tests/test_index_gpu.py.
+// the CPU oracle are compared SiteScore by SiteScore in tests/test_index_gpu.py.  calcAffineScore, makeGapArray and setPerfect are
+// index_probe_shared.h's, shared with index_probe_long.hip and used here with BBIndex's constants (ProfBBMap) over the plain
+// location array (LocInts).  slowWalk3's site bookkeeping is this kernel's own copy of recordSite (see slowWalk3W).
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <cstdio>
 
 #include "bbmap_amd.h"
-#include "index_common.h"
-#include "wave_prims.h"
-
-void bbmap_set_error(const char *msg);
+#include "index_probe_shared.h"
 
 namespace bbidxw {
 using namespace bbidx;
@@ -140,13 +139,6 @@ struct WL {
     GlobalInts sites;          // uniform
 };
 
-__device__ __forceinline__ int adjustSite(const U &u, int a, int offset, int baseChrom) {
-    // a site in the first `offset` bases of its chromosome maps to position 0 of that chromosome (branch-free: both forms
-    // are a handful of ALU ops, and a per-lane branch here would sit in the innermost loop of the probe)
-    const int below = u.c.toNumber(0, u.c.chromOf(a, baseChrom));
-    return (a & u.c.siteMask) >= offset ? a - offset : below;
-}
-
 // BBIndex.maxQuickScore :2473-2487 over lanes 0..n-1 (offsets ascending: the coverage of maxScoreZ :2948-2964 is
 // sum(min(k, next - this)) + k)
 __device__ __forceinline__ int maxQuickScoreW(const U &u, int off, int ksc, int n) {
@@ -242,7 +234,7 @@ __device__ __forceinline__ void popSite(const U &u, WL &L, int site, int cutoff,
         if (__ballot(hit && !dies && L.nbuf == 0)) refillLists(L);
         // per-lane cursor update as selects: no EXEC juggling in the innermost loop
         const bool adv = hit && !dies;
-        const int nv = adjustSite(u, L.nb[0], L.offs, baseChrom);
+        const int nv = adjustSite(u.c, L.nb[0], L.offs, baseChrom);
         L.row = adv ? row : L.row; L.value = adv ? nv : L.value;
         L.hv = hit ? (dies ? INT_MAX : nv) : L.hv;
 #pragma unroll
@@ -288,7 +280,7 @@ __device__ __forceinline__ void bulkSkip(const U &u, WL &L, int site, int lo, in
     while (__ballot(act)) {
         const int probe = bracketed ? a + ((b - a) >> 1) : ((b - a > step) ? a + step : b);   // (row indices reach 2^31: no a + b)
         const int idx = act ? probe : 0;
-        const int v = adjustSite(u, L.sites[idx], L.offs, baseChrom);
+        const int v = adjustSite(u.c, L.sites[idx], L.offs, baseChrom);
         if (act) {
             if (v < T) {
                 a = probe;
@@ -303,7 +295,7 @@ __device__ __forceinline__ void bulkSkip(const U &u, WL &L, int site, int lo, in
     WORK(counter, (unsigned)total);
     if (moved) {
         L.row = np;
-        L.value = adjustSite(u, L.sites[np], L.offs, baseChrom);
+        L.value = adjustSite(u.c, L.sites[np], L.offs, baseChrom);
         L.hv = L.value;
     }
     refillLists(L);
@@ -325,7 +317,7 @@ __device__ __forceinline__ int batchPop(const U &u, WL &L, int lo, int hi, int c
     const bool live = L.hv != INT_MAX;
     const bool hasNext = live && L.row + 1 < L.stop;
     if (__ballot(hasNext && L.nbuf == 0)) refillLists(L);
-    const int nx = adjustSite(u, L.nb[0], L.offs, baseChrom);            // the list's second entry (where hasNext)
+    const int nx = adjustSite(u.c, L.nb[0], L.offs, baseChrom);            // the list's second entry (where hasNext)
     const int W = wmin(hasNext ? nx : L.hv);
     const u64 B = __builtin_amdgcn_sicmp(L.hv, W, 40);                    // heads < W
     if (popc(B) < 2) return 0;
@@ -447,7 +439,7 @@ template <bool MAPS, int WLEN> __device__ __forceinline__ bool cycleGather(U &u,
         for (int q = 0; q < 4; q++) {
             const int e = e0 + q;
             if (e < E) {
-                const int v = adjustSite(u, raw[q], oj[q], baseChrom);
+                const int v = adjustSite(u.c, raw[q], oj[q], baseChrom);
                 C.ent[e] = v; C.isoq[e] = (unsigned short)min(qs[q], 65535);
 #pragma unroll
                 for (int g = 0; MAPS && g < 2; g++) {
@@ -642,61 +634,6 @@ template <bool LONG> __device__ __forceinline__ void findMaxQscore2W(U &u, WL &L
     outQ = topQscore; outHits = maxHits;
 }
 
-// MultiStateAligner11tsJNI.calcAffineScore(locArray, baseScores, bases, minContig) :871-1027 over the LDS location
-// array, 64 bases per step.  Sequential state of the reference and how it is recovered:
-//   lastValue  = the previous element                       -> loc[p-1]
-//   lastLoc    = the last positive element before p         -> highest set bit of the "positive" ballot below p
-//   timeInMode = length of the run of -1 ending at p        -> distance to the highest "not -1" bit below p
-//   contig     = equal-to-previous streak                   -> popcount of "equal" events since the last reset event
-template <int WLEN> __device__ __forceinline__ int calcAffineScoreW(const U &u, const WaveLds<WLEN> &S, int strand, int minContig) {
-    const int blen = u.blen, lane = u.lane;
-    int score = 0, carryLastLoc = -3, carryRun = 0, carryContig = 0, maxContig = 0;
-    for (int base = 0; base < blen; base += 64) {
-        const int p = base + lane;
-        const bool valid = p < blen;
-        const int loc = valid ? S.loc[p] : 0;
-        const int prev = (valid && p > 0) ? S.loc[p - 1] : -1;
-        const bool pos = valid && loc > 0, neg1 = valid && loc == -1;
-        const u64 posM = __ballot(pos), n1M = __ballot(neg1);
-        const u64 lt = lt_mask(lane);
-        const u64 mlo = posM & lt;
-        const int lastLoc = mlo ? S.loc[base + hibit(mlo)] : carryLastLoc;
-        int c = 0, ev = 0;                                   // ev: 1 equal, 2 restart, 3 indel
-        if (pos) {
-            const int bs = S.bsc[strand ? blen - 1 - p : p];
-            if (loc == prev) { c = 100 + bs; ev = 1; }
-            else if (loc == lastLoc || lastLoc < 0) { c = 70 + bs; ev = 2; }
-            else if (loc < lastLoc) { c = 70 + bs + calcDelScoreApprox(lastLoc - loc + 1); ev = 3; }
-            else { c = 70 + bs + insCum(min(loc - lastLoc, 5)); ev = 3; }
-        } else if (neg1) {
-            const u64 nb = ~n1M & lt;
-            const int t = nb ? lane - hibit(nb) : lane + 1 + carryRun;
-            c = subArr(t);
-        }
-        score += wsum(c);
-        if (minContig > 1) {
-            const u64 EM = __ballot(ev == 1), SM = __ballot(ev == 2), IM = __ballot(ev == 3), RM = SM | IM;
-            int cval = 0;
-            if (ev == 1) {
-                const u64 rlo = RM & lt;
-                if (rlo) { const int r = hibit(rlo); cval = popc(EM & lt & gt_mask(r)) + 1 + (int)((SM >> r) & 1); }
-                else cval = popc(EM & lt) + 1 + carryContig;
-            } else if (ev == 2) cval = 1;
-            maxContig = max(maxContig, wmax(cval));
-            const u64 all = EM | RM;
-            if (all) carryContig = rl(cval, hibit(all));
-        }
-        if (posM) carryLastLoc = rl(loc, hibit(posM));
-        const int last = min(63, blen - 1 - base);
-        if ((n1M >> last) & 1) {
-            const u64 nbAll = ~n1M & (lt_mask(last) | (1ull << last));
-            carryRun = nbAll ? last - hibit(nbAll) : last + 1 + carryRun;
-        } else carryRun = 0;
-    }
-    if (minContig > 1 && maxContig < minContig) score = min(score, -50 * blen);
-    return score;
-}
-
 // BBIndex.extendScore :2558-2833
 template <int WLEN> __device__ __forceinline__ int extendScoreW(U &u, WaveLds<WLEN> &S, int strand, int value, int offs, int numHits, int chrom, int centerIndex) {
     const bbidx_params &p = u.ix->p;
@@ -774,7 +711,7 @@ template <int WLEN> __device__ __forceinline__ int extendScoreW(U &u, WaveLds<WL
     }
     for (int i = lane; i < blen; i += 64) if (rb[i] == 'N') S.loc[i] = -2;
     wsync();
-    return uni(calcAffineScoreW(u, S, strand, p.kfilter));
+    return uni(calcAffineScore<ProfBBMap, LocInts>(u, S, strand, p.kfilter));
 }
 
 // An upper bound of extendScore for a site with at most three hit keys in range (up to three diagonals), from one pass over the
@@ -850,83 +787,13 @@ template <int WLEN> __device__ __forceinline__ int singleKeyScoreLane(const U &u
                 const int b = rb[q], r = (int)((w >> (8 * t)) & 255u);
                 if (b == 'N') { run = 0; prevA = false; }
                 else if (b == r) { score += (prevA ? 100 : 70) + (int)S.bsc[strand ? blen - 1 - q : q]; prevA = true; run = 0; }
-                else { run++; score += subArr(run); prevA = false; }
+                else { run++; score += subArr<ProfBBMap>(run); prevA = false; }
             }
         }
         w = nxt;
     }
     return score;
 }
-
-// BBIndex.makeGapArray :2837-2878 -- rare (a site spanning more than MINGAP + read length); one lane walks LDS
-template <int WLEN> __device__ __forceinline__ int makeGapArrayW(const U &u, WaveLds<WLEN> &S, int minLoc, int minGap) {
-    if (u.lane == 0) {
-        int *locArray = S.loc;
-        const int n = u.blen;
-        int gaps = 0; bool doSort = false;
-        if (locArray[0] < 0) locArray[0] = minLoc;
-        for (int i = 1; i < n; i++) {
-            if (locArray[i] < 0) locArray[i] = locArray[i - 1] + 1; else locArray[i] += i;
-            if (locArray[i] < locArray[i - 1]) doSort = true;
-        }
-        if (doSort) {
-            for (int i = 1; i < n; i++) { const int v = locArray[i]; int j = i - 1; while (j >= 0 && locArray[j] > v) { locArray[j + 1] = locArray[j]; j--; } locArray[j + 1] = v; }
-        }
-        for (int i = 1; i < n; i++) if (locArray[i] - locArray[i - 1] > minGap) gaps++;
-        int len = 0;
-        if (gaps >= 1) {
-            len = 2 + gaps * 2;
-            if (len > BBIDX_MAX_GAPS) len = -1;
-            else {
-                S.gaps[0] = locArray[0]; S.gaps[len - 1] = locArray[n - 1];
-                for (int i = 1, j = 1; i < n; i++) if (locArray[i] - locArray[i - 1] > minGap) { S.gaps[j] = locArray[i - 1]; S.gaps[j + 1] = locArray[i]; j += 2; }
-            }
-        }
-        S.ngaps = len;
-    }
-    wsync();
-    return __builtin_amdgcn_readfirstlane(S.ngaps);
-}
-
-// SiteScore.setPerfect (current/stream/SiteScore.java:239-292): order-independent form
-template <int WLEN> __device__ __forceinline__ void setPerfectW(const U &u, const WaveLds<WLEN> &S, int chrom, int strand, int start, int stop, int &perfectOut, int &semiOut) {
-    const int blen = u.blen;
-    perfectOut = 0; semiOut = 0;
-    if (blen != stop - start + 1) return;
-    const uint8_t *ref = u.ix->chromArr[chrom];
-    const int reflen = u.ix->chromArrLen[chrom];
-    const uint8_t *rb = S.base[strand];
-    bool perfect = true;
-    int refloc = start, readloc = 0, N = 0;
-    const int mx = min(stop, reflen - 1), nlimit = blen / 2;
-    if (start < 0) { N -= start; readloc -= start; refloc -= start; perfect = false; }
-    if (stop >= reflen) { N += (stop - reflen + 1); perfect = false; }
-    if (N > nlimit) return;
-    bool anyHard = false, anyCN = false, anyBad = false;
-    const int total = uni(mx - refloc + 1);                 // bases compared; lanes past the end re-read the last one
-    for (int j0 = 0; j0 < total; j0 += 64) {
-        const bool in = j0 + u.lane < total;
-        const int j = in ? j0 + u.lane : total - 1;
-        const int c = rb[readloc + j], r = ref[refloc + j];
-        const bool bad = in && (c != r || c == 'N'), hard = bad && r != 'N', cn = bad && c == 'N';
-        const u64 badM = __ballot(bad);
-        if (badM) {
-            anyBad = true;
-            if (__ballot(hard)) { anyHard = true; break; }
-            if (__ballot(cn)) anyCN = true;
-            N += popc(badM);
-            if (N > nlimit) break;
-        }
-    }
-    if (anyHard || N > nlimit) return;
-    const bool semi = !anyCN;
-    semiOut = semi ? 1 : 0;
-    perfectOut = (perfect && !anyBad && semi && N == 0) ? 1 : 0;
-}
-__device__ __forceinline__ bool overlap(int a1, int b1, int a2, int b2) { return a2 <= b1 && b2 >= a1; }
-
-struct SiteOut { bbidx_site *v; int n, cap; bool overflow; };
-struct PrevSite { int idx, chrom, strand, start, stop, score, perfect, semiperfect, ngaps; };
 
 // BBIndex.slowWalk3 :1219-1706
 template <bool LONG, int WLEN> __device__ __forceinline__ void slowWalk3W(U &u, WaveLds<WLEN> &S, CycleLds *C, WL &L, int strand, int numKeys, int mqs, int baseChrom_,
@@ -944,7 +811,7 @@ template <bool LONG, int WLEN> __device__ __forceinline__ void slowWalk3W(U &u, 
     int cutoff = max(minScore, (int)(currentTopScore * DYN_SCORE));
     int qcutoff = max(bestScores[2], minQuickScore);
     int bestqscore = bestScores[3], maxHits = bestScores[1], perfectsFound = bestScores[5];
-    int approxHitsCutoff = calcApproxHitsCutoff(p, numKeys, maxHits, p.minApproxHitsToKeep, currentTopScore >= maxScore);
+    int approxHitsCutoff = calcApproxHitsCutoff<ProfBBMap>(p, numKeys, maxHits, p.minApproxHitsToKeep, currentTopScore >= maxScore);
     if (approxHitsCutoff > numHits) return;
     const bool shortCircuit = allBasesCovered && numKeys == numHits && filter_by_qscore;
     if (currentTopScore >= maxScore) qcutoff = max(qcutoff, (int)(mqs * DYN_QSCORE_PERFECT));
@@ -1000,15 +867,19 @@ template <bool LONG, int WLEN> __device__ __forceinline__ void slowWalk3W(U &u, 
                 }
                 if (score == maxScore) {
                     qcutoff = max(qcutoff, (int)(mqs * DYN_QSCORE_PERFECT));
-                    approxHitsCutoff = calcApproxHitsCutoff(p, numKeys, maxHits, p.minApproxHitsToKeep, true);
+                    approxHitsCutoff = calcApproxHitsCutoff<ProfBBMap>(p, numKeys, maxHits, p.minApproxHitsToKeep, true);
                 }
                 if (score >= cutoff) { qcutoff = max(qcutoff, (int)(qscore * DYN_QSCORE)); bestqscore = max(qscore, bestqscore); }
             }
             PH_WALK(u, seqMode ? 4 : 2);
+            // The site bookkeeping below is index_probe_shared.h's recordSite word for word, over this function's locals.  It is a
+            // copy on purpose: with the walk state in one WalkState struct (recordSite called or the block written out, either way)
+            // probe_wave_kernel<true,160> takes 63.4-63.6 ms per 2 M reads instead of 62.3-62.5.  A change to either
+            // copy belongs in both; tests/test_index_gpu.py::test_site_bookkeeping_arms_through_every_route compares them arm by arm.
             if (score >= cutoff) {
                 if (score > currentTopScore) {
                     maxHits = max(approxHits, maxHits);
-                    approxHitsCutoff = calcApproxHitsCutoff(p, numKeys, maxHits, approxHitsCutoff, currentTopScore >= maxScore);
+                    approxHitsCutoff = calcApproxHitsCutoff<ProfBBMap>(p, numKeys, maxHits, approxHitsCutoff, currentTopScore >= maxScore);
                     cutoff = max(cutoff, (int)(score * DYN_SCORE));
                     if (score >= maxScore) cutoff = max(cutoff, (int)(score * 0.95f));
                     currentTopScore = score;
@@ -1018,7 +889,7 @@ template <bool LONG, int WLEN> __device__ __forceinline__ void slowWalk3W(U &u, 
                 const int site3 = u.c.siteOf(mapStop) + blen - 1;
                 int ngaps = 0;
                 if (site3 - site2 >= MINGAP + blen && locArrayValid) {
-                    ngaps = makeGapArrayW(u, S, site2, MINGAP);
+                    ngaps = makeGapArray<LocInts>(u, S, site2, MINGAP);
                     if (ngaps < 0) ngaps = 0;
                     if (ngaps > 0) {
                         if (lane == 0) { S.gaps[0] = min(S.gaps[0], site2); S.gaps[ngaps - 1] = max(S.gaps[ngaps - 1], site3); }
@@ -1050,7 +921,7 @@ template <bool LONG, int WLEN> __device__ __forceinline__ void slowWalk3W(U &u, 
                             pv.perfect = pv.semiperfect = 1;
                         } else {
                             pv.stop = maxStop;
-                            setPerfectW(u, S, pv.chrom, pv.strand, pv.start, pv.stop, pv.perfect, pv.semiperfect);
+                            setPerfect(u, S, pv.chrom, pv.strand, pv.start, pv.stop, pv.perfect, pv.semiperfect);
                         }
                         pv.score = betterScore;
                         wb = 2;
@@ -1062,7 +933,7 @@ template <bool LONG, int WLEN> __device__ __forceinline__ void slowWalk3W(U &u, 
                             pv.perfect = pv.semiperfect = 1;
                         } else {
                             pv.start = minStart;
-                            setPerfectW(u, S, pv.chrom, pv.strand, pv.start, pv.stop, pv.perfect, pv.semiperfect);
+                            setPerfect(u, S, pv.chrom, pv.strand, pv.start, pv.stop, pv.perfect, pv.semiperfect);
                         }
                         pv.score = betterScore;
                         wb = 3;
@@ -1080,7 +951,7 @@ template <bool LONG, int WLEN> __device__ __forceinline__ void slowWalk3W(U &u, 
                 pv.score = uni(pv.score); pv.perfect = uni(pv.perfect); pv.semiperfect = uni(pv.semiperfect); perfectsFound = uni(perfectsFound);
                 if (uni(makeNew)) {
                     int sp = perfect1 ? 1 : 0, ssemi = sp;
-                    if (!perfect1) setPerfectW(u, S, chrom, strand, site2, site3, sp, ssemi);
+                    if (!perfect1) setPerfect(u, S, chrom, strand, site2, site3, sp, ssemi);
                     sp = uni(sp); ssemi = uni(ssemi);
                     const int sg = withGaps ? ngaps : 0;
                     if (ssl.n >= ssl.cap) { ssl.overflow = true; finished = true; }
@@ -1230,32 +1101,6 @@ template <bool LONG, int WLEN> __device__ __forceinline__ void slowWalk3W(U &u, 
     bestScores[5] = perfectsFound;
 }
 
-// Solver.valueOfElement (current/align2/Solver.java:97-151)
-__device__ __forceinline__ long long valueOfElement(const int *offsets, int noffsets, const int *lengths, float keyWeight, int chunk,
-                                    const int *lists, int numlists, int index, long long pointsPerSite) {
-    const long long PPL = 30000, PPB1 = 6000, BONUS_END = 40000, WIDTH = 5500, SPACING = -30;
-    if (numlists < 1) return 0;
-    const int prospect = lists[index];
-    if (lengths[prospect] == 0) return -999999;
-    long long valuep = PPL + (PPL * 2 / numlists) + ((PPL * 10) / lengths[prospect]);
-    const long long valuem = pointsPerSite * lengths[prospect];
-    if (prospect == 0 || prospect == noffsets - 1) valuep += BONUS_END;
-    if (numlists == 1) { valuep += (WIDTH + PPB1) * chunk; return ((long long)__fmul_rn((float)valuep, keyWeight)) + valuem; }
-    const int first = lists[0], last = lists[numlists - 1];
-    const int offL = (prospect == first ? -1 : offsets[lists[index - 1]]);
-    const int offP = offsets[prospect];
-    const int offR = (prospect == last ? offsets[noffsets - 1] + 1 : offsets[lists[index + 1]]);
-    const int oldL = offP - offL, oldR = offR - offP, newS = offR - offL;
-    valuep += (long long)((oldL * oldL + oldR * oldR) - (newS * newS)) * SPACING;
-    int uniquelyCovered;
-    if (prospect == first) uniquelyCovered = offR - offP;
-    else if (prospect == last) uniquelyCovered = offP - offL;
-    else { const int b = offR - (offL + chunk); uniquelyCovered = b > 0 ? b : 0; }
-    if (prospect == first || prospect == last) valuep += (PPB1 + WIDTH) * uniquelyCovered;
-    else valuep += PPB1 * uniquelyCovered;
-    return ((long long)__fmul_rn((float)valuep, keyWeight)) + valuem;
-}
-
 // BBIndex.trimExcessHitListsByGreedy :266-350 (+ Solver.findWorstGreedy :46-95): lane j evaluates list position j,
 // the "first strict prefix minimum below the early-termination score" rule comes from an exclusive prefix-min scan.
 // x = lengths[lane] (COUNTS of the lane's key), key = keys[lane]; both are updated in place.
@@ -1345,7 +1190,7 @@ template <bool LONG, int WLEN> __device__ __forceinline__ int makeListsW(const U
     const bool live = u.lane < nh;
     L.row = __shfl(h.start, src); L.stop = L.row + __shfl(h.len, src); L.offs = __shfl(off, src); L.ksc = __shfl(ksc, src);
     const int first = __shfl(h.first, src);
-    L.value = live ? adjustSite(u, first, L.offs, baseChrom) : LANE_UNUSED;
+    L.value = live ? adjustSite(u.c, first, L.offs, baseChrom) : LANE_UNUSED;
     L.hv = live ? L.value : INT_MAX;
 #pragma unroll
     for (int j = 0; j < NB; j++) L.nb[j] = 0;
@@ -1570,10 +1415,10 @@ template <bool LONG, int WLEN> __global__ __launch_bounds__(64 * WAVES_PER_BLOCK
             if (bestScores[1] < p.minApproxHitsToKeep) dead = true;
             else if ((float)bestScores[3] < __fmul_rn((float)mqs, MIN_QSCORE_MULT2)) dead = true;
             else if (bestScores[3] >= mqs && pretend) {
-                hitsCutoff = calcApproxHitsCutoff(p, n, bestScores[1], p.minApproxHitsToKeep, true);
+                hitsCutoff = calcApproxHitsCutoff<ProfBBMap>(p, n, bestScores[1], p.minApproxHitsToKeep, true);
                 qscoreCutoff = max(qscoreCutoff, (int)(bestScores[3] * DYN_QSCORE_PERFECT));
             } else {
-                hitsCutoff = calcApproxHitsCutoff(p, n, bestScores[1], p.minApproxHitsToKeep, false);
+                hitsCutoff = calcApproxHitsCutoff<ProfBBMap>(p, n, bestScores[1], p.minApproxHitsToKeep, false);
                 qscoreCutoff = max(qscoreCutoff, (int)(bestScores[3] * PRESCAN_QSCORE_THRESH));
             }
         }

@@ -551,6 +551,12 @@ static inline int overlap(int a1, int b1, int a2, int b2) { return a2 <= b1 && b
 /* ------------------------------------------------------------------------------------ slowWalk3 */
 typedef struct { orc_site *v; int n, cap, overflow; } site_list;
 
+/* arm counters of slowWalk3's site bookkeeping, for the tests (which arms a problem set really takes; not thread-safe: meaningful
+ * after single-threaded runs): 0 same limits, 1-3 same start: perfect2 / perfect1 / extend, 4-6 same stop: perfect2 / perfect1 / extend,
+ * 7 overlapping but new (class 5), 8 new site without gaps, 9 new site with gaps, 10 list overflow, 11 stop after two perfects */
+static int64_t g_arm[12];
+void orc_index_arm_counts(int64_t *out12, int reset) { memcpy(out12, g_arm, sizeof g_arm); if (reset) memset(g_arm, 0, sizeof g_arm); }
+
 static void slow_walk3(const walker *w, int block, const int *starts, const int *stops, const uint8_t *bases, int blen,
                        const int8_t *baseScores, const int *keyScores, const int *offsets, int numKeys,
                        int baseChrom_, int strand, site_list *ssl, int *bestScores, int allBasesCovered,
@@ -646,7 +652,9 @@ static void slow_walk3(const walker *w, int block, const int *starts, const int 
                         prevSS->score = betterScore;
                         prevSS->perfect = (prevSS->perfect || perfect1 || perfect2);
                         if (prevSS->perfect) prevSS->semiperfect = 1;
+                        g_arm[0]++;
                     } else if (shortEnough && prevSS->start == site2 && !prevSS->semiperfect) {
+                        g_arm[perfect2 ? 1 : perfect1 ? 2 : 3]++;
                         if (perfect2) { }
                         else if (perfect1) {
                             prevSS->stop = site3; if (prevSS->ngaps) prevSS->gaps[prevSS->ngaps - 1] = site3;
@@ -658,6 +666,7 @@ static void slow_walk3(const walker *w, int block, const int *starts, const int 
                         }
                         prevSS->score = betterScore;
                     } else if (shortEnough && prevSS->stop == site3 && !prevSS->semiperfect) {
+                        g_arm[perfect2 ? 4 : perfect1 ? 5 : 6]++;
                         if (perfect2) { }
                         else if (perfect1) {
                             prevSS->start = site2; if (prevSS->ngaps) prevSS->gaps[0] = site2;
@@ -674,6 +683,7 @@ static void slow_walk3(const walker *w, int block, const int *starts, const int 
                         ss.perfect = ss.semiperfect = perfect1;
                         if (!perfect1) set_perfect(w->ix, &ss, bases, blen);
                         haveSS = 1;
+                        g_arm[7]++;
                     }
                 } else if (inbounds) {
                     memset(&ss, 0, sizeof ss);
@@ -682,9 +692,10 @@ static void slow_walk3(const walker *w, int block, const int *starts, const int 
                     if (!perfect1) set_perfect(w->ix, &ss, bases, blen);
                     ss.ngaps = ngaps; for (int g = 0; g < ngaps; g++) ss.gaps[g] = gapArr[g];
                     haveSS = 1;
+                    g_arm[ngaps > 0 ? 9 : 8]++;
                 }
                 if (haveSS) {
-                    if (ssl->n >= ssl->cap) { ssl->overflow = 1; finished = 1; }
+                    if (ssl->n >= ssl->cap) { ssl->overflow = 1; finished = 1; g_arm[10]++; }
                     else {
                         ssl->v[ssl->n] = ss;
                         const int idx = ssl->n++;
@@ -692,7 +703,7 @@ static void slow_walk3(const walker *w, int block, const int *starts, const int 
                             const orc_site *pv = prevIdx >= 0 ? &ssl->v[prevIdx] : NULL;
                             if (!pv || !pv->perfect || !(pv->chrom == ss.chrom && pv->strand == ss.strand && overlap(ss.start, ss.stop, pv->start, pv->stop))) {
                                 perfectsFound++;
-                                if (p->quitAfterTwoPerfects && perfectsFound >= 2) { prevIdx = idx; break; }
+                                if (p->quitAfterTwoPerfects && perfectsFound >= 2) { prevIdx = idx; g_arm[11]++; break; }
                             }
                         }
                         prevIdx = idx;

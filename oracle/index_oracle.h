@@ -71,6 +71,10 @@ int orc_index_find(const orc_index *ix, const uint8_t *basesP, const uint8_t *ba
                    const int8_t *baseScoresP, const int32_t *keyScoresP, const int32_t *offsets, int nkeys,
                    orc_site *out, int cap, int64_t *stats);
 
+/* How often each arm of slowWalk3's site bookkeeping ran since the last reset (12 x int64, see g_arm in index_oracle.c); for the
+ * tests, not thread-safe. */
+void orc_index_arm_counts(int64_t *out12, int reset);
+
 /* KeyRing.makeOffsets(readlen, blocksize, density, minKeys) (KeyRing.java:255-297, :186-229).  Returns count. */
 int orc_make_offsets(int readlen, int blocksize, float density, int minKeysDesired, int32_t *out, int cap);
 

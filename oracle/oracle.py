@@ -333,6 +333,19 @@ class OracleIndex:
                     perfect=o.perfect, semiperfect=o.semiperfect, gaps=list(o.gaps[:o.ngaps])) for o in out[:n]]
         return (res, st.tolist()) if want_stats else res
 
+    ARMS = ("same_limits", "same_start_perfect2", "same_start_perfect1", "same_start_extend", "same_stop_perfect2",
+            "same_stop_perfect1", "same_stop_extend", "overlapping_new", "new_site", "new_site_with_gaps", "overflow",
+            "two_perfects")
+
+    def arm_counts(self, reset=True):
+        """How often each arm of slowWalk3's site bookkeeping ran in this library since the last reset (index_oracle.c: g_arm);
+        single-threaded runs only."""
+        out = np.zeros(len(self.ARMS), np.int64)
+        self.L.orc_index_arm_counts.argtypes = [C.c_void_p, C.c_int]
+        self.L.orc_index_arm_counts.restype = None
+        self.L.orc_index_arm_counts(out.ctypes.data, 1 if reset else 0)
+        return dict(zip(self.ARMS, out.tolist()))
+
 
 class OracleIndexView(OracleIndex):
     """The oracle's probe over index arrays that already exist (a device-built index exported to the host; the GPU tests show

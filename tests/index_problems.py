@@ -75,3 +75,20 @@ def make_reads(seed, genomes, n, read_len=150, k=13, density=1.9):
             bs = [rng.randint(0, 30) for _ in range(L)]
         out.append((bp, revcomp(bp), bs, ks, offs, (ci + 1, strand, st)))
     return out
+
+
+# Two seeds of the set-up below reach every arm of slowWalk3's site bookkeeping that can be reached at all (counted on the oracle,
+# see tests/test_oracle_index.py): seed 7 extends a site at the same stop by a perfect one, seed 26 extends one at the same start.
+BOOKKEEPING_SEEDS = (7, 26)
+BOOKKEEPING_K, BOOKKEEPING_CHROMBITS = 10, 1
+BOOKKEEPING_CAPS = (48, 2)          # the second run of the same reads overflows the site list
+
+
+def bookkeeping_problems():
+    """The fixed "bookkeeping" problem set: [(genomes, reads)] with two chromosomes of 40 kb and 30 kb per seed, for k = 10 and
+    chromBits = 1, to be probed once per cap of BOOKKEEPING_CAPS."""
+    out = []
+    for s in BOOKKEEPING_SEEDS:
+        genomes = [make_genome(1000 + s, 40000), make_genome(2000 + s, 30000)]
+        out.append((genomes, make_reads(s, genomes, 300, k=BOOKKEEPING_K)))
+    return out

@@ -5,6 +5,7 @@ import pytest
 
 from bbmap_amd.index import HostIndex, DeviceIndex
 from oracle.oracle import OracleIndex
+from tests import index_problems as IP
 from tests.index_problems import make_genome, make_reads
 
 pytestmark = pytest.mark.gpu
@@ -48,6 +49,31 @@ def test_single_chromosome_k13():
     genomes = [make_genome(31, 250000)]
     reads = make_reads(7, genomes, 600, k=13)
     assert run_case(genomes, 13, None, reads) > 400
+
+
+def test_site_bookkeeping_arms_through_every_route():
+    """The problem set on which the oracle takes every reachable arm of slowWalk3's site merge (tests/test_oracle_index.py counts
+    them), SiteScore by SiteScore (gap arrays, perfect and semiperfect included) through the wave kernel's four forms, the
+    per-lane kernel and the long-read kernel with BBIndex's constants; with a cap of 2 every route reports overflow for exactly
+    the oracle's reads."""
+    k, chromBits = IP.BOOKKEEPING_K, IP.BOOKKEEPING_CHROMBITS
+    for genomes, reads in IP.bookkeeping_problems():
+        oi = OracleIndex(genomes, k=k, chromBits=chromBits)
+        di = DeviceIndex(HostIndex(genomes, k=k, chromBits=chromBits))
+        di.set_kernel("long")
+        for cap in IP.BOOKKEEPING_CAPS:
+            assert run_case(genomes, k, chromBits, reads, cap=cap) > 100            # reads with a site list that fits the cap
+            exp = []
+            for bp, bm, bs, ks, offs, truth in reads:
+                try:
+                    exp.append(oi.find(bp, bm, bs, ks, offs, cap=cap))
+                except RuntimeError:
+                    exp.append(None)
+            assert (cap == 2) == any(e is None for e in exp)
+            got = di.find_batch([(bp, bs, ks, offs) for bp, bm, bs, ks, offs, t in reads], max_sites=cap)
+            for i, r in enumerate(reads):
+                assert got[i] == exp[i], "long kernel, cap %d, read %d (truth %s): %s != %s" % (cap, i, r[5], got[i], exp[i])
+        di.close()
 
 
 def test_two_blocks_small_k():

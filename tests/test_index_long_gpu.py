@@ -100,7 +100,11 @@ def test_pacbio_profile_index_and_probe():
     found = _compare(di, oi, reads, 64)
     assert found >= 30
     # the true site is among the sites of nearly every non-junk read
+    oi.arm_counts()
     exp = [oi.find(bp, bm, bs, ks, offs, cap=64) for bp, bm, bs, ks, offs, t in reads]
+    # the site merge of this profile is exercised: same limits, an extension, a new site with a gap array
+    arms = oi.arm_counts()
+    assert arms["same_limits"] >= 1 and arms["same_stop_extend"] + arms["same_start_extend"] >= 1 and arms["new_site_with_gaps"] >= 1, arms
     hits = 0
     for (bp, bm, bs, ks, offs, (chrom, strand, st)), sites in zip(reads, exp):
         hits += any(s["chrom"] == chrom and s["strand"] == strand and abs(s["start"] - st) < 400 for s in sites)

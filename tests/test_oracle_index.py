@@ -5,6 +5,7 @@ import numpy as np
 
 from bbmap_amd.index import HostIndex
 from oracle.oracle import OracleIndex, make_offsets
+from tests import index_problems as IP
 from tests.index_problems import make_genome, make_reads, revcomp
 
 
@@ -61,3 +62,40 @@ def test_mutated_reads_mostly_found_near_truth():
             assert r["start"] <= r["stop"] and r["hits"] >= 1
             assert not r["perfect"] or r["semiperfect"]
     assert found > 0.8 * total
+
+
+# Arms of the site bookkeeping no input reaches.  Both perfect2 arms need a previous site with score == maxScore on a fully defined
+# read that is not semiperfect, but such a score only enters a stored site together with perfect = semiperfect = 1 (as a new site,
+# through the same-limits arm or through a perfect1 arm).  The same-start perfect1 arm needs a perfect site whose start equals the
+# previous site's: a perfect site starts at its own centre (every base lies on the centre's diagonal), the previous site starts at
+# or below ITS centre (the centre key's bases always go to the centre's diagonal, merges only lower a start), and centres are
+# visited in strictly ascending order.  A search over seeds 0..299 of the set-up of bookkeeping_problems() never reached them.
+UNREACHABLE_ARMS = ("same_start_perfect2", "same_stop_perfect2", "same_start_perfect1")
+
+
+def test_bookkeeping_set_reaches_every_arm_of_the_site_merge():
+    import time
+    t0 = time.time()
+    total = dict.fromkeys(OracleIndex.ARMS, 0)
+    for genomes, reads in IP.bookkeeping_problems():
+        oi = OracleIndex(genomes, k=IP.BOOKKEEPING_K, chromBits=IP.BOOKKEEPING_CHROMBITS)
+        oi.arm_counts()
+        for cap in IP.BOOKKEEPING_CAPS:
+            overflows = 0
+            for bp, bm, bs, ks, offs, truth in reads:
+                try:
+                    oi.find(bp, bm, bs, ks, offs, cap=cap)
+                except RuntimeError:
+                    overflows += 1
+            counts = oi.arm_counts()
+            assert (overflows > 0) == (cap == 2) and (counts["overflow"] > 0) == (cap == 2), (cap, overflows, counts)
+            for arm, n in counts.items():
+                total[arm] += n
+    seconds = time.time() - t0
+    print(total, "%.2f s" % seconds)
+    for arm in OracleIndex.ARMS:
+        if arm in UNREACHABLE_ARMS:
+            assert total[arm] == 0, (arm, total)
+        else:
+            assert total[arm] >= 1, (arm, total)
+    assert seconds < 3.0, seconds
