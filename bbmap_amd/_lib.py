@@ -25,6 +25,7 @@ EXPORTS = [
     "bbmap_get_final", "bbmap_set_average_pair_dist", "bbmap_final_batch_device",
     "bbidx_set_scaffolds", "bbmap_get_scaffold_records",
     "bbmap_get_sam_records", "bbmap_get_sam",
+    "bbkeys_device_workspace_bytes", "bbkeys_make_batch_device",
 ]
 
 

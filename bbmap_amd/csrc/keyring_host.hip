@@ -3,7 +3,8 @@
 // In the reference this is per-read Java on the mapping thread, float arithmetic on the read's qualities: key error probabilities
 // (QualityTools.makeKeyProbs), key placement (KeyRing.makeOffsets3), key scores (QualityTools.makeKeyScores) and base scores
 // (QualityTools.makeByteScoreArray).  Its integer outputs -- offsets[K], keyScoresP[K], baseScoresP[L] -- are what the device probe
-// takes (bbidx_read + keyinfo + baseScores, include/bbmap_amd.h), so it stays on the host here too.
+// takes (bbidx_read + keyinfo + baseScores, include/bbmap_amd.h).  This is the host form, read by read on the calling thread, and the
+// reference for the device form beside it (keyring_device.hip: bbkeys_make_batch_device, byte for byte the same output).
 // Java float semantics: every operation below is a single-precision IEEE operation (the library is built with -ffp-contract=off
 // -fno-fast-math); Math.round(float) is floor(x + 0.5) evaluated exactly, Math.ceil / Math.pow / Math.log10 work on doubles.
 #include <cmath>
@@ -12,25 +13,13 @@
 #include <vector>
 
 #include "bbmap_amd.h"
+#include "keyring_shared.h"
 
 void bbmap_set_error(const char *msg);
 
 namespace {
 
-struct QualTables {
-    float probError[128], probCorrect[128], probCorrectInverse[128];
-    QualTables() {                                      // QualityTools.java:475-480, :519-539
-        for (int i = 0; i < 128; i++) probError[i] = (float)pow(10.0, 0 - .1 * i);
-        probError[0] = .8f;
-        for (int i = 0; i < 128; i++) { probCorrect[i] = 1 - probError[i]; probCorrectInverse[i] = 1 / probCorrect[i]; }
-    }
-};
-const QualTables &tables() { static const QualTables t; return t; }
-
-inline int java_round(float f) { return (int)floor((double)f + 0.5); }          // Math.round(float)
-inline int imin(int a, int b) { return a < b ? a : b; }
-inline int imax(int a, int b) { return a > b ? a : b; }
-inline bool fully_defined(int b) { const int u = b & ~32; return b < 128 && (u == 'A' || u == 'C' || u == 'G' || u == 'T' || u == 'U'); }
+using namespace bbkeys;          // keyring_shared.h: the quality tables, java_round, fully_defined, desired_keys_from_density
 
 // QualityTools.makeKeyProbs(quality, bases, keylen, out, useModulo=false) :188-247 / :250-279
 void make_key_probs(const uint8_t *quality, int len, int keylen, float *out) {
@@ -53,14 +42,6 @@ void make_key_probs(const uint8_t *quality, int len, int keylen, float *out) {
         out[a + 1] = 1 - key1;
         if (timeSinceZero < keylen) out[a + 1] = 1;
     }
-}
-
-// KeyRing.desiredKeysFromDensity :269-282
-int desired_keys_from_density(int readlen, int blocksize, float density, int minKeysDesired) {
-    const int slots = readlen - blocksize + 1;
-    int desired = (int)ceil((double)((readlen * density) / blocksize));
-    desired = imax(minKeysDesired, desired);
-    return imin(slots, desired);
 }
 
 // KeyRing.makeOffsets3 :396-506 (KEEP_BAD_KEYS = false); returns the number of offsets written, 0 for null
@@ -115,12 +96,7 @@ int avg_quality_by_probability(const uint8_t *bases, const uint8_t *quality, int
     const QualTables &T = tables();
     float sum = 0;
     for (int i = 0; i < len; i++) if (fully_defined(bases[i])) sum += T.probError[quality[i] & 127];
-    const float p = sum / len;
-    const double prob = 1 - (double)(1 - p);
-    double phred;
-    if (prob >= 1) phred = 0; else if (prob <= 0.000001) phred = 60; else phred = -10 * log10(prob);
-    const long q = (long)floor(phred + 0.5);
-    return (int)(q < 0 ? 0 : (q > 41 ? 41 : q));          // Read.MAX_CALLED_QUALITY = 41; only `< 2` is ever asked of this value here
+    return avg_quality_from_p(sum / len);
 }
 
 }  // namespace

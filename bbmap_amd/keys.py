@@ -1,5 +1,6 @@
-"""Binding of bbkeys_*: the probe's per-read inputs (key offsets, key scores, base scores), made on the host exactly where the
-reference makes them -- AbstractMapThread.quickMap up to its findAdvanced call (current/align2/AbstractMapThread.java:642-728)."""
+"""Binding of bbkeys_*: the probe's per-read inputs (key offsets, key scores, base scores) -- AbstractMapThread.quickMap up to its
+findAdvanced call (current/align2/AbstractMapThread.java:642-728).  make_keys / make_batch run the host form over numpy arrays,
+make_batch_device the device form over torch tensors; both give byte for byte the same output."""
 import ctypes as C
 
 import numpy as np
@@ -71,3 +72,67 @@ def make_batch(reads, qualities=None, cfg=None):
                                    None if qblob is None else qblob.ctypes.data, recs.ctypes.data, keyinfo.ctypes.data, cap, bs.ctypes.data,
                                    C.byref(used)), "bbkeys_make_batch")
     return recs, blob, bs, keyinfo[:max(1, used.value)].copy()
+
+
+_workspace = {}          # torch device -> the uint8 tensor make_batch_device hands to the library, grown on demand
+
+
+def _bind_device(L):
+    L.bbkeys_device_workspace_bytes.argtypes = [C.POINTER(bbkeys_config), C.c_int64, C.c_int64]
+    L.bbkeys_device_workspace_bytes.restype = C.c_int64
+    L.bbkeys_make_batch_device.argtypes = [C.POINTER(bbkeys_config), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    L.bbkeys_make_batch_device.restype = C.c_int
+
+
+def workspace_bytes(cfg, n_reads, total_bases):
+    L = _lib.load()
+    _bind_device(L)
+    nb = L.bbkeys_device_workspace_bytes(C.byref(cfg), n_reads, total_bases)
+    if nb < 0:
+        _lib.check(int(nb), "bbkeys_device_workspace_bytes")
+    return int(nb)
+
+
+def keyinfo_bound(cfg, n_reads, total_bases):
+    """Ints of keyinfo that hold the keys of any n_reads reads with total_bases bases in all: a read gets at most
+    max(2, ceil(len * keyDensity / k)) keys (KeyRing.desiredKeysFromDensity), and never more than len."""
+    per_base = float(cfg.keyDensity) / cfg.k
+    return 2 * min(total_bases, 3 * n_reads + int(np.ceil(total_bases * per_base * 1.001)) + 1)
+
+
+def make_batch_device(recs, bases, quality=None, cfg=None, keyinfo_cap=None):
+    """bbkeys_make_batch_device: the key stage over a batch that is already in device memory.  recs: the uint8 view of READ_DTYPE as
+    Mapper.reads holds it (bases_off and len filled in), bases / quality: uint8 device tensors (quality numeric phred, or None).
+    Fills recs' keys_off / nkeys in place and returns (recs, keyinfo[:used], base_scores), device tensors; keyinfo_cap: ints of
+    keyinfo to allocate (default: enough for any qualities).  Runs on the current stream and waits for it.  As with the mapper, torch
+    must have been imported before the library is first loaded (bbmap_amd.mapper imports it at its top), so that both use one HIP
+    runtime."""
+    import torch
+    L = _lib.load()
+    _bind_device(L)
+    cfg = cfg or default_config()
+    dev = bases.device
+    assert recs.dtype == torch.uint8 and recs.is_contiguous() and recs.numel() % READ_DTYPE.itemsize == 0 and recs.device == dev
+    assert bases.dtype == torch.uint8 and bases.is_contiguous()
+    assert quality is None or (quality.dtype == torch.uint8 and quality.is_contiguous() and quality.device == dev and quality.numel() >= bases.numel())
+    n = recs.numel() // READ_DTYPE.itemsize
+    total = int(recs.view(torch.int32).view(-1, 6)[:, 4].clamp(min=0).sum(dtype=torch.int64).item()) if n else 0
+    cap = keyinfo_bound(cfg, n, total) if keyinfo_cap is None else int(keyinfo_cap)
+    keyinfo = torch.empty(max(1, cap), dtype=torch.int32, device=dev)
+    base_scores = torch.zeros(max(1, bases.numel()), dtype=torch.int8, device=dev)
+    need = workspace_bytes(cfg, n, total)
+    ws = _workspace.get(dev)
+    if ws is None or ws.numel() < need:
+        _workspace[dev] = ws = torch.empty(need + need // 8 + 256, dtype=torch.uint8, device=dev)
+    used = C.c_int64(0)
+    if bases.numel() == 0:          # (an empty tensor has no address; the library wants one even for reads without bases)
+        bases = torch.zeros(1, dtype=torch.uint8, device=dev)
+        quality = None if quality is None else bases
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = L.bbkeys_make_batch_device(C.byref(cfg), C.c_void_p(stream), n, recs.data_ptr(), bases.data_ptr(),
+                                        None if quality is None else quality.data_ptr(), keyinfo.data_ptr(), cap, base_scores.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), C.byref(used))
+    _lib.check(rc, "bbkeys_make_batch_device")
+    return recs, keyinfo[:used.value], base_scores

@@ -174,6 +174,51 @@ class Mapper:
         self.keyinfo = torch.from_numpy(np.ascontiguousarray(keyinfo, np.int32)).to(self.dev)
         return self
 
+    @classmethod
+    def from_reads(cls, di, lens, bases, quality=None, kcfg=None, paired=False, device=0, max_sites=32, profile=0, **cfg_kw):
+        """from_records for reads that have no keys yet: lens (one per read) and the bases blob the reads lie in back to back, with
+        their numeric phred qualities at the same offsets or None.  Uploads them and runs quickMap's key stage on the device
+        (bbmap_amd.keys.make_batch_device), so reads, keyinfo and base_scores exist in device memory only.  kcfg: a bbkeys_config
+        (default: keys.default_config(profile)); profile and cfg_kw as in from_records."""
+        from . import keys as K
+        self = cls.__new__(cls)
+        self.L = _lib.load()
+        _bind(self.L)
+        lens = np.ascontiguousarray(lens, np.int32)
+        n = len(lens)
+        recs = np.zeros(n, READ_DTYPE)
+        recs["len"] = lens
+        if n > 1:
+            recs["bases_off"][1:] = np.cumsum(lens[:-1].astype(np.int64))
+        blob = np.ascontiguousarray(bases, np.uint8).reshape(-1)
+        assert blob.size >= int(lens.astype(np.int64).sum())
+        self.di, self.n, self.paired = di, n, paired
+        self.read_len = int(lens.max()) if n else 0
+        self.dev = torch.device("cuda", device)
+        if profile == 0:
+            di.set_max_read_len(max(1, self.read_len))
+        cfg = bbmap_config()
+        _lib.check(self.L.bbmap_default_config_profile(profile, C.byref(cfg)), "bbmap_default_config_profile")
+        cfg.device, cfg.paired, cfg.max_reads, cfg.max_read_len, cfg.max_sites = device, int(paired), n, max(1, self.read_len), max_sites
+        for k, v in cfg_kw.items():
+            setattr(cfg, k, v)
+        self.cfg = cfg
+        h = C.c_void_p()
+        _lib.check(self.L.bbmap_create(di.h, C.byref(cfg), C.byref(h)), "bbmap_create")
+        self.h = h
+        self.total_bytes = int(blob.size)
+        self.bases = torch.zeros(2 * self.total_bytes, dtype=torch.uint8, device=self.dev)
+        self.bases[: self.total_bytes].copy_(torch.from_numpy(blob))
+        q = None
+        if quality is not None:
+            qblob = np.ascontiguousarray(quality, np.uint8).reshape(-1)
+            assert qblob.size == blob.size
+            q = torch.from_numpy(qblob).to(self.dev)
+        self.reads = torch.from_numpy(recs.view(np.uint8).reshape(-1).copy()).to(self.dev)
+        _, keyinfo, self.base_scores = K.make_batch_device(self.reads, self.bases[: self.total_bytes], q, kcfg or K.default_config(profile))
+        self.keyinfo = keyinfo if keyinfo.numel() else torch.zeros(1, dtype=torch.int32, device=self.dev)
+        return self
+
     def close(self):
         if getattr(self, "h", None):
             self.L.bbmap_destroy(self.h)

@@ -427,11 +427,13 @@ int bbidx_set_scaffolds(bbidx_ctx *ctx, int32_t nchroms, const int32_t *counts, 
                         const int32_t *const *lengths, int32_t inter_scaffold_padding);
 
 /* =====================================================================================
- * The probe's per-read inputs, host side: AbstractMapThread.quickMap up to its findAdvanced call
+ * The probe's per-read inputs: AbstractMapThread.quickMap up to its findAdvanced call
  *   (current/align2/AbstractMapThread.java:642-728): key error probabilities from the qualities (QualityTools.makeKeyProbs,
  *   current/align2/QualityTools.java:188-279), key placement (KeyRing.makeOffsets3, current/align2/KeyRing.java:396-506, with the
  *   density window of :663-676), key scores (QualityTools.makeKeyScores :125-133) and base scores (makeByteScoreArray :145-181).
- *   Float code on the mapping thread in the reference, host code here; its integer outputs are the probe's inputs.
+ *   Float code on the mapping thread in the reference; its integer outputs are the probe's inputs.  Two forms with byte for byte the
+ *   same output: host code, read by read (bbkeys_make, bbkeys_make_batch), and kernels over a batch that is already in device memory
+ *   (bbkeys_make_batch_device: one read per lane, no libm on the device).
  * ===================================================================================== */
 typedef struct bbkeys_config {
     int32_t k;                      /* KEYLEN */
@@ -452,6 +454,22 @@ int bbkeys_make(const bbkeys_config *cfg, const uint8_t *bases, const uint8_t *q
 int bbkeys_make_batch(const bbkeys_config *cfg, int64_t n_reads, const int64_t *bases_off, const int32_t *lens,
                       const uint8_t *bases, const uint8_t *quality, bbidx_read *reads, int32_t *keyinfo, int64_t keyinfo_cap,
                       int8_t *baseScores, int64_t *keyinfo_used);
+/* bytes of device workspace bbkeys_make_batch_device needs for a batch of n_reads reads and total_bases bases (the sum of the reads'
+ * len); < 0 on a bad argument */
+int64_t bbkeys_device_workspace_bytes(const bbkeys_config *cfg, int64_t n_reads, int64_t total_bases);
+/* Device form of bbkeys_make_batch.  reads[i].bases_off / .len are inputs, .keys_off / .nkeys outputs; reads, bases, quality (or
+ * NULL), keyinfo, baseScores and workspace (256-byte aligned) are device pointers on the current device.  Enqueues on `stream` and
+ * waits for it (the key total is needed on the host); *keyinfo_used (host) = ints written.  Writes baseScores over the reads'
+ * [bases_off, bases_off + len) ranges only and keyinfo[0 .. *keyinfo_used) only; makes no device allocation.
+ *   BBMAP_E_ARG before anything is launched: a bad argument, or a workspace smaller than n_reads alone demands.  The lengths live on
+ *     the device, so the full test -- workspace_bytes >= bbkeys_device_workspace_bytes(cfg, n_reads, sum of len) -- follows once they
+ *     have been summed: BBMAP_E_ARG with nothing but the workspace written.
+ *   BBMAP_E_ARG when the keys need more than keyinfo_cap ints: keyinfo and reads are untouched (baseScores are written) and
+ *     *keyinfo_used = the size needed, so the caller can retry.
+ *   BBMAP_E_NODEVICE without a gfx950 device.  n_reads == 0: BBMAP_OK, *keyinfo_used = 0. */
+int bbkeys_make_batch_device(const bbkeys_config *cfg, void *stream, int64_t n_reads, bbidx_read *reads,
+                             const uint8_t *bases, const uint8_t *quality, int32_t *keyinfo, int64_t keyinfo_cap,
+                             int8_t *baseScores, void *workspace, int64_t workspace_bytes, int64_t *keyinfo_used);
 
 /* =====================================================================================
  * Batch helpers (device-resident) used by the mapper below; also callable on their own.
