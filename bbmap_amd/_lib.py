@@ -26,6 +26,8 @@ EXPORTS = [
     "bbidx_set_scaffolds", "bbmap_get_scaffold_records",
     "bbmap_get_sam_records", "bbmap_get_sam",
     "bbkeys_device_workspace_bytes", "bbkeys_make_batch_device",
+    "bbpipe_run_stats_device", "bbmap_add_run_stats", "bbmap_get_run_stats", "bbmap_reset_run_stats", "bbmap_set_adaptive", "bbmap_set_truth",
+    "bbmap_get_adaptive_state",
 ]
 
 

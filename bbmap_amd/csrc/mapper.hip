@@ -30,6 +30,7 @@
 
 #include "bbmap_amd.h"
 #include "index_ctx.h"
+#include "run_stats.h"
 #include "sam_records.h"
 #include "scaffold.h"
 
@@ -54,6 +55,7 @@ struct Settings {
     float minRatio, ratioPaired, ratioPreRescue;
     int slowAlignPadding, slowRescuePadding, extraPadding, tipSearchDist, maxPairDist, averagePairDist, maxRescueDist,
         maxRescueMismatches, maxTrimSitesToRetain, trimList, doRescue, alignColumns, clearzone3, maxIndel, expLimit, paired;
+    int rescueSkip;             // rescue() returns at once: "mating is not working" (AbstractMapThread.java:1146; bbmap_set_adaptive)
     // the aligner class's points (MultiStateAligner11ts: jni/MultiStateAligner11tsJNI.c:18-98; MultiStateAligner9PacBio:
     // current/align2/MultiStateAligner9PacBio.java:2375-2407): POINTS_MATCH, POINTS_MATCH2, POINTS_SUB / SUB2 / SUB3,
     // min(POINTS_DEL, POINTS_INS - POINTS_MATCH2) of maxImperfectScore, and CLEARZONE1e = 2*MATCH2 - MATCH - SUB + 1
@@ -884,7 +886,7 @@ __global__ __launch_bounds__(128) void rescue_plan_kernel(const Dev D) {
     na = remove_low_quality_paired(sa, na, max_quality(D.S, lenA), D.S.ratioPreRescue, D.S.ratioPreRescue);
     D.mcount[ra] = na;
     const int searchDist = imin(D.S.maxPairDist, 2 * D.S.averagePairDist + 100);
-    if (searchDist > D.S.maxRescueDist || na == 0) { D.pres[p] = pr; return; }
+    if (D.S.rescueSkip || searchDist > D.S.maxRescueDist || na == 0) { D.pres[p] = pr; return; }        // :1146-1151
     const int maxLooseSw = max_quality(D.S, L), maxAnchorSw = max_quality(D.S, lenA), maxImp = max_imperfect(D.S, L);
     const int bestLoose = nl == 0 ? 0 : sl[0].slowScore, bestAnchor = sa[0].slowScore;
     if (bestLoose == maxLooseSw && bestAnchor == maxAnchorSw && sa[0].pairedScore > 0) { D.pres[p] = pr; return; }
@@ -1239,6 +1241,13 @@ struct bbmap_ctx {
     void *d_samTmp = nullptr; size_t samTmpBytes = 0;
     uint8_t *d_samText = nullptr; size_t samTextCap = 0;
     long long samTextBytes = 0;
+    // run statistics (bbmap_add_run_stats): the running counters and the insert-size histogram, allocated on first use
+    unsigned long long *d_runStats = nullptr, *d_insertHist = nullptr;
+    bool statsCounted = false;      // the last batch is in the counters already
+    int adaptive = 0;               // BBMAP_ADAPT_*
+    long long numMatedSeen = 0;     // numMated after the last accumulation the insert-length rule looked at
+    const bbmap_truth *truthNext = nullptr;     // bbmap_set_truth: for the next batch's own accumulation
+    hipStream_t statsStream = nullptr;          // the stream of the last accumulation: the only work that writes the counters
 };
 
 static thread_local char g_merr[320];
@@ -1339,7 +1348,7 @@ static int create_impl(bbidx_ctx *index, const bbmap_config *cfg, bbmap_ctx *par
     S.tipSearchDist = cfg->tipSearchDist; S.maxPairDist = cfg->maxPairDist; S.averagePairDist = cfg->averagePairDist;
     S.maxRescueDist = cfg->maxRescueDist; S.maxRescueMismatches = cfg->maxRescueMismatches; S.maxTrimSitesToRetain = cfg->maxTrimSitesToRetain;
     S.trimList = cfg->trimList; S.doRescue = cfg->doRescue; S.alignColumns = cfg->alignColumns; S.clearzone3 = cfg->clearzone3;
-    S.maxIndel = index->dev.p.maxIndel; S.paired = cfg->paired;
+    S.maxIndel = index->dev.p.maxIndel; S.paired = cfg->paired; S.rescueSkip = 0;
     if (pacbio) { S.ptsMatch = 90; S.ptsMatch2 = 100; S.ptsSub = -137; S.ptsSub2 = -49; S.ptsSub3 = -25; S.impDelta = -305; }   // min(-292, -205 - 100)
     else { S.ptsMatch = 70; S.ptsMatch2 = 100; S.ptsSub = -127; S.ptsSub2 = -51; S.ptsSub3 = -25; S.impDelta = -495; }          // min(-472, -395 - 100)
     S.clearzone1e = 2 * S.ptsMatch2 - S.ptsMatch - S.ptsSub + 1;
@@ -1869,15 +1878,11 @@ static int tier_finish(bbmap_ctx *c, hipStream_t stream) {
     return BBMAP_OK;
 }
 
-extern "C" int bbmap_map_batch_device(bbmap_ctx *c, void *stream_, int64_t n_reads, const bbidx_read *reads, uint8_t *bases,
-                                      int64_t minus_delta, const int8_t *baseScores, const int32_t *keyinfo) {
-    if (!c) return mfail(BBMAP_E_ARG, "bbmap_map_batch_device: null context");
-    if (n_reads < 0 || n_reads > c->cfg.max_reads) return mfail(BBMAP_E_ARG, "bbmap_map_batch_device: more reads than the context was made for");
-    if (c->cfg.paired && (n_reads & 1)) return mfail(BBMAP_E_ARG, "bbmap_map_batch_device: paired mode takes an even number of reads");
-    if (n_reads == 0) { c->ran = false; return BBMAP_OK; }
-    if (!reads || !bases || !baseScores || !keyinfo) return mfail(BBMAP_E_ARG, "bbmap_map_batch_device: null buffer");
-    hipStream_t stream = (hipStream_t)stream_;
-    MHIP(hipSetDevice(c->cfg.device));
+static int rescue_skip_rule(bbmap_ctx *c, bool *skip);
+static int adapt_after_batch(bbmap_ctx *c, hipStream_t stream);
+
+static int map_batch_device(bbmap_ctx *c, hipStream_t stream, int64_t n_reads, const bbidx_read *reads, uint8_t *bases,
+                            int64_t minus_delta, const int8_t *baseScores, const int32_t *keyinfo) {
     c->batch = {n_reads, reads, bases, minus_delta, baseScores, keyinfo};
     c->tierStarted = false; c->tierReads = 0;
     if (c->tier) c->tier->ran = false;
@@ -1911,6 +1916,30 @@ extern "C" int bbmap_map_batch_device(bbmap_ctx *c, void *stream_, int64_t n_rea
     return BBMAP_OK;
 }
 
+extern "C" int bbmap_map_batch_device(bbmap_ctx *c, void *stream_, int64_t n_reads, const bbidx_read *reads, uint8_t *bases,
+                                      int64_t minus_delta, const int8_t *baseScores, const int32_t *keyinfo) {
+    if (!c) return mfail(BBMAP_E_ARG, "bbmap_map_batch_device: null context");
+    if (n_reads < 0 || n_reads > c->cfg.max_reads) return mfail(BBMAP_E_ARG, "bbmap_map_batch_device: more reads than the context was made for");
+    if (c->cfg.paired && (n_reads & 1)) return mfail(BBMAP_E_ARG, "bbmap_map_batch_device: paired mode takes an even number of reads");
+    if (n_reads == 0) { c->ran = false; c->truthNext = nullptr; return BBMAP_OK; }      // (the truth array was for this batch alone)
+    if (!reads || !bases || !baseScores || !keyinfo) return mfail(BBMAP_E_ARG, "bbmap_map_batch_device: null buffer");
+    hipStream_t stream = (hipStream_t)stream_;
+    MHIP(hipSetDevice(c->cfg.device));
+    c->statsCounted = false;
+    const bbmap_truth *truth = c->truthNext;
+    c->truthNext = nullptr;
+    bool skip = false;
+    if (c->adaptive & BBMAP_ADAPT_RESCUE_SKIP) MTRY(rescue_skip_rule(c, &skip));
+    c->S.rescueSkip = skip ? 1 : 0;
+    if (c->tier) c->tier->S.rescueSkip = c->S.rescueSkip;
+    MTRY(map_batch_device(c, stream, n_reads, reads, bases, minus_delta, baseScores, keyinfo));
+    if (c->adaptive && c->S.finalStage) {
+        MTRY(bbmap_add_run_stats(c, stream, truth));
+        MTRY(adapt_after_batch(c, stream));
+    }
+    return BBMAP_OK;
+}
+
 // The final alignment stage alone, over site lists the caller provides (see include/bbmap_amd.h).
 extern "C" int bbmap_final_batch_device(bbmap_ctx *c, void *stream_, int64_t n_reads, const bbidx_read *reads, uint8_t *bases, int64_t minus_delta,
                                         const bbmap_msite *sites, const int32_t *nsites) {
@@ -1922,6 +1951,7 @@ extern "C" int bbmap_final_batch_device(bbmap_ctx *c, void *stream_, int64_t n_r
     MHIP(hipSetDevice(c->cfg.device));
     c->tierStarted = false; c->tierReads = 0;
     if (c->tier) c->tier->ran = false;
+    c->statsCounted = false;
     memset(&c->stats, 0, sizeof c->stats);
     c->stats.reads = n_reads;
     c->batch = {n_reads, reads, bases, minus_delta, nullptr, nullptr};
@@ -2137,6 +2167,19 @@ extern "C" int bbmap_get_final(bbmap_ctx *c, int64_t n_reads, bbmap_final *out, 
     return BBMAP_OK;
 }
 
+// read -> overflow-tier record of the last batch (-1 = not a tier read); *out = nullptr when the tier mapped no read
+static int tier_index(bbmap_ctx *c, hipStream_t stream, long long n, const int **out) {
+    *out = nullptr;
+    if (!(c->tier && c->tierReads > 0 && c->tier->ran && n > 0)) return BBMAP_OK;
+    if (!c->d_scafTier) MTRY(dalloc(c, &c->d_scafTier, (size_t)c->cfg.max_reads));
+    MHIP(hipMemsetAsync(c->d_scafTier, 0xff, (size_t)n * 4, stream));
+    hipLaunchKernelGGL(bbmapper::tier_index_kernel, dim3((unsigned)((c->tierReads + 255) / 256)), dim3(256), 0, stream, c->d_tierReadIds,
+                       c->tierReads, n, c->d_scafTier);
+    MHIP(hipGetLastError());
+    *out = c->d_scafTier;
+    return BBMAP_OK;
+}
+
 extern "C" int bbmap_get_scaffold_records(bbmap_ctx *c, void *stream_, const bbmap_scafrec **out) {
     if (!c || !out) return mfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: null argument");
     if (!c->S.finalStage) return mfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: the context runs without the final stage (bbmap_config.finalStage)");
@@ -2148,15 +2191,10 @@ extern "C" int bbmap_get_scaffold_records(bbmap_ctx *c, void *stream_, const bbm
     const long long n = c->stats.reads;
     if (!c->d_scafRec) {
         MTRY(dalloc(c, &c->d_scafRec, (size_t)c->cfg.max_reads));
-        MTRY(dalloc(c, &c->d_scafTier, (size_t)c->cfg.max_reads));
     }
     const int *tierIdx = nullptr; const bbmap_final *tfin = nullptr; const uint8_t *tpool = nullptr;
-    if (c->tier && c->tierReads > 0 && c->tier->ran && n > 0) {
-        MHIP(hipMemsetAsync(c->d_scafTier, 0xff, (size_t)n * 4, stream));
-        hipLaunchKernelGGL(bbmapper::tier_index_kernel, dim3((unsigned)((c->tierReads + 255) / 256)), dim3(256), 0, stream, c->d_tierReadIds,
-                           c->tierReads, n, c->d_scafTier);
-        tierIdx = c->d_scafTier; tfin = c->tier->d_final; tpool = c->tier->d_pool;
-    }
+    MTRY(tier_index(c, stream, n, &tierIdx));
+    if (tierIdx) { tfin = c->tier->d_final; tpool = c->tier->d_pool; }
     const long long units = c->cfg.paired ? n / 2 : n;
     if (units > 0)
         hipLaunchKernelGGL(bbmapper::scaffold_coords_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, stream, T, c->d_final, c->d_pool,
@@ -2190,6 +2228,7 @@ extern "C" int bbmap_get_sam_records(bbmap_ctx *c, void *stream_, int32_t flags,
     }
     bbsam::Args a;
     a.fin = c->d_final; a.pool = c->d_pool; a.tfin = nullptr; a.tpool = nullptr; a.tierIdx = nullptr;
+    // (bbmap_get_scaffold_records above went through tier_index under this same condition: d_scafTier is allocated and filled on `stream`)
     if (c->tier && c->tierReads > 0 && c->tier->ran && n > 0) { a.tierIdx = c->d_scafTier; a.tfin = c->tier->d_final; a.tpool = c->tier->d_pool; }
     a.scaf = scaf; a.reads = c->batch.reads; a.bases = c->batch.bases;
     a.chromArr = c->d_chromArr; a.chromArrLen = c->d_chromArrLen;
@@ -2233,6 +2272,125 @@ extern "C" int bbmap_get_sam(bbmap_ctx *c, int64_t n_reads, int32_t flags, bbmap
     if (n_reads > 0) MHIP(hipMemcpy(out, recs, (size_t)n_reads * sizeof(bbmap_samrec), hipMemcpyDeviceToHost));    // (waits for the null stream)
     if (text_out && total > 0 && total <= text_cap) MHIP(hipMemcpy(text_out, text, (size_t)total, hipMemcpyDeviceToHost));
     if (text_bytes) *text_bytes = total;
+    return BBMAP_OK;
+}
+
+// ---- run statistics (run_stats.hip) and the adaptive state they drive
+static int run_stats_buffers(bbmap_ctx *c) {
+    if (c->d_runStats) return BBMAP_OK;
+    MTRY(dalloc(c, &c->d_insertHist, (size_t)BBMAP_INSERT_HIST_BINS));
+    MHIP(hipMemset(c->d_insertHist, 0, 8 * (size_t)BBMAP_INSERT_HIST_BINS));
+    unsigned long long *p = nullptr;
+    MTRY(dalloc(c, &p, (size_t)bbrunstats::N_COUNTERS));
+    MHIP(hipMemset(p, 0, sizeof(bbmap_runstats)));
+    c->d_runStats = p;
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_add_run_stats(bbmap_ctx *c, void *stream_, const bbmap_truth *truth) {
+    if (!c) return mfail(BBMAP_E_ARG, "bbmap_add_run_stats: null context");
+    if (!c->S.finalStage) return mfail(BBMAP_E_ARG, "bbmap_add_run_stats: the context runs without the final stage (bbmap_config.finalStage)");
+    if (!c->ran) return mfail(BBMAP_E_ARG, "bbmap_add_run_stats: no batch has been mapped yet");
+    if (c->statsCounted) return mfail(BBMAP_E_ARG, "bbmap_add_run_stats: the last batch has been counted already");
+    if (!c->batch.reads || c->batch.n_reads != c->stats.reads) return mfail(BBMAP_E_ARG, "bbmap_add_run_stats: the context does not hold the last batch's reads");
+    hipStream_t stream = (hipStream_t)stream_;
+    MHIP(hipSetDevice(c->cfg.device));
+    MTRY(run_stats_buffers(c));
+    const long long n = c->stats.reads;
+    bbrunstats::Args a = {};
+    a.reads = c->batch.reads;
+    a.fin = c->d_final; a.pool = c->d_pool; a.sites = c->d_ms; a.nsites = c->d_mcount; a.cap = c->cfg.max_sites;
+    MTRY(tier_index(c, stream, n, &a.tierIdx));
+    if (a.tierIdx) { const bbmap_ctx *t = c->tier; a.tfin = t->d_final; a.tpool = t->d_pool; a.tsites = t->d_ms; a.tnsites = t->d_mcount; a.tcap = t->cfg.max_sites; }
+    a.truth = truth; a.n = n; a.paired = c->cfg.paired;
+    a.ptsMatch = c->S.ptsMatch; a.ptsMatch2 = c->S.ptsMatch2;
+    a.thresh = 0; a.maxPairDist = c->cfg.maxPairDist;
+    MHIP(bbrunstats::launch(a, c->d_runStats, c->d_insertHist, stream));
+    c->statsCounted = true; c->statsStream = stream;
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_get_run_stats(bbmap_ctx *c, bbmap_runstats *out, int64_t *ihist_out) {
+    if (!c || !out) return mfail(BBMAP_E_ARG, "bbmap_get_run_stats: null argument");
+    MHIP(hipSetDevice(c->cfg.device));
+    if (!c->d_runStats) {
+        memset(out, 0, sizeof *out);
+        if (ihist_out) memset(ihist_out, 0, 8 * (size_t)BBMAP_INSERT_HIST_BINS);
+        return BBMAP_OK;
+    }
+    MHIP(hipStreamSynchronize(c->statsStream));            // the counters are written on that stream only
+    MHIP(hipMemcpy(out, c->d_runStats, sizeof *out, hipMemcpyDeviceToHost));
+    if (ihist_out) MHIP(hipMemcpy(ihist_out, c->d_insertHist, 8 * (size_t)BBMAP_INSERT_HIST_BINS, hipMemcpyDeviceToHost));
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_reset_run_stats(bbmap_ctx *c) {
+    if (!c) return mfail(BBMAP_E_ARG, "bbmap_reset_run_stats: null context");
+    c->numMatedSeen = 0;
+    if (!c->d_runStats) return BBMAP_OK;
+    MHIP(hipSetDevice(c->cfg.device));
+    MHIP(hipMemsetAsync(c->d_runStats, 0, sizeof(bbmap_runstats), c->statsStream));      // behind the last accumulation
+    MHIP(hipMemsetAsync(c->d_insertHist, 0, 8 * (size_t)BBMAP_INSERT_HIST_BINS, c->statsStream));
+    MHIP(hipStreamSynchronize(c->statsStream));
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_set_adaptive(bbmap_ctx *c, int32_t flags) {
+    if (!c) return mfail(BBMAP_E_ARG, "bbmap_set_adaptive: null context");
+    if (flags & ~(BBMAP_ADAPT_INSERT_LENGTH | BBMAP_ADAPT_RESCUE_SKIP)) return mfail(BBMAP_E_ARG, "bbmap_set_adaptive: unknown flag bits");
+    if (flags && !c->S.finalStage) return mfail(BBMAP_E_ARG, "bbmap_set_adaptive: the context runs without the final stage (bbmap_config.finalStage)");
+    c->adaptive = flags;
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_set_truth(bbmap_ctx *c, const bbmap_truth *truth) {
+    if (!c) return mfail(BBMAP_E_ARG, "bbmap_set_truth: null context");
+    c->truthNext = truth;
+    return BBMAP_OK;
+}
+
+// `if(mappedRetained2>1000 && numMated*20L<mappedRetained2){return;}` (AbstractMapThread.java:1146) on the running counters
+static int rescue_skip_rule(bbmap_ctx *c, bool *skip) {
+    *skip = false;
+    if (!c->d_runStats) return BBMAP_OK;
+    bbmap_runstats rs;
+    MHIP(hipStreamSynchronize(c->statsStream));            // not the device: only that stream's work writes the counters
+    MHIP(hipMemcpy(&rs, c->d_runStats, sizeof rs, hipMemcpyDeviceToHost));
+    *skip = rs.mappedRetained2 > 1000 && rs.numMated * 20LL < rs.mappedRetained2;
+    return BBMAP_OK;
+}
+
+// `if(DYNAMIC_INSERT_LENGTH && numMated>1000 && r.paired()){AVERAGE_PAIR_DIST=(int)(innerLengthSum*1f/numMated);}`
+// (BBMapThread.java:1307-1309) once per batch.  "The batch held a paired read" is tested as "numMated moved": calcStatistics1 adds one
+// to numMated for exactly the pairs whose mate 1 is paired() (AbstractMapThread.java:1542-1543; a paired read is mapped), so the two are
+// equivalent.  Java's arithmetic: long -> float,
+// float * 1f, numMated -> float, float division, truncation (this file is compiled with contraction off).  One deviation: inner
+// lengths clamp at MIN_PAIR_DIST -160, so the quotient can be negative and Java would store it; bbmap_set_average_pair_dist takes no
+// negative distance (the pairing code never met one), so a negative quotient leaves the value as it was.
+static int adapt_after_batch(bbmap_ctx *c, hipStream_t stream) {
+    if (!(c->adaptive & BBMAP_ADAPT_INSERT_LENGTH)) return BBMAP_OK;
+    bbmap_runstats rs;
+    MHIP(hipMemcpyAsync(&rs, c->d_runStats, sizeof rs, hipMemcpyDeviceToHost, stream));
+    MHIP(hipStreamSynchronize(stream));
+    const bool heldPaired = rs.numMated > c->numMatedSeen;
+    c->numMatedSeen = rs.numMated;
+    if (rs.numMated > 1000 && heldPaired) {
+        volatile float sum = (float)rs.innerLengthSum, cnt = (float)rs.numMated;
+        const float q = sum * 1.0f / cnt;
+        const int v = (int)q;
+        if (v >= 0) MTRY(bbmap_set_average_pair_dist(c, v));
+    }
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_get_adaptive_state(bbmap_ctx *c, int32_t *averagePairDist, int32_t *rescueSkipped) {
+    if (!c) return mfail(BBMAP_E_ARG, "bbmap_get_adaptive_state: null context");
+    if (averagePairDist) *averagePairDist = c->cfg.averagePairDist;
+    if (rescueSkipped) {
+        bool skip = false;
+        if (c->adaptive & BBMAP_ADAPT_RESCUE_SKIP) { MHIP(hipSetDevice(c->cfg.device)); MTRY(rescue_skip_rule(c, &skip)); }
+        *rescueSkipped = skip ? 1 : 0;
+    }
     return BBMAP_OK;
 }
 

@@ -94,6 +94,15 @@ def _bind(L):
     L.bbmap_get_sam_records.restype = C.c_int
     L.bbmap_get_sam.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.bbmap_get_sam.restype = C.c_int
+    L.bbmap_add_run_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bbmap_get_run_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bbmap_reset_run_stats.argtypes = [C.c_void_p]
+    L.bbmap_set_adaptive.argtypes = [C.c_void_p, C.c_int32]
+    L.bbmap_set_truth.argtypes = [C.c_void_p, C.c_void_p]
+    L.bbmap_get_adaptive_state.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    for f in ("bbmap_add_run_stats", "bbmap_get_run_stats", "bbmap_reset_run_stats", "bbmap_set_adaptive", "bbmap_set_truth",
+              "bbmap_get_adaptive_state"):
+        getattr(L, f).restype = C.c_int
     for f in ("bbmap_default_config", "bbmap_create", "bbmap_map_batch_device", "bbmap_get_output", "bbmap_last_stats",
               "bbmap_get_overflow_output"):
         getattr(L, f).restype = C.c_int
@@ -235,6 +244,20 @@ class Mapper:
         assert reads_u8.size == self.total_bytes
         self.bases[: self.total_bytes].copy_(torch.from_numpy(np.ascontiguousarray(reads_u8).reshape(-1)))
 
+    def load_records(self, recs, bases, base_scores, keyinfo):
+        """Another batch for a context made by from_records, laid out the same way: no more reads than the context was made for and
+        none longer than its longest."""
+        recs = np.ascontiguousarray(recs, READ_DTYPE)
+        assert 0 < len(recs) <= self.cfg.max_reads and int(recs["len"].max()) <= self.cfg.max_read_len
+        blob = np.ascontiguousarray(bases, np.uint8)
+        self.n, self.total_bytes = len(recs), int(blob.size)
+        self.bases = torch.zeros(2 * self.total_bytes, dtype=torch.uint8, device=self.dev)
+        self.bases[: self.total_bytes].copy_(torch.from_numpy(blob))
+        self.base_scores = torch.from_numpy(np.ascontiguousarray(base_scores, np.int8)).to(self.dev)
+        assert self.base_scores.numel() >= self.total_bytes
+        self.reads = torch.from_numpy(recs.view(np.uint8).reshape(-1).copy()).to(self.dev)
+        self.keyinfo = torch.from_numpy(np.ascontiguousarray(keyinfo, np.int32)).to(self.dev)
+
     def step(self, bases=None):
         """Maps the resident batch; returns when it is done (bbmap_map_batch_device waits for its stream).  bases: another
         device buffer of 2 * n_reads * read_len bytes holding the batch's plus strands in its first half (a host that streams
@@ -321,6 +344,47 @@ class Mapper:
 
     def set_average_pair_dist(self, v):
         _lib.check(self.L.bbmap_set_average_pair_dist(self.h, int(v)), "bbmap_set_average_pair_dist")
+
+    def _truth_tensor(self, truth):
+        from .runstats import TRUTH_DTYPE
+        t = np.ascontiguousarray(truth, TRUTH_DTYPE)
+        assert len(t) == self.n
+        return torch.from_numpy(t.view(np.uint8).reshape(-1).copy()).to(self.dev)
+
+    def add_run_stats(self, truth=None):
+        """bbmap_add_run_stats: adds the last step, overflow tier included, to the context's running counters and insert-size
+        histogram.  truth: TRUTH_DTYPE[n] (chrom < 0 = none for that read) or None.  A second call for one step raises."""
+        d = None if truth is None else self._truth_tensor(truth)
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(self.L.bbmap_add_run_stats(self.h, C.c_void_p(stream), None if d is None else C.c_void_p(d.data_ptr())),
+                   "bbmap_add_run_stats")
+        torch.cuda.current_stream().synchronize()          # (the truth tensor may go now)
+
+    def run_stats(self, with_hist=True):
+        """bbmap_get_run_stats: (RUNSTATS_DTYPE scalar, int64[INSERT_HIST_BINS] or None)."""
+        from .runstats import RUNSTATS_DTYPE, INSERT_HIST_BINS
+        rs = np.zeros(1, RUNSTATS_DTYPE)
+        hist = np.zeros(INSERT_HIST_BINS, np.int64) if with_hist else None
+        _lib.check(self.L.bbmap_get_run_stats(self.h, rs.ctypes.data, None if hist is None else hist.ctypes.data), "bbmap_get_run_stats")
+        return rs[0], hist
+
+    def reset_run_stats(self):
+        _lib.check(self.L.bbmap_reset_run_stats(self.h), "bbmap_reset_run_stats")
+
+    def set_adaptive(self, flags):
+        """bbmap_set_adaptive: ADAPT_INSERT_LENGTH | ADAPT_RESCUE_SKIP (bbmap_amd.runstats); step() then counts each batch itself."""
+        _lib.check(self.L.bbmap_set_adaptive(self.h, int(flags)), "bbmap_set_adaptive")
+
+    def set_truth(self, truth):
+        """bbmap_set_truth: truth records for the next step's own accumulation (adaptive contexts); None clears."""
+        self._truth = None if truth is None else self._truth_tensor(truth)      # kept alive until the next step has used it
+        _lib.check(self.L.bbmap_set_truth(self.h, None if self._truth is None else C.c_void_p(self._truth.data_ptr())), "bbmap_set_truth")
+
+    def adaptive_state(self):
+        """bbmap_get_adaptive_state: (averagePairDist, rescueSkipped)."""
+        a, r = C.c_int32(0), C.c_int32(0)
+        _lib.check(self.L.bbmap_get_adaptive_state(self.h, C.byref(a), C.byref(r)), "bbmap_get_adaptive_state")
+        return a.value, r.value
 
     def pack_sites(self, counts, offsets, packed):
         """The last step's site lists without their empty slots (bbmap_pack_sites_device), enqueued on the current stream:

@@ -515,9 +515,10 @@ int bbpipe_quick_rescue_device(void *stream, int64_t n_jobs, const bbresc_job *j
  *                        policy, genMatchString -> genMatchStringForSite -> realign_new (AbstractMapThread.java:860-1068,
  *                        TranslateColorspaceRead.java:229-653: up to three fillLimited and one fillUnlimited per call, again in rounds),
  *                        fixXY / clipTipIndels / toLocalAlignment, applyClearzone3 and the tip penalty -> bbmap_final per read
- *   Not carried over: per-thread adaptive state of the Java mapper (DYNAMIC_INSERT_LENGTH: the caller feeds averagePairDist, see
- *   bbmap_set_average_pair_dist; the "mating is not working" skip of rescue()), the non-default output policies (ambiguous=toss/
- *   random/all, secondary alignments, identity / edit filters, local alignment).
+ *   Adaptive state of the Java mapper (DYNAMIC_INSERT_LENGTH, the "mating is not working" skip of rescue()): opt-in through
+ *   bbmap_set_adaptive, driven by the run statistics (bbmap_add_run_stats), batch by batch and per context.
+ *   Not carried over: the non-default output policies (ambiguous=toss/random/all, secondary alignments, identity / edit filters,
+ *   local alignment).
  *   Scaffolds: with a table set (bbidx_set_scaffolds) quickMap's tail drops sites that span two scaffolds, and
  *   bbmap_get_scaffold_records gives SamLine's scaffold coordinates, and bbmap_get_sam_records the rest of SamLine's constructor
  *   (FLAG, POS / PNEXT / TLEN, MAPQ, CIGAR, NM, AM, MD); names, SEQ / QUAL text and file I/O stay with the host.
@@ -764,6 +765,173 @@ int bbmap_get_sam_records(bbmap_ctx *ctx, void *stream, int32_t flags, const bbm
 int bbmap_get_sam(bbmap_ctx *ctx, int64_t n_reads, int32_t flags, bbmap_samrec *out, uint8_t *text_out, int64_t text_cap,
                   int64_t *text_bytes);
 int bbmap_last_stats(bbmap_ctx *ctx, bbmap_stats *out);
+
+/* =====================================================================================
+ * Run statistics and the adaptive state they drive
+ *   AbstractMapThread.calcStatistics1 / calcStatistics2 (current/align2/AbstractMapThread.java:1478-1641, :1644-1770; called from
+ *   BBMapThread.java:730, :1359-1360) with calcCorrectness (:2615-2689) and Read.countErrors: the counters behind the table BBMap prints
+ *   at the end of a run, summed on the device over the final records, the match-string pool and the site lists after the final stage
+ *   (run_stats.hip).  Also the insert-size histogram (AbstractMapThread.java:524, ReadStats.addToInsertHistogram(r, false),
+ *   current/align2/ReadStats.java:578-592, with Read.insertSizeMapped, current/stream/Read.java:2618-2670): mate 1 of paired pairs,
+ *   x = min(MAXINSERTLEN, insert), counted when x > 0, BBMAP_INSERT_HIST_BINS = MAXINSERTLEN + 1 bins (ReadStats.java:1313).
+ *   Fixed at the reference's defaults: AMBIGUOUS_TOSS = false, OUTPUT_PAIRED_ONLY = false.  The splice counter (readCountSplice) is left
+ *   out: SamLine.INTRON_LIMIT stays at Integer.MAX_VALUE, so it can never move.  The host's: perfectHit (`topScore==maxPossibleQuickScore`)
+ *   and lowQualityReadsDiscarded / lowQualityBasesDiscarded need quickMap's return value, which the mapper does not keep; consequently
+ *   an unmapped read always counts as noHit.  `elements>0` (a read's list is not empty) selects the mapped branch, as in the reference;
+ *   a read flagged BBMAP_NSITES_OVERFLOW / _MATE_OVERFLOW has no list.
+ * ===================================================================================== */
+enum { BBMAP_INSERT_HIST_BINS = 40001 };
+enum { BBMAP_RUNSTATS_MAX_WAVES = 8192 };   /* wavefronts of the statistics kernel's persistent grid (one read per wavefront and turn) */
+typedef struct bbmap_runstats {
+    /* mate 1: calcStatistics1 (every read of a single-ended run counts as mate 1) */
+    int64_t mappedRetained1;                    /* AbstractMapThread.java:1533 / :1683 */
+    int64_t mappedRetainedBases1;               /* :1534 / :1684 */
+    int64_t ambiguousBestAlignment1;            /* :1484-1485 / :1647-1648 (AMBIGUOUS_TOSS = false: ambiguous and mapped) */
+    int64_t ambiguousBestAlignmentBases1;       /* :1486 / :1649 */
+    int64_t matchCountM1;                       /* :1517 / :1669; Read.countErrors, current/stream/Read.java:2189-2240: `m` */
+    int64_t matchCountS1;                       /* :1518 / :1670: `S` */
+    int64_t matchCountD1;                       /* :1519 / :1671: `D` */
+    int64_t matchCountI1;                       /* :1520 / :1672: `I`, `X` and `Y` */
+    int64_t matchCountN1;                       /* :1521 / :1673: `N` and `C` */
+    int64_t readCountS1;                        /* :1523 / :1675 */
+    int64_t readCountD1;                        /* :1524 / :1676 */
+    int64_t readCountI1;                        /* :1525 / :1677 */
+    int64_t readCountN1;                        /* :1527 / :1678 */
+    int64_t readCountE1;                        /* :1529 / :1680 */
+    int64_t rescuedP1;                          /* :1535-1537 / :1685-1687 */
+    int64_t rescuedM1;                          /* :1539 / :1689 */
+    int64_t perfectMatch1;                      /* :1565-1566 / :1693-1694: `r.perfect() || (maxSwScore>0 && r.topSite().slowScore==maxSwScore)`, maxSwScore = maxQuality(len) */
+    int64_t perfectMatchBases1;                 /* :1567 / :1695 */
+    int64_t perfectHitCount1;                   /* :1574-1575 / :1702-1703 */
+    int64_t semiPerfectHitCount1;               /* :1578-1579 / :1706-1707 */
+    int64_t semiperfectMatch1;                  /* :1583 / :1711 */
+    int64_t semiperfectMatchBases1;             /* :1584 / :1712 */
+    int64_t siteSum1;                           /* :1605 / :1733 */
+    int64_t topSiteSum1;                        /* :1606 / :1734 (calcCorrectness :2645) */
+    int64_t uniqueHit1;                         /* :1609 / :1737 */
+    int64_t noHit1;                             /* :1639 / :1766 (every unmapped read: see above) */
+    int64_t firstSiteCorrectP1;                 /* :1587 / :1715 (calcCorrectness :2663-2666, isCorrectHit :2692-2700) */
+    int64_t firstSiteCorrectM1;                 /* :1588 / :1716 */
+    int64_t firstSiteCorrectPaired1;            /* :1589 / :1717 */
+    int64_t firstSiteCorrectSolo1;              /* :1590 / :1718 */
+    int64_t firstSiteCorrectRescued1;           /* :1591 / :1719 */
+    int64_t firstSiteIncorrect1;                /* :1593 / :1721 */
+    int64_t firstSiteCorrectLoose1;             /* :1600 / :1728 (isCorrectHitLoose :2712-2719 with thresh + 20, :2664) */
+    int64_t firstSiteIncorrectLoose1;           /* :1602 / :1730 */
+    int64_t truePositiveP1;                     /* :1613 / :1741 */
+    int64_t truePositiveM1;                     /* :1614 / :1742 */
+    int64_t totalCorrectSites1;                 /* :1615 / :1743 */
+    int64_t correctUniqueHit1;                  /* :1619 / :1747 */
+    int64_t correctMultiHit1;                   /* :1621 / :1749 */
+    int64_t correctLowHit1;                     /* :1624 / :1752 */
+    int64_t falsePositive1;                     /* :1629 / :1757 */
+    int64_t readsUsed1;                         /* :3029-3030: reads taken from the input */
+    int64_t basesUsed1;                         /* :494, :504-505 */
+    /* mate 2: calcStatistics2 (every read of a single-ended run counts as mate 1) */
+    int64_t mappedRetained2;                    /* AbstractMapThread.java:1533 / :1683 */
+    int64_t mappedRetainedBases2;               /* :1534 / :1684 */
+    int64_t ambiguousBestAlignment2;            /* :1484-1485 / :1647-1648 (AMBIGUOUS_TOSS = false: ambiguous and mapped) */
+    int64_t ambiguousBestAlignmentBases2;       /* :1486 / :1649 */
+    int64_t matchCountM2;                       /* :1517 / :1669; Read.countErrors, current/stream/Read.java:2189-2240: `m` */
+    int64_t matchCountS2;                       /* :1518 / :1670: `S` */
+    int64_t matchCountD2;                       /* :1519 / :1671: `D` */
+    int64_t matchCountI2;                       /* :1520 / :1672: `I`, `X` and `Y` */
+    int64_t matchCountN2;                       /* :1521 / :1673: `N` and `C` */
+    int64_t readCountS2;                        /* :1523 / :1675 */
+    int64_t readCountD2;                        /* :1524 / :1676 */
+    int64_t readCountI2;                        /* :1525 / :1677 */
+    int64_t readCountN2;                        /* :1527 / :1678 */
+    int64_t readCountE2;                        /* :1529 / :1680 */
+    int64_t rescuedP2;                          /* :1535-1537 / :1685-1687 */
+    int64_t rescuedM2;                          /* :1539 / :1689 */
+    int64_t perfectMatch2;                      /* :1565-1566 / :1693-1694: `r.perfect() || (maxSwScore>0 && r.topSite().slowScore==maxSwScore)`, maxSwScore = maxQuality(len) */
+    int64_t perfectMatchBases2;                 /* :1567 / :1695 */
+    int64_t perfectHitCount2;                   /* :1574-1575 / :1702-1703 */
+    int64_t semiPerfectHitCount2;               /* :1578-1579 / :1706-1707 */
+    int64_t semiperfectMatch2;                  /* :1583 / :1711 */
+    int64_t semiperfectMatchBases2;             /* :1584 / :1712 */
+    int64_t siteSum2;                           /* :1605 / :1733 */
+    int64_t topSiteSum2;                        /* :1606 / :1734 (calcCorrectness :2645) */
+    int64_t uniqueHit2;                         /* :1609 / :1737 */
+    int64_t noHit2;                             /* :1639 / :1766 (every unmapped read: see above) */
+    int64_t firstSiteCorrectP2;                 /* :1587 / :1715 (calcCorrectness :2663-2666, isCorrectHit :2692-2700) */
+    int64_t firstSiteCorrectM2;                 /* :1588 / :1716 */
+    int64_t firstSiteCorrectPaired2;            /* :1589 / :1717 */
+    int64_t firstSiteCorrectSolo2;              /* :1590 / :1718 */
+    int64_t firstSiteCorrectRescued2;           /* :1591 / :1719 */
+    int64_t firstSiteIncorrect2;                /* :1593 / :1721 */
+    int64_t firstSiteCorrectLoose2;             /* :1600 / :1728 (isCorrectHitLoose :2712-2719 with thresh + 20, :2664) */
+    int64_t firstSiteIncorrectLoose2;           /* :1602 / :1730 */
+    int64_t truePositiveP2;                     /* :1613 / :1741 */
+    int64_t truePositiveM2;                     /* :1614 / :1742 */
+    int64_t totalCorrectSites2;                 /* :1615 / :1743 */
+    int64_t correctUniqueHit2;                  /* :1619 / :1747 */
+    int64_t correctMultiHit2;                   /* :1621 / :1749 */
+    int64_t correctLowHit2;                     /* :1624 / :1752 */
+    int64_t falsePositive2;                     /* :1629 / :1757 */
+    int64_t readsUsed2;                         /* :3029-3030: reads taken from the input */
+    int64_t basesUsed2;                         /* :494, :504-505 */
+    /* pair level, calcStatistics1 */
+    int64_t bothUnmapped;                       /* :1490, :1493 */
+    int64_t bothUnmappedBases;                  /* :1491, :1494 */
+    int64_t numMated;                           /* :1543 */
+    int64_t numMatedBases;                      /* :1544: len1 + len2 with `len2=(r2==null ? 0 : r.length())` (:1481), which is mate 1's length: 2 * len1 per pair */
+    int64_t badPairs;                           /* :1561 */
+    int64_t badPairBases;                       /* :1562: 2 * len1, as numMatedBases */
+    int64_t innerLengthSum;                     /* :1557, after the MAX_PAIR_DIST / MIN_PAIR_DIST (-160) clamp of :1555-1556 (:2974-2975) */
+    int64_t outerLengthSum;                     /* :1558 */
+    int64_t insertSizeSum;                      /* :1559 */
+    int64_t reserved;
+} bbmap_runstats;                  /* 96 x 8 = 768 bytes */
+/* calcCorrectness' `original` for a read: r.originalSite of a synthetic read.  chrom < 0: no truth for that read (site 0 is its own
+ * original, :2623-2627). */
+typedef struct bbmap_truth { int32_t chrom, strand, start, stop; } bbmap_truth;   /* 16 bytes */
+/* The raw form over device arrays the caller owns: reads (len is used), one final record per read with its string in `pool` at
+ * match_off, sites = n_reads x cap records with nsites[r] of them in use (<= 0: an empty list).  paired: reads 2p and 2p + 1 are
+ * mates.  scheme (BBMSA_SCHEME_*) gives maxQuality(len) for the perfectMatch rule; thresh is calcCorrectness' THRESH (CORRECT_THRESH,
+ * current/align2/AbstractMapper.java:2651, default 0); MAX_PAIR_DIST is 32000.  truth: one record per read, or NULL.  counters (device,
+ * ADDED to; zero it first) and ihist (device, BBMAP_INSERT_HIST_BINS entries, added to; may be NULL: no histogram).  Enqueues on
+ * `stream`. */
+int bbpipe_run_stats_device(void *stream, int64_t n_reads, int32_t paired, int32_t scheme, int32_t thresh, const bbidx_read *reads,
+                            const bbmap_final *finals, const uint8_t *pool, const bbmap_msite *sites, const int32_t *nsites, int32_t cap,
+                            const bbmap_truth *truth, bbmap_runstats *counters, int64_t *ihist);
+/* Adds the last batch (bbmap_map_batch_device or bbmap_final_batch_device), overflow tier included, to the context's running counters
+ * and histogram; enqueues on `stream`.  truth: a device array of one record per read of the batch, or NULL.  The context's own
+ * scoring scheme and cfg.maxPairDist are used, thresh is 0.  BBMAP_E_ARG: the context runs without the final stage, no batch has been
+ * mapped, or this batch has been counted already (a second call changes nothing). */
+int bbmap_add_run_stats(bbmap_ctx *ctx, void *stream, const bbmap_truth *truth);
+/* Waits for the stream of the last accumulation (the only work that writes the counters; not for the whole device) and copies the
+ * running counters; ihist_out: BBMAP_INSERT_HIST_BINS entries, or NULL.  That stream must still exist. */
+int bbmap_get_run_stats(bbmap_ctx *ctx, bbmap_runstats *out, int64_t *ihist_out);
+/* Zeroes counters and histogram behind the last accumulation, on its stream, and waits for that stream (which must still exist). */
+int bbmap_reset_run_stats(bbmap_ctx *ctx);
+/* The mapper's adaptive state: the two rules of the reference that read these counters.  flags = 0 (default): nothing changes.
+ *   BBMAP_ADAPT_INSERT_LENGTH  DYNAMIC_INSERT_LENGTH (current/align2/BBMapThread.java:1307-1309): after a batch that held a paired read,
+ *     if numMated > 1000, the average pair distance for the batches to come becomes (int)(innerLengthSum*1f/numMated) -- Java's
+ *     arithmetic: long -> float, float division, truncation -- set as bbmap_set_average_pair_dist sets it (the overflow tier follows).
+ *     "Held a paired read" is tested as "numMated moved", which is the same thing (numMated counts exactly the pairs whose mate 1 is
+ *     paired(), AbstractMapThread.java:1542-1543).  Deviation: inner lengths clamp at -160, so the quotient can be negative and Java
+ *     would store it; bbmap_set_average_pair_dist takes no negative distance, so a negative quotient leaves the value as it was.
+ *   BBMAP_ADAPT_RESCUE_SKIP    the "mating is not working" return of rescue() (AbstractMapThread.java:1146): a batch starts with
+ *     rescue()'s body skipped when `mappedRetained2>1000 && numMated*20L<mappedRetained2` holds on the running counters (the sort,
+ *     removeLowQualitySitesPaired and mergeDuplicateSites around the call, BBMapThread.java:1083-1095, still run).
+ * With either bit set bbmap_map_batch_device adds the batch to the counters itself at its end, with the array given by
+ * bbmap_set_truth for that one batch (else none); an explicit bbmap_add_run_stats for that batch is then refused as a second count.
+ * Cost: with BBMAP_ADAPT_RESCUE_SKIP every bbmap_map_batch_device begins by waiting for the stream of the last accumulation and
+ * copying the counters back (768 bytes); with BBMAP_ADAPT_INSERT_LENGTH it ends with the same wait and copy on its own stream.
+ * The stream of the last accumulation is a handle the caller gave in an earlier call: it must still exist at every later
+ * bbmap_map_batch_device under BBMAP_ADAPT_RESCUE_SKIP, bbmap_get_run_stats, bbmap_reset_run_stats and bbmap_get_adaptive_state.
+ * Granularity: the reference moves this state pair by pair and per mapping thread; here it moves batch by batch and per context.
+ * With batches of one pair the two are the same sequence. */
+enum { BBMAP_ADAPT_INSERT_LENGTH = 1, BBMAP_ADAPT_RESCUE_SKIP = 2 };
+int bbmap_set_adaptive(bbmap_ctx *ctx, int32_t flags);
+/* Truth records (device, one per read) for the NEXT batch's own accumulation under bbmap_set_adaptive; forgotten after that batch,
+ * an empty one (n_reads = 0) included. */
+int bbmap_set_truth(bbmap_ctx *ctx, const bbmap_truth *truth);
+/* averagePairDist as the batches to come will use it; rescueSkipped = 1 when the next batch would start with rescue skipped (the
+ * rule on the running counters, BBMAP_ADAPT_RESCUE_SKIP set; waits for the stream of the last accumulation, as bbmap_get_run_stats
+ * does).  Either pointer may be NULL. */
+int bbmap_get_adaptive_state(bbmap_ctx *ctx, int32_t *averagePairDist, int32_t *rescueSkipped);
 /* The last batch's site lists without their empty slots, for a host that copies them back: counts (n_reads + 1 ints), offsets
  * (n_reads + 1 int64: exclusive prefix sums, offsets[n_reads] = total) and packed (packed_cap records) are device buffers of the
  * caller's; read r's counts[r] sites are packed[offsets[r] ...] (0 for a read without a list, a flagged one, or one the overflow
