@@ -1,0 +1,123 @@
+// Host-side context of the mapper's entry points (mapper_host.hip: creation and the batch driver; mapper_output.hip: everything that
+// reads a finished batch), and the error and launch helpers both files use.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <thread>
+#include <vector>
+
+#include "bbmap_amd.h"
+#include "index_ctx.h"
+#include "mapper_dev.h"
+#include "msa_ctx.h"
+
+void bbmap_set_error(const char *msg);
+
+// A device buffer that is allocated on first use and replaced by a larger one when a call needs more (contents are not kept).
+// (hidden: its inline members are no symbols of the library)
+struct __attribute__((visibility("hidden"))) DevBuf {
+    void *p = nullptr; size_t cap = 0;
+    // Room for `need` bytes.  slack: added when the buffer has to grow, so that sizes creeping up do not reallocate every batch.
+    // busy: a stream whose queued work may still use the old buffer; it is waited for before the buffer is freed.
+    hipError_t grow(size_t need, size_t slack = 0, const hipStream_t *busy = nullptr) {
+        if (need <= cap) return hipSuccess;
+        if (p) {
+            if (busy) { const hipError_t e = hipStreamSynchronize(*busy); if (e != hipSuccess) return e; }
+            release();
+        }
+        const hipError_t e = hipMalloc(&p, need + slack);
+        if (e == hipSuccess) cap = need + slack;
+        return e;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+// bbmap_map_batch's device copies (reads, bases of both strands, base scores, keyinfo, counts, offsets, packed sites), the scan
+// scratch of bbmap_pack_sites_device, and bbmap_get_sam_records' scan scratch and text blob
+enum { HIO_READS, HIO_BASES, HIO_SCORES, HIO_KEYINFO, HIO_COUNTS, HIO_OFFSETS, HIO_PACKED, BUF_PACK_TMP, BUF_SAM_TMP, BUF_SAM_TEXT, BUF_COUNT };
+
+struct bbmap_ctx {
+    bbmap_config cfg;
+    bbidx_ctx *index;
+    hipStream_t hostStream = nullptr;   // bbmap_map_batch (host buffers in and out) runs on it
+    bbidx_launch probeLs;       // this context's probe launches: queue, work counters, events (the index is shared, read-only; index_ctx.h)
+    bbmsa_ctx *msa, *msaGapped;
+    bbmapper::Settings S;
+    std::vector<void *> allocs;
+    // device buffers
+    bbidx_site *d_psites; int *d_pnsites;
+    bbmap_msite *d_ms; int *d_mcount, *d_near;
+    bbmapper::SlowState *d_slow;
+    int *d_active[2];
+    unsigned *d_counters;
+    bbmsa_job *d_jobs; bbmap_jobinfo *d_jinfo; bbmsa_result *d_results; uint8_t *d_match;
+    bbmsa_job *d_gjobs; bbmsa_gaps *d_ggaps; bbmap_jobinfo *d_ginfo; bbmsa_result *d_gresults; uint8_t *d_gmatch;
+    bbresc_job *d_rjobs; bbmapper::RescInfo *d_rinfo; bbresc_result *d_rres; bbmapper::PairResc *d_pres; bbmap_msite *d_rsite;
+    const uint8_t *const *d_chromArr; const int *d_chromArrLen; const uint8_t *refsBase;
+    int *d_chromMin;
+    long long *d_chromOff;
+    long long jobCap, gjobCap, rescCap;
+    bbmapper::FinalRead *d_fin; bbmap_final *d_final; uint8_t *d_pool; long long poolUnits, poolUsed, finalFills;
+    int matchStride, gmatchStride, maxRows, plainColumns;
+    unsigned *h_counters;           // pinned
+    hipEvent_t ev[bbmapper::EV_COUNT];
+    bbmap_stats stats;
+    long long nJobs, nGapped;
+    bool ran;
+    // overflow tier: a second, small context with long site lists for the reads whose list did not fit max_sites
+    bbmap_ctx *tier;
+    bool ownsMsa;
+    long long narrowMinJobs;        // plain-context launches with at least this many fills run the narrow kernel (BBMAP_NARROW_MIN_JOBS)
+    bool sortWide;                  // the second context hands its fills on widest first (BBMAP_SORT_WIDE=0 switches it off)
+    int *d_tierUnits; bbidx_read *d_tierReads; int *d_tierReadIds;
+    long long tierReads;            // reads the tier mapped in the last batch
+    // The tier's pass runs beside the main pass (its reads are known once begin_kernel has run): its own stream, driven by its
+    // own host thread, joined at the end of the batch.
+    hipStream_t tierStream;
+    // second-context fills (few jobs, wide windows: a handful of waves per CU) run on a stream of their own beside the plain ones
+    hipStream_t dpStream; hipEvent_t evFork, evJoin;
+    std::thread tierThread;
+    bool tierStarted;
+    int tierRc; char tierErr[320];
+    long long overAfterBegin;       // reads flagged by the probe (CNT_OVERFLOWED after begin_kernel)
+    struct BatchArgs { int64_t n_reads; const bbidx_read *reads; uint8_t *bases; int64_t minus_delta; const int8_t *baseScores; const int32_t *keyinfo; } batch;
+    DevBuf buf[BUF_COUNT];          // HIO_* / BUF_*: kept between calls, grown on demand
+    // bbmap_get_scaffold_records: its output (max_reads records) and the read -> overflow-tier record map, allocated on first use
+    bbmap_scafrec *d_scafRec = nullptr;
+    int *d_scafTier = nullptr;
+    // bbmap_get_sam_records: records, per-read byte counts and their prefix sums, the MAPQ table (allocated on first use)
+    bbmap_samrec *d_samRec = nullptr;
+    int *d_samCounts = nullptr;
+    long long *d_samOffsets = nullptr;
+    float *d_mapqMax = nullptr;
+    long long samTextBytes = 0;
+    // run statistics (bbmap_add_run_stats): the running counters and the insert-size histogram, allocated on first use
+    unsigned long long *d_runStats = nullptr, *d_insertHist = nullptr;
+    bool statsCounted = false;      // the last batch is in the counters already
+    int adaptive = 0;               // BBMAP_ADAPT_*
+    long long numMatedSeen = 0;     // numMated after the last accumulation the insert-length rule looked at
+    const bbmap_truth *truthNext = nullptr;     // bbmap_set_truth: for the next batch's own accumulation
+    hipStream_t statsStream = nullptr;          // the stream of the last accumulation: the only work that writes the counters
+};
+
+static thread_local char g_merr[320];
+#define MHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { snprintf(g_merr, sizeof g_merr, "%s failed: %s", #expr, hipGetErrorString(e_)); bbmap_set_error(g_merr); return BBMAP_E_HIP; } } while (0)
+#define MTRY(expr) do { const int rc_ = (expr); if (rc_ != BBMAP_OK) return rc_; } while (0)
+static int mfail(int code, const char *msg) { bbmap_set_error(msg); return code; }
+
+// kernel<<<ceil(threads / TB), TB, 0, stream>>>(args...)
+template <unsigned TB, class K, class... A> static int launch(K kernel, long long threads, hipStream_t stream, const A &...args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((threads + TB - 1) / TB)), dim3(TB), 0, stream, args...);
+    MHIP(hipGetLastError());
+    return BBMAP_OK;
+}
+
+// a device array of the context's that lives until bbmap_destroy
+template <class T> static int dalloc(bbmap_ctx *c, T **p, size_t count) {
+    void *d = nullptr;
+    const size_t bytes = (count ? count : 1) * sizeof(T);
+    if (hipMalloc(&d, bytes) != hipSuccess) return mfail(BBMAP_E_NOMEM, "bbmap_create: device allocation failed");
+    c->allocs.push_back(d);
+    *p = (T *)d;
+    return BBMAP_OK;
+}

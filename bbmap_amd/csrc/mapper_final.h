@@ -1,6 +1,6 @@
 // The FINAL ALIGNMENT STAGE of the device mapper: everything BBMapThread.processRead / processReadPair do after the rescue stage,
 // i.e. the calls that produce the coordinates, the score and the match string (CIGAR) BBMap prints.  Included by mapper.hip
-// inside namespace bbmapper (it uses that file's SiteScore / GapTools / list helpers, Dev and emit machinery).
+// inside namespace bbmapper (it uses that file's SiteScore / GapTools / list helpers and emit machinery, and mapper_dev.h's Dev and FinalRead).
 //
 //   processRead tail        current/align2/BBMapThread.java:492-732
 //   processReadPair tail    current/align2/BBMapThread.java:1116-1356
@@ -28,27 +28,6 @@
 // One thread per read (per pair in the two policy kernels): the work per read is a few hundred bytes of string walking.
 
 // ---------------------------------------------------------------------------------------------- per-read state
-struct FinalRead {
-    // stream.Read's mapping fields
-    int mapped, paired, ambiguous, perfect, rescued;
-    int chrom, strand, start, stop, mapScore;
-    int match;                  // pool reference of Read.match (0 = null), length in matchLen
-    int matchLen;
-    // genMatchString's state
-    int pc;                     // where to resume (PC_*), PC_DONE when the read has finished
-    int i;                      // loop index over the sites
-    int best, scoreChanged, sorting, topObj_, pairedLost;
-    int oldSlow, oldScoreS;     // the site's scores before its match string was made
-    // genMatchStringForSite
-    int oldScoreG, gstep;
-    // realign_new
-    int recur, padding, forbidIndels, fixXY, minValid;
-    int scoreNoIndel, minLoc, maxLoc, old0, epl, epr, fillKind, minscore, pending, haveMax, cols3;
-    int seq;                    // fills issued for this read so far (continues scoreSlow's / rescue's numbering)
-    int needLocal;              // the end kernel: toLocalAlignment is due (second pass, with pool space reserved)
-    int reservedI;
-};
-
 enum { PC_DONE = 0, PC_SITE_LOOP, PC_GEN_START, PC_REALIGN_START, PC_EMIT_FILL, PC_FILL_BACK, PC_REALIGN_POST, PC_GEN_AFTER_REALIGN,
        PC_GEN_CLIP, PC_SITE_DONE, PC_AFTER_LOOP, PC_SORT_LOOP, PC_FINISH };
 
@@ -63,10 +42,10 @@ __device__ inline uint8_t *pool_ptr(const Dev &D, int ref) { return D.pool + 4ll
 // Bump allocation in 4-byte units; 0 = the pool is full (nothing changed; the host grows it before the round is repeated).  One
 // atomicAdd, no compare-and-swap loop (a million threads retrying on one word took seconds): a request that does not fit leaves the
 // counter beyond the capacity, so every later request of the round fails too, the strings handed out so far are exactly
-// [0, smallest `old` of a failed request), and the host sets the counter back to that before the next round (counters[21]).
+// [0, smallest `old` of a failed request), and the host sets the counter back to that before the next round (counters[CNT_POOL_AT_FAILURE]).
 __device__ int pool_alloc_units(const Dev &D, unsigned units) {
-    const unsigned old = atomicAdd(&D.counters[20], units);
-    if ((long long)old + units > D.poolUnits) { atomicMin(&D.counters[21], old); atomicAdd(&D.counters[22], 1u); return 0; }
+    const unsigned old = atomicAdd(&D.counters[CNT_POOL_UNITS], units);
+    if ((long long)old + units > D.poolUnits) { atomicMin(&D.counters[CNT_POOL_AT_FAILURE], old); atomicAdd(&D.counters[CNT_POOL_FAILED], 1u); return 0; }
     return (int)old + 1;
 }
 __device__ inline unsigned pool_units(int bytes) { return (unsigned)((bytes + 3) >> 2) + 1u; }
@@ -916,8 +895,8 @@ __global__ __launch_bounds__(128, FINAL_ROUND_MIN_BLOCKS) void final_round_kerne
         if (wantEmit) wide = final_fill_is_wide(D, D.ms[r * D.cap + cur], f.minLoc, f.maxLoc);
         const unsigned long long mp = __ballot(wantEmit && !wide), mg = __ballot(wantEmit && wide);
         unsigned bp = 0, bg = 0;
-        if (mp) { if (lane == __builtin_ctzll(mp)) bp = atomicAdd(&D.counters[0], (unsigned)__builtin_popcountll(mp)); bp = __shfl(bp, __builtin_ctzll(mp)); }
-        if (mg) { if (lane == __builtin_ctzll(mg)) bg = atomicAdd(&D.counters[1], (unsigned)__builtin_popcountll(mg)); bg = __shfl(bg, __builtin_ctzll(mg)); }
+        if (mp) { if (lane == __builtin_ctzll(mp)) bp = atomicAdd(&D.counters[CNT_FILLS], (unsigned)__builtin_popcountll(mp)); bp = __shfl(bp, __builtin_ctzll(mp)); }
+        if (mg) { if (lane == __builtin_ctzll(mg)) bg = atomicAdd(&D.counters[CNT_GAPPED_FILLS], (unsigned)__builtin_popcountll(mg)); bg = __shfl(bg, __builtin_ctzll(mg)); }
         if (wantEmit) {
             const unsigned long long below = (1ull << lane) - 1ull;
             const unsigned k = wide ? bg + (unsigned)__builtin_popcountll(mg & below) : bp + (unsigned)__builtin_popcountll(mp & below);
@@ -931,7 +910,7 @@ __global__ __launch_bounds__(128, FINAL_ROUND_MIN_BLOCKS) void final_round_kerne
     const unsigned long long m = __ballot(stillActive);
     if (m) {
         unsigned base = 0;
-        if (lane == __builtin_ctzll(m)) base = atomicAdd(&D.counters[2], (unsigned)__builtin_popcountll(m));
+        if (lane == __builtin_ctzll(m)) base = atomicAdd(&D.counters[CNT_NEXT_ACTIVE], (unsigned)__builtin_popcountll(m));
         base = __shfl(base, __builtin_ctzll(m));
         if (stillActive) D.activeOut[base + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = (int)r;
     }
@@ -1123,8 +1102,8 @@ __global__ __launch_bounds__(128) void final_end_kernel(const Dev D) {
         if (f2.mapScore <= 0 && n2 > 0) { r_clear_mapping(f2, n2); f1.paired = 0; }
         remove_duplicate_best_sites(s1, n1); remove_duplicate_best_sites(s2, n2);
         f1.needLocal = f1.mapped && contains_xyc(D, f1); f2.needLocal = f2.mapped && contains_xyc(D, f2);
-        if (f1.needLocal) { site_set_match(s1[0], f1.match, f1.matchLen); atomicAdd(&D.counters[24], 1u); atomicAdd(&D.counters[25], (unsigned)((f1.matchLen + 4 * D.reads[r1].len + 64) >> 2)); }
-        if (f2.needLocal) { site_set_match(s2[0], f2.match, f2.matchLen); atomicAdd(&D.counters[24], 1u); atomicAdd(&D.counters[25], (unsigned)((f2.matchLen + 4 * D.reads[r2].len + 64) >> 2)); }
+        if (f1.needLocal) { site_set_match(s1[0], f1.match, f1.matchLen); atomicAdd(&D.counters[CNT_LOCAL_READS], 1u); atomicAdd(&D.counters[CNT_LOCAL_UNITS], (unsigned)((f1.matchLen + 4 * D.reads[r1].len + 64) >> 2)); }
+        if (f2.needLocal) { site_set_match(s2[0], f2.match, f2.matchLen); atomicAdd(&D.counters[CNT_LOCAL_READS], 1u); atomicAdd(&D.counters[CNT_LOCAL_UNITS], (unsigned)((f2.matchLen + 4 * D.reads[r2].len + 64) >> 2)); }
         D.mcount[r1] = n1; D.mcount[r2] = n2; D.fin[r1] = f1; D.fin[r2] = f2;
     } else {
         if (u >= D.nreads) return;
@@ -1149,7 +1128,7 @@ __global__ __launch_bounds__(128) void final_end_kernel(const Dev D) {
             }
         }
         f.needLocal = f.mapped && contains_xyc(D, f);
-        if (f.needLocal) { atomicAdd(&D.counters[24], 1u); atomicAdd(&D.counters[25], (unsigned)((f.matchLen + 4 * L + 64) >> 2)); }
+        if (f.needLocal) { atomicAdd(&D.counters[CNT_LOCAL_READS], 1u); atomicAdd(&D.counters[CNT_LOCAL_UNITS], (unsigned)((f.matchLen + 4 * L + 64) >> 2)); }
         D.mcount[u] = n; D.fin[u] = f;
     }
 }

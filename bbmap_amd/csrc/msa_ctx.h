@@ -61,7 +61,7 @@ struct bbmsa_ctx {
 };
 
 
-// Internal (mapper.hip).  The mapper switches the narrow kernel off for launches it cannot help: small ones (one job per lane is a
+// Internal (mapper_host.hip, which includes this header through mapper_ctx.h).  The mapper switches the narrow kernel off for launches it cannot help: small ones (one job per lane is a
 // ~1.5 ms dependent chain however few jobs there are, in front of the wavefront kernel on the same stream) and the final alignment
 // stage's (realign_new pads its windows by >= 6 columns and passes minScore - 120: no such fill fits the 16-diagonal band).
 void bbmsa_use_narrow(bbmsa_ctx *c, bool on);

@@ -1,5 +1,5 @@
 // Batch helpers of the mapper that are wave-cooperative byte scans: reverse complement of a read batch and the paired-read
-// rescue scan (AbstractMapThread.quickRescue).  The control flow that decides which sites are aligned lives in mapper.hip.
+// rescue scan (AbstractMapThread.quickRescue).  The control flow that decides which sites are aligned lives in mapper.hip (kernels) and mapper_host.hip (their driver).
 #include <hip/hip_runtime.h>
 
 #include <climits>

@@ -5,7 +5,7 @@
 // 64 symbols per step with ballots.  What a line needs of the mate (mapped, scaffold, pos, strand, score, length) it reads from the
 // mate's own records: the single-scaffold rule has been applied to both mates by the coordinate kernel, whose bbmap_scafrec array is
 // this kernel's input.  Three launches and no atomics: sam_size_kernel (every fixed-size field and the string lengths), a device-wide
-// exclusive scan of the per-read byte counts (host side, mapper.hip), sam_emit_kernel (the same walk again, writing).
+// exclusive scan of the per-read byte counts (host side, bbmap_get_sam_records in mapper_output.hip), sam_emit_kernel (the same walk again, writing).
 //
 // Fixed at the reference's defaults: SOFT_CLIP = true, PENALIZE_AMBIG = true, INTRON_LIMIT = Integer.MAX_VALUE (no `N` operator, no
 // dropped deletion), MAKE_NM_TAG / MAKE_AM_TAG on; primary alignments only (Read.secondary, discarded and invalid are false).

@@ -1,4 +1,5 @@
-"""GPU tests of the final alignment stage of the device mapper (bbmap_amd/csrc/mapper_final.h: genMatchString -> genMatchStringForSite ->
+"""GPU tests of the final alignment stage of the device mapper (kernels in bbmap_amd/csrc/mapper_final.h, their rounds driven by
+run_final_stage in mapper_host.hip: genMatchString -> genMatchStringForSite ->
 realign_new, fixXY / clipTipIndels / toLocalAlignment, final pairing, penalties) against its CPU restatement oracle/final_stage.inc:
 the per-read final records (what BBMap prints), the match strings byte for byte, the site lists after the stage and every fill.
 The whole-flow comparison on ordinary reads is in test_mapper_gpu.py / test_golden_phix.py (both sides run the stage by default);
