@@ -13,12 +13,11 @@
 // see oracle/banded_oracle.c for the list of differences.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-#include <cstring>
 #include <new>
 #include <vector>
 
 #include "bbmap_amd.h"
+#include "host_common.h"
 
 namespace bbband {
 
@@ -247,40 +246,28 @@ __global__ __launch_bounds__(256) void banded_kernel(const Params p) {
 
 }  // namespace bbband
 
-void bbmap_set_error(const char *msg);   // msa_host.hip
-static thread_local char g_berr[256] = "";
-
 struct bbband_ctx {
     int device, maxWidth, variant, G, blocks, ldsBytes;
     unsigned int *d_queue;
 };
 
-static int bfail(int code, const char *msg) { bbmap_set_error(msg); return code; }
-
-#define BHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { snprintf(g_berr, sizeof g_berr, "%s failed: %s", #expr, hipGetErrorString(e_)); bbmap_set_error(g_berr); return BBMAP_E_HIP; } } while (0)
-
 extern "C" int bbband_create(const bbband_config *cfg, bbband_ctx **out) {
-    if (!cfg || !out) return bfail(BBMAP_E_ARG, "bbband_create: null argument");
+    if (!cfg || !out) return bbfail(BBMAP_E_ARG, "bbband_create: null argument");
     *out = nullptr;
-    if (cfg->width < 1 || cfg->width > 1023) return bfail(BBMAP_E_ARG, "bbband_create: width must be 1..1023");
+    if (cfg->width < 1 || cfg->width > 1023) return bbfail(BBMAP_E_ARG, "bbband_create: width must be 1..1023");
     if (cfg->semantics != BBBAND_SEMANTICS_JNI_C && cfg->semantics != BBBAND_SEMANTICS_JAVA)
-        return bfail(BBMAP_E_ARG, "bbband_create: unknown semantics");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return bfail(BBMAP_E_NODEVICE, "bbband_create: no HIP device (no CPU path)");
-    if (cfg->device < 0 || cfg->device >= ndev) return bfail(BBMAP_E_ARG, "bbband_create: bad device ordinal");
-    BHIP(hipSetDevice(cfg->device));
+        return bbfail(BBMAP_E_ARG, "bbband_create: unknown semantics");
     hipDeviceProp_t prop;
-    BHIP(hipGetDeviceProperties(&prop, cfg->device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return bfail(BBMAP_E_NODEVICE, "bbband_create: this build targets gfx950 only");
+    BBTRY(bb_use_gfx950("bbband_create", cfg->device, &prop));
     bbband_ctx *c = new (std::nothrow) bbband_ctx();
-    if (!c) return bfail(BBMAP_E_NOMEM, "bbband_create: out of memory");
+    if (!c) return bbfail(BBMAP_E_NOMEM, "bbband_create: out of memory");
     c->device = cfg->device;
     c->maxWidth = (cfg->width < 3 ? 3 : cfg->width) | 1;            // BandedAligner.java:13
     c->variant = cfg->semantics;
     c->G = c->maxWidth <= 16 ? 16 : (c->maxWidth <= 32 ? 32 : 64);
     c->ldsBytes = 4 * (64 / c->G) * 2 * (c->maxWidth + 2) * 4;
     c->blocks = prop.multiProcessorCount * 8;
-    BHIP(hipMalloc(&c->d_queue, 64));
+    BBHIP(hipMalloc(&c->d_queue, 64));
     *out = c;
     return BBMAP_OK;
 }
@@ -294,13 +281,13 @@ extern "C" void bbband_destroy(bbband_ctx *c) {
 
 extern "C" int bbband_align_batch_device(bbband_ctx *c, void *stream_, int64_t n, const bbband_job *jobs,
                                          const uint8_t *seqs, bbband_result *results) {
-    if (!c) return bfail(BBMAP_E_ARG, "bbband_align_batch_device: null context");
-    if (n < 0 || n > 0x7fffffffLL) return bfail(BBMAP_E_ARG, "bbband_align_batch_device: n_jobs out of range");
+    if (!c) return bbfail(BBMAP_E_ARG, "bbband_align_batch_device: null context");
+    if (n < 0 || n > 0x7fffffffLL) return bbfail(BBMAP_E_ARG, "bbband_align_batch_device: n_jobs out of range");
     if (n == 0) return BBMAP_OK;
-    if (!jobs || !seqs || !results) return bfail(BBMAP_E_ARG, "bbband_align_batch_device: null buffer");
+    if (!jobs || !seqs || !results) return bbfail(BBMAP_E_ARG, "bbband_align_batch_device: null buffer");
     hipStream_t stream = (hipStream_t)stream_;
-    BHIP(hipSetDevice(c->device));
-    BHIP(hipMemsetAsync(c->d_queue, 0, 64, stream));
+    BBHIP(hipSetDevice(c->device));
+    BBHIP(hipMemsetAsync(c->d_queue, 0, 64, stream));
     bbband::Params p;
     p.jobs = jobs; p.seqs = seqs; p.results = results; p.njobs = n; p.queue = c->d_queue;
     p.maxWidth = c->maxWidth; p.variant = c->variant; p.G = c->G;
@@ -308,40 +295,30 @@ extern "C" int bbband_align_batch_device(bbband_ctx *c, void *stream_, int64_t n
     long long blocks = (n + perBlock - 1) / perBlock;
     if (blocks > c->blocks) blocks = c->blocks;
     hipLaunchKernelGGL(bbband::banded_kernel, dim3((unsigned)blocks), dim3(256), (size_t)c->ldsBytes, stream, p);
-    BHIP(hipGetLastError());
+    BBHIP(hipGetLastError());
     return BBMAP_OK;
 }
 
 extern "C" int bbband_align_batch(bbband_ctx *c, int64_t n, const bbband_job *jobs,
                                   const uint8_t *seqs, int64_t seq_bytes, bbband_result *results) {
-    if (!c) return bfail(BBMAP_E_ARG, "bbband_align_batch: null context");
+    if (!c) return bbfail(BBMAP_E_ARG, "bbband_align_batch: null context");
     if (n == 0) return BBMAP_OK;
-    if (n < 0 || !jobs || !seqs || !results || seq_bytes < 0) return bfail(BBMAP_E_ARG, "bbband_align_batch: bad argument");
+    if (n < 0 || !jobs || !seqs || !results || seq_bytes < 0) return bbfail(BBMAP_E_ARG, "bbband_align_batch: bad argument");
     for (int64_t i = 0; i < n; i++) {
         const bbband_job &j = jobs[i];
         if (j.query_len < 0 || j.ref_len < 0 || j.query_off < 0 || j.ref_off < 0 ||
             j.query_off + j.query_len > seq_bytes || j.ref_off + j.ref_len > seq_bytes)
-            return bfail(BBMAP_E_ARG, "bbband_align_batch: a sequence lies outside the seqs buffer");
+            return bbfail(BBMAP_E_ARG, "bbband_align_batch: a sequence lies outside the seqs buffer");
     }
-    BHIP(hipSetDevice(c->device));
-    bbband_job *dj = nullptr; uint8_t *ds = nullptr; bbband_result *dr = nullptr;
-    int rc = BBMAP_OK;
-#define BGO(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { snprintf(g_berr, sizeof g_berr, "%s failed: %s", #expr, hipGetErrorString(e_)); bbmap_set_error(g_berr); rc = BBMAP_E_HIP; goto done; } } while (0)
-    BGO(hipMalloc(&dj, (size_t)n * sizeof(bbband_job)));
-    BGO(hipMalloc(&ds, (size_t)(seq_bytes > 0 ? seq_bytes : 1)));
-    BGO(hipMalloc(&dr, (size_t)n * sizeof(bbband_result)));
-    BGO(hipMemcpy(dj, jobs, (size_t)n * sizeof(bbband_job), hipMemcpyHostToDevice));
-    BGO(hipMemcpy(ds, seqs, (size_t)seq_bytes, hipMemcpyHostToDevice));
-    rc = bbband_align_batch_device(c, nullptr, n, dj, ds, dr);
-    if (rc != BBMAP_OK) goto done;
-    BGO(hipStreamSynchronize(nullptr));
-    BGO(hipMemcpy(results, dr, (size_t)n * sizeof(bbband_result), hipMemcpyDeviceToHost));
-done:
-    if (dj) (void)hipFree(dj);
-    if (ds) (void)hipFree(ds);
-    if (dr) (void)hipFree(dr);
-    return rc;
-#undef BGO
+    BBHIP(hipSetDevice(c->device));
+    DevTmp<bbband_job> dj; DevTmp<uint8_t> ds; DevTmp<bbband_result> dr;
+    BBTRY(dj.upload(jobs, (size_t)n));
+    BBTRY(ds.upload(seqs, (size_t)seq_bytes));
+    BBTRY(dr.alloc((size_t)n));
+    BBTRY(bbband_align_batch_device(c, nullptr, n, dj, ds, dr));
+    BBHIP(hipStreamSynchronize(nullptr));
+    BBHIP(hipMemcpy(results, dr, (size_t)n * sizeof(bbband_result), hipMemcpyDeviceToHost));
+    return BBMAP_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -352,31 +329,28 @@ done:
 namespace {
 struct PairBatch {
     bbband_ctx *c; int64_t n; const bbband_pair *pairs; bool exact;
-    uint8_t *d_seqs = nullptr; bbband_job *d_jobs = nullptr; bbband_result *d_res = nullptr;
+    DevTmp<uint8_t> d_seqs; DevTmp<bbband_job> d_jobs; DevTmp<bbband_result> d_res;
     std::vector<bbband_job> jobs; std::vector<bbband_result> res;
-    ~PairBatch() { if (d_seqs) (void)hipFree(d_seqs); if (d_jobs) (void)hipFree(d_jobs); if (d_res) (void)hipFree(d_res); }
     int init(const uint8_t *seqs, int64_t seq_bytes) {
         for (int64_t i = 0; i < n; i++) {
             const bbband_pair &p = pairs[i];
             if (p.query_len < 0 || p.ref_len < 0 || p.query_off < 0 || p.ref_off < 0 || p.query_off + p.query_len > seq_bytes || p.ref_off + p.ref_len > seq_bytes)
-                return bfail(BBMAP_E_ARG, "bbband pair batch: a sequence lies outside the seqs buffer");
+                return bbfail(BBMAP_E_ARG, "bbband pair batch: a sequence lies outside the seqs buffer");
         }
-        BHIP(hipSetDevice(c->device));
-        BHIP(hipMalloc(&d_seqs, (size_t)(seq_bytes > 0 ? seq_bytes : 1)));
-        BHIP(hipMemcpy(d_seqs, seqs, (size_t)seq_bytes, hipMemcpyHostToDevice));
-        BHIP(hipMalloc(&d_jobs, (size_t)(2 * n) * sizeof(bbband_job)));
-        BHIP(hipMalloc(&d_res, (size_t)(2 * n) * sizeof(bbband_result)));
+        BBHIP(hipSetDevice(c->device));
+        BBTRY(d_seqs.upload(seqs, (size_t)seq_bytes));
+        BBTRY(d_jobs.alloc((size_t)(2 * n)));
+        BBTRY(d_res.alloc((size_t)(2 * n)));
         jobs.resize((size_t)(2 * n)); res.resize((size_t)(2 * n));
         return BBMAP_OK;
     }
     // one launch over `m` jobs already written to jobs[0..m)
     int run(int64_t m) {
         if (m == 0) return BBMAP_OK;
-        BHIP(hipMemcpy(d_jobs, jobs.data(), (size_t)m * sizeof(bbband_job), hipMemcpyHostToDevice));
-        const int rc = bbband_align_batch_device(c, nullptr, m, d_jobs, d_seqs, d_res);
-        if (rc != BBMAP_OK) return rc;
-        BHIP(hipStreamSynchronize(nullptr));
-        BHIP(hipMemcpy(res.data(), d_res, (size_t)m * sizeof(bbband_result), hipMemcpyDeviceToHost));
+        BBHIP(hipMemcpy(d_jobs, jobs.data(), (size_t)m * sizeof(bbband_job), hipMemcpyHostToDevice));
+        BBTRY(bbband_align_batch_device(c, nullptr, m, d_jobs, d_seqs, d_res));
+        BBHIP(hipStreamSynchronize(nullptr));
+        BBHIP(hipMemcpy(res.data(), d_res, (size_t)m * sizeof(bbband_result), hipMemcpyDeviceToHost));
         return BBMAP_OK;
     }
     bbband_job job(int64_t i, int dir, int qstart, int rstart, int maxEdits) const {
@@ -425,7 +399,7 @@ struct PairBatch {
 
 extern "C" int bbband_align_quadruple_batch(bbband_ctx *c, int64_t n, const bbband_pair *pairs, const uint8_t *seqs, int64_t seq_bytes,
                                             int32_t maxEdits, int32_t exact, int32_t *edits) {
-    if (!c || n < 0 || (n > 0 && (!pairs || !seqs || !edits)) || seq_bytes < 0) return bfail(BBMAP_E_ARG, "bbband_align_quadruple_batch: bad argument");
+    if (!c || n < 0 || (n > 0 && (!pairs || !seqs || !edits)) || seq_bytes < 0) return bbfail(BBMAP_E_ARG, "bbband_align_quadruple_batch: bad argument");
     if (n == 0) return BBMAP_OK;
     PairBatch B{c, n, pairs, exact != 0};
     int rc = B.init(seqs, seq_bytes);
@@ -440,7 +414,7 @@ extern "C" int bbband_align_quadruple_batch(bbband_ctx *c, int64_t n, const bbba
 
 extern "C" int bbband_align_quadruple_progressive_batch(bbband_ctx *c, int64_t n, const bbband_pair *pairs, const uint8_t *seqs, int64_t seq_bytes,
                                                         int32_t minEdits, int32_t maxEdits, int32_t exact, int32_t *edits) {
-    if (!c || n < 0 || (n > 0 && (!pairs || !seqs || !edits)) || seq_bytes < 0) return bfail(BBMAP_E_ARG, "bbband_align_quadruple_progressive_batch: bad argument");
+    if (!c || n < 0 || (n > 0 && (!pairs || !seqs || !edits)) || seq_bytes < 0) return bbfail(BBMAP_E_ARG, "bbband_align_quadruple_progressive_batch: bad argument");
     if (n == 0) return BBMAP_OK;
     PairBatch B{c, n, pairs, exact != 0};
     int rc = B.init(seqs, seq_bytes);
@@ -481,7 +455,7 @@ extern "C" int bbband_align_quadruple_progressive_batch(bbband_ctx *c, int64_t n
 
 extern "C" int bbband_align_double_batch(bbband_ctx *c, int64_t n, const bbband_pair *pairs, const uint8_t *seqs, int64_t seq_bytes,
                                          int32_t maxEdits, int32_t exact, int32_t *edits) {
-    if (!c || n < 0 || (n > 0 && (!pairs || !seqs || !edits)) || seq_bytes < 0) return bfail(BBMAP_E_ARG, "bbband_align_double_batch: bad argument");
+    if (!c || n < 0 || (n > 0 && (!pairs || !seqs || !edits)) || seq_bytes < 0) return bbfail(BBMAP_E_ARG, "bbband_align_double_batch: bad argument");
     if (n == 0) return BBMAP_OK;
     PairBatch B{c, n, pairs, exact != 0};
     int rc = B.init(seqs, seq_bytes);

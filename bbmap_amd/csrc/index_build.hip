@@ -20,15 +20,15 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "bbmap_amd.h"
+#include "host_common.h"
 #include "index_common.h"
 #include "index_ctx.h"
-
-void bbmap_set_error(const char *msg);
 
 namespace bbidxb {
 using namespace bbidx;
@@ -139,9 +139,6 @@ __global__ void bincount_kernel(const int *v, long long n, unsigned long long *b
 
 }  // namespace bbidxb
 
-static thread_local char g_berr[256];
-#define BHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { snprintf(g_berr, sizeof g_berr, "%s failed: %s", #expr, hipGetErrorString(e_)); bbmap_set_error(g_berr); rc = BBMAP_E_HIP; goto fail; } } while (0)
-
 // Tools.makeLengthHistogram3/4 with its int32 wrap of counts[ptr]*ptr
 static void length_histogram(const std::vector<unsigned long long> &cnt, int mx, int *hist, int buckets = 1000) {
     long long total = 0;
@@ -198,212 +195,194 @@ extern "C" int bbidx_build(int32_t device, int32_t k, int32_t chromBits, int32_t
 
 extern "C" int bbidx_build_profile(int32_t device, int32_t profile, int32_t k, int32_t chromBits, int32_t nchroms,
                                    const uint8_t *const *chromArr, const int32_t *chromArrLen, bbidx_ctx **out) {
-    if (!out || !chromArr || !chromArrLen) { bbmap_set_error("bbidx_build: null argument"); return BBMAP_E_ARG; }
+    if (!out || !chromArr || !chromArrLen) return bbfail(BBMAP_E_ARG, "bbidx_build: null argument");
     *out = nullptr;
-    if (profile != BBIDX_PROFILE_BBMAP && profile != BBIDX_PROFILE_PACBIO) { bbmap_set_error("bbidx_build: unknown profile"); return BBMAP_E_ARG; }
+    if (profile != BBIDX_PROFILE_BBMAP && profile != BBIDX_PROFILE_PACBIO) return bbfail(BBMAP_E_ARG, "bbidx_build: unknown profile");
     if (k <= 0) k = profile == BBIDX_PROFILE_PACBIO ? 12 : 13;            // BBMapPacBio.java:51 / BBMap.java:48
-    if (k < 8 || k > 15 || nchroms < 1 || chromBits > 16) { bbmap_set_error("bbidx_build: bad geometry (k must be 8..15)"); return BBMAP_E_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { bbmap_set_error("bbidx_build: no HIP device (no CPU path)"); return BBMAP_E_NODEVICE; }
-    if (device < 0 || device >= ndev) { bbmap_set_error("bbidx_build: bad device ordinal"); return BBMAP_E_ARG; }
-    int rc = BBMAP_OK;
-    bbidx_ctx *c = nullptr;
-    unsigned *d_keys = nullptr, *d_keys2 = nullptr, *d_clump = nullptr;
-    int *d_sites2 = nullptr, *d_max = nullptr, *d_countsRaw = nullptr;
-    unsigned long long *d_total = nullptr, *d_defined = nullptr, *d_bins = nullptr;
-    void *d_tmp = nullptr;
-    hipStream_t cs = nullptr, us = nullptr;             // kernels / uploads
-    std::vector<hipEvent_t> evUp;
+    if (k < 8 || k > 15 || nchroms < 1 || chromBits > 16) return bbfail(BBMAP_E_ARG, "bbidx_build: bad geometry (k must be 8..15)");
+    hipDeviceProp_t prop;
+    BBTRY(bb_use_gfx950("bbidx_build", device, &prop));
+    // Scopes, in the order they end: `run` first (on failure both streams are drained before anything they may still use goes
+    // away; the upload events and the streams are destroyed either way), then the work buffers, last the context on failure.
+    struct Ctx { bbidx_ctx *c = nullptr; ~Ctx() { if (c) bbidx_destroy(c); } } ctx;
+    DevTmp<unsigned> d_keys, d_keys2, d_clump;
+    DevTmp<int> d_sites2, d_max, d_countsRaw;
+    DevTmp<unsigned long long> d_total, d_defined, d_bins;
+    DevTmp<char> d_tmp;
+    struct Run {
+        hipStream_t cs = nullptr, us = nullptr;         // kernels / uploads
+        std::vector<hipEvent_t> evUp;
+        bool ok = false;
+        ~Run() {
+            if (!ok && cs) (void)hipStreamSynchronize(cs);
+            if (!ok && us) (void)hipStreamSynchronize(us);
+            for (hipEvent_t e : evUp) if (e) (void)hipEventDestroy(e);
+            if (cs) (void)hipStreamDestroy(cs);
+            if (us) (void)hipStreamDestroy(us);
+        }
+    } run;
+    hipStream_t &cs = run.cs, &us = run.us;
+    std::vector<hipEvent_t> &evUp = run.evUp;
     const bool timers = getenv("BBIDX_BUILD_TIMERS") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
     double msUpload = 0;
-    {
-        if (hipSetDevice(device) != hipSuccess) { bbmap_set_error("bbidx_build: hipSetDevice failed"); return BBMAP_E_HIP; }
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) != hipSuccess) { bbmap_set_error("bbidx_build: hipGetDeviceProperties failed"); return BBMAP_E_HIP; }
-        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) { bbmap_set_error("bbidx_build: this build targets gfx950 only"); return BBMAP_E_NODEVICE; }
-        int maxlen = 0;
-        for (int ch = 1; ch <= nchroms; ch++) { if (chromArrLen[ch] < 0 || !chromArr[ch]) { bbmap_set_error("bbidx_build: bad chromosome"); return BBMAP_E_ARG; } if (chromArrLen[ch] > maxlen) maxlen = chromArrLen[ch]; }
-        if (chromBits < 0) {                                     // RefToIndex.AUTO_CHROMBITS, BBMap.java:317-321
-            int bl = 0; for (unsigned v = (unsigned)maxlen; v; v >>= 1) bl++;
-            chromBits = (32 - bl) - 1; if (chromBits > 16) chromBits = 16; if (chromBits < 0) chromBits = 0;
-        }
-        if (maxlen > (int)(0xFFFFFFFFu >> (chromBits + 1))) { bbmap_set_error("bbidx_build: a chromosome does not fit the site encoding for this chromBits"); return BBMAP_E_ARG; }
-        c = new (std::nothrow) bbidx_ctx();
-        if (!c) { bbmap_set_error("bbidx_build: out of memory"); return BBMAP_E_NOMEM; }
-        c->device = device; c->kernelKind = BBIDX_KERNEL_AUTO; c->blocks = prop.multiProcessorCount * 8;
-        c->totalSites = 0; c->maxReadLen = BBIDX_MAX_READ_LEN;
-        c->maxGroups = bbidx_env_max_groups();
-        memset(&c->dev, 0, sizeof c->dev);
-        const int nblocks = (nchroms >> chromBits) + 1;
-        const int cpb = 1 << chromBits, shift = 31 - chromBits, lowMask = cpb - 1;
-        const long long nkeys = 1LL << (2 * k);
-        const unsigned kb = (unsigned)((nkeys + 255) / 256);
-        c->dev.p.k = k; c->dev.p.chromBits = chromBits; c->dev.p.minChrom = 1; c->dev.p.maxChrom = nchroms; c->dev.p.profile = profile; c->dev.p.reserved = 0;
-        c->dev.nblocks = nblocks; c->dev.nchroms = nchroms;
-
-        // Per block: positions, and the largest block sizes the work buffers (allocated once: a hipFree per block is a device-wide
-        // synchronisation, and the next block's chromosomes are meant to upload while this block sorts)
-        std::vector<long long> blockPos((size_t)nblocks, 0);
-        long long maxPos = 0;
-        for (int b = 0; b < nblocks; b++) {
-            const int first = b * cpb > 1 ? b * cpb : 1, last = (b * cpb + cpb - 1) < nchroms ? (b * cpb + cpb - 1) : nchroms;
-            long long npos = 0;
-            for (int ch = first; ch <= last; ch++) npos += chromArrLen[ch] > k ? chromArrLen[ch] - k : 0;
-            if (npos > 0x7fffffffLL - 64) { bbmap_set_error("bbidx_build: more than 2^31 - 64 positions in one block"); rc = BBMAP_E_ARG; goto fail; }   // (cursor look-ahead stays in int range)
-            blockPos[(size_t)b] = npos; c->totalSites += npos;
-            if (npos > maxPos) maxPos = npos;
-        }
-        BHIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-        BHIP(hipStreamCreateWithFlags(&us, hipStreamNonBlocking));
-        std::vector<const uint8_t *> hc((size_t)nchroms + 1, nullptr);
-        for (int ch = 1; ch <= nchroms; ch++) {
-            void *d = nullptr;
-            BHIP(hipMalloc(&d, (size_t)(chromArrLen[ch] > 0 ? chromArrLen[ch] : 1)));
-            c->allocs.push_back(d);
-            hc[(size_t)ch] = (const uint8_t *)d;
-        }
-        BHIP(hipMalloc(&d_total, (size_t)nkeys * 8));
-        BHIP(hipMalloc(&d_clump, (size_t)nkeys * 4));
-        BHIP(hipMalloc(&d_defined, 8));
-        BHIP(hipMalloc(&d_max, 4));
-        BHIP(hipMemsetAsync(d_total, 0, (size_t)nkeys * 8, cs));
-        BHIP(hipMemsetAsync(d_clump, 0, (size_t)nkeys * 4, cs));
-        BHIP(hipMemsetAsync(d_defined, 0, 8, cs));
-        BHIP(hipMemsetAsync(d_max, 0, 4, cs));
-        BHIP(hipMalloc(&d_keys, (size_t)(maxPos > 0 ? maxPos : 1) * 4));
-        BHIP(hipMalloc(&d_keys2, (size_t)(maxPos > 0 ? maxPos : 1) * 4));
-        BHIP(hipMalloc(&d_sites2, (size_t)(maxPos > 0 ? maxPos : 1) * 4));
-        size_t tmpNeed = 0;
-        if (maxPos > 0) {
-            BHIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmpNeed, d_keys, d_keys2, d_sites2, (int *)d_sites2, (int)maxPos, 0, 2 * k, cs));
-            BHIP(hipMalloc(&d_tmp, tmpNeed));
-        }
-
-        std::vector<const int *> hs((size_t)nblocks, nullptr), hsi((size_t)nblocks, nullptr);
-        evUp.resize((size_t)nblocks, nullptr);
-        for (int b = 0; b < nblocks; b++) {
-            const int first = b * cpb > 1 ? b * cpb : 1, last = (b * cpb + cpb - 1) < nchroms ? (b * cpb + cpb - 1) : nchroms;
-            const long long npos = blockPos[(size_t)b];
-            // this block's chromosomes go up on the upload stream while the previous block is still being sorted on the other
-            const double u0 = since();
-            for (int ch = first; ch <= last; ch++)
-                if (chromArrLen[ch] > 0) BHIP(hipMemcpyAsync((void *)hc[(size_t)ch], chromArr[ch], (size_t)chromArrLen[ch], hipMemcpyHostToDevice, us));
-            BHIP(hipEventCreateWithFlags(&evUp[(size_t)b], hipEventDisableTiming));
-            BHIP(hipEventRecord(evUp[(size_t)b], us));
-            msUpload += since() - u0;
-            BHIP(hipStreamWaitEvent(cs, evUp[(size_t)b], 0));
-            int *d_sites = nullptr, *d_starts = nullptr;
-            BHIP(hipMalloc(&d_starts, (size_t)(nkeys + 1) * 4)); c->allocs.push_back(d_starts);
-            BHIP(hipMalloc(&d_sites, (size_t)(npos > 0 ? npos : 1) * 4)); c->allocs.push_back(d_sites);
-            long long off = 0;
-            for (int ch = first; ch <= last; ch++) {
-                const int len = chromArrLen[ch];
-                if (len <= 0) continue;
-                unsigned eb = (unsigned)((len + 255) / 256);
-                if (eb > 8192u) eb = 8192u;
-                hipLaunchKernelGGL(bbidxb::emit_kernel, dim3(eb), dim3(256), 0, cs, hc[(size_t)ch], len, k, ch, shift, lowMask,
-                                   d_keys + off, d_sites2 + off, d_defined);
-                BHIP(hipGetLastError());
-                off += len > k ? len - k : 0;
-            }
-            if (npos > 0) {
-                size_t need = tmpNeed;
-                BHIP(hipcub::DeviceRadixSort::SortPairs(d_tmp, need, d_keys, d_keys2, d_sites2, d_sites, (int)npos, 0, 2 * k, cs));
-            }
-            hipLaunchKernelGGL(bbidxb::starts_from_sorted_kernel, dim3((unsigned)((npos + 1 + 255) / 256)), dim3(256), 0, cs, d_keys2, npos, d_starts, nkeys);
-            hipLaunchKernelGGL(bbidxb::accumulate_counts, dim3(kb), dim3(256), 0, cs, d_starts, d_total, nkeys);
-            if (npos > 1)
-                hipLaunchKernelGGL(bbidxb::clump_kernel, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0, cs,
-                                   d_keys2, d_sites, d_starts + nkeys, k, d_clump);
-            BHIP(hipGetLastError());
-            hs[(size_t)b] = d_starts; hsi[(size_t)b] = d_sites;
-        }
-        // COUNTS, clumpy keys, length histogram
-        int *d_counts = nullptr;
-        BHIP(hipMalloc(&d_counts, (size_t)nkeys * 4)); c->allocs.push_back(d_counts);
-        BHIP(hipMalloc(&d_countsRaw, (size_t)nkeys * 4));
-        hipLaunchKernelGGL(bbidxb::combine_counts, dim3(kb), dim3(256), 0, cs, d_total, d_countsRaw, k, nkeys);
-        BHIP(hipMemcpyAsync(d_counts, d_countsRaw, (size_t)nkeys * 4, hipMemcpyDeviceToDevice, cs));
-        hipLaunchKernelGGL(bbidxb::zero_clumpy, dim3(kb), dim3(256), 0, cs, d_clump, d_countsRaw, d_counts, k, nkeys,
-                           profile == BBIDX_PROFILE_PACBIO ? 2800 : 2000, profile == BBIDX_PROFILE_PACBIO ? 0.8f : 0.75f);   // CLUMPY_MIN_LENGTH_INDEX, CLUMPY_FRACTION
-        hipLaunchKernelGGL(bbidxb::max_kernel, dim3(2048), dim3(256), 0, cs, d_counts, nkeys, d_max);
-        BHIP(hipGetLastError());
-        int mx = 0;
-        BHIP(hipMemcpyAsync(&mx, d_max, 4, hipMemcpyDeviceToHost, cs));
-        BHIP(hipStreamSynchronize(cs));
-        const double msLists = since();
-        BHIP(hipMalloc(&d_bins, (size_t)(mx + 1) * 8));
-        BHIP(hipMemsetAsync(d_bins, 0, (size_t)(mx + 1) * 8, cs));
-        hipLaunchKernelGGL(bbidxb::bincount_kernel, dim3(2048), dim3(256), 0, cs, d_counts, nkeys, d_bins, mx + 1);
-        BHIP(hipGetLastError());
-        std::vector<unsigned long long> bins((size_t)mx + 1);
-        BHIP(hipMemcpyAsync(bins.data(), d_bins, (size_t)(mx + 1) * 8, hipMemcpyDeviceToHost, cs));
-        unsigned long long defined = 0;
-        BHIP(hipMemcpyAsync(&defined, d_defined, 8, hipMemcpyDeviceToHost, cs));
-        BHIP(hipStreamSynchronize(cs));
-        int hist[1001];
-        length_histogram(bins, mx, hist);
-        derive_params(c->dev.p, (long long)defined, hist);
-        c->dev.counts = d_counts;
-
-        auto up = [&](const void *host, size_t bytes, const void **dev) -> int {
-            void *d = nullptr;
-            if (hipMalloc(&d, bytes ? bytes : 1) != hipSuccess) return BBMAP_E_HIP;
-            c->allocs.push_back(d);
-            if (bytes && hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return BBMAP_E_HIP;
-            *dev = d;
-            return BBMAP_OK;
-        };
-        std::vector<int> clen((size_t)nchroms + 1, 0);
-        for (int ch = 1; ch <= nchroms; ch++) clen[(size_t)ch] = chromArrLen[ch];
-        if (up(hist, sizeof hist, (const void **)&c->dev.lengthHistogram) != BBMAP_OK ||
-            up(hs.data(), hs.size() * sizeof(void *), (const void **)&c->dev.starts) != BBMAP_OK ||
-            up(hsi.data(), hsi.size() * sizeof(void *), (const void **)&c->dev.sites) != BBMAP_OK ||
-            up(hc.data(), hc.size() * sizeof(void *), (const void **)&c->dev.chromArr) != BBMAP_OK ||
-            up(clen.data(), clen.size() * 4, (const void **)&c->dev.chromArrLen) != BBMAP_OK ||
-            up(clen.data(), clen.size() * 4, (const void **)&c->dev.chromLengths) != BBMAP_OK) {
-            bbmap_set_error("bbidx_build: device allocation failed"); rc = BBMAP_E_HIP; goto fail;
-        }
-        const double msStats = since();
-        rc = bbidx_finish_create(c, hs, hsi);
-        if (rc != BBMAP_OK) goto fail;
-        if (timers) fprintf(stderr, "bbidx_build: lists of %d block(s) %.1f ms (of which the host spent %.1f ms handing chromosomes to the upload stream), "
-                                    "COUNTS / histogram %.1f ms, fused key tables %.1f ms\n", nblocks, msLists, msUpload, msStats - msLists, since() - msStats);
+    int maxlen = 0;
+    for (int ch = 1; ch <= nchroms; ch++) { if (chromArrLen[ch] < 0 || !chromArr[ch]) return bbfail(BBMAP_E_ARG, "bbidx_build: bad chromosome"); if (chromArrLen[ch] > maxlen) maxlen = chromArrLen[ch]; }
+    if (chromBits < 0) {                                     // RefToIndex.AUTO_CHROMBITS, BBMap.java:317-321
+        int bl = 0; for (unsigned v = (unsigned)maxlen; v; v >>= 1) bl++;
+        chromBits = (32 - bl) - 1; if (chromBits > 16) chromBits = 16; if (chromBits < 0) chromBits = 0;
     }
-    for (hipEvent_t e : evUp) if (e) (void)hipEventDestroy(e);
-    if (cs) (void)hipStreamDestroy(cs);
-    if (us) (void)hipStreamDestroy(us);
-    if (d_tmp) (void)hipFree(d_tmp);
-    (void)hipFree(d_keys); (void)hipFree(d_keys2); (void)hipFree(d_sites2);
-    (void)hipFree(d_total); (void)hipFree(d_clump); (void)hipFree(d_defined);
-    (void)hipFree(d_max); (void)hipFree(d_countsRaw); if (d_bins) (void)hipFree(d_bins);
-    *out = c;
+    if (maxlen > (int)(0xFFFFFFFFu >> (chromBits + 1))) return bbfail(BBMAP_E_ARG, "bbidx_build: a chromosome does not fit the site encoding for this chromBits");
+    bbidx_ctx *const c = ctx.c = new (std::nothrow) bbidx_ctx();
+    if (!c) return bbfail(BBMAP_E_NOMEM, "bbidx_build: out of memory");
+    c->device = device; c->kernelKind = BBIDX_KERNEL_AUTO; c->blocks = prop.multiProcessorCount * 8;
+    c->totalSites = 0; c->maxReadLen = BBIDX_MAX_READ_LEN;
+    c->maxGroups = bbidx_env_max_groups();
+    memset(&c->dev, 0, sizeof c->dev);
+    const int nblocks = (nchroms >> chromBits) + 1;
+    const int cpb = 1 << chromBits, shift = 31 - chromBits, lowMask = cpb - 1;
+    const long long nkeys = 1LL << (2 * k);
+    const unsigned kb = (unsigned)((nkeys + 255) / 256);
+    c->dev.p.k = k; c->dev.p.chromBits = chromBits; c->dev.p.minChrom = 1; c->dev.p.maxChrom = nchroms; c->dev.p.profile = profile; c->dev.p.reserved = 0;
+    c->dev.nblocks = nblocks; c->dev.nchroms = nchroms;
+
+    // Per block: positions, and the largest block sizes the work buffers (allocated once: a hipFree per block is a device-wide
+    // synchronisation, and the next block's chromosomes are meant to upload while this block sorts)
+    std::vector<long long> blockPos((size_t)nblocks, 0);
+    long long maxPos = 0;
+    for (int b = 0; b < nblocks; b++) {
+        const int first = b * cpb > 1 ? b * cpb : 1, last = (b * cpb + cpb - 1) < nchroms ? (b * cpb + cpb - 1) : nchroms;
+        long long npos = 0;
+        for (int ch = first; ch <= last; ch++) npos += chromArrLen[ch] > k ? chromArrLen[ch] - k : 0;
+        if (npos > 0x7fffffffLL - 64) return bbfail(BBMAP_E_ARG, "bbidx_build: more than 2^31 - 64 positions in one block");   // (cursor look-ahead stays in int range)
+        blockPos[(size_t)b] = npos; c->totalSites += npos;
+        if (npos > maxPos) maxPos = npos;
+    }
+    BBHIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+    BBHIP(hipStreamCreateWithFlags(&us, hipStreamNonBlocking));
+    std::vector<const uint8_t *> hc((size_t)nchroms + 1, nullptr);
+    for (int ch = 1; ch <= nchroms; ch++) {
+        void *d = nullptr;
+        BBHIP(hipMalloc(&d, (size_t)(chromArrLen[ch] > 0 ? chromArrLen[ch] : 1)));
+        c->allocs.push_back(d);
+        hc[(size_t)ch] = (const uint8_t *)d;
+    }
+    BBTRY(d_total.alloc((size_t)nkeys));
+    BBTRY(d_clump.alloc((size_t)nkeys));
+    BBTRY(d_defined.alloc(1));
+    BBTRY(d_max.alloc(1));
+    BBHIP(hipMemsetAsync(d_total, 0, (size_t)nkeys * 8, cs));
+    BBHIP(hipMemsetAsync(d_clump, 0, (size_t)nkeys * 4, cs));
+    BBHIP(hipMemsetAsync(d_defined, 0, 8, cs));
+    BBHIP(hipMemsetAsync(d_max, 0, 4, cs));
+    BBTRY(d_keys.alloc((size_t)maxPos));
+    BBTRY(d_keys2.alloc((size_t)maxPos));
+    BBTRY(d_sites2.alloc((size_t)maxPos));
+    size_t tmpNeed = 0;
+    if (maxPos > 0) {
+        BBHIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmpNeed, d_keys.p, d_keys2.p, d_sites2.p, d_sites2.p, (int)maxPos, 0, 2 * k, cs));
+        BBTRY(d_tmp.alloc(tmpNeed));
+    }
+
+    std::vector<const int *> hs((size_t)nblocks, nullptr), hsi((size_t)nblocks, nullptr);
+    evUp.resize((size_t)nblocks, nullptr);
+    for (int b = 0; b < nblocks; b++) {
+        const int first = b * cpb > 1 ? b * cpb : 1, last = (b * cpb + cpb - 1) < nchroms ? (b * cpb + cpb - 1) : nchroms;
+        const long long npos = blockPos[(size_t)b];
+        // this block's chromosomes go up on the upload stream while the previous block is still being sorted on the other
+        const double u0 = since();
+        for (int ch = first; ch <= last; ch++)
+            if (chromArrLen[ch] > 0) BBHIP(hipMemcpyAsync((void *)hc[(size_t)ch], chromArr[ch], (size_t)chromArrLen[ch], hipMemcpyHostToDevice, us));
+        BBHIP(hipEventCreateWithFlags(&evUp[(size_t)b], hipEventDisableTiming));
+        BBHIP(hipEventRecord(evUp[(size_t)b], us));
+        msUpload += since() - u0;
+        BBHIP(hipStreamWaitEvent(cs, evUp[(size_t)b], 0));
+        int *d_sites = nullptr, *d_starts = nullptr;
+        BBHIP(hipMalloc(&d_starts, (size_t)(nkeys + 1) * 4)); c->allocs.push_back(d_starts);
+        BBHIP(hipMalloc(&d_sites, (size_t)(npos > 0 ? npos : 1) * 4)); c->allocs.push_back(d_sites);
+        long long off = 0;
+        for (int ch = first; ch <= last; ch++) {
+            const int len = chromArrLen[ch];
+            if (len <= 0) continue;
+            unsigned eb = (unsigned)((len + 255) / 256);
+            if (eb > 8192u) eb = 8192u;
+            hipLaunchKernelGGL(bbidxb::emit_kernel, dim3(eb), dim3(256), 0, cs, hc[(size_t)ch], len, k, ch, shift, lowMask,
+                               d_keys + off, d_sites2 + off, d_defined);
+            BBHIP(hipGetLastError());
+            off += len > k ? len - k : 0;
+        }
+        if (npos > 0) {
+            size_t need = tmpNeed;
+            BBHIP(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, need, d_keys.p, d_keys2.p, d_sites2.p, d_sites, (int)npos, 0, 2 * k, cs));
+        }
+        hipLaunchKernelGGL(bbidxb::starts_from_sorted_kernel, dim3((unsigned)((npos + 1 + 255) / 256)), dim3(256), 0, cs, d_keys2, npos, d_starts, nkeys);
+        hipLaunchKernelGGL(bbidxb::accumulate_counts, dim3(kb), dim3(256), 0, cs, d_starts, d_total, nkeys);
+        if (npos > 1)
+            hipLaunchKernelGGL(bbidxb::clump_kernel, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0, cs,
+                               d_keys2, d_sites, d_starts + nkeys, k, d_clump);
+        BBHIP(hipGetLastError());
+        hs[(size_t)b] = d_starts; hsi[(size_t)b] = d_sites;
+    }
+    // COUNTS, clumpy keys, length histogram
+    int *d_counts = nullptr;
+    BBHIP(hipMalloc(&d_counts, (size_t)nkeys * 4)); c->allocs.push_back(d_counts);
+    BBTRY(d_countsRaw.alloc((size_t)nkeys));
+    hipLaunchKernelGGL(bbidxb::combine_counts, dim3(kb), dim3(256), 0, cs, d_total, d_countsRaw, k, nkeys);
+    BBHIP(hipMemcpyAsync(d_counts, d_countsRaw, (size_t)nkeys * 4, hipMemcpyDeviceToDevice, cs));
+    hipLaunchKernelGGL(bbidxb::zero_clumpy, dim3(kb), dim3(256), 0, cs, d_clump, d_countsRaw, d_counts, k, nkeys,
+                       profile == BBIDX_PROFILE_PACBIO ? 2800 : 2000, profile == BBIDX_PROFILE_PACBIO ? 0.8f : 0.75f);   // CLUMPY_MIN_LENGTH_INDEX, CLUMPY_FRACTION
+    hipLaunchKernelGGL(bbidxb::max_kernel, dim3(2048), dim3(256), 0, cs, d_counts, nkeys, d_max);
+    BBHIP(hipGetLastError());
+    int mx = 0;
+    BBHIP(hipMemcpyAsync(&mx, d_max, 4, hipMemcpyDeviceToHost, cs));
+    BBHIP(hipStreamSynchronize(cs));
+    const double msLists = since();
+    BBTRY(d_bins.alloc((size_t)mx + 1));
+    BBHIP(hipMemsetAsync(d_bins, 0, (size_t)(mx + 1) * 8, cs));
+    hipLaunchKernelGGL(bbidxb::bincount_kernel, dim3(2048), dim3(256), 0, cs, d_counts, nkeys, d_bins, mx + 1);
+    BBHIP(hipGetLastError());
+    std::vector<unsigned long long> bins((size_t)mx + 1);
+    BBHIP(hipMemcpyAsync(bins.data(), d_bins, (size_t)(mx + 1) * 8, hipMemcpyDeviceToHost, cs));
+    unsigned long long defined = 0;
+    BBHIP(hipMemcpyAsync(&defined, d_defined, 8, hipMemcpyDeviceToHost, cs));
+    BBHIP(hipStreamSynchronize(cs));
+    int hist[1001];
+    length_histogram(bins, mx, hist);
+    derive_params(c->dev.p, (long long)defined, hist);
+    c->dev.counts = d_counts;
+
+    auto up = [&](const void *host, size_t bytes, const void **dev) -> int {
+        void *d = nullptr;
+        if (hipMalloc(&d, bytes ? bytes : 1) != hipSuccess) return BBMAP_E_HIP;
+        c->allocs.push_back(d);
+        if (bytes && hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return BBMAP_E_HIP;
+        *dev = d;
+        return BBMAP_OK;
+    };
+    std::vector<int> clen((size_t)nchroms + 1, 0);
+    for (int ch = 1; ch <= nchroms; ch++) clen[(size_t)ch] = chromArrLen[ch];
+    if (up(hist, sizeof hist, (const void **)&c->dev.lengthHistogram) != BBMAP_OK ||
+        up(hs.data(), hs.size() * sizeof(void *), (const void **)&c->dev.starts) != BBMAP_OK ||
+        up(hsi.data(), hsi.size() * sizeof(void *), (const void **)&c->dev.sites) != BBMAP_OK ||
+        up(hc.data(), hc.size() * sizeof(void *), (const void **)&c->dev.chromArr) != BBMAP_OK ||
+        up(clen.data(), clen.size() * 4, (const void **)&c->dev.chromArrLen) != BBMAP_OK ||
+        up(clen.data(), clen.size() * 4, (const void **)&c->dev.chromLengths) != BBMAP_OK) {
+        return bbfail(BBMAP_E_HIP, "bbidx_build: device allocation failed");
+    }
+    const double msStats = since();
+    BBTRY(bbidx_finish_create(c, hs, hsi));
+    if (timers) fprintf(stderr, "bbidx_build: lists of %d block(s) %.1f ms (of which the host spent %.1f ms handing chromosomes to the upload stream), "
+                                "COUNTS / histogram %.1f ms, fused key tables %.1f ms\n", nblocks, msLists, msUpload, msStats - msLists, since() - msStats);
+    run.ok = true;
+    *out = ctx.c;
+    ctx.c = nullptr;
     return BBMAP_OK;
-fail:
-    if (cs) (void)hipStreamSynchronize(cs);
-    if (us) (void)hipStreamSynchronize(us);
-    for (hipEvent_t e : evUp) if (e) (void)hipEventDestroy(e);
-    if (cs) (void)hipStreamDestroy(cs);
-    if (us) (void)hipStreamDestroy(us);
-    if (d_tmp) (void)hipFree(d_tmp);
-    if (d_keys) (void)hipFree(d_keys);
-    if (d_keys2) (void)hipFree(d_keys2);
-    if (d_sites2) (void)hipFree(d_sites2);
-    if (d_total) (void)hipFree(d_total);
-    if (d_clump) (void)hipFree(d_clump);
-    if (d_defined) (void)hipFree(d_defined);
-    if (d_max) (void)hipFree(d_max);
-    if (d_countsRaw) (void)hipFree(d_countsRaw);
-    if (d_bins) (void)hipFree(d_bins);
-    if (c) bbidx_destroy(c);
-    return rc;
 }
 
 // the tunables bbidx_build derived (or bbidx_create was given)
 extern "C" int bbidx_get_params(bbidx_ctx *c, bbidx_params *out) {
-    if (!c || !out) { bbmap_set_error("bbidx_get_params: null argument"); return BBMAP_E_ARG; }
+    if (!c || !out) return bbfail(BBMAP_E_ARG, "bbidx_get_params: null argument");
     *out = c->dev.p;
     return BBMAP_OK;
 }
@@ -412,25 +391,20 @@ extern "C" int bbidx_get_params(bbidx_ctx *c, bbidx_params *out) {
 // starts[4^k]; counts: 4^k ints; lengthHistogram: 1001 ints.
 extern "C" int bbidx_export_block(bbidx_ctx *c, int32_t block, int32_t *starts, int32_t *sites, int64_t sites_cap,
                                   int32_t *counts, int32_t *lengthHistogram) {
-    if (!c || block < 0 || block >= c->dev.nblocks) { bbmap_set_error("bbidx_export_block: bad argument"); return BBMAP_E_ARG; }
-    int rc = BBMAP_OK;
+    if (!c || block < 0 || block >= c->dev.nblocks) return bbfail(BBMAP_E_ARG, "bbidx_export_block: bad argument");
     const size_t nkeys = (size_t)1 << (2 * c->dev.p.k);
-    {
-        if (hipSetDevice(c->device) != hipSuccess) { bbmap_set_error("bbidx_export_block: hipSetDevice failed"); return BBMAP_E_HIP; }
-        const int *dst = nullptr, *dsi = nullptr;
-        BHIP(hipMemcpy(&dst, c->dev.starts + block, sizeof(void *), hipMemcpyDeviceToHost));
-        BHIP(hipMemcpy(&dsi, c->dev.sites + block, sizeof(void *), hipMemcpyDeviceToHost));
-        int n = 0;
-        BHIP(hipMemcpy(&n, dst + nkeys, 4, hipMemcpyDeviceToHost));
-        if (starts) BHIP(hipMemcpy(starts, dst, (nkeys + 1) * 4, hipMemcpyDeviceToHost));
-        if (sites) {
-            if (sites_cap < n) { bbmap_set_error("bbidx_export_block: sites buffer too small"); return BBMAP_E_ARG; }
-            if (n > 0) BHIP(hipMemcpy(sites, dsi, (size_t)n * 4, hipMemcpyDeviceToHost));
-        }
-        if (counts) BHIP(hipMemcpy(counts, c->dev.counts, nkeys * 4, hipMemcpyDeviceToHost));
-        if (lengthHistogram) BHIP(hipMemcpy(lengthHistogram, c->dev.lengthHistogram, 1001 * 4, hipMemcpyDeviceToHost));
+    BBHIP(hipSetDevice(c->device));
+    const int *dst = nullptr, *dsi = nullptr;
+    BBHIP(hipMemcpy(&dst, c->dev.starts + block, sizeof(void *), hipMemcpyDeviceToHost));
+    BBHIP(hipMemcpy(&dsi, c->dev.sites + block, sizeof(void *), hipMemcpyDeviceToHost));
+    int n = 0;
+    BBHIP(hipMemcpy(&n, dst + nkeys, 4, hipMemcpyDeviceToHost));
+    if (starts) BBHIP(hipMemcpy(starts, dst, (nkeys + 1) * 4, hipMemcpyDeviceToHost));
+    if (sites) {
+        if (sites_cap < n) return bbfail(BBMAP_E_ARG, "bbidx_export_block: sites buffer too small");
+        if (n > 0) BBHIP(hipMemcpy(sites, dsi, (size_t)n * 4, hipMemcpyDeviceToHost));
     }
+    if (counts) BBHIP(hipMemcpy(counts, c->dev.counts, nkeys * 4, hipMemcpyDeviceToHost));
+    if (lengthHistogram) BBHIP(hipMemcpy(lengthHistogram, c->dev.lengthHistogram, 1001 * 4, hipMemcpyDeviceToHost));
     return BBMAP_OK;
-fail:
-    return rc;
 }

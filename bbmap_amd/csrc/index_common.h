@@ -57,6 +57,8 @@ struct Params {
     uint8_t *rcOut;                // optional: reverse complement of every probed read, same offsets as `bases`
     unsigned long long *stats;     // [STAT_SHARDS][8]: prescan entries, walk entries, extendScore calls, ref bytes, sites written
 };
+// the per-lane kernel (index_probe.hip), launched by the dispatcher in index_host.hip
+__global__ __launch_bounds__(64) void probe_kernel(const Params P);
 
 __device__ inline int base_num(int b) {
     switch (b) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2;

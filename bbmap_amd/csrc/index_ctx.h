@@ -1,4 +1,6 @@
-// Host-side context of the index-probe entry points (index_probe.hip, index_build.hip).
+// Host-side context of the index-probe entry points (index_host.hip: creation, the dispatcher over the three probe kernels and what
+// reads a finished launch; index_build.hip: the device build), also seen by the launchers of index_probe_wave.hip and
+// index_probe_long.hip, by scaffold_table.hip and by the mapper.
 #pragma once
 #include <hip/hip_runtime.h>
 

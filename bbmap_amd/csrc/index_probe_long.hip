@@ -29,9 +29,9 @@
 #include <mutex>
 
 #include <climits>
-#include <cstdio>
 
 #include "bbmap_amd.h"
+#include "host_common.h"
 #include "index_ctx.h"
 #include "index_probe_shared.h"
 
@@ -906,18 +906,14 @@ static int long_cus(int profile) {                     // of the CURRENT device 
 int bbidx_long_blocks(int profile) { return long_cus(profile) * LONG_MAX_BLOCKS_PER_CU; }
 
 int bbidx_launch_long(const bbidx::Params &P, hipStream_t stream, int profile, int *ws, int blocks, int maxGroups, bbidx_launch *ls) {
-    static thread_local char msg[256];
     // the batch's maxima size the LDS layout, and with it the number of resident wavefronts (one host round trip; the kernel runs
     // for milliseconds per read)
     unsigned int mx[2] = {0, 0};
     {
         const long long n = P.nreads;
         hipLaunchKernelGGL(bbidxl::long_maxima_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, P.reads, n, P.queue + 8);
-        if (hipMemcpyAsync(mx, P.queue + 8, sizeof mx, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
-            snprintf(msg, sizeof msg, "probe_long_kernel: reading the batch's maxima failed: %s", hipGetErrorString(hipGetLastError()));
-            bbmap_set_error(msg);
-            return BBMAP_E_HIP;
-        }
+        BBHIP(hipMemcpyAsync(mx, P.queue + 8, sizeof mx, hipMemcpyDeviceToHost, stream));
+        BBHIP(hipStreamSynchronize(stream));
     }
     bbidxl::LongParams Q;
     Q.P = P; Q.ws = ws;
@@ -938,11 +934,6 @@ int bbidx_launch_long(const bbidx::Params &P, hipStream_t stream, int profile, i
     ls->lastLongGroups = nb; ls->longMaxLen = Q.maxLen; ls->longMaxKeys = Q.maxKeys;
     if (profile) hipLaunchKernelGGL(bbidxl::probe_long_kernel<bbidxl::ProfPacBio>, dim3((unsigned)nb), dim3(64), lds, stream, Q);
     else hipLaunchKernelGGL(bbidxl::probe_long_kernel<bbidxl::ProfBBMap>, dim3((unsigned)nb), dim3(64), lds, stream, Q);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(msg, sizeof msg, "probe_long_kernel launch failed: %s", hipGetErrorString(e));
-        bbmap_set_error(msg);
-        return BBMAP_E_HIP;
-    }
+    BBHIP(hipGetLastError());
     return BBMAP_OK;
 }

@@ -16,8 +16,6 @@
 #include "index_common.h"
 #include "wave_prims.h"
 
-void bbmap_set_error(const char *msg);   // msa_host.hip
-
 namespace bbidx {
 
 struct ProfBBMap {      // BBIndex.java:3168-3305 ; MultiStateAligner11tsJNI.java:871-1027, jni/MultiStateAligner11tsJNI.c:18-98

@@ -26,9 +26,9 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cstdio>
 
 #include "bbmap_amd.h"
+#include "host_common.h"
 #include "index_probe_shared.h"
 
 namespace bbidxw {
@@ -1504,12 +1504,6 @@ int bbidx_launch_wave(const bbidx::Params &P, hipStream_t stream, bool longLists
         if (shortReads) hipLaunchKernelGGL((probe_wave_kernel<false, WSHORTLEN>), g, b, 0, stream, P);
         else hipLaunchKernelGGL((probe_wave_kernel<false, WMAXLEN>), g, b, 0, stream, P);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        static thread_local char msg[256];
-        snprintf(msg, sizeof msg, "probe_wave_kernel launch failed: %s", hipGetErrorString(e));
-        bbmap_set_error(msg);
-        return BBMAP_E_HIP;
-    }
+    BBHIP(hipGetLastError());
     return BBMAP_OK;
 }

@@ -20,14 +20,12 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include <cstdio>
 #include <cstring>
 #include <mutex>
 
 #include "bbmap_amd.h"
+#include "host_common.h"
 #include "keyring_shared.h"
-
-void bbmap_set_error(const char *msg);
 
 namespace bbkeys {
 
@@ -276,10 +274,6 @@ __global__ void bbkeys_pack_kernel(long long n, bbidx_read *reads, const long lo
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-static int kfail(int rc, const char *msg) { bbmap_set_error(msg); return rc; }
-#define KHIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { char b_[256]; snprintf(b_, sizeof b_, "%s: %s", #x, hipGetErrorString(e_)); \
-                                                                  bbmap_set_error(b_); return BBMAP_E_HIP; } } while (0)
-
 static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct Layout {                          // byte offsets into the caller's workspace; everything up to `bits` follows from n alone
@@ -332,30 +326,24 @@ static float avg_quality_flip() {
 // once per process and device: the gfx950 check and the upload of the tables
 static int prepare_device(float &flip) {
     static std::mutex mu;
-    static int state[64];                // 0 = not looked at, 1 = ready, < 0 = the error
+    static bool ready[64];
     static float flipValue;
-    int ndev = 0, dev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return kfail(BBMAP_E_NODEVICE, "bbkeys_make_batch_device: no HIP device (no CPU path)");
-    KHIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return kfail(BBMAP_E_ARG, "bbkeys_make_batch_device: device ordinal beyond 63");
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;       // (a machine without a device: the check below says so)
+    if (dev < 0 || dev >= 64) return bbfail(BBMAP_E_ARG, "bbkeys_make_batch_device: device ordinal beyond 63");
     std::lock_guard<std::mutex> lock(mu);
-    if (state[dev] == 0) {
-        hipDeviceProp_t prop;
-        KHIP(hipGetDeviceProperties(&prop, dev));
-        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) state[dev] = BBMAP_E_NODEVICE;
-        else {
-            static DevTables h;
-            const QualTables &T = tables();
-            for (int i = 0; i < 128; i++) {
-                h.probError[i] = T.probError[i]; h.probCorrect[i] = T.probCorrect[i]; h.probCorrectInverse[i] = T.probCorrectInverse[i];
-                h.baseScore[i] = (int8_t)(java_round(100 * T.probCorrect[i]) - 100);
-            }
-            KHIP(hipMemcpyToSymbol(HIP_SYMBOL(g_tables), &h, sizeof h));
-            flipValue = avg_quality_flip();
-            state[dev] = 1;
+    if (!ready[dev]) {
+        BBTRY(bb_use_gfx950("bbkeys_make_batch_device", dev));
+        static DevTables h;
+        const QualTables &T = tables();
+        for (int i = 0; i < 128; i++) {
+            h.probError[i] = T.probError[i]; h.probCorrect[i] = T.probCorrect[i]; h.probCorrectInverse[i] = T.probCorrectInverse[i];
+            h.baseScore[i] = (int8_t)(java_round(100 * T.probCorrect[i]) - 100);
         }
+        BBHIP(hipMemcpyToSymbol(HIP_SYMBOL(g_tables), &h, sizeof h));
+        flipValue = avg_quality_flip();
+        ready[dev] = true;
     }
-    if (state[dev] < 0) return kfail(BBMAP_E_NODEVICE, "bbkeys_make_batch_device: this build targets gfx950 only");
     flip = flipValue;
     return BBMAP_OK;
 }
@@ -363,7 +351,7 @@ static int prepare_device(float &flip) {
 }  // namespace bbkeys
 
 extern "C" int64_t bbkeys_device_workspace_bytes(const bbkeys_config *cfg, int64_t n_reads, int64_t total_bases) {
-    if (!bbkeys::good_config(cfg) || n_reads < 0 || n_reads >= 0x7fffffff || total_bases < 0) return bbkeys::kfail(BBMAP_E_ARG, "bbkeys_device_workspace_bytes: bad argument");
+    if (!bbkeys::good_config(cfg) || n_reads < 0 || n_reads >= 0x7fffffff || total_bases < 0) return bbfail(BBMAP_E_ARG, "bbkeys_device_workspace_bytes: bad argument");
     bbkeys::Layout L;
     const int rc = bbkeys::make_layout(cfg, n_reads, total_bases, L);
     return rc != BBMAP_OK ? rc : (int64_t)L.total;
@@ -375,8 +363,8 @@ extern "C" int bbkeys_make_batch_device(const bbkeys_config *cfg, void *stream_,
     using namespace bbkeys;
     if (!good_config(cfg) || n_reads < 0 || n_reads >= 0x7fffffff || keyinfo_cap < 0 || workspace_bytes < 0 || !keyinfo_used ||
         (n_reads > 0 && (!reads || !bases || !keyinfo || !baseScores || !workspace)))
-        return kfail(BBMAP_E_ARG, "bbkeys_make_batch_device: bad argument");
-    if (((uintptr_t)workspace & 255) != 0) return kfail(BBMAP_E_ARG, "bbkeys_make_batch_device: the workspace must be 256-byte aligned");
+        return bbfail(BBMAP_E_ARG, "bbkeys_make_batch_device: bad argument");
+    if (((uintptr_t)workspace & 255) != 0) return bbfail(BBMAP_E_ARG, "bbkeys_make_batch_device: the workspace must be 256-byte aligned");
     float flip = 0;
     const int prc = prepare_device(flip);
     if (prc != BBMAP_OK) return prc;
@@ -389,7 +377,7 @@ extern "C" int bbkeys_make_batch_device(const bbkeys_config *cfg, void *stream_,
     Layout L;
     int rc = make_layout(cfg, n, 0, L);
     if (rc != BBMAP_OK) return rc;
-    if ((size_t)workspace_bytes < L.total) return kfail(BBMAP_E_ARG, "bbkeys_make_batch_device: workspace too small (bbkeys_device_workspace_bytes)");
+    if ((size_t)workspace_bytes < L.total) return bbfail(BBMAP_E_ARG, "bbkeys_make_batch_device: workspace too small (bbkeys_device_workspace_bytes)");
     char *ws = (char *)workspace;
     auto I = [&](size_t at) { return (int *)(ws + at); };
     auto LL = [&](size_t at) { return (long long *)(ws + at); };
@@ -398,41 +386,41 @@ extern "C" int bbkeys_make_batch_device(const bbkeys_config *cfg, void *stream_,
     auto wideLens = hipcub::TransformInputIterator<long long, ToLL, const int *>((const int *)I(L.lens), ToLL());
     auto wideKeys = hipcub::TransformInputIterator<long long, ToLL, const int *>((const int *)I(L.nkeys2), ToLL());
     size_t scanBytes = 0;
-    KHIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes, wideBound, LL(L.slotOff), (int)(n + 1), stream));
-    if (scanBytes > L.scanTmpBytes) return kfail(BBMAP_E_HIP, "bbkeys_make_batch_device: hipcub's scan asks for more temporary storage than the workspace reserves");
+    BBHIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes, wideBound, LL(L.slotOff), (int)(n + 1), stream));
+    if (scanBytes > L.scanTmpBytes) return bbfail(BBMAP_E_HIP, "bbkeys_make_batch_device: hipcub's scan asks for more temporary storage than the workspace reserves");
     hipLaunchKernelGGL(bbkeys_bound_kernel, grid, block, 0, stream, *cfg, n, (const bbidx_read *)reads, I(L.bound), I(L.lens));
-    KHIP(hipGetLastError());
-    KHIP(hipcub::DeviceScan::ExclusiveSum(ws + L.scanTmp, scanBytes, wideBound, LL(L.slotOff), (int)(n + 1), stream));
-    KHIP(hipcub::DeviceScan::ExclusiveSum(ws + L.scanTmp, scanBytes, wideLens, LL(L.lenOff), (int)(n + 1), stream));
+    BBHIP(hipGetLastError());
+    BBHIP(hipcub::DeviceScan::ExclusiveSum(ws + L.scanTmp, scanBytes, wideBound, LL(L.slotOff), (int)(n + 1), stream));
+    BBHIP(hipcub::DeviceScan::ExclusiveSum(ws + L.scanTmp, scanBytes, wideLens, LL(L.lenOff), (int)(n + 1), stream));
     long long totals[2] = {0, 0};        // {slots, bases}
-    KHIP(hipMemcpyAsync(&totals[0], LL(L.slotOff) + n, 8, hipMemcpyDeviceToHost, stream));
-    KHIP(hipMemcpyAsync(&totals[1], LL(L.lenOff) + n, 8, hipMemcpyDeviceToHost, stream));
-    KHIP(hipStreamSynchronize(stream));
+    BBHIP(hipMemcpyAsync(&totals[0], LL(L.slotOff) + n, 8, hipMemcpyDeviceToHost, stream));
+    BBHIP(hipMemcpyAsync(&totals[1], LL(L.lenOff) + n, 8, hipMemcpyDeviceToHost, stream));
+    BBHIP(hipStreamSynchronize(stream));
     rc = make_layout(cfg, n, totals[1], L);
     if (rc != BBMAP_OK) return rc;
     if ((size_t)workspace_bytes < L.total || totals[0] > L.slotCap)
-        return kfail(BBMAP_E_ARG, "bbkeys_make_batch_device: workspace too small for the bases of these reads (bbkeys_device_workspace_bytes)");
+        return bbfail(BBMAP_E_ARG, "bbkeys_make_batch_device: workspace too small for the bases of these reads (bbkeys_device_workspace_bytes)");
 
     KeyArgs A;
     A.cfg = *cfg; A.n = n; A.reads = reads; A.bases = bases; A.quality = quality; A.baseScores = baseScores;
     A.slotOff = LL(L.slotOff); A.lenOff = LL(L.lenOff); A.slotCap = L.slotCap; A.wordCap = L.wordCap;
     A.tmpOffsets = I(L.tmpOffsets); A.tmpScores = I(L.tmpScores); A.bits = (unsigned *)(ws + L.bits);
     A.nkeys2 = I(L.nkeys2); A.tooSmall = I(L.flag); A.avgQualityFlip = flip;
-    KHIP(hipMemsetAsync(ws + L.flag, 0, 4, stream));
+    BBHIP(hipMemsetAsync(ws + L.flag, 0, 4, stream));
     hipLaunchKernelGGL(bbkeys_make_kernel, grid, block, 0, stream, A);
-    KHIP(hipGetLastError());
-    KHIP(hipcub::DeviceScan::ExclusiveSum(ws + L.scanTmp, scanBytes, wideKeys, LL(L.keyOff), (int)(n + 1), stream));
+    BBHIP(hipGetLastError());
+    BBHIP(hipcub::DeviceScan::ExclusiveSum(ws + L.scanTmp, scanBytes, wideKeys, LL(L.keyOff), (int)(n + 1), stream));
     long long used = 0;
     int tooSmall = 0;
-    KHIP(hipMemcpyAsync(&used, LL(L.keyOff) + n, 8, hipMemcpyDeviceToHost, stream));
-    KHIP(hipMemcpyAsync(&tooSmall, ws + L.flag, 4, hipMemcpyDeviceToHost, stream));
-    KHIP(hipStreamSynchronize(stream));
-    if (tooSmall) return kfail(BBMAP_E_ARG, "bbkeys_make_batch_device: a read's keys did not fit the workspace");
+    BBHIP(hipMemcpyAsync(&used, LL(L.keyOff) + n, 8, hipMemcpyDeviceToHost, stream));
+    BBHIP(hipMemcpyAsync(&tooSmall, ws + L.flag, 4, hipMemcpyDeviceToHost, stream));
+    BBHIP(hipStreamSynchronize(stream));
+    if (tooSmall) return bbfail(BBMAP_E_ARG, "bbkeys_make_batch_device: a read's keys did not fit the workspace");
     *keyinfo_used = used;
-    if (used > keyinfo_cap) return kfail(BBMAP_E_ARG, "bbkeys_make_batch_device: keyinfo buffer too small (*keyinfo_used = the size needed)");
+    if (used > keyinfo_cap) return bbfail(BBMAP_E_ARG, "bbkeys_make_batch_device: keyinfo buffer too small (*keyinfo_used = the size needed)");
     hipLaunchKernelGGL(bbkeys_pack_kernel, grid, block, 0, stream, n, reads, (const long long *)LL(L.slotOff), (const long long *)LL(L.keyOff),
                        (const int *)I(L.nkeys2), (const int *)I(L.tmpOffsets), (const int *)I(L.tmpScores), keyinfo);
-    KHIP(hipGetLastError());
-    KHIP(hipStreamSynchronize(stream));
+    BBHIP(hipGetLastError());
+    BBHIP(hipStreamSynchronize(stream));
     return BBMAP_OK;
 }

@@ -8,14 +8,12 @@
 // Java float semantics: every operation below is a single-precision IEEE operation (the library is built with -ffp-contract=off
 // -fno-fast-math); Math.round(float) is floor(x + 0.5) evaluated exactly, Math.ceil / Math.pow / Math.log10 work on doubles.
 #include <cmath>
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "bbmap_amd.h"
+#include "host_common.h"
 #include "keyring_shared.h"
-
-void bbmap_set_error(const char *msg);
 
 namespace {
 
@@ -102,7 +100,7 @@ int avg_quality_by_probability(const uint8_t *bases, const uint8_t *quality, int
 }  // namespace
 
 extern "C" int bbkeys_default_config(int32_t profile, bbkeys_config *cfg) {
-    if (!cfg || (profile != BBIDX_PROFILE_BBMAP && profile != BBIDX_PROFILE_PACBIO)) { bbmap_set_error("bbkeys_default_config: bad argument"); return BBMAP_E_ARG; }
+    if (!cfg || (profile != BBIDX_PROFILE_BBMAP && profile != BBIDX_PROFILE_PACBIO)) return bbfail(BBMAP_E_ARG, "bbkeys_default_config: bad argument");
     memset(cfg, 0, sizeof *cfg);
     if (profile == BBIDX_PROFILE_PACBIO) {     // BBMapPacBio.setDefaults, current/align2/BBMapPacBio.java:51-58
         cfg->k = 12; cfg->keyDensity = 3.5f; cfg->maxKeyDensity = 4.5f; cfg->minKeyDensity = 2.8f; cfg->maxDesiredKeys = 63;
@@ -115,7 +113,7 @@ extern "C" int bbkeys_default_config(int32_t profile, bbkeys_config *cfg) {
 
 extern "C" int bbkeys_make(const bbkeys_config *cfg, const uint8_t *bases, const uint8_t *quality, int32_t len,
                            int32_t *offsets, int32_t *keyScores, int32_t cap, int8_t *baseScores) {
-    if (!cfg || !bases || len < 0 || !offsets || !keyScores || !baseScores || cfg->k < 1) { bbmap_set_error("bbkeys_make: bad argument"); return BBMAP_E_ARG; }
+    if (!cfg || !bases || len < 0 || !offsets || !keyScores || !baseScores || cfg->k < 1) return bbfail(BBMAP_E_ARG, "bbkeys_make: bad argument");
     const int K = cfg->k;
     // makeByteScoreArray(quality, 100, out, negative=true) :145-181 -- written in every case (the probe reads it for any read it is given)
     {
@@ -144,7 +142,7 @@ extern "C" int bbkeys_make(const bbkeys_config *cfg, const uint8_t *bases, const
     const int n = make_offsets3(keyProbs.data(), len, K, keyDen2, keyDen3, 2, cfg->semiperfectMode != 0, offs);
     if (n == 0 || n < cfg->minApproxHitsToKeep) return 0;                                  // :701
     if (quality && avg_quality_by_probability(bases, quality, len) < 2) return 0;
-    if (n > cap) { bbmap_set_error("bbkeys_make: more keys than the caller's buffers hold"); return BBMAP_E_ARG; }
+    if (n > cap) return bbfail(BBMAP_E_ARG, "bbkeys_make: more keys than the caller's buffers hold");
     // makeKeyScores(keyProbs, keyProbLen, range, baseKeyScore, keyScoresAll) :712-724, QualityTools.java:125-133
     const int a = 100 * K, baseKeyScore = a / 8, range = a - baseKeyScore;                  // BASE_KEY_HIT_SCORE = BASE_HIT_SCORE * KEYLEN
     float probAllErrors = 1.0f;
@@ -164,7 +162,7 @@ extern "C" int bbkeys_make(const bbkeys_config *cfg, const uint8_t *bases, const
 extern "C" int bbkeys_make_batch(const bbkeys_config *cfg, int64_t n_reads, const int64_t *bases_off, const int32_t *lens,
                                  const uint8_t *bases, const uint8_t *quality, bbidx_read *reads, int32_t *keyinfo, int64_t keyinfo_cap,
                                  int8_t *baseScores, int64_t *keyinfo_used) {
-    if (!cfg || !bases_off || !lens || !bases || !reads || !keyinfo || !baseScores || n_reads < 0) { bbmap_set_error("bbkeys_make_batch: bad argument"); return BBMAP_E_ARG; }
+    if (!cfg || !bases_off || !lens || !bases || !reads || !keyinfo || !baseScores || n_reads < 0) return bbfail(BBMAP_E_ARG, "bbkeys_make_batch: bad argument");
     int64_t used = 0;
     std::vector<int32_t> o, s;
     for (int64_t i = 0; i < n_reads; i++) {
@@ -173,7 +171,7 @@ extern "C" int bbkeys_make_batch(const bbkeys_config *cfg, int64_t n_reads, cons
         o.resize((size_t)cap); s.resize((size_t)cap);
         const int n = bbkeys_make(cfg, bases + bases_off[i], quality ? quality + bases_off[i] : nullptr, len, o.data(), s.data(), cap, baseScores + bases_off[i]);
         if (n < 0) return n;
-        if (used + 2 * (int64_t)n > keyinfo_cap) { bbmap_set_error("bbkeys_make_batch: keyinfo buffer too small"); return BBMAP_E_ARG; }
+        if (used + 2 * (int64_t)n > keyinfo_cap) return bbfail(BBMAP_E_ARG, "bbkeys_make_batch: keyinfo buffer too small");
         reads[i].bases_off = bases_off[i]; reads[i].keys_off = used; reads[i].len = len; reads[i].nkeys = n;
         memcpy(keyinfo + used, o.data(), sizeof(int32_t) * (size_t)n);
         memcpy(keyinfo + used + n, s.data(), sizeof(int32_t) * (size_t)n);

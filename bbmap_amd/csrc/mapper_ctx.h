@@ -1,5 +1,5 @@
 // Host-side context of the mapper's entry points (mapper_host.hip: creation and the batch driver; mapper_output.hip: everything that
-// reads a finished batch), and the error and launch helpers both files use.
+// reads a finished batch).  The error and launch helpers and DevBuf are the library's common ones (host_common.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,30 +8,11 @@
 #include <vector>
 
 #include "bbmap_amd.h"
+#include "host_common.h"
 #include "index_ctx.h"
 #include "mapper_dev.h"
 #include "msa_ctx.h"
 
-void bbmap_set_error(const char *msg);
-
-// A device buffer that is allocated on first use and replaced by a larger one when a call needs more (contents are not kept).
-// (hidden: its inline members are no symbols of the library)
-struct __attribute__((visibility("hidden"))) DevBuf {
-    void *p = nullptr; size_t cap = 0;
-    // Room for `need` bytes.  slack: added when the buffer has to grow, so that sizes creeping up do not reallocate every batch.
-    // busy: a stream whose queued work may still use the old buffer; it is waited for before the buffer is freed.
-    hipError_t grow(size_t need, size_t slack = 0, const hipStream_t *busy = nullptr) {
-        if (need <= cap) return hipSuccess;
-        if (p) {
-            if (busy) { const hipError_t e = hipStreamSynchronize(*busy); if (e != hipSuccess) return e; }
-            release();
-        }
-        const hipError_t e = hipMalloc(&p, need + slack);
-        if (e == hipSuccess) cap = need + slack;
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
 // bbmap_map_batch's device copies (reads, bases of both strands, base scores, keyinfo, counts, offsets, packed sites), the scan
 // scratch of bbmap_pack_sites_device, and bbmap_get_sam_records' scan scratch and text blob
 enum { HIO_READS, HIO_BASES, HIO_SCORES, HIO_KEYINFO, HIO_COUNTS, HIO_OFFSETS, HIO_PACKED, BUF_PACK_TMP, BUF_SAM_TMP, BUF_SAM_TEXT, BUF_COUNT };
@@ -100,23 +81,11 @@ struct bbmap_ctx {
     hipStream_t statsStream = nullptr;          // the stream of the last accumulation: the only work that writes the counters
 };
 
-static thread_local char g_merr[320];
-#define MHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { snprintf(g_merr, sizeof g_merr, "%s failed: %s", #expr, hipGetErrorString(e_)); bbmap_set_error(g_merr); return BBMAP_E_HIP; } } while (0)
-#define MTRY(expr) do { const int rc_ = (expr); if (rc_ != BBMAP_OK) return rc_; } while (0)
-static int mfail(int code, const char *msg) { bbmap_set_error(msg); return code; }
-
-// kernel<<<ceil(threads / TB), TB, 0, stream>>>(args...)
-template <unsigned TB, class K, class... A> static int launch(K kernel, long long threads, hipStream_t stream, const A &...args) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((threads + TB - 1) / TB)), dim3(TB), 0, stream, args...);
-    MHIP(hipGetLastError());
-    return BBMAP_OK;
-}
-
 // a device array of the context's that lives until bbmap_destroy
 template <class T> static int dalloc(bbmap_ctx *c, T **p, size_t count) {
     void *d = nullptr;
     const size_t bytes = (count ? count : 1) * sizeof(T);
-    if (hipMalloc(&d, bytes) != hipSuccess) return mfail(BBMAP_E_NOMEM, "bbmap_create: device allocation failed");
+    if (hipMalloc(&d, bytes) != hipSuccess) return bbfail(BBMAP_E_NOMEM, "bbmap_create: device allocation failed");
     c->allocs.push_back(d);
     *p = (T *)d;
     return BBMAP_OK;

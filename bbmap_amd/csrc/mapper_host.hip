@@ -15,7 +15,7 @@
 using namespace bbmapper;
 
 extern "C" int bbmap_default_config_profile(int32_t profile, bbmap_config *c) {
-    if (!c || (profile != BBIDX_PROFILE_BBMAP && profile != BBIDX_PROFILE_PACBIO)) return mfail(BBMAP_E_ARG, "bbmap_default_config: bad argument");
+    if (!c || (profile != BBIDX_PROFILE_BBMAP && profile != BBIDX_PROFILE_PACBIO)) return bbfail(BBMAP_E_ARG, "bbmap_default_config: bad argument");
     memset(c, 0, sizeof *c);
     c->paired = 0; c->max_reads = 0; c->max_sites = 32;
     c->extraPadding = 10; c->maxPairDist = 32000; c->averagePairDist = 100; c->maxRescueDist = 1200; c->maxRescueMismatches = 32;
@@ -55,21 +55,21 @@ extern "C" void bbmap_destroy(bbmap_ctx *c) {
 
 // parent != null: the overflow tier of `parent` (longer job logs per read)
 static int create_impl(bbidx_ctx *index, const bbmap_config *cfg, bbmap_ctx *parent, bbmap_ctx **out) {
-    if (!index || !cfg || !out) return mfail(BBMAP_E_ARG, "bbmap_create: null argument");
+    if (!index || !cfg || !out) return bbfail(BBMAP_E_ARG, "bbmap_create: null argument");
     *out = nullptr;
     const int profile = cfg->reserved[3];
-    if (profile != BBIDX_PROFILE_BBMAP && profile != BBIDX_PROFILE_PACBIO) return mfail(BBMAP_E_ARG, "bbmap_create: unknown profile (bbmap_config.reserved[3])");
-    if (profile != index->dev.p.profile) return mfail(BBMAP_E_ARG, "bbmap_create: the index was built for the other profile (BBIDX_PROFILE_*)");
+    if (profile != BBIDX_PROFILE_BBMAP && profile != BBIDX_PROFILE_PACBIO) return bbfail(BBMAP_E_ARG, "bbmap_create: unknown profile (bbmap_config.reserved[3])");
+    if (profile != index->dev.p.profile) return bbfail(BBMAP_E_ARG, "bbmap_create: the index was built for the other profile (BBIDX_PROFILE_*)");
     const bool pacbio = profile == BBIDX_PROFILE_PACBIO;
     if (cfg->max_reads < 1 || cfg->max_read_len < 1 || cfg->max_read_len > (pacbio ? BBIDX_PACBIO_MAX_READ_LEN : 600))
-        return mfail(BBMAP_E_ARG, "bbmap_create: max_reads >= 1 and max_read_len in 1..600 (1..6016 for BBIDX_PROFILE_PACBIO)");
-    if (cfg->max_sites < 1 || cfg->max_sites > BBMAP_MAX_SITES_LIMIT) return mfail(BBMAP_E_ARG, "bbmap_create: max_sites must be 1..4096");
-    if (cfg->paired && (cfg->max_reads & 1)) return mfail(BBMAP_E_ARG, "bbmap_create: paired mode takes an even number of reads");
-    if (cfg->msaMaxColumns < 64 || cfg->msaMaxColumns > (pacbio ? 8192 : 4096)) return mfail(BBMAP_E_ARG, "bbmap_create: msaMaxColumns must be 64..4096 (..8192 for BBIDX_PROFILE_PACBIO)");
-    if (cfg->device != index->device) return mfail(BBMAP_E_ARG, "bbmap_create: the index lives on another device");
-    MHIP(hipSetDevice(cfg->device));
+        return bbfail(BBMAP_E_ARG, "bbmap_create: max_reads >= 1 and max_read_len in 1..600 (1..6016 for BBIDX_PROFILE_PACBIO)");
+    if (cfg->max_sites < 1 || cfg->max_sites > BBMAP_MAX_SITES_LIMIT) return bbfail(BBMAP_E_ARG, "bbmap_create: max_sites must be 1..4096");
+    if (cfg->paired && (cfg->max_reads & 1)) return bbfail(BBMAP_E_ARG, "bbmap_create: paired mode takes an even number of reads");
+    if (cfg->msaMaxColumns < 64 || cfg->msaMaxColumns > (pacbio ? 8192 : 4096)) return bbfail(BBMAP_E_ARG, "bbmap_create: msaMaxColumns must be 64..4096 (..8192 for BBIDX_PROFILE_PACBIO)");
+    if (cfg->device != index->device) return bbfail(BBMAP_E_ARG, "bbmap_create: the index lives on another device");
+    BBHIP(hipSetDevice(cfg->device));
     bbmap_ctx *c = new (std::nothrow) bbmap_ctx();
-    if (!c) return mfail(BBMAP_E_NOMEM, "bbmap_create: out of host memory");
+    if (!c) return bbfail(BBMAP_E_NOMEM, "bbmap_create: out of host memory");
     c->cfg = *cfg; c->index = index;
     int rc = BBMAP_OK;
     auto bail = [&](int code) { bbmap_destroy(c); return code; };
@@ -95,7 +95,7 @@ static int create_impl(bbidx_ctx *index, const bbmap_config *cfg, bbmap_ctx *par
     S.ptsDel5 = -1; S.ptsGap = -2;
     // finalStage: 0 off, 1 the profile's own mapping thread (BBMapThread / BBMapThreadPacBio), 2 BBMapThread's whatever the profile
     // (the parity seam: the oracle restates that tail only, oracle/mapper_oracle.c:758)
-    if (pacbio && (cfg->finalStage < 0 || cfg->finalStage > 2)) return bail(mfail(BBMAP_E_ARG, "bbmap_create: finalStage must be 0, 1 or 2"));
+    if (pacbio && (cfg->finalStage < 0 || cfg->finalStage > 2)) return bail(bbfail(BBMAP_E_ARG, "bbmap_create: finalStage must be 0, 1 or 2"));
     S.finalStage = cfg->finalStage ? 1 : 0;
     S.finalPolicy = (pacbio && cfg->finalStage == 1) ? 1 : 0;
     {   // BBMapThreadPacBio.java:38-41, :112-115; BBMapThread.java:38-44
@@ -191,18 +191,18 @@ static int create_impl(bbidx_ctx *index, const bbmap_config *cfg, bbmap_ctx *par
     c->d_chromArr = index->dev.chromArr; c->d_chromArrLen = index->dev.chromArrLen;
     {
         std::vector<const uint8_t *> hc((size_t)nch + 1);
-        if (hipMemcpy(hc.data(), index->dev.chromArr, sizeof(void *) * hc.size(), hipMemcpyDeviceToHost) != hipSuccess) return bail(mfail(BBMAP_E_HIP, "bbmap_create: reading the chromosome table failed"));
+        if (hipMemcpy(hc.data(), index->dev.chromArr, sizeof(void *) * hc.size(), hipMemcpyDeviceToHost) != hipSuccess) return bail(bbfail(BBMAP_E_HIP, "bbmap_create: reading the chromosome table failed"));
         c->refsBase = hc[1];
         std::vector<long long> off((size_t)nch + 1, 0);
         for (int i = 1; i <= nch; i++) off[(size_t)i] = (long long)(hc[(size_t)i] - hc[1]);
-        if (hipMemcpy(c->d_chromOff, off.data(), 8 * off.size(), hipMemcpyHostToDevice) != hipSuccess) return bail(mfail(BBMAP_E_HIP, "bbmap_create: upload failed"));
-        if (hipMemset(c->d_chromMin, 0, 4 * ((size_t)nch + 1)) != hipSuccess) return bail(mfail(BBMAP_E_HIP, "bbmap_create: memset failed"));
+        if (hipMemcpy(c->d_chromOff, off.data(), 8 * off.size(), hipMemcpyHostToDevice) != hipSuccess) return bail(bbfail(BBMAP_E_HIP, "bbmap_create: upload failed"));
+        if (hipMemset(c->d_chromMin, 0, 4 * ((size_t)nch + 1)) != hipSuccess) return bail(bbfail(BBMAP_E_HIP, "bbmap_create: memset failed"));
     }
-    if (hipHostMalloc((void **)&c->h_counters, CNT_WORDS * 4) != hipSuccess) return bail(mfail(BBMAP_E_NOMEM, "bbmap_create: pinned allocation failed"));
-    for (hipEvent_t &e : c->ev) if (hipEventCreate(&e) != hipSuccess) return bail(mfail(BBMAP_E_HIP, "bbmap_create: hipEventCreate failed"));
+    if (hipHostMalloc((void **)&c->h_counters, CNT_WORDS * 4) != hipSuccess) return bail(bbfail(BBMAP_E_NOMEM, "bbmap_create: pinned allocation failed"));
+    for (hipEvent_t &e : c->ev) if (hipEventCreate(&e) != hipSuccess) return bail(bbfail(BBMAP_E_HIP, "bbmap_create: hipEventCreate failed"));
     if (!getenv("BBMAP_SERIAL_DP") && !pacbio) {
         if (hipStreamCreateWithFlags(&c->dpStream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming) != hipSuccess) return bail(mfail(BBMAP_E_HIP, "bbmap_create: stream / event creation failed"));
+            hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming) != hipSuccess) return bail(bbfail(BBMAP_E_HIP, "bbmap_create: stream / event creation failed"));
     }
     *out = c;
     return BBMAP_OK;
@@ -210,7 +210,7 @@ static int create_impl(bbidx_ctx *index, const bbmap_config *cfg, bbmap_ctx *par
 
 extern "C" int bbmap_create(bbidx_ctx *index, const bbmap_config *cfg, bbmap_ctx **out) {
     bbmap_ctx *c = nullptr;
-    MTRY(create_impl(index, cfg, nullptr, &c));
+    BBTRY(create_impl(index, cfg, nullptr, &c));
     // reserved[1]: reads the overflow tier holds (0 = 4096, < 0 = no tier); reserved[2]: its max_sites (0 = 1024)
     if (cfg->reserved[1] >= 0) {
         bbmap_config tc = *cfg;
@@ -227,7 +227,7 @@ extern "C" int bbmap_create(bbidx_ctx *index, const bbmap_config *cfg, bbmap_ctx
             const long long units = cfg->paired ? cfg->max_reads / 2 : cfg->max_reads;
             if (dalloc(c, &c->d_tierUnits, (size_t)units + 1) != BBMAP_OK || dalloc(c, &c->d_tierReads, (size_t)tn) != BBMAP_OK ||
                 dalloc(c, &c->d_tierReadIds, (size_t)tn) != BBMAP_OK) { bbmap_destroy(c); return BBMAP_E_NOMEM; }
-            if (hipStreamCreateWithFlags(&c->tierStream, hipStreamNonBlocking) != hipSuccess) { bbmap_destroy(c); return mfail(BBMAP_E_HIP, "bbmap_create: hipStreamCreate failed"); }
+            if (hipStreamCreateWithFlags(&c->tierStream, hipStreamNonBlocking) != hipSuccess) { bbmap_destroy(c); return bbfail(BBMAP_E_HIP, "bbmap_create: hipStreamCreate failed"); }
         }
     }
     *out = c;
@@ -235,16 +235,16 @@ extern "C" int bbmap_create(bbidx_ctx *index, const bbmap_config *cfg, bbmap_ctx
 }
 
 static int read_counters(bbmap_ctx *c, hipStream_t stream) {
-    MHIP(hipMemcpyAsync(c->h_counters, c->d_counters, CNT_WORDS * 4, hipMemcpyDeviceToHost, stream));
-    MHIP(hipStreamSynchronize(stream));
+    BBHIP(hipMemcpyAsync(c->h_counters, c->d_counters, CNT_WORDS * 4, hipMemcpyDeviceToHost, stream));
+    BBHIP(hipStreamSynchronize(stream));
     return BBMAP_OK;
 }
 
 // Replaces a device array by a larger one (contents kept), in stream order; the old one is freed once the stream has passed.
 template <class T> static int regrow(bbmap_ctx *c, hipStream_t stream, T **p, size_t oldCount, size_t newCount, std::vector<void *> &dead) {
     void *d = nullptr;
-    if (hipMalloc(&d, (newCount ? newCount : 1) * sizeof(T)) != hipSuccess) return mfail(BBMAP_E_NOMEM, "bbmap_map_batch_device: growing a fill log failed (device memory)");
-    if (oldCount) MHIP(hipMemcpyAsync(d, *p, oldCount * sizeof(T), hipMemcpyDeviceToDevice, stream));
+    if (hipMalloc(&d, (newCount ? newCount : 1) * sizeof(T)) != hipSuccess) return bbfail(BBMAP_E_NOMEM, "bbmap_map_batch_device: growing a fill log failed (device memory)");
+    if (oldCount) BBHIP(hipMemcpyAsync(d, *p, oldCount * sizeof(T), hipMemcpyDeviceToDevice, stream));
     for (void *&q : c->allocs) if (q == (void *)*p) q = d;
     dead.push_back((void *)*p);
     *p = (T *)d;
@@ -264,24 +264,24 @@ static int grow_logs(bbmap_ctx *c, hipStream_t stream, Dev &D, long long needJob
     std::vector<void *> &dead = guard.v;
     if (needJobs > c->jobCap) {
         long long nc = c->jobCap * 2; if (nc < needJobs) nc = needJobs + needJobs / 4 + 1024;
-        MTRY(regrow(c, stream, &c->d_jobs, (size_t)usedJobs, (size_t)nc, dead));
-        MTRY(regrow(c, stream, &c->d_jinfo, (size_t)usedJobs, (size_t)nc, dead));
-        MTRY(regrow(c, stream, &c->d_results, (size_t)usedJobs, (size_t)nc, dead));
-        MTRY(regrow(c, stream, &c->d_match, (size_t)usedJobs * c->matchStride, (size_t)nc * c->matchStride, dead));
+        BBTRY(regrow(c, stream, &c->d_jobs, (size_t)usedJobs, (size_t)nc, dead));
+        BBTRY(regrow(c, stream, &c->d_jinfo, (size_t)usedJobs, (size_t)nc, dead));
+        BBTRY(regrow(c, stream, &c->d_results, (size_t)usedJobs, (size_t)nc, dead));
+        BBTRY(regrow(c, stream, &c->d_match, (size_t)usedJobs * c->matchStride, (size_t)nc * c->matchStride, dead));
         c->jobCap = nc;
     }
     if (needGapped > c->gjobCap) {
         long long nc = c->gjobCap * 2; if (nc < needGapped) nc = needGapped + needGapped / 4 + 1024;
-        MTRY(regrow(c, stream, &c->d_gjobs, (size_t)usedGapped, (size_t)nc, dead));
-        MTRY(regrow(c, stream, &c->d_ggaps, (size_t)usedGapped, (size_t)nc, dead));
-        MTRY(regrow(c, stream, &c->d_ginfo, (size_t)usedGapped, (size_t)nc, dead));
-        MTRY(regrow(c, stream, &c->d_gresults, (size_t)usedGapped, (size_t)nc, dead));
-        MTRY(regrow(c, stream, &c->d_gmatch, (size_t)usedGapped * c->gmatchStride, (size_t)nc * c->gmatchStride, dead));
+        BBTRY(regrow(c, stream, &c->d_gjobs, (size_t)usedGapped, (size_t)nc, dead));
+        BBTRY(regrow(c, stream, &c->d_ggaps, (size_t)usedGapped, (size_t)nc, dead));
+        BBTRY(regrow(c, stream, &c->d_ginfo, (size_t)usedGapped, (size_t)nc, dead));
+        BBTRY(regrow(c, stream, &c->d_gresults, (size_t)usedGapped, (size_t)nc, dead));
+        BBTRY(regrow(c, stream, &c->d_gmatch, (size_t)usedGapped * c->gmatchStride, (size_t)nc * c->gmatchStride, dead));
         c->gjobCap = nc;
     }
     c->h_counters[CNT_STAGE_FILLS] = (unsigned)usedJobs; c->h_counters[CNT_STAGE_GAPPED] = (unsigned)usedGapped;
-    MHIP(hipMemcpyAsync(c->d_counters + CNT_FILLS, c->h_counters + CNT_STAGE_FILLS, 8, hipMemcpyHostToDevice, stream));      // both words
-    MHIP(hipStreamSynchronize(stream));
+    BBHIP(hipMemcpyAsync(c->d_counters + CNT_FILLS, c->h_counters + CNT_STAGE_FILLS, 8, hipMemcpyHostToDevice, stream));      // both words
+    BBHIP(hipStreamSynchronize(stream));
     D.jobs = c->d_jobs; D.jinfo = c->d_jinfo; D.results = c->d_results; D.match = c->d_match; D.jobCap = c->jobCap;
     D.gjobs = c->d_gjobs; D.ggaps = c->d_ggaps; D.ginfo = c->d_ginfo; D.gresults = c->d_gresults; D.gmatch = c->d_gmatch; D.gjobCap = c->gjobCap;
     c->stats.log_growths += 1.0f;              // (how often the logs grew in this batch)
@@ -303,20 +303,20 @@ static int run_fills(bbmap_ctx *c, hipStream_t stream, const uint8_t *bases, lon
     // persistent blocks fill the rest (and the slots the others free)
     hipStream_t gs = (c->dpStream && nNew > 0) ? c->dpStream : stream;
     if (gNew > 0) {
-        if (gs != stream) { MHIP(hipEventRecord(c->evFork, stream)); MHIP(hipStreamWaitEvent(gs, c->evFork, 0)); }
-        MTRY(bbmsa_align_gapped_batch_device(c->msaGapped, gs, gNew, c->d_gjobs + gBase, c->d_ggaps + gBase, bases, c->refsBase,
+        if (gs != stream) { BBHIP(hipEventRecord(c->evFork, stream)); BBHIP(hipStreamWaitEvent(gs, c->evFork, 0)); }
+        BBTRY(bbmsa_align_gapped_batch_device(c->msaGapped, gs, gNew, c->d_gjobs + gBase, c->d_ggaps + gBase, bases, c->refsBase,
                                              c->d_gresults + gBase, c->d_gmatch + gBase * c->gmatchStride, c->gmatchStride));
-        if (gs != stream) { MHIP(hipEventRecord(c->evJoin, gs)); if (nNew > 0) MTRY(bbmsa_wait_first_pass(c->msaGapped, stream)); }
+        if (gs != stream) { BBHIP(hipEventRecord(c->evJoin, gs)); if (nNew > 0) BBTRY(bbmsa_wait_first_pass(c->msaGapped, stream)); }
     }
     if (nNew > 0)
-        MTRY(bbmsa_align_batch_device(c->msa, stream, nNew, c->d_jobs + jobBase, bases, c->refsBase, c->d_results + jobBase,
+        BBTRY(bbmsa_align_batch_device(c->msa, stream, nNew, c->d_jobs + jobBase, bases, c->refsBase, c->d_results + jobBase,
                                       c->d_match + jobBase * c->matchStride, c->matchStride));
     // which routes the launches took (host flags of the DP contexts, no device read-back)
     const int r1 = nNew > 0 ? bbmsa_last_route_flags(c->msa) : 0;
     const int r2 = gNew > 0 ? bbmsa_last_route_flags(c->msaGapped) : 0;
     c->stats.dp_narrow_launches += (r1 & 1) + (r2 & 1);
     c->stats.dp_sorted_launches += ((r1 >> 1) & 1) + ((r2 >> 1) & 1);
-    if (gNew > 0 && gs != stream) MHIP(hipStreamWaitEvent(stream, c->evJoin, 0));
+    if (gNew > 0 && gs != stream) BBHIP(hipStreamWaitEvent(stream, c->evJoin, 0));
     return BBMAP_OK;
 }
 
@@ -352,13 +352,13 @@ struct Rounds {
 };
 // first half: the round's kernel over the active list, and its counters
 template <class K> static int round_begin(bbmap_ctx *c, hipStream_t stream, Dev &D, Rounds &R, K kernel) {
-    MHIP(hipMemsetAsync(c->d_counters + CNT_NEXT_ACTIVE, 0, 4, stream));
+    BBHIP(hipMemsetAsync(c->d_counters + CNT_NEXT_ACTIVE, 0, 4, stream));
     if (R.finalStage) {
-        MHIP(hipMemsetAsync(c->d_counters + CNT_POOL_AT_FAILURE, 0xff, 4, stream));
-        MHIP(hipMemsetAsync(c->d_counters + CNT_POOL_FAILED, 0, 4, stream));
+        BBHIP(hipMemsetAsync(c->d_counters + CNT_POOL_AT_FAILURE, 0xff, 4, stream));
+        BBHIP(hipMemsetAsync(c->d_counters + CNT_POOL_FAILED, 0, 4, stream));
     }
     D.activeIn = R.first ? nullptr : c->d_active[R.cur]; D.nActiveIn = (int)R.nActive; D.activeOut = c->d_active[1 - R.cur];
-    MTRY(launch<128>(kernel, R.nActive, stream, D));
+    BBTRY(launch<128>(kernel, R.nActive, stream, D));
     return read_counters(c, stream);
 }
 // second half: the fills the round asked for, larger logs when it asked for more than there was room for, the next active list
@@ -366,11 +366,11 @@ static int round_end(bbmap_ctx *c, hipStream_t stream, Dev &D, Rounds &R, const 
     add_dp_ms(c, R.ranPlain, R.ranGapped);          // (the round before this one: its launches are over)
     const long long asked = c->h_counters[CNT_FILLS], gasked = c->h_counters[CNT_GAPPED_FILLS];
     const long long total = asked < c->jobCap ? asked : c->jobCap, gtotal = gasked < c->gjobCap ? gasked : c->gjobCap;     // entries really written
-    MTRY(run_fills(c, stream, bases, R.jobBase, total - R.jobBase, R.gBase, gtotal - R.gBase, R.finalStage));
+    BBTRY(run_fills(c, stream, bases, R.jobBase, total - R.jobBase, R.gBase, gtotal - R.gBase, R.finalStage));
     R.ranPlain = total > R.jobBase; R.ranGapped = gtotal > R.gBase;
     R.jobBase = total; R.gBase = gtotal;
     // a log was too small: the reads that found no room ask again next round (emit_fill's NO_ROOM), after it has grown
-    if (asked > c->jobCap || gasked > c->gjobCap) MTRY(grow_logs(c, stream, D, asked, gasked, total, gtotal));
+    if (asked > c->jobCap || gasked > c->gjobCap) BBTRY(grow_logs(c, stream, D, asked, gasked, total, gtotal));
     R.nActive = c->h_counters[CNT_NEXT_ACTIVE];
     R.cur = 1 - R.cur; R.first = false;
     return BBMAP_OK;
@@ -378,14 +378,14 @@ static int round_end(bbmap_ctx *c, hipStream_t stream, Dev &D, Rounds &R, const 
 
 // Replaces the final stage's match-string pool by one of `units` units, the first `used` of them kept.
 static int grow_pool(bbmap_ctx *c, hipStream_t stream, Dev &D, long long used, long long units, bool setCounter) {
-    if (units > 0x7ffffff0LL) return mfail(BBMAP_E_NOMEM, "bbmap_map_batch_device: the final stage's match strings exceed 8 GB; map smaller batches");
+    if (units > 0x7ffffff0LL) return bbfail(BBMAP_E_NOMEM, "bbmap_map_batch_device: the final stage's match strings exceed 8 GB; map smaller batches");
     DeadArrays guard(stream);                          // (frees the old pool when this scope is left, also on an error return)
-    MTRY(regrow(c, stream, &c->d_pool, (size_t)used * 4, (size_t)units * 4, guard.v));
+    BBTRY(regrow(c, stream, &c->d_pool, (size_t)used * 4, (size_t)units * 4, guard.v));
     if (setCounter) {                                  // the device counter back to the units really handed out
         c->h_counters[CNT_STAGE_POOL] = (unsigned)used;
-        MHIP(hipMemcpyAsync(c->d_counters + CNT_POOL_UNITS, c->h_counters + CNT_STAGE_POOL, 4, hipMemcpyHostToDevice, stream));
+        BBHIP(hipMemcpyAsync(c->d_counters + CNT_POOL_UNITS, c->h_counters + CNT_STAGE_POOL, 4, hipMemcpyHostToDevice, stream));
     }
-    MHIP(hipStreamSynchronize(stream));
+    BBHIP(hipStreamSynchronize(stream));
     c->poolUnits = units; D.pool = c->d_pool; D.poolUnits = units;
     return BBMAP_OK;
 }
@@ -398,29 +398,29 @@ static int run_final_stage(bbmap_ctx *c, hipStream_t stream, Dev &D, int64_t n_r
     const unsigned *h = c->h_counters;
     D.fin = c->d_fin; D.finalOut = c->d_final; D.pool = c->d_pool; D.poolUnits = c->poolUnits;
     D.match = c->d_match; D.gmatch = c->d_gmatch; D.matchStride = c->matchStride; D.gmatchStride = c->gmatchStride;
-    MTRY(launch<128>(final_begin_kernel, units, stream, D));
+    BBTRY(launch<128>(final_begin_kernel, units, stream, D));
     Rounds R; R.finalStage = true; R.jobBase = jobBase; R.gBase = gBase; R.nActive = n_reads;
     for (int round = 0; R.nActive > 0; round++) {
-        if (round > 64 * c->cfg.max_sites + 64) return mfail(BBMAP_E_HIP, "bbmap_map_batch_device: the final stage does not come to an end (internal error)");
-        MTRY(round_begin(c, stream, D, R, final_round_kernel));
-        MTRY(round_end(c, stream, D, R, bases));
+        if (round > 64 * c->cfg.max_sites + 64) return bbfail(BBMAP_E_HIP, "bbmap_map_batch_device: the final stage does not come to an end (internal error)");
+        BBTRY(round_begin(c, stream, D, R, final_round_kernel));
+        BBTRY(round_end(c, stream, D, R, bases));
         if (h[CNT_POOL_FAILED] > 0) {           // the match-string pool was full for some reads: they repeat their step next round
             const long long used = h[CNT_POOL_AT_FAILURE];                      // units handed out before the first request that failed
             long long nu = c->poolUnits * 2, need = used + ((long long)h[CNT_POOL_UNITS] - used) * 2 + 65536;
             if (nu < need) nu = need;
-            MTRY(grow_pool(c, stream, D, used, nu, true));
+            BBTRY(grow_pool(c, stream, D, used, nu, true));
         }
         finalRounds++;
     }
-    MHIP(hipStreamSynchronize(stream));
+    BBHIP(hipStreamSynchronize(stream));
     add_dp_ms(c, R.ranPlain, R.ranGapped);
-    MHIP(hipMemsetAsync(c->d_counters + CNT_LOCAL_READS, 0, 8, stream));       // and CNT_LOCAL_UNITS behind it
-    MTRY(launch<128>(final_end_kernel, units, stream, D));
-    MTRY(read_counters(c, stream));
+    BBHIP(hipMemsetAsync(c->d_counters + CNT_LOCAL_READS, 0, 8, stream));       // and CNT_LOCAL_UNITS behind it
+    BBTRY(launch<128>(final_end_kernel, units, stream, D));
+    BBTRY(read_counters(c, stream));
     finalLocal = h[CNT_LOCAL_READS];
     const long long used = h[CNT_POOL_UNITS], local = h[CNT_LOCAL_UNITS];
-    if (used + local + 64 > c->poolUnits) MTRY(grow_pool(c, stream, D, used, used + local + 65536, false));      // room for toLocalAlignment's strings
-    MTRY(launch<128>(final_local_kernel, units, stream, D));
+    if (used + local + 64 > c->poolUnits) BBTRY(grow_pool(c, stream, D, used, used + local + 65536, false));      // room for toLocalAlignment's strings
+    BBTRY(launch<128>(final_local_kernel, units, stream, D));
     return BBMAP_OK;
 }
 
@@ -441,8 +441,8 @@ static void fill_dev(bbmap_ctx *c, Dev &D, int64_t n_reads, const bbidx_read *re
 // The end of a batch: its counters and stage times become bbmap_stats.  whole: the whole flow ran (map_records); else the final stage
 // alone (bbmap_final_batch_device), which has no other stage's counts or times.  fillsBefore: log entries used before the final stage.
 static int finish_stats(bbmap_ctx *c, hipStream_t stream, bool whole, long long fillsBefore, long long finalRounds, long long finalLocal) {
-    MHIP(hipEventRecord(c->ev[EV_FINAL_END], stream));
-    MTRY(read_counters(c, stream));
+    BBHIP(hipEventRecord(c->ev[EV_FINAL_END], stream));
+    BBTRY(read_counters(c, stream));
     const unsigned *h = c->h_counters;
     const hipEvent_t *ev = c->ev;
     c->poolUsed = 4ll * h[CNT_POOL_UNITS];
@@ -472,26 +472,26 @@ static int map_records(bbmap_ctx *c, hipStream_t stream, int64_t n_reads, const 
                        int64_t minus_delta, const int8_t *baseScores, const int32_t *keyinfo, bool writeRc) {
     memset(&c->stats, 0, sizeof c->stats);
     c->stats.reads = n_reads;
-    MHIP(hipMemsetAsync(c->d_counters, 0, CNT_WORDS * 4, stream));
-    MHIP(hipEventRecord(c->ev[EV_START], stream));
+    BBHIP(hipMemsetAsync(c->d_counters, 0, CNT_WORDS * 4, stream));
+    BBHIP(hipEventRecord(c->ev[EV_START], stream));
     // ---- probe (BBIndex.findAdvanced); reverse complements are written on the way
-    MTRY(bbidx_find_batch_device_with(c->index, &c->probeLs, stream, n_reads, reads, bases, baseScores, keyinfo, c->d_psites, c->cfg.max_sites,
+    BBTRY(bbidx_find_batch_device_with(c->index, &c->probeLs, stream, n_reads, reads, bases, baseScores, keyinfo, c->d_psites, c->cfg.max_sites,
                                       c->d_pnsites, writeRc ? bases + minus_delta : nullptr));
-    MHIP(hipEventRecord(c->ev[EV_PROBE_END], stream));
+    BBHIP(hipEventRecord(c->ev[EV_PROBE_END], stream));
     Dev D;
     fill_dev(c, D, n_reads, reads, bases, minus_delta);
     const long long units = c->cfg.paired ? n_reads / 2 : n_reads;
-    MTRY(launch<128>(begin_kernel, units, stream, D));
+    BBTRY(launch<128>(begin_kernel, units, stream, D));
     if (c->tier) {                       // the units the probe flagged: known now, so the tier can work beside the rest of this pass
-        MTRY(launch<128>(collect_overflow_kernel, units, stream, c->d_mcount, units, c->cfg.paired, c->d_tierUnits, c->d_counters + CNT_TIER_FOUND));
+        BBTRY(launch<128>(collect_overflow_kernel, units, stream, c->d_mcount, units, c->cfg.paired, c->d_tierUnits, c->d_counters + CNT_TIER_FOUND));
     }
-    MHIP(hipEventRecord(c->ev[EV_BEGIN_END], stream));
-    MTRY(launch<128>(score_kernel, n_reads, stream, D));
-    MHIP(hipEventRecord(c->ev[EV_SCORE_END], stream));
+    BBHIP(hipEventRecord(c->ev[EV_BEGIN_END], stream));
+    BBTRY(launch<128>(score_kernel, n_reads, stream, D));
+    BBHIP(hipEventRecord(c->ev[EV_SCORE_END], stream));
     // ---- scoreSlow in rounds
     Rounds R; R.finalStage = false; R.jobBase = R.gBase = 0; R.nActive = n_reads;
     for (int round = 0; R.nActive > 0 && round < 4 * c->cfg.max_sites + 4; round++) {
-        MTRY(round_begin(c, stream, D, R, slow_round_kernel));
+        BBTRY(round_begin(c, stream, D, R, slow_round_kernel));
         if (round == 0) {
             // the probe is over: its statistics are read now
             float pms = 0; long long ps[5];       // (not for the tier's own pass: the synchronous copy inside would wait for the main stream)
@@ -499,55 +499,55 @@ static int map_records(bbmap_ctx *c, hipStream_t stream, int64_t n_reads, const 
             c->overAfterBegin = c->h_counters[CNT_OVERFLOWED];
             if (c->tier && c->h_counters[CNT_TIER_FOUND] > 0 && c->tier->msa != c->msa) tier_start_async(c, c->h_counters[CNT_TIER_FOUND]);     // (a tier that borrows the DP context runs after the pass)
         }
-        MTRY(round_end(c, stream, D, R, bases));
+        BBTRY(round_end(c, stream, D, R, bases));
         c->stats.rounds++;
     }
     long long jobBase = R.jobBase, gBase = R.gBase;
-    MHIP(hipEventRecord(c->ev[EV_SLOW_END], stream));
-    MTRY(launch<128>(finish_kernel, n_reads, stream, D));
-    MHIP(hipEventRecord(c->ev[EV_FINISH_END], stream));
+    BBHIP(hipEventRecord(c->ev[EV_SLOW_END], stream));
+    BBTRY(launch<128>(finish_kernel, n_reads, stream, D));
+    BBHIP(hipEventRecord(c->ev[EV_FINISH_END], stream));
     // ---- rescue: mate 1 anchors, then mate 2
     if (c->cfg.paired && c->cfg.doRescue) {
         const long long pairs = n_reads / 2;
         for (int pass = 0; pass < 2; pass++) {
             D.pass = pass;
             // each pass gets its own region of the search list: reset the search counter, keep the fills' counters
-            MHIP(hipMemsetAsync(c->d_counters + CNT_RESCUE_SEARCHES, 0, 4, stream));
-            MTRY(launch<128>(rescue_plan_kernel, pairs, stream, D));
-            MTRY(read_counters(c, stream));
+            BBHIP(hipMemsetAsync(c->d_counters + CNT_RESCUE_SEARCHES, 0, 4, stream));
+            BBTRY(launch<128>(rescue_plan_kernel, pairs, stream, D));
+            BBTRY(read_counters(c, stream));
             const long long nsearch = c->h_counters[CNT_RESCUE_SEARCHES];
-            if (nsearch > c->rescCap) return mfail(BBMAP_E_NOMEM, "bbmap_map_batch_device: rescue list full");
+            if (nsearch > c->rescCap) return bbfail(BBMAP_E_NOMEM, "bbmap_map_batch_device: rescue list full");
             c->stats.rescue_scans += nsearch;
             if (nsearch == 0) {
-                MTRY(launch<128>(rescue_finish_kernel, pairs, stream, D));
+                BBTRY(launch<128>(rescue_finish_kernel, pairs, stream, D));
                 continue;
             }
             hipEvent_t q0 = c->ev[EV_QUICK_BEGIN], q1 = c->ev[EV_QUICK_END];
-            MHIP(hipEventRecord(q0, stream));
-            MTRY(bbpipe_quick_rescue_device(stream, nsearch, c->d_rjobs, bases, (const int64_t *)c->d_chromOff, c->d_chromArrLen, c->d_chromMin, c->refsBase,
+            BBHIP(hipEventRecord(q0, stream));
+            BBTRY(bbpipe_quick_rescue_device(stream, nsearch, c->d_rjobs, bases, (const int64_t *)c->d_chromOff, c->d_chromArrLen, c->d_chromMin, c->refsBase,
                                             c->d_rres, c->S.ptsMatch, c->S.ptsMatch2, 1, 100));
-            MHIP(hipEventRecord(q1, stream));
+            BBHIP(hipEventRecord(q1, stream));
             // every search issues at most one fill, into either log: room for all of them before the kernel that writes them
-            if (jobBase + nsearch > c->jobCap || gBase + nsearch > c->gjobCap) MTRY(grow_logs(c, stream, D, jobBase + nsearch, gBase + nsearch, jobBase, gBase));
-            MTRY(launch<128>(rescue_prep_kernel, pairs, stream, D));
-            MTRY(read_counters(c, stream));
+            if (jobBase + nsearch > c->jobCap || gBase + nsearch > c->gjobCap) BBTRY(grow_logs(c, stream, D, jobBase + nsearch, gBase + nsearch, jobBase, gBase));
+            BBTRY(launch<128>(rescue_prep_kernel, pairs, stream, D));
+            BBTRY(read_counters(c, stream));
             { float ms = 0; if (hipEventElapsedTime(&ms, q0, q1) == hipSuccess) c->stats.ms_quick_rescue += ms; }
             const long long total = c->h_counters[CNT_FILLS], gtotal = c->h_counters[CNT_GAPPED_FILLS];
-            if (total > c->jobCap || gtotal > c->gjobCap) return mfail(BBMAP_E_HIP, "bbmap_map_batch_device: rescue fills beyond the reserved log entries (internal error)");
-            MTRY(run_fills(c, stream, bases, jobBase, total - jobBase, gBase, gtotal - gBase));
+            if (total > c->jobCap || gtotal > c->gjobCap) return bbfail(BBMAP_E_HIP, "bbmap_map_batch_device: rescue fills beyond the reserved log entries (internal error)");
+            BBTRY(run_fills(c, stream, bases, jobBase, total - jobBase, gBase, gtotal - gBase));
             const bool ranPlain = total > jobBase, ranGapped = gtotal > gBase;
             jobBase = total; gBase = gtotal;
-            MTRY(launch<128>(rescue_finish_kernel, pairs, stream, D));
-            MHIP(hipStreamSynchronize(stream));
+            BBTRY(launch<128>(rescue_finish_kernel, pairs, stream, D));
+            BBHIP(hipStreamSynchronize(stream));
             add_dp_ms(c, ranPlain, ranGapped);
         }
     }
-    MHIP(hipEventRecord(c->ev[EV_RESCUE_END], stream));
+    BBHIP(hipEventRecord(c->ev[EV_RESCUE_END], stream));
     // ---- the final alignment stage
     c->finalFills = 0; c->poolUsed = 0;
     long long finalRounds = 0, finalLocal = 0;
-    if (c->S.finalStage) MTRY(run_final_stage(c, stream, D, n_reads, bases, jobBase, gBase, finalRounds, finalLocal));
-    MTRY(finish_stats(c, stream, true, jobBase + gBase, finalRounds, finalLocal));
+    if (c->S.finalStage) BBTRY(run_final_stage(c, stream, D, n_reads, bases, jobBase, gBase, finalRounds, finalLocal));
+    BBTRY(finish_stats(c, stream, true, jobBase + gBase, finalRounds, finalLocal));
     c->ran = true;
     return BBMAP_OK;
 }
@@ -563,17 +563,17 @@ static int tier_pass(bbmap_ctx *c, hipStream_t s, long long found) {
     const int paired = c->cfg.paired;
     c->tierReads = 0; t->ran = false;
     std::vector<int> ids((size_t)found);
-    MHIP(hipMemcpyAsync(ids.data(), c->d_tierUnits, 4 * (size_t)found, hipMemcpyDeviceToHost, s));
-    MHIP(hipStreamSynchronize(s));
+    BBHIP(hipMemcpyAsync(ids.data(), c->d_tierUnits, 4 * (size_t)found, hipMemcpyDeviceToHost, s));
+    BBHIP(hipStreamSynchronize(s));
     std::sort(ids.begin(), ids.end());
     const long long room = paired ? t->cfg.max_reads / 2 : t->cfg.max_reads;
     const long long take = found < room ? found : room;           // the first `room` units in read order; the rest stay flagged
-    MHIP(hipMemcpyAsync(c->d_tierUnits, ids.data(), 4 * (size_t)take, hipMemcpyHostToDevice, s));
-    MTRY(launch<128>(gather_reads_kernel, take, s, B.reads, c->d_tierUnits, (int)take, paired, c->d_tierReads, c->d_tierReadIds));
-    MHIP(hipStreamSynchronize(s));                                // `ids` is done with
+    BBHIP(hipMemcpyAsync(c->d_tierUnits, ids.data(), 4 * (size_t)take, hipMemcpyHostToDevice, s));
+    BBTRY(launch<128>(gather_reads_kernel, take, s, B.reads, c->d_tierUnits, (int)take, paired, c->d_tierReads, c->d_tierReadIds));
+    BBHIP(hipStreamSynchronize(s));                                // `ids` is done with
     const long long tn = paired ? 2 * take : take;
     // the reverse complements of these reads are in place (the main probe wrote them)
-    MTRY(map_records(t, s, tn, c->d_tierReads, B.bases, B.minus_delta, B.baseScores, B.keyinfo, false));
+    BBTRY(map_records(t, s, tn, c->d_tierReads, B.bases, B.minus_delta, B.baseScores, B.keyinfo, false));
     c->tierReads = tn;
     return BBMAP_OK;
 }
@@ -593,9 +593,9 @@ static int tier_finish(bbmap_ctx *c, hipStream_t stream) {
     bbmap_ctx *t = c->tier;
     const long long tn = c->tierReads;
     if (tn == 0) return BBMAP_OK;
-    MHIP(hipMemsetAsync(c->d_counters + CNT_TIER_RESOLVED, 0, 4, stream));
-    MTRY(launch<128>(mark_tier_kernel, tn, stream, c->d_mcount, t->d_mcount, c->d_tierReadIds, (int)tn, c->d_counters + CNT_TIER_RESOLVED));
-    MTRY(read_counters(c, stream));
+    BBHIP(hipMemsetAsync(c->d_counters + CNT_TIER_RESOLVED, 0, 4, stream));
+    BBTRY(launch<128>(mark_tier_kernel, tn, stream, c->d_mcount, t->d_mcount, c->d_tierReadIds, (int)tn, c->d_counters + CNT_TIER_RESOLVED));
+    BBTRY(read_counters(c, stream));
     bbmap_stats &st = c->stats; const bbmap_stats &ts = t->stats;
     st.reads_reprobed = tn;
     st.reads_overflowed -= (long long)c->h_counters[CNT_TIER_RESOLVED];
@@ -617,8 +617,8 @@ static int rescue_skip_rule(bbmap_ctx *c, bool *skip) {
     *skip = false;
     if (!c->d_runStats) return BBMAP_OK;
     bbmap_runstats rs;
-    MHIP(hipStreamSynchronize(c->statsStream));            // not the device: only that stream's work writes the counters
-    MHIP(hipMemcpy(&rs, c->d_runStats, sizeof rs, hipMemcpyDeviceToHost));
+    BBHIP(hipStreamSynchronize(c->statsStream));            // not the device: only that stream's work writes the counters
+    BBHIP(hipMemcpy(&rs, c->d_runStats, sizeof rs, hipMemcpyDeviceToHost));
     *skip = rs.mappedRetained2 > 1000 && rs.numMated * 20LL < rs.mappedRetained2;
     return BBMAP_OK;
 }
@@ -633,25 +633,25 @@ static int rescue_skip_rule(bbmap_ctx *c, bool *skip) {
 static int adapt_after_batch(bbmap_ctx *c, hipStream_t stream) {
     if (!(c->adaptive & BBMAP_ADAPT_INSERT_LENGTH)) return BBMAP_OK;
     bbmap_runstats rs;
-    MHIP(hipMemcpyAsync(&rs, c->d_runStats, sizeof rs, hipMemcpyDeviceToHost, stream));
-    MHIP(hipStreamSynchronize(stream));
+    BBHIP(hipMemcpyAsync(&rs, c->d_runStats, sizeof rs, hipMemcpyDeviceToHost, stream));
+    BBHIP(hipStreamSynchronize(stream));
     const bool heldPaired = rs.numMated > c->numMatedSeen;
     c->numMatedSeen = rs.numMated;
     if (rs.numMated > 1000 && heldPaired) {
         volatile float sum = (float)rs.innerLengthSum, cnt = (float)rs.numMated;
         const float q = sum * 1.0f / cnt;
         const int v = (int)q;
-        if (v >= 0) MTRY(bbmap_set_average_pair_dist(c, v));
+        if (v >= 0) BBTRY(bbmap_set_average_pair_dist(c, v));
     }
     return BBMAP_OK;
 }
 
 extern "C" int bbmap_get_adaptive_state(bbmap_ctx *c, int32_t *averagePairDist, int32_t *rescueSkipped) {
-    if (!c) return mfail(BBMAP_E_ARG, "bbmap_get_adaptive_state: null context");
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_get_adaptive_state: null context");
     if (averagePairDist) *averagePairDist = c->cfg.averagePairDist;
     if (rescueSkipped) {
         bool skip = false;
-        if (c->adaptive & BBMAP_ADAPT_RESCUE_SKIP) { MHIP(hipSetDevice(c->cfg.device)); MTRY(rescue_skip_rule(c, &skip)); }
+        if (c->adaptive & BBMAP_ADAPT_RESCUE_SKIP) { BBHIP(hipSetDevice(c->cfg.device)); BBTRY(rescue_skip_rule(c, &skip)); }
         *rescueSkipped = skip ? 1 : 0;
     }
     return BBMAP_OK;
@@ -668,22 +668,22 @@ static int map_batch_device(bbmap_ctx *c, hipStream_t stream, int64_t n_reads, c
     // process at the next batch's assignment
     if (c->tierStarted) {
         c->tierThread.join();
-        if (rc == BBMAP_OK && c->tierRc != BBMAP_OK) return mfail(c->tierRc, c->tierErr);
+        if (rc == BBMAP_OK && c->tierRc != BBMAP_OK) return bbfail(c->tierRc, "%s", c->tierErr);
     }
-    MTRY(rc);
-    if (c->tier) MHIP(hipEventRecord(e0, stream));
+    BBTRY(rc);
+    if (c->tier) BBHIP(hipEventRecord(e0, stream));
     if (!c->tier || c->stats.reads_overflowed == 0) return BBMAP_OK;
     if (c->stats.reads_overflowed > c->overAfterBegin || !c->tierStarted) {
         // lists that outgrew max_sites in rescue: one more tier pass, over every flagged read
         const long long units = c->cfg.paired ? n_reads / 2 : n_reads;
-            MHIP(hipMemsetAsync(c->d_counters + CNT_TIER_FOUND, 0, 4, stream));
-        MTRY(launch<128>(collect_overflow_kernel, units, stream, c->d_mcount, units, c->cfg.paired, c->d_tierUnits, c->d_counters + CNT_TIER_FOUND));
-        MTRY(read_counters(c, stream));
-        if (c->h_counters[CNT_TIER_FOUND] > 0) MTRY(tier_pass(c, stream, c->h_counters[CNT_TIER_FOUND]));
+            BBHIP(hipMemsetAsync(c->d_counters + CNT_TIER_FOUND, 0, 4, stream));
+        BBTRY(launch<128>(collect_overflow_kernel, units, stream, c->d_mcount, units, c->cfg.paired, c->d_tierUnits, c->d_counters + CNT_TIER_FOUND));
+        BBTRY(read_counters(c, stream));
+        if (c->h_counters[CNT_TIER_FOUND] > 0) BBTRY(tier_pass(c, stream, c->h_counters[CNT_TIER_FOUND]));
     }
-    MTRY(tier_finish(c, stream));
-    MHIP(hipEventRecord(e1, stream));
-    MHIP(hipStreamSynchronize(stream));
+    BBTRY(tier_finish(c, stream));
+    BBHIP(hipEventRecord(e1, stream));
+    BBHIP(hipStreamSynchronize(stream));
     (void)hipEventElapsedTime(&c->stats.ms_overflow, e0, e1);      // what the tier added to the batch after the main pass
     c->stats.ms_total += c->stats.ms_overflow;
     return BBMAP_OK;
@@ -691,24 +691,24 @@ static int map_batch_device(bbmap_ctx *c, hipStream_t stream, int64_t n_reads, c
 
 extern "C" int bbmap_map_batch_device(bbmap_ctx *c, void *stream_, int64_t n_reads, const bbidx_read *reads, uint8_t *bases,
                                       int64_t minus_delta, const int8_t *baseScores, const int32_t *keyinfo) {
-    if (!c) return mfail(BBMAP_E_ARG, "bbmap_map_batch_device: null context");
-    if (n_reads < 0 || n_reads > c->cfg.max_reads) return mfail(BBMAP_E_ARG, "bbmap_map_batch_device: more reads than the context was made for");
-    if (c->cfg.paired && (n_reads & 1)) return mfail(BBMAP_E_ARG, "bbmap_map_batch_device: paired mode takes an even number of reads");
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_map_batch_device: null context");
+    if (n_reads < 0 || n_reads > c->cfg.max_reads) return bbfail(BBMAP_E_ARG, "bbmap_map_batch_device: more reads than the context was made for");
+    if (c->cfg.paired && (n_reads & 1)) return bbfail(BBMAP_E_ARG, "bbmap_map_batch_device: paired mode takes an even number of reads");
     if (n_reads == 0) { c->ran = false; c->truthNext = nullptr; return BBMAP_OK; }      // (the truth array was for this batch alone)
-    if (!reads || !bases || !baseScores || !keyinfo) return mfail(BBMAP_E_ARG, "bbmap_map_batch_device: null buffer");
+    if (!reads || !bases || !baseScores || !keyinfo) return bbfail(BBMAP_E_ARG, "bbmap_map_batch_device: null buffer");
     hipStream_t stream = (hipStream_t)stream_;
-    MHIP(hipSetDevice(c->cfg.device));
+    BBHIP(hipSetDevice(c->cfg.device));
     c->statsCounted = false;
     const bbmap_truth *truth = c->truthNext;
     c->truthNext = nullptr;
     bool skip = false;
-    if (c->adaptive & BBMAP_ADAPT_RESCUE_SKIP) MTRY(rescue_skip_rule(c, &skip));
+    if (c->adaptive & BBMAP_ADAPT_RESCUE_SKIP) BBTRY(rescue_skip_rule(c, &skip));
     c->S.rescueSkip = skip ? 1 : 0;
     if (c->tier) c->tier->S.rescueSkip = c->S.rescueSkip;
-    MTRY(map_batch_device(c, stream, n_reads, reads, bases, minus_delta, baseScores, keyinfo));
+    BBTRY(map_batch_device(c, stream, n_reads, reads, bases, minus_delta, baseScores, keyinfo));
     if (c->adaptive && c->S.finalStage) {
-        MTRY(bbmap_add_run_stats(c, stream, truth));
-        MTRY(adapt_after_batch(c, stream));
+        BBTRY(bbmap_add_run_stats(c, stream, truth));
+        BBTRY(adapt_after_batch(c, stream));
     }
     return BBMAP_OK;
 }
@@ -716,28 +716,28 @@ extern "C" int bbmap_map_batch_device(bbmap_ctx *c, void *stream_, int64_t n_rea
 // The final alignment stage alone, over site lists the caller provides (see include/bbmap_amd.h).
 extern "C" int bbmap_final_batch_device(bbmap_ctx *c, void *stream_, int64_t n_reads, const bbidx_read *reads, uint8_t *bases, int64_t minus_delta,
                                         const bbmap_msite *sites, const int32_t *nsites) {
-    if (!c) return mfail(BBMAP_E_ARG, "bbmap_final_batch_device: null context");
-    if (!c->S.finalStage) return mfail(BBMAP_E_ARG, "bbmap_final_batch_device: the context was created without the final stage");
-    if (n_reads < 1 || n_reads > c->cfg.max_reads || (c->cfg.paired && (n_reads & 1))) return mfail(BBMAP_E_ARG, "bbmap_final_batch_device: bad read count");
-    if (!reads || !bases || !sites || !nsites) return mfail(BBMAP_E_ARG, "bbmap_final_batch_device: null buffer");
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_final_batch_device: null context");
+    if (!c->S.finalStage) return bbfail(BBMAP_E_ARG, "bbmap_final_batch_device: the context was created without the final stage");
+    if (n_reads < 1 || n_reads > c->cfg.max_reads || (c->cfg.paired && (n_reads & 1))) return bbfail(BBMAP_E_ARG, "bbmap_final_batch_device: bad read count");
+    if (!reads || !bases || !sites || !nsites) return bbfail(BBMAP_E_ARG, "bbmap_final_batch_device: null buffer");
     hipStream_t stream = (hipStream_t)stream_;
-    MHIP(hipSetDevice(c->cfg.device));
+    BBHIP(hipSetDevice(c->cfg.device));
     c->tierStarted = false; c->tierReads = 0;
     if (c->tier) c->tier->ran = false;
     c->statsCounted = false;
     memset(&c->stats, 0, sizeof c->stats);
     c->stats.reads = n_reads;
     c->batch = {n_reads, reads, bases, minus_delta, nullptr, nullptr};
-    MHIP(hipMemsetAsync(c->d_counters, 0, CNT_WORDS * 4, stream));
-    MHIP(hipMemsetAsync(c->d_slow, 0, sizeof(SlowState) * (size_t)n_reads, stream));      // fills are numbered from 0
-    MHIP(hipMemcpyAsync(c->d_ms, sites, sizeof(bbmap_msite) * (size_t)n_reads * (size_t)c->cfg.max_sites, hipMemcpyDeviceToDevice, stream));
-    MHIP(hipMemcpyAsync(c->d_mcount, nsites, 4 * (size_t)n_reads, hipMemcpyDeviceToDevice, stream));
-    MHIP(hipEventRecord(c->ev[EV_RESCUE_END], stream));
+    BBHIP(hipMemsetAsync(c->d_counters, 0, CNT_WORDS * 4, stream));
+    BBHIP(hipMemsetAsync(c->d_slow, 0, sizeof(SlowState) * (size_t)n_reads, stream));      // fills are numbered from 0
+    BBHIP(hipMemcpyAsync(c->d_ms, sites, sizeof(bbmap_msite) * (size_t)n_reads * (size_t)c->cfg.max_sites, hipMemcpyDeviceToDevice, stream));
+    BBHIP(hipMemcpyAsync(c->d_mcount, nsites, 4 * (size_t)n_reads, hipMemcpyDeviceToDevice, stream));
+    BBHIP(hipEventRecord(c->ev[EV_RESCUE_END], stream));
     Dev D;
     fill_dev(c, D, n_reads, reads, bases, minus_delta);
     long long finalRounds = 0, finalLocal = 0;
-    MTRY(run_final_stage(c, stream, D, n_reads, bases, 0, 0, finalRounds, finalLocal));
-    MTRY(finish_stats(c, stream, false, 0, finalRounds, finalLocal));
+    BBTRY(run_final_stage(c, stream, D, n_reads, bases, 0, 0, finalRounds, finalLocal));
+    BBTRY(finish_stats(c, stream, false, 0, finalRounds, finalLocal));
     c->ran = true;
     return BBMAP_OK;
 }

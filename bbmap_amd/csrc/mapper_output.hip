@@ -17,22 +17,22 @@ using namespace bbmapper;
 // mapped by the overflow tier) at packed[offsets[r] ...], offsets = exclusive prefix sums of counts (offsets[n] = their total).
 extern "C" int bbmap_pack_sites_device(bbmap_ctx *c, void *stream_, int64_t n_reads, int32_t *counts, int64_t *offsets, bbmap_msite *packed,
                                        int64_t packed_cap) {
-    if (!c || !counts || !offsets || !packed) return mfail(BBMAP_E_ARG, "bbmap_pack_sites_device: null argument");
-    if (!c->ran || n_reads != c->stats.reads) return mfail(BBMAP_E_ARG, "bbmap_pack_sites_device: n_reads is not the last batch's");
+    if (!c || !counts || !offsets || !packed) return bbfail(BBMAP_E_ARG, "bbmap_pack_sites_device: null argument");
+    if (!c->ran || n_reads != c->stats.reads) return bbfail(BBMAP_E_ARG, "bbmap_pack_sites_device: n_reads is not the last batch's");
     hipStream_t stream = (hipStream_t)stream_;
-    MHIP(hipSetDevice(c->cfg.device));
+    BBHIP(hipSetDevice(c->cfg.device));
     const long long n = n_reads;
     size_t need = 0;
     // (the scan's accumulator type follows its INPUT type: the counts go in as long long so that offsets beyond 2^31 records stay exact)
     auto wide = hipcub::TransformInputIterator<long long, ToLL, const int *>((const int *)counts, ToLL());
-    MHIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, wide, (long long *)offsets, (int)(n + 1), stream));
-    MHIP(c->buf[BUF_PACK_TMP].grow(need, 0, &stream));          // (exact size; the stream may still be scanning in the old one)
+    BBHIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, wide, (long long *)offsets, (int)(n + 1), stream));
+    BBHIP(c->buf[BUF_PACK_TMP].grow(need, 0, &stream));          // (exact size; the stream may still be scanning in the old one)
     // counts has n + 1 entries for the scan (the last one a zero), so that offsets[n] is the total
-    MTRY(launch<256>(pack_counts_kernel, n, stream, c->d_mcount, n, counts));
-    MHIP(hipMemsetAsync(counts + n, 0, 4, stream));
-    MHIP(hipcub::DeviceScan::ExclusiveSum(c->buf[BUF_PACK_TMP].p, need, wide, (long long *)offsets, (int)(n + 1), stream));
+    BBTRY(launch<256>(pack_counts_kernel, n, stream, c->d_mcount, n, counts));
+    BBHIP(hipMemsetAsync(counts + n, 0, 4, stream));
+    BBHIP(hipcub::DeviceScan::ExclusiveSum(c->buf[BUF_PACK_TMP].p, need, wide, (long long *)offsets, (int)(n + 1), stream));
     const long long threads = n * c->cfg.max_sites * 8;
-    MTRY(launch<256>(pack_sites_kernel, threads, stream, c->d_ms, c->d_mcount, (const long long *)offsets, n, c->cfg.max_sites, (long long)packed_cap, packed));
+    BBTRY(launch<256>(pack_sites_kernel, threads, stream, c->d_ms, c->d_mcount, (const long long *)offsets, n, c->cfg.max_sites, (long long)packed_cap, packed));
     return BBMAP_OK;
 }
 
@@ -41,64 +41,64 @@ extern "C" int bbmap_pack_sites_device(bbmap_ctx *c, void *stream_, int64_t n_re
 extern "C" int bbmap_map_batch(bbmap_ctx *c, int64_t n_reads, const bbidx_read *reads, const uint8_t *bases, int64_t bases_bytes,
                                const int8_t *baseScores, const int32_t *keyinfo, int64_t keyinfo_ints, int32_t *nsites_out,
                                int64_t *offsets_out, bbmap_msite *sites_out, int64_t sites_cap, int64_t *total_out) {
-    if (!c) return mfail(BBMAP_E_ARG, "bbmap_map_batch: null context");
-    if (n_reads < 0 || n_reads > c->cfg.max_reads) return mfail(BBMAP_E_ARG, "bbmap_map_batch: more reads than the context was made for");
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_map_batch: null context");
+    if (n_reads < 0 || n_reads > c->cfg.max_reads) return bbfail(BBMAP_E_ARG, "bbmap_map_batch: more reads than the context was made for");
     if (total_out) *total_out = 0;
     if (n_reads == 0) return BBMAP_OK;
     if (!reads || !bases || !baseScores || !keyinfo || !nsites_out || !offsets_out || (sites_cap > 0 && !sites_out) || sites_cap < 0 ||
         bases_bytes < 0 || keyinfo_ints < 0)
-        return mfail(BBMAP_E_ARG, "bbmap_map_batch: bad argument");
+        return bbfail(BBMAP_E_ARG, "bbmap_map_batch: bad argument");
     for (int64_t r = 0; r < n_reads; r++) {
         const bbidx_read &rd = reads[r];
         if (rd.len < 0 || rd.bases_off < 0 || rd.bases_off + rd.len > bases_bytes)
-            return mfail(BBMAP_E_ARG, "bbmap_map_batch: a read lies outside the bases buffer");
+            return bbfail(BBMAP_E_ARG, "bbmap_map_batch: a read lies outside the bases buffer");
         if (rd.nkeys < 0 || rd.keys_off < 0 || rd.keys_off + 2LL * rd.nkeys > keyinfo_ints)
-            return mfail(BBMAP_E_ARG, "bbmap_map_batch: a read's key offsets and scores lie outside keyinfo");
+            return bbfail(BBMAP_E_ARG, "bbmap_map_batch: a read's key offsets and scores lie outside keyinfo");
         // the probe kernels index the read with these offsets (LDS and global memory): every key inside its read, offsets ascending
         // (KeyRing.makeOffsets3 gives them so), no more keys than the profile's kernels take
         if (rd.nkeys > (c->cfg.reserved[3] == BBIDX_PROFILE_PACBIO ? BBIDX_PACBIO_MAX_KEYS : BBIDX_MAX_KEYS))
-            return mfail(BBMAP_E_ARG, "bbmap_map_batch: a read has more keys than the index profile allows (BBIDX_MAX_KEYS / BBIDX_PACBIO_MAX_KEYS)");
+            return bbfail(BBMAP_E_ARG, "bbmap_map_batch: a read has more keys than the index profile allows (BBIDX_MAX_KEYS / BBIDX_PACBIO_MAX_KEYS)");
         const int kk = c->index->dev.p.k;
         for (int q = 0; q < rd.nkeys; q++) {
             const int o = keyinfo[rd.keys_off + q];
             if (o < 0 || o + kk > rd.len || (q > 0 && o < keyinfo[rd.keys_off + q - 1]))
-                return mfail(BBMAP_E_ARG, "bbmap_map_batch: a key offset lies outside its read, or the offsets are not ascending");
+                return bbfail(BBMAP_E_ARG, "bbmap_map_batch: a key offset lies outside its read, or the offsets are not ascending");
         }
     }
-    MHIP(hipSetDevice(c->cfg.device));
+    BBHIP(hipSetDevice(c->cfg.device));
     const size_t nb = (size_t)bases_bytes;
     DevBuf *io = c->buf;
     auto room = [io](int i, size_t need) { return io[i].grow(need, need / 4 + 256); };      // (nothing is in flight on them between calls)
-    MHIP(room(HIO_READS, (size_t)n_reads * sizeof(bbidx_read)));
-    MHIP(room(HIO_BASES, 2 * nb + 16));
-    MHIP(room(HIO_SCORES, nb + 16));
-    MHIP(room(HIO_KEYINFO, (size_t)keyinfo_ints * 4 + 16));
-    MHIP(room(HIO_COUNTS, (size_t)(n_reads + 1) * 4));
-    MHIP(room(HIO_OFFSETS, (size_t)(n_reads + 1) * 8));
-    MHIP(room(HIO_PACKED, (size_t)(sites_cap > 0 ? sites_cap : 1) * sizeof(bbmap_msite)));
+    BBHIP(room(HIO_READS, (size_t)n_reads * sizeof(bbidx_read)));
+    BBHIP(room(HIO_BASES, 2 * nb + 16));
+    BBHIP(room(HIO_SCORES, nb + 16));
+    BBHIP(room(HIO_KEYINFO, (size_t)keyinfo_ints * 4 + 16));
+    BBHIP(room(HIO_COUNTS, (size_t)(n_reads + 1) * 4));
+    BBHIP(room(HIO_OFFSETS, (size_t)(n_reads + 1) * 8));
+    BBHIP(room(HIO_PACKED, (size_t)(sites_cap > 0 ? sites_cap : 1) * sizeof(bbmap_msite)));
     // A stream of this context's own, non-blocking: several mapping threads, each with its own bbmap_ctx on one shared index (BBMap's
     // thread model), then overlap on the GPU instead of queueing behind one another on the legacy default stream.
-    if (!c->hostStream) MHIP(hipStreamCreateWithFlags(&c->hostStream, hipStreamNonBlocking));
+    if (!c->hostStream) BBHIP(hipStreamCreateWithFlags(&c->hostStream, hipStreamNonBlocking));
     hipStream_t hs = c->hostStream;
-    MHIP(hipMemcpyAsync(io[HIO_READS].p, reads, (size_t)n_reads * sizeof(bbidx_read), hipMemcpyHostToDevice, hs));
-    MHIP(hipMemcpyAsync(io[HIO_BASES].p, bases, nb, hipMemcpyHostToDevice, hs));
-    MHIP(hipMemcpyAsync(io[HIO_SCORES].p, baseScores, nb, hipMemcpyHostToDevice, hs));
-    MHIP(hipMemcpyAsync(io[HIO_KEYINFO].p, keyinfo, (size_t)keyinfo_ints * 4, hipMemcpyHostToDevice, hs));
-    MTRY(bbmap_map_batch_device(c, hs, n_reads, (const bbidx_read *)io[HIO_READS].p, (uint8_t *)io[HIO_BASES].p, (int64_t)nb,
+    BBHIP(hipMemcpyAsync(io[HIO_READS].p, reads, (size_t)n_reads * sizeof(bbidx_read), hipMemcpyHostToDevice, hs));
+    BBHIP(hipMemcpyAsync(io[HIO_BASES].p, bases, nb, hipMemcpyHostToDevice, hs));
+    BBHIP(hipMemcpyAsync(io[HIO_SCORES].p, baseScores, nb, hipMemcpyHostToDevice, hs));
+    BBHIP(hipMemcpyAsync(io[HIO_KEYINFO].p, keyinfo, (size_t)keyinfo_ints * 4, hipMemcpyHostToDevice, hs));
+    BBTRY(bbmap_map_batch_device(c, hs, n_reads, (const bbidx_read *)io[HIO_READS].p, (uint8_t *)io[HIO_BASES].p, (int64_t)nb,
                                 (const int8_t *)io[HIO_SCORES].p, (const int32_t *)io[HIO_KEYINFO].p));
-    MTRY(bbmap_pack_sites_device(c, hs, n_reads, (int32_t *)io[HIO_COUNTS].p, (int64_t *)io[HIO_OFFSETS].p, (bbmap_msite *)io[HIO_PACKED].p, sites_cap));
-    MHIP(hipMemcpyAsync(nsites_out, c->d_mcount, (size_t)n_reads * 4, hipMemcpyDeviceToHost, hs));      // counts, or the flags (-1, -2, -3)
-    MHIP(hipMemcpyAsync(offsets_out, io[HIO_OFFSETS].p, (size_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, hs));
-    MHIP(hipStreamSynchronize(hs));
+    BBTRY(bbmap_pack_sites_device(c, hs, n_reads, (int32_t *)io[HIO_COUNTS].p, (int64_t *)io[HIO_OFFSETS].p, (bbmap_msite *)io[HIO_PACKED].p, sites_cap));
+    BBHIP(hipMemcpyAsync(nsites_out, c->d_mcount, (size_t)n_reads * 4, hipMemcpyDeviceToHost, hs));      // counts, or the flags (-1, -2, -3)
+    BBHIP(hipMemcpyAsync(offsets_out, io[HIO_OFFSETS].p, (size_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, hs));
+    BBHIP(hipStreamSynchronize(hs));
     long long total = offsets_out[n_reads];
     const long long have = total < sites_cap ? total : sites_cap;
-    if (have > 0) { MHIP(hipMemcpyAsync(sites_out, io[HIO_PACKED].p, (size_t)have * sizeof(bbmap_msite), hipMemcpyDeviceToHost, hs)); MHIP(hipStreamSynchronize(hs)); }
+    if (have > 0) { BBHIP(hipMemcpyAsync(sites_out, io[HIO_PACKED].p, (size_t)have * sizeof(bbmap_msite), hipMemcpyDeviceToHost, hs)); BBHIP(hipStreamSynchronize(hs)); }
     bbmap_overflow_output ov;
-    MTRY(bbmap_get_overflow_output(c, &ov));
+    BBTRY(bbmap_get_overflow_output(c, &ov));
     if (ov.n_reads > 0) {
         std::vector<int32_t> ids((size_t)ov.n_reads), tn((size_t)ov.n_reads);
-        MHIP(hipMemcpy(ids.data(), ov.read_ids, (size_t)ov.n_reads * 4, hipMemcpyDeviceToHost));
-        MHIP(hipMemcpy(tn.data(), ov.out.nsites, (size_t)ov.n_reads * 4, hipMemcpyDeviceToHost));
+        BBHIP(hipMemcpy(ids.data(), ov.read_ids, (size_t)ov.n_reads * 4, hipMemcpyDeviceToHost));
+        BBHIP(hipMemcpy(tn.data(), ov.out.nsites, (size_t)ov.n_reads * 4, hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < ov.n_reads; i++) {
             const int32_t r = ids[(size_t)i];
             if (r < 0 || r >= n_reads || nsites_out[r] != BBMAP_NSITES_IN_TIER) continue;
@@ -106,7 +106,7 @@ extern "C" int bbmap_map_batch(bbmap_ctx *c, int64_t n_reads, const bbidx_read *
             offsets_out[r] = total;
             if (tn[(size_t)i] <= 0) continue;
             if (total + tn[(size_t)i] <= sites_cap)
-                MHIP(hipMemcpy(sites_out + total, ov.out.sites + i * (int64_t)ov.out.cap, (size_t)tn[(size_t)i] * sizeof(bbmap_msite), hipMemcpyDeviceToHost));
+                BBHIP(hipMemcpy(sites_out + total, ov.out.sites + i * (int64_t)ov.out.cap, (size_t)tn[(size_t)i] * sizeof(bbmap_msite), hipMemcpyDeviceToHost));
             total += tn[(size_t)i];
         }
     }
@@ -115,8 +115,8 @@ extern "C" int bbmap_map_batch(bbmap_ctx *c, int64_t n_reads, const bbidx_read *
 }
 
 extern "C" int bbmap_get_overflow_output(bbmap_ctx *c, bbmap_overflow_output *o) {
-    if (!c || !o) return mfail(BBMAP_E_ARG, "bbmap_get_overflow_output: null argument");
-    if (!c->ran) return mfail(BBMAP_E_ARG, "bbmap_get_overflow_output: no batch has been mapped yet");
+    if (!c || !o) return bbfail(BBMAP_E_ARG, "bbmap_get_overflow_output: null argument");
+    if (!c->ran) return bbfail(BBMAP_E_ARG, "bbmap_get_overflow_output: no batch has been mapped yet");
     memset(o, 0, sizeof *o);
     if (!c->tier || c->tierReads == 0 || !c->tier->ran) return BBMAP_OK;
     o->n_reads = c->tierReads; o->read_ids = c->d_tierReadIds;
@@ -124,8 +124,8 @@ extern "C" int bbmap_get_overflow_output(bbmap_ctx *c, bbmap_overflow_output *o)
 }
 
 extern "C" int bbmap_get_output(bbmap_ctx *c, bbmap_output *o) {
-    if (!c || !o) return mfail(BBMAP_E_ARG, "bbmap_get_output: null argument");
-    if (!c->ran) return mfail(BBMAP_E_ARG, "bbmap_get_output: no batch has been mapped yet");
+    if (!c || !o) return bbfail(BBMAP_E_ARG, "bbmap_get_output: null argument");
+    if (!c->ran) return bbfail(BBMAP_E_ARG, "bbmap_get_output: no batch has been mapped yet");
     memset(o, 0, sizeof *o);
     o->sites = c->d_ms; o->nsites = c->d_mcount; o->cap = c->cfg.max_sites;
     o->match_stride = c->matchStride; o->gmatch_stride = c->gmatchStride;
@@ -137,8 +137,8 @@ extern "C" int bbmap_get_output(bbmap_ctx *c, bbmap_output *o) {
 }
 
 extern "C" int bbmap_set_average_pair_dist(bbmap_ctx *c, int32_t v) {
-    if (!c) return mfail(BBMAP_E_ARG, "bbmap_set_average_pair_dist: null context");
-    if (v < 0) return mfail(BBMAP_E_ARG, "bbmap_set_average_pair_dist: negative distance");
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_set_average_pair_dist: null context");
+    if (v < 0) return bbfail(BBMAP_E_ARG, "bbmap_set_average_pair_dist: negative distance");
     c->S.averagePairDist = v; c->cfg.averagePairDist = v;
     if (c->tier) { c->tier->S.averagePairDist = v; c->tier->cfg.averagePairDist = v; }
     return BBMAP_OK;
@@ -146,27 +146,27 @@ extern "C" int bbmap_set_average_pair_dist(bbmap_ctx *c, int32_t v) {
 
 // The last batch's final records on the host, overflow tier included; match strings packed in read order.
 extern "C" int bbmap_get_final(bbmap_ctx *c, int64_t n_reads, bbmap_final *out, uint8_t *match_out, int64_t match_cap, int64_t *match_bytes) {
-    if (!c || !out) return mfail(BBMAP_E_ARG, "bbmap_get_final: null argument");
-    if (!c->S.finalStage) return mfail(BBMAP_E_ARG, "bbmap_get_final: the context runs without the final stage (bbmap_config.finalStage)");
-    if (!c->ran || n_reads != c->stats.reads) return mfail(BBMAP_E_ARG, "bbmap_get_final: n_reads is not the last batch's");
-    if (match_cap < 0 || (match_cap > 0 && !match_out)) return mfail(BBMAP_E_ARG, "bbmap_get_final: bad match buffer");
-    MHIP(hipSetDevice(c->cfg.device));
-    MHIP(hipMemcpy(out, c->d_final, (size_t)n_reads * sizeof(bbmap_final), hipMemcpyDeviceToHost));
+    if (!c || !out) return bbfail(BBMAP_E_ARG, "bbmap_get_final: null argument");
+    if (!c->S.finalStage) return bbfail(BBMAP_E_ARG, "bbmap_get_final: the context runs without the final stage (bbmap_config.finalStage)");
+    if (!c->ran || n_reads != c->stats.reads) return bbfail(BBMAP_E_ARG, "bbmap_get_final: n_reads is not the last batch's");
+    if (match_cap < 0 || (match_cap > 0 && !match_out)) return bbfail(BBMAP_E_ARG, "bbmap_get_final: bad match buffer");
+    BBHIP(hipSetDevice(c->cfg.device));
+    BBHIP(hipMemcpy(out, c->d_final, (size_t)n_reads * sizeof(bbmap_final), hipMemcpyDeviceToHost));
     std::vector<uint8_t> pool, tpool;
     if (match_out) {
         pool.resize((size_t)c->poolUsed + 4);
-        if (c->poolUsed > 0) MHIP(hipMemcpy(pool.data(), c->d_pool, (size_t)c->poolUsed, hipMemcpyDeviceToHost));
+        if (c->poolUsed > 0) BBHIP(hipMemcpy(pool.data(), c->d_pool, (size_t)c->poolUsed, hipMemcpyDeviceToHost));
     }
     std::vector<uint8_t> fromTier((size_t)n_reads, 0);
     if (c->tier && c->tierReads > 0 && c->tier->ran) {
         bbmap_ctx *t = c->tier;
         std::vector<int32_t> ids((size_t)c->tierReads);
         std::vector<bbmap_final> tf((size_t)c->tierReads);
-        MHIP(hipMemcpy(ids.data(), c->d_tierReadIds, (size_t)c->tierReads * 4, hipMemcpyDeviceToHost));
-        MHIP(hipMemcpy(tf.data(), t->d_final, (size_t)c->tierReads * sizeof(bbmap_final), hipMemcpyDeviceToHost));
+        BBHIP(hipMemcpy(ids.data(), c->d_tierReadIds, (size_t)c->tierReads * 4, hipMemcpyDeviceToHost));
+        BBHIP(hipMemcpy(tf.data(), t->d_final, (size_t)c->tierReads * sizeof(bbmap_final), hipMemcpyDeviceToHost));
         if (match_out) {
             tpool.resize((size_t)t->poolUsed + 4);
-            if (t->poolUsed > 0) MHIP(hipMemcpy(tpool.data(), t->d_pool, (size_t)t->poolUsed, hipMemcpyDeviceToHost));
+            if (t->poolUsed > 0) BBHIP(hipMemcpy(tpool.data(), t->d_pool, (size_t)t->poolUsed, hipMemcpyDeviceToHost));
         }
         for (long long i = 0; i < c->tierReads; i++) {
             const int32_t r = ids[(size_t)i];
@@ -180,7 +180,7 @@ extern "C" int bbmap_get_final(bbmap_ctx *c, int64_t n_reads, bbmap_final *out, 
         if (f.match_len <= 0) { f.match_off = 0; continue; }
         if (match_out) {
             const std::vector<uint8_t> &src = fromTier[(size_t)r] ? tpool : pool;
-            if (f.match_off < 0 || f.match_off + f.match_len > (int64_t)src.size()) return mfail(BBMAP_E_HIP, "bbmap_get_final: a match string lies outside its pool (internal error)");
+            if (f.match_off < 0 || f.match_off + f.match_len > (int64_t)src.size()) return bbfail(BBMAP_E_HIP, "bbmap_get_final: a match string lies outside its pool (internal error)");
             if (used + f.match_len <= match_cap) memcpy(match_out + used, src.data() + f.match_off, (size_t)f.match_len);
         }
         f.match_off = used; used += f.match_len;
@@ -193,31 +193,31 @@ extern "C" int bbmap_get_final(bbmap_ctx *c, int64_t n_reads, bbmap_final *out, 
 static int tier_index(bbmap_ctx *c, hipStream_t stream, long long n, const int **out) {
     *out = nullptr;
     if (!(c->tier && c->tierReads > 0 && c->tier->ran && n > 0)) return BBMAP_OK;
-    if (!c->d_scafTier) MTRY(dalloc(c, &c->d_scafTier, (size_t)c->cfg.max_reads));
-    MHIP(hipMemsetAsync(c->d_scafTier, 0xff, (size_t)n * 4, stream));
-    MTRY(launch<256>(tier_index_kernel, c->tierReads, stream, c->d_tierReadIds, c->tierReads, n, c->d_scafTier));
+    if (!c->d_scafTier) BBTRY(dalloc(c, &c->d_scafTier, (size_t)c->cfg.max_reads));
+    BBHIP(hipMemsetAsync(c->d_scafTier, 0xff, (size_t)n * 4, stream));
+    BBTRY(launch<256>(tier_index_kernel, c->tierReads, stream, c->d_tierReadIds, c->tierReads, n, c->d_scafTier));
     *out = c->d_scafTier;
     return BBMAP_OK;
 }
 
 extern "C" int bbmap_get_scaffold_records(bbmap_ctx *c, void *stream_, const bbmap_scafrec **out) {
-    if (!c || !out) return mfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: null argument");
-    if (!c->S.finalStage) return mfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: the context runs without the final stage (bbmap_config.finalStage)");
-    if (!c->ran) return mfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: no batch has been mapped yet");
+    if (!c || !out) return bbfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: null argument");
+    if (!c->S.finalStage) return bbfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: the context runs without the final stage (bbmap_config.finalStage)");
+    if (!c->ran) return bbfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: no batch has been mapped yet");
     const bbscaf::Table T = c->index->scaf;
-    if (!T.off) return mfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: the index has no scaffold table (bbidx_set_scaffolds)");
-    MHIP(hipSetDevice(c->cfg.device));
+    if (!T.off) return bbfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: the index has no scaffold table (bbidx_set_scaffolds)");
+    BBHIP(hipSetDevice(c->cfg.device));
     hipStream_t stream = (hipStream_t)stream_;
     const long long n = c->stats.reads;
     if (!c->d_scafRec) {
-        MTRY(dalloc(c, &c->d_scafRec, (size_t)c->cfg.max_reads));
+        BBTRY(dalloc(c, &c->d_scafRec, (size_t)c->cfg.max_reads));
     }
     const int *tierIdx = nullptr; const bbmap_final *tfin = nullptr; const uint8_t *tpool = nullptr;
-    MTRY(tier_index(c, stream, n, &tierIdx));
+    BBTRY(tier_index(c, stream, n, &tierIdx));
     if (tierIdx) { tfin = c->tier->d_final; tpool = c->tier->d_pool; }
     const long long units = c->cfg.paired ? n / 2 : n;
     if (units > 0)          // one wavefront per unit
-        MTRY(launch<256>(scaffold_coords_kernel, 64 * units, stream, T, c->d_final, c->d_pool, tfin, tpool, tierIdx, units, c->cfg.paired, c->d_scafRec));
+        BBTRY(launch<256>(scaffold_coords_kernel, 64 * units, stream, T, c->d_final, c->d_pool, tfin, tpool, tierIdx, units, c->cfg.paired, c->d_scafRec));
     *out = c->d_scafRec;
     return BBMAP_OK;
 }
@@ -226,23 +226,23 @@ extern "C" int bbmap_get_scaffold_records(bbmap_ctx *c, void *stream_, const bbm
 // of the per-read byte counts, the emit pass.  The blob's size comes back once between the scan and the emit pass (it sizes the blob).
 extern "C" int bbmap_get_sam_records(bbmap_ctx *c, void *stream_, int32_t flags, const bbmap_samrec **recs, const uint8_t **text,
                                      int64_t *text_bytes) {
-    if (!c || !recs || !text) return mfail(BBMAP_E_ARG, "bbmap_get_sam_records: null argument");
-    if (flags & ~(BBMAP_SAM_CIGAR13 | BBMAP_SAM_MD)) return mfail(BBMAP_E_ARG, "bbmap_get_sam_records: unknown flag bits");
+    if (!c || !recs || !text) return bbfail(BBMAP_E_ARG, "bbmap_get_sam_records: null argument");
+    if (flags & ~(BBMAP_SAM_CIGAR13 | BBMAP_SAM_MD)) return bbfail(BBMAP_E_ARG, "bbmap_get_sam_records: unknown flag bits");
     const bbmap_scafrec *scaf = nullptr;
-    MTRY(bbmap_get_scaffold_records(c, stream_, &scaf));    // its error cases are this call's: no final stage, no batch, no scaffold table
+    BBTRY(bbmap_get_scaffold_records(c, stream_, &scaf));    // its error cases are this call's: no final stage, no batch, no scaffold table
     if (!c->batch.reads || !c->batch.bases || c->batch.n_reads != c->stats.reads)
-        return mfail(BBMAP_E_ARG, "bbmap_get_sam_records: the context does not hold the last batch's reads");
+        return bbfail(BBMAP_E_ARG, "bbmap_get_sam_records: the context does not hold the last batch's reads");
     hipStream_t stream = (hipStream_t)stream_;
     const long long n = c->stats.reads;
     const int maxLen = c->cfg.max_read_len;
     if (!c->d_samRec) {
-        MTRY(dalloc(c, &c->d_samRec, (size_t)c->cfg.max_reads));
-        MTRY(dalloc(c, &c->d_samCounts, (size_t)c->cfg.max_reads + 1));
-        MTRY(dalloc(c, &c->d_samOffsets, (size_t)c->cfg.max_reads + 1));
-        MTRY(dalloc(c, &c->d_mapqMax, (size_t)maxLen + 1));
+        BBTRY(dalloc(c, &c->d_samRec, (size_t)c->cfg.max_reads));
+        BBTRY(dalloc(c, &c->d_samCounts, (size_t)c->cfg.max_reads + 1));
+        BBTRY(dalloc(c, &c->d_samOffsets, (size_t)c->cfg.max_reads + 1));
+        BBTRY(dalloc(c, &c->d_mapqMax, (size_t)maxLen + 1));
         std::vector<float> table((size_t)maxLen + 1);
         bbsam::fill_mapq_max(table.data(), maxLen);
-        MHIP(hipMemcpy(c->d_mapqMax, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
+        BBHIP(hipMemcpy(c->d_mapqMax, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     bbsam::Args a;
     a.fin = c->d_final; a.pool = c->d_pool; a.tfin = nullptr; a.tpool = nullptr; a.tierIdx = nullptr;
@@ -254,17 +254,17 @@ extern "C" int bbmap_get_sam_records(bbmap_ctx *c, void *stream_, int32_t flags,
     a.n = n; a.paired = c->cfg.paired; a.flags = flags;
     size_t need = 0;
     auto wide = hipcub::TransformInputIterator<long long, ToLL, const int *>((const int *)c->d_samCounts, ToLL());
-    MHIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, wide, c->d_samOffsets, (int)(n + 1), stream));
-    MHIP(c->buf[BUF_SAM_TMP].grow(need, 0, &stream));
-    MHIP(bbsam::launch_size(a, c->d_samRec, c->d_samCounts, stream));
-    MHIP(hipMemsetAsync(c->d_samCounts + n, 0, 4, stream));                 // n + 1 entries, so that offsets[n] is the total
-    MHIP(hipcub::DeviceScan::ExclusiveSum(c->buf[BUF_SAM_TMP].p, need, wide, c->d_samOffsets, (int)(n + 1), stream));
+    BBHIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, wide, c->d_samOffsets, (int)(n + 1), stream));
+    BBHIP(c->buf[BUF_SAM_TMP].grow(need, 0, &stream));
+    BBHIP(bbsam::launch_size(a, c->d_samRec, c->d_samCounts, stream));
+    BBHIP(hipMemsetAsync(c->d_samCounts + n, 0, 4, stream));                 // n + 1 entries, so that offsets[n] is the total
+    BBHIP(hipcub::DeviceScan::ExclusiveSum(c->buf[BUF_SAM_TMP].p, need, wide, c->d_samOffsets, (int)(n + 1), stream));
     long long total = 0;
-    MHIP(hipMemcpyAsync(&total, c->d_samOffsets + n, 8, hipMemcpyDeviceToHost, stream));
-    MHIP(hipStreamSynchronize(stream));
-    MHIP(c->buf[BUF_SAM_TEXT].grow((size_t)total, (size_t)total / 4 + 256));       // (the stream has just been waited for)
+    BBHIP(hipMemcpyAsync(&total, c->d_samOffsets + n, 8, hipMemcpyDeviceToHost, stream));
+    BBHIP(hipStreamSynchronize(stream));
+    BBHIP(c->buf[BUF_SAM_TEXT].grow((size_t)total, (size_t)total / 4 + 256));       // (the stream has just been waited for)
     uint8_t *blob = (uint8_t *)c->buf[BUF_SAM_TEXT].p;
-    MHIP(bbsam::launch_emit(a, c->d_samRec, c->d_samOffsets, blob, stream));
+    BBHIP(bbsam::launch_emit(a, c->d_samRec, c->d_samOffsets, blob, stream));
     c->samTextBytes = total;
     *recs = c->d_samRec; *text = blob;
     if (text_bytes) *text_bytes = total;
@@ -274,13 +274,13 @@ extern "C" int bbmap_get_sam_records(bbmap_ctx *c, void *stream_, int32_t flags,
 // Host form: the records and the blob as they are on the device (packed in read order already), two copies.
 extern "C" int bbmap_get_sam(bbmap_ctx *c, int64_t n_reads, int32_t flags, bbmap_samrec *out, uint8_t *text_out, int64_t text_cap,
                              int64_t *text_bytes) {
-    if (!c || !out) return mfail(BBMAP_E_ARG, "bbmap_get_sam: null argument");
-    if (!c->ran || n_reads != c->stats.reads) return mfail(BBMAP_E_ARG, "bbmap_get_sam: n_reads is not the last batch's");
-    if (text_cap < 0 || (text_cap > 0 && !text_out)) return mfail(BBMAP_E_ARG, "bbmap_get_sam: bad text buffer");
+    if (!c || !out) return bbfail(BBMAP_E_ARG, "bbmap_get_sam: null argument");
+    if (!c->ran || n_reads != c->stats.reads) return bbfail(BBMAP_E_ARG, "bbmap_get_sam: n_reads is not the last batch's");
+    if (text_cap < 0 || (text_cap > 0 && !text_out)) return bbfail(BBMAP_E_ARG, "bbmap_get_sam: bad text buffer");
     const bbmap_samrec *recs = nullptr; const uint8_t *text = nullptr; int64_t total = 0;
-    MTRY(bbmap_get_sam_records(c, nullptr, flags, &recs, &text, &total));
-    if (n_reads > 0) MHIP(hipMemcpy(out, recs, (size_t)n_reads * sizeof(bbmap_samrec), hipMemcpyDeviceToHost));    // (waits for the null stream)
-    if (text_out && total > 0 && total <= text_cap) MHIP(hipMemcpy(text_out, text, (size_t)total, hipMemcpyDeviceToHost));
+    BBTRY(bbmap_get_sam_records(c, nullptr, flags, &recs, &text, &total));
+    if (n_reads > 0) BBHIP(hipMemcpy(out, recs, (size_t)n_reads * sizeof(bbmap_samrec), hipMemcpyDeviceToHost));    // (waits for the null stream)
+    if (text_out && total > 0 && total <= text_cap) BBHIP(hipMemcpy(text_out, text, (size_t)total, hipMemcpyDeviceToHost));
     if (text_bytes) *text_bytes = total;
     return BBMAP_OK;
 }
@@ -288,97 +288,97 @@ extern "C" int bbmap_get_sam(bbmap_ctx *c, int64_t n_reads, int32_t flags, bbmap
 // ---- run statistics (run_stats.hip) and the adaptive state they drive
 static int run_stats_buffers(bbmap_ctx *c) {
     if (c->d_runStats) return BBMAP_OK;
-    MTRY(dalloc(c, &c->d_insertHist, (size_t)BBMAP_INSERT_HIST_BINS));
-    MHIP(hipMemset(c->d_insertHist, 0, 8 * (size_t)BBMAP_INSERT_HIST_BINS));
+    BBTRY(dalloc(c, &c->d_insertHist, (size_t)BBMAP_INSERT_HIST_BINS));
+    BBHIP(hipMemset(c->d_insertHist, 0, 8 * (size_t)BBMAP_INSERT_HIST_BINS));
     unsigned long long *p = nullptr;
-    MTRY(dalloc(c, &p, (size_t)bbrunstats::N_COUNTERS));
-    MHIP(hipMemset(p, 0, sizeof(bbmap_runstats)));
+    BBTRY(dalloc(c, &p, (size_t)bbrunstats::N_COUNTERS));
+    BBHIP(hipMemset(p, 0, sizeof(bbmap_runstats)));
     c->d_runStats = p;
     return BBMAP_OK;
 }
 
 extern "C" int bbmap_add_run_stats(bbmap_ctx *c, void *stream_, const bbmap_truth *truth) {
-    if (!c) return mfail(BBMAP_E_ARG, "bbmap_add_run_stats: null context");
-    if (!c->S.finalStage) return mfail(BBMAP_E_ARG, "bbmap_add_run_stats: the context runs without the final stage (bbmap_config.finalStage)");
-    if (!c->ran) return mfail(BBMAP_E_ARG, "bbmap_add_run_stats: no batch has been mapped yet");
-    if (c->statsCounted) return mfail(BBMAP_E_ARG, "bbmap_add_run_stats: the last batch has been counted already");
-    if (!c->batch.reads || c->batch.n_reads != c->stats.reads) return mfail(BBMAP_E_ARG, "bbmap_add_run_stats: the context does not hold the last batch's reads");
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_add_run_stats: null context");
+    if (!c->S.finalStage) return bbfail(BBMAP_E_ARG, "bbmap_add_run_stats: the context runs without the final stage (bbmap_config.finalStage)");
+    if (!c->ran) return bbfail(BBMAP_E_ARG, "bbmap_add_run_stats: no batch has been mapped yet");
+    if (c->statsCounted) return bbfail(BBMAP_E_ARG, "bbmap_add_run_stats: the last batch has been counted already");
+    if (!c->batch.reads || c->batch.n_reads != c->stats.reads) return bbfail(BBMAP_E_ARG, "bbmap_add_run_stats: the context does not hold the last batch's reads");
     hipStream_t stream = (hipStream_t)stream_;
-    MHIP(hipSetDevice(c->cfg.device));
-    MTRY(run_stats_buffers(c));
+    BBHIP(hipSetDevice(c->cfg.device));
+    BBTRY(run_stats_buffers(c));
     const long long n = c->stats.reads;
     bbrunstats::Args a = {};
     a.reads = c->batch.reads;
     a.fin = c->d_final; a.pool = c->d_pool; a.sites = c->d_ms; a.nsites = c->d_mcount; a.cap = c->cfg.max_sites;
-    MTRY(tier_index(c, stream, n, &a.tierIdx));
+    BBTRY(tier_index(c, stream, n, &a.tierIdx));
     if (a.tierIdx) { const bbmap_ctx *t = c->tier; a.tfin = t->d_final; a.tpool = t->d_pool; a.tsites = t->d_ms; a.tnsites = t->d_mcount; a.tcap = t->cfg.max_sites; }
     a.truth = truth; a.n = n; a.paired = c->cfg.paired;
     a.ptsMatch = c->S.ptsMatch; a.ptsMatch2 = c->S.ptsMatch2;
     a.thresh = 0; a.maxPairDist = c->cfg.maxPairDist;
-    MHIP(bbrunstats::launch(a, c->d_runStats, c->d_insertHist, stream));
+    BBHIP(bbrunstats::launch(a, c->d_runStats, c->d_insertHist, stream));
     c->statsCounted = true; c->statsStream = stream;
     return BBMAP_OK;
 }
 
 extern "C" int bbmap_get_run_stats(bbmap_ctx *c, bbmap_runstats *out, int64_t *ihist_out) {
-    if (!c || !out) return mfail(BBMAP_E_ARG, "bbmap_get_run_stats: null argument");
-    MHIP(hipSetDevice(c->cfg.device));
+    if (!c || !out) return bbfail(BBMAP_E_ARG, "bbmap_get_run_stats: null argument");
+    BBHIP(hipSetDevice(c->cfg.device));
     if (!c->d_runStats) {
         memset(out, 0, sizeof *out);
         if (ihist_out) memset(ihist_out, 0, 8 * (size_t)BBMAP_INSERT_HIST_BINS);
         return BBMAP_OK;
     }
-    MHIP(hipStreamSynchronize(c->statsStream));            // the counters are written on that stream only
-    MHIP(hipMemcpy(out, c->d_runStats, sizeof *out, hipMemcpyDeviceToHost));
-    if (ihist_out) MHIP(hipMemcpy(ihist_out, c->d_insertHist, 8 * (size_t)BBMAP_INSERT_HIST_BINS, hipMemcpyDeviceToHost));
+    BBHIP(hipStreamSynchronize(c->statsStream));            // the counters are written on that stream only
+    BBHIP(hipMemcpy(out, c->d_runStats, sizeof *out, hipMemcpyDeviceToHost));
+    if (ihist_out) BBHIP(hipMemcpy(ihist_out, c->d_insertHist, 8 * (size_t)BBMAP_INSERT_HIST_BINS, hipMemcpyDeviceToHost));
     return BBMAP_OK;
 }
 
 extern "C" int bbmap_reset_run_stats(bbmap_ctx *c) {
-    if (!c) return mfail(BBMAP_E_ARG, "bbmap_reset_run_stats: null context");
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_reset_run_stats: null context");
     c->numMatedSeen = 0;
     if (!c->d_runStats) return BBMAP_OK;
-    MHIP(hipSetDevice(c->cfg.device));
-    MHIP(hipMemsetAsync(c->d_runStats, 0, sizeof(bbmap_runstats), c->statsStream));      // behind the last accumulation
-    MHIP(hipMemsetAsync(c->d_insertHist, 0, 8 * (size_t)BBMAP_INSERT_HIST_BINS, c->statsStream));
-    MHIP(hipStreamSynchronize(c->statsStream));
+    BBHIP(hipSetDevice(c->cfg.device));
+    BBHIP(hipMemsetAsync(c->d_runStats, 0, sizeof(bbmap_runstats), c->statsStream));      // behind the last accumulation
+    BBHIP(hipMemsetAsync(c->d_insertHist, 0, 8 * (size_t)BBMAP_INSERT_HIST_BINS, c->statsStream));
+    BBHIP(hipStreamSynchronize(c->statsStream));
     return BBMAP_OK;
 }
 
 extern "C" int bbmap_set_adaptive(bbmap_ctx *c, int32_t flags) {
-    if (!c) return mfail(BBMAP_E_ARG, "bbmap_set_adaptive: null context");
-    if (flags & ~(BBMAP_ADAPT_INSERT_LENGTH | BBMAP_ADAPT_RESCUE_SKIP)) return mfail(BBMAP_E_ARG, "bbmap_set_adaptive: unknown flag bits");
-    if (flags && !c->S.finalStage) return mfail(BBMAP_E_ARG, "bbmap_set_adaptive: the context runs without the final stage (bbmap_config.finalStage)");
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_set_adaptive: null context");
+    if (flags & ~(BBMAP_ADAPT_INSERT_LENGTH | BBMAP_ADAPT_RESCUE_SKIP)) return bbfail(BBMAP_E_ARG, "bbmap_set_adaptive: unknown flag bits");
+    if (flags && !c->S.finalStage) return bbfail(BBMAP_E_ARG, "bbmap_set_adaptive: the context runs without the final stage (bbmap_config.finalStage)");
     c->adaptive = flags;
     return BBMAP_OK;
 }
 
 extern "C" int bbmap_set_truth(bbmap_ctx *c, const bbmap_truth *truth) {
-    if (!c) return mfail(BBMAP_E_ARG, "bbmap_set_truth: null context");
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_set_truth: null context");
     c->truthNext = truth;
     return BBMAP_OK;
 }
 
 extern "C" int bbidx_get_chrom_table(bbidx_ctx *ix, int32_t *nchroms, const uint8_t **chromArr, int32_t *chromArrLen, int32_t cap) {
-    if (!ix || !nchroms) return mfail(BBMAP_E_ARG, "bbidx_get_chrom_table: null argument");
+    if (!ix || !nchroms) return bbfail(BBMAP_E_ARG, "bbidx_get_chrom_table: null argument");
     *nchroms = ix->dev.nchroms;
     if (!chromArr && !chromArrLen) return BBMAP_OK;
-    if (cap < ix->dev.nchroms + 1) return mfail(BBMAP_E_ARG, "bbidx_get_chrom_table: buffers too small (need nchroms + 1 entries)");
-    MHIP(hipSetDevice(ix->device));
-    if (chromArr) MHIP(hipMemcpy(chromArr, ix->dev.chromArr, sizeof(void *) * (size_t)(ix->dev.nchroms + 1), hipMemcpyDeviceToHost));
-    if (chromArrLen) MHIP(hipMemcpy(chromArrLen, ix->dev.chromArrLen, 4 * (size_t)(ix->dev.nchroms + 1), hipMemcpyDeviceToHost));
+    if (cap < ix->dev.nchroms + 1) return bbfail(BBMAP_E_ARG, "bbidx_get_chrom_table: buffers too small (need nchroms + 1 entries)");
+    BBHIP(hipSetDevice(ix->device));
+    if (chromArr) BBHIP(hipMemcpy(chromArr, ix->dev.chromArr, sizeof(void *) * (size_t)(ix->dev.nchroms + 1), hipMemcpyDeviceToHost));
+    if (chromArrLen) BBHIP(hipMemcpy(chromArrLen, ix->dev.chromArrLen, 4 * (size_t)(ix->dev.nchroms + 1), hipMemcpyDeviceToHost));
     return BBMAP_OK;
 }
 
 extern "C" int bbmap_last_stats(bbmap_ctx *c, bbmap_stats *out) {
-    if (!c || !out) return mfail(BBMAP_E_ARG, "bbmap_last_stats: null argument");
-    if (!c->ran) return mfail(BBMAP_E_ARG, "bbmap_last_stats: no batch has been mapped yet");
+    if (!c || !out) return bbfail(BBMAP_E_ARG, "bbmap_last_stats: null argument");
+    if (!c->ran) return bbfail(BBMAP_E_ARG, "bbmap_last_stats: no batch has been mapped yet");
     *out = c->stats;
     return BBMAP_OK;
 }
 
 extern "C" int bbmap_copy_to_host(void *dst, const void *src_device, int64_t bytes) {
-    if (bytes < 0 || (bytes > 0 && (!dst || !src_device))) return mfail(BBMAP_E_ARG, "bbmap_copy_to_host: bad argument");
-    if (bytes > 0) MHIP(hipMemcpy(dst, src_device, (size_t)bytes, hipMemcpyDeviceToHost));
+    if (bytes < 0 || (bytes > 0 && (!dst || !src_device))) return bbfail(BBMAP_E_ARG, "bbmap_copy_to_host: bad argument");
+    if (bytes > 0) BBHIP(hipMemcpy(dst, src_device, (size_t)bytes, hipMemcpyDeviceToHost));
     return BBMAP_OK;
 }

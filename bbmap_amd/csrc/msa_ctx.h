@@ -3,63 +3,63 @@
 #include <hip/hip_runtime.h>
 
 #include "bbmap_amd.h"
+#include "host_common.h"
 
 struct bbmsa_ctx {
-    bbmsa_config cfg;
-    int device;
-    int numCUs;
-    int scheme;                 // BBMSA_SCHEME_*
+    bbmsa_config cfg = {};
+    int device = 0;
+    int numCUs = 0;
+    int scheme = 0;             // BBMSA_SCHEME_*
     // fast kernel geometry
-    int G, R, fastCols, tmpBytes, blocks, ldsBytes, tableLen, wideTableLen;
-    long long dirSlotDwords;
-    unsigned int *d_dir;
-    unsigned int *d_counters;   // [0]=fast queue, [1]=slow count, [2]=generic queue
-    int *d_slowList;
-    long long slowCap;
+    int G = 0, R = 0, fastCols = 0, tmpBytes = 0, blocks = 0, ldsBytes = 0, tableLen = 0, wideTableLen = 0;
+    long long dirSlotDwords = 0;
+    unsigned int *d_dir = nullptr;
+    unsigned int *d_counters = nullptr;   // [0]=fast queue, [1]=slow count, [2]=generic queue
+    DevBuf slowList;            // ints: the jobs the wavefront kernel hands on; as long as the largest launch so far
     // generic kernel
-    int genThreads;
-    int *d_matrix;
-    int *d_limits;
+    int genThreads = 0;
+    int *d_matrix = nullptr;
+    int *d_limits = nullptr;
     // wide pass: the wavefront kernel again, 64 lanes per job and one job per 64-thread block, with an LDS column buffer as
     // wide as maxColumns, for the jobs the first pass found too wide for its own buffer (0 blocks = not needed)
-    int wideR, wideCols, wideTmpBytes, wideBlocks, wideLdsBytes;
-    long long wideDirSlotDwords;
-    unsigned int *d_wideDir;
-    int *d_slowList2;
+    int wideR = 0, wideCols = 0, wideTmpBytes = 0, wideBlocks = 0, wideLdsBytes = 0;
+    long long wideDirSlotDwords = 0;
+    unsigned int *d_wideDir = nullptr;
+    DevBuf slowList2;           // the wide pass's own hand-over list (only with a wide pass), as long as slowList
     // narrow-window kernel (msa_fill_narrow.hip): one job per lane
-    int narrowBlocks, narrowSlack;     // 0 blocks = disabled
-    bool narrowOff;                    // switched off by the caller for launches whose jobs it cannot take (bbmsa_use_narrow)
-    bool narrowUsed;                   // whether the last launch ran it
-    bool lastSorted, lastLatency, lastIndirect;   // the last launch's route (bbmsa_last_route): width-sorted first pass, latency route,
-                                                  // job count read on the device
+    int narrowBlocks = 0, narrowSlack = 0;     // 0 blocks = disabled
+    bool narrowOff = false;            // switched off by the caller for launches whose jobs it cannot take (bbmsa_use_narrow)
+    bool narrowUsed = false;           // whether the last launch ran it
+    bool lastSorted = false, lastLatency = false, lastIndirect = false;   // the last launch's route (bbmsa_last_route): width-sorted first pass,
+                                                                          // latency route, job count read on the device
     // widest windows first (bbmsa_sort_by_width): two jobs share a wavefront and step together, so a 600-column job beside a
     // 200-column one idles half the wave for 400 steps; in width order neighbours are alike, and the longest jobs do not end up last
-    bool sortByWidth;
-    unsigned int *d_widthHist;
-    long long latencyJobs;             // launches with at most this many jobs go straight to the 64-lane geometry (bbmsa_set_latency_jobs)
-    unsigned long long *d_narrowDir;
-    int *d_fastList;
-    long long fastCap;
-    // gapped-reference scratch (msa_gapped.hip), grown on demand
-    uint8_t *d_gref;
-    int *d_gaux;
-    bbmsa_job *d_gjobs;
-    long long gappedCap;
-    hipEvent_t ev[4];      // start, after wavefront kernel, after generic kernel, after narrow kernel
-    bool timed;
-    bool banded;
-    bool legacyOnly;            // created with BBMSA_LEGACY_ONLY: bbmsa_fill_submit / _collect / _packed only
-    struct bbmsa_legacy *legacy;   // the per-call service of such a context (msa_legacy.hip)
+    bool sortByWidth = false;
+    unsigned int *d_widthHist = nullptr;
+    long long latencyJobs = 0;         // launches with at most this many jobs go straight to the 64-lane geometry (bbmsa_set_latency_jobs)
+    unsigned long long *d_narrowDir = nullptr;
+    DevBuf fastList;            // ints: the wavefront kernel's job list when the narrow kernel or the width sort writes one
+    // gapped-reference scratch (msa_gapped.hip), grown on demand: gapped references, their bookkeeping, the derived jobs
+    DevBuf gref, gaux, gjobs;
+    hipEvent_t ev[4] = {};  // start, after wavefront kernel, after generic kernel, after narrow kernel
+    bool timed = false;
+    bool banded = false;
+    bool legacyOnly = false;    // created with BBMSA_LEGACY_ONLY: bbmsa_fill_submit / _collect / _packed only
+    struct bbmsa_legacy *legacy = nullptr;   // the per-call service of such a context (msa_legacy.hip)
     // strip-tiled wavefront kernel of the 9PacBio scheme (msa_fill_strip.hip)
-    int stripBlocks, stripLds;
-    long long stripDwords, stripSlotDwords;
-    int *d_stripBoundary;
-    uint8_t *d_stripTmp;
+    int stripBlocks = 0, stripLds = 0;
+    long long stripDwords = 0, stripSlotDwords = 0;
+    int *d_stripBoundary = nullptr;
+    uint8_t *d_stripTmp = nullptr;
     // pipelined form of the strip kernel for launches with few jobs: pipeK wavefronts per job, pipeSlots jobs at a time
-    int pipeK, pipeSlots, pipeJobsMax;
-    int *d_pipeBoundary, *d_pipeSync;
+    int pipeK = 0, pipeSlots = 0, pipeJobsMax = 0;
+    int *d_pipeBoundary = nullptr, *d_pipeSync = nullptr;
 };
 
+// msa_host.hip.  n_jobs_dev == NULL: n_jobs jobs.  Otherwise n_jobs is the capacity of the buffers and the kernels read the real
+// count from *n_jobs_dev when they run.
+int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t *n_jobs_dev, const bbmsa_job *jobs,
+                     const uint8_t *reads, const uint8_t *refs, bbmsa_result *results, uint8_t *match, int32_t match_stride);
 
 // Internal (mapper_host.hip, which includes this header through mapper_ctx.h).  The mapper switches the narrow kernel off for launches it cannot help: small ones (one job per lane is a
 // ~1.5 ms dependent chain however few jobs there are, in front of the wavefront kernel on the same stream) and the final alignment

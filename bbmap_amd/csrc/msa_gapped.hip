@@ -12,13 +12,10 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cstdio>
-#include <cstring>
 
+#include "host_common.h"
 #include "msa_common.h"
 #include "msa_ctx.h"
-
-void bbmap_set_error(const char *msg);
 
 namespace bbmsa {
 
@@ -160,43 +157,29 @@ __global__ __launch_bounds__(256) void gref_post_kernel(const GappedParams P, bb
 
 }  // namespace bbmsa
 
-static thread_local char g_gerr[256];
-#define GHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { snprintf(g_gerr, sizeof g_gerr, "%s failed: %s", #expr, hipGetErrorString(e_)); bbmap_set_error(g_gerr); return BBMAP_E_HIP; } } while (0)
-
-int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t *n_jobs_dev, const bbmsa_job *jobs,
-                     const uint8_t *reads, const uint8_t *refs, bbmsa_result *results, uint8_t *match, int32_t match_stride);   // msa_host.hip
-
 static int gapped_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t *n_jobs_dev, const bbmsa_job *jobs,
                        const bbmsa_gaps *gaps, const uint8_t *reads, const uint8_t *refs,
                        bbmsa_result *results, uint8_t *match, int32_t match_stride) {
-    if (!c) { bbmap_set_error("bbmsa_align_gapped_batch_device: null context"); return BBMAP_E_ARG; }
-    if (n_jobs < 0 || n_jobs > 0x7fffffffLL) { bbmap_set_error("bbmsa_align_gapped_batch_device: n_jobs out of range"); return BBMAP_E_ARG; }
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmsa_align_gapped_batch_device: null context");
+    if (n_jobs < 0 || n_jobs > 0x7fffffffLL) return bbfail(BBMAP_E_ARG, "bbmsa_align_gapped_batch_device: n_jobs out of range");
     if (n_jobs == 0) return BBMAP_OK;
-    if (!jobs || !gaps || !reads || !refs || !results) { bbmap_set_error("bbmsa_align_gapped_batch_device: null buffer"); return BBMAP_E_ARG; }
+    if (!jobs || !gaps || !reads || !refs || !results) return bbfail(BBMAP_E_ARG, "bbmsa_align_gapped_batch_device: null buffer");
     hipStream_t stream = (hipStream_t)stream_;
-    GHIP(hipSetDevice(c->device));
+    BBHIP(hipSetDevice(c->device));
     const int glen = c->cfg.maxColumns + 2;
-    if (n_jobs > c->gappedCap) {
-        GHIP(hipStreamSynchronize(stream));
-        if (c->d_gref) { (void)hipFree(c->d_gref); c->d_gref = nullptr; }
-        if (c->d_gaux) { (void)hipFree(c->d_gaux); c->d_gaux = nullptr; }
-        if (c->d_gjobs) { (void)hipFree(c->d_gjobs); c->d_gjobs = nullptr; }
-        c->gappedCap = 0;
-        GHIP(hipMalloc(&c->d_gref, (size_t)n_jobs * (size_t)glen));
-        GHIP(hipMalloc(&c->d_gaux, (size_t)n_jobs * 16));
-        GHIP(hipMalloc(&c->d_gjobs, (size_t)n_jobs * sizeof(bbmsa_job)));
-        c->gappedCap = n_jobs;
-    }
+    BBHIP(c->gref.grow((size_t)n_jobs * (size_t)glen, 0, &stream));
+    BBHIP(c->gaux.grow((size_t)n_jobs * 16, 0, &stream));
+    BBHIP(c->gjobs.grow((size_t)n_jobs * sizeof(bbmsa_job), 0, &stream));
+    bbmsa_job *const gjobs = c->gjobs.as<bbmsa_job>();
     bbmsa::GappedParams P;
-    P.jobs = jobs; P.gaps = gaps; P.refs = refs; P.out_jobs = c->d_gjobs; P.gref = c->d_gref; P.aux = c->d_gaux;
+    P.jobs = jobs; P.gaps = gaps; P.refs = refs; P.out_jobs = gjobs; P.gref = c->gref.as<uint8_t>(); P.aux = c->gaux.as<int>();
     P.njobs = n_jobs; P.njobs_dev = n_jobs_dev; P.glen = glen; P.maxColumns = c->cfg.maxColumns;
     const unsigned blocks = (unsigned)((n_jobs + 3) / 4);                       // one wavefront per job, 4 per block
     hipLaunchKernelGGL(bbmsa::make_gref_kernel, dim3(blocks), dim3(256), 0, stream, P);
-    GHIP(hipGetLastError());
-    const int rc = bbmsa_align_impl(c, stream_, n_jobs, n_jobs_dev, c->d_gjobs, reads, refs, results, match, match_stride);
-    if (rc != BBMAP_OK) return rc;
+    BBHIP(hipGetLastError());
+    BBTRY(bbmsa_align_impl(c, stream_, n_jobs, n_jobs_dev, gjobs, reads, refs, results, match, match_stride));
     hipLaunchKernelGGL(bbmsa::gref_post_kernel, dim3(blocks), dim3(256), 0, stream, P, results);
-    GHIP(hipGetLastError());
+    BBHIP(hipGetLastError());
     return BBMAP_OK;
 }
 
@@ -209,55 +192,37 @@ extern "C" int bbmsa_align_gapped_batch_device(bbmsa_ctx *c, void *stream_, int6
 extern "C" int bbmsa_align_gapped_batch_device_indirect(bbmsa_ctx *c, void *stream_, const uint32_t *n_jobs_dev, int64_t max_jobs,
                                                         const bbmsa_job *jobs, const bbmsa_gaps *gaps, const uint8_t *reads,
                                                         const uint8_t *refs, bbmsa_result *results, uint8_t *match, int32_t match_stride) {
-    if (!n_jobs_dev) { bbmap_set_error("bbmsa_align_gapped_batch_device_indirect: null counter"); return BBMAP_E_ARG; }
+    if (!n_jobs_dev) return bbfail(BBMAP_E_ARG, "bbmsa_align_gapped_batch_device_indirect: null counter");
     return gapped_impl(c, stream_, max_jobs, n_jobs_dev, jobs, gaps, reads, refs, results, match, match_stride);
 }
 
 extern "C" int bbmsa_align_gapped_batch(bbmsa_ctx *c, int64_t n_jobs, const bbmsa_job *jobs, const bbmsa_gaps *gaps,
                                         const uint8_t *reads, int64_t reads_bytes, const uint8_t *refs, int64_t refs_bytes,
                                         bbmsa_result *results, uint8_t *match, int32_t match_stride) {
-    if (!c) { bbmap_set_error("bbmsa_align_gapped_batch: null context"); return BBMAP_E_ARG; }
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmsa_align_gapped_batch: null context");
     if (n_jobs == 0) return BBMAP_OK;
-    if (n_jobs < 0 || !jobs || !gaps || !reads || !refs || !results || reads_bytes < 0 || refs_bytes < 0) {
-        bbmap_set_error("bbmsa_align_gapped_batch: bad argument"); return BBMAP_E_ARG;
-    }
+    if (n_jobs < 0 || !jobs || !gaps || !reads || !refs || !results || reads_bytes < 0 || refs_bytes < 0)
+        return bbfail(BBMAP_E_ARG, "bbmsa_align_gapped_batch: bad argument");
     for (int64_t i = 0; i < n_jobs; i++) {
         const bbmsa_job &j = jobs[i];
         if (j.read_len < 0 || j.read_off < 0 || j.read_off + j.read_len > reads_bytes ||
-            j.ref_len < 0 || j.ref_off < 0 || j.ref_off + j.ref_len > refs_bytes) {
-            bbmap_set_error("bbmsa_align_gapped_batch: a job lies outside its buffers"); return BBMAP_E_ARG;
-        }
-        if (gaps[i].ngaps <= 0 && !(j.flags & BBMSA_CLAMP_WINDOW) && (j.refStartLoc < 0 || j.refEndLoc >= j.ref_len)) {
-            bbmap_set_error("bbmsa_align_gapped_batch: window outside its reference array"); return BBMAP_E_ARG;
-        }
+            j.ref_len < 0 || j.ref_off < 0 || j.ref_off + j.ref_len > refs_bytes)
+            return bbfail(BBMAP_E_ARG, "bbmsa_align_gapped_batch: a job lies outside its buffers");
+        if (gaps[i].ngaps <= 0 && !(j.flags & BBMSA_CLAMP_WINDOW) && (j.refStartLoc < 0 || j.refEndLoc >= j.ref_len))
+            return bbfail(BBMAP_E_ARG, "bbmsa_align_gapped_batch: window outside its reference array");
     }
-    GHIP(hipSetDevice(c->device));
-    bbmsa_job *d_jobs = nullptr; bbmsa_gaps *d_gaps = nullptr; uint8_t *d_reads = nullptr, *d_refs = nullptr, *d_match = nullptr; bbmsa_result *d_res = nullptr;
-    int rc = BBMAP_OK;
-#define GGO(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { snprintf(g_gerr, sizeof g_gerr, "%s failed: %s", #expr, hipGetErrorString(e_)); bbmap_set_error(g_gerr); rc = BBMAP_E_HIP; goto done; } } while (0)
-    GGO(hipMalloc(&d_jobs, (size_t)n_jobs * sizeof(bbmsa_job)));
-    GGO(hipMalloc(&d_gaps, (size_t)n_jobs * sizeof(bbmsa_gaps)));
-    GGO(hipMalloc(&d_reads, (size_t)(reads_bytes > 0 ? reads_bytes : 1)));
-    GGO(hipMalloc(&d_refs, (size_t)(refs_bytes > 0 ? refs_bytes : 1)));
-    GGO(hipMalloc(&d_res, (size_t)n_jobs * sizeof(bbmsa_result)));
-    if (match) GGO(hipMalloc(&d_match, (size_t)n_jobs * (size_t)match_stride));
-    GGO(hipMemcpy(d_jobs, jobs, (size_t)n_jobs * sizeof(bbmsa_job), hipMemcpyHostToDevice));
-    GGO(hipMemcpy(d_gaps, gaps, (size_t)n_jobs * sizeof(bbmsa_gaps), hipMemcpyHostToDevice));
-    GGO(hipMemcpy(d_reads, reads, (size_t)reads_bytes, hipMemcpyHostToDevice));
-    GGO(hipMemcpy(d_refs, refs, (size_t)refs_bytes, hipMemcpyHostToDevice));
-    GGO(hipMemset(d_res, 0xff, (size_t)n_jobs * sizeof(bbmsa_result)));
-    rc = bbmsa_align_gapped_batch_device(c, nullptr, n_jobs, d_jobs, d_gaps, d_reads, d_refs, d_res, d_match, match_stride);
-    if (rc != BBMAP_OK) goto done;
-    GGO(hipStreamSynchronize(nullptr));
-    GGO(hipMemcpy(results, d_res, (size_t)n_jobs * sizeof(bbmsa_result), hipMemcpyDeviceToHost));
-    if (match) GGO(hipMemcpy(match, d_match, (size_t)n_jobs * (size_t)match_stride, hipMemcpyDeviceToHost));
-done:
-    if (d_jobs) (void)hipFree(d_jobs);
-    if (d_gaps) (void)hipFree(d_gaps);
-    if (d_reads) (void)hipFree(d_reads);
-    if (d_refs) (void)hipFree(d_refs);
-    if (d_res) (void)hipFree(d_res);
-    if (d_match) (void)hipFree(d_match);
-    return rc;
-#undef GGO
+    BBHIP(hipSetDevice(c->device));
+    DevTmp<bbmsa_job> d_jobs; DevTmp<bbmsa_gaps> d_gaps; DevTmp<uint8_t> d_reads, d_refs, d_match; DevTmp<bbmsa_result> d_res;
+    BBTRY(d_jobs.upload(jobs, (size_t)n_jobs));
+    BBTRY(d_gaps.upload(gaps, (size_t)n_jobs));
+    BBTRY(d_reads.upload(reads, (size_t)reads_bytes));
+    BBTRY(d_refs.upload(refs, (size_t)refs_bytes));
+    BBTRY(d_res.alloc((size_t)n_jobs));
+    if (match) BBTRY(d_match.alloc((size_t)n_jobs * (size_t)match_stride));
+    BBHIP(hipMemset(d_res, 0xff, (size_t)n_jobs * sizeof(bbmsa_result)));
+    BBTRY(bbmsa_align_gapped_batch_device(c, nullptr, n_jobs, d_jobs, d_gaps, d_reads, d_refs, d_res, d_match, match_stride));
+    BBHIP(hipStreamSynchronize(nullptr));
+    BBHIP(hipMemcpy(results, d_res, (size_t)n_jobs * sizeof(bbmsa_result), hipMemcpyDeviceToHost));
+    if (match) BBHIP(hipMemcpy(match, d_match, (size_t)n_jobs * (size_t)match_stride, hipMemcpyDeviceToHost));
+    return BBMAP_OK;
 }

@@ -5,13 +5,11 @@
 
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <new>
 
+#include "host_common.h"
 #include "msa_common.h"
-
-int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t *n_jobs_dev, const bbmsa_job *jobs,
-                     const uint8_t *reads, const uint8_t *refs, bbmsa_result *results, uint8_t *match, int32_t match_stride);
+#include "msa_ctx.h"
 
 namespace bbmsa {
 struct StripParams {            // msa_fill_strip.hip
@@ -57,32 +55,6 @@ __global__ void width_scatter_kernel(const bbmsa_job *jobs, long long n, int max
 }
 }  // namespace bbmsa
 
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char *fmt, const char *detail = "") {
-    snprintf(g_err, sizeof g_err, fmt, detail);
-    return code;
-}
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            snprintf(g_err, sizeof g_err, "%s failed: %s", #expr, hipGetErrorString(e_));  \
-            return BBMAP_E_HIP;                                                            \
-        }                                                                                  \
-    } while (0)
-
-#include "msa_ctx.h"
-
-extern "C" const char *bbmap_last_error(void) { return g_err; }
-void bbmap_set_error(const char *msg) { snprintf(g_err, sizeof g_err, "%s", msg); }
-extern "C" int bbmap_abi_version(void) { return BBMAP_AMD_ABI_VERSION; }
-
-static int env_int(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
-}
-
 // The wavefront kernel's second geometry: 64 lanes per job, one job per 64-thread block, an LDS column buffer as wide as maxColumns.
 // It takes the windows wider than the first pass's buffer (the wide pass) and, at the caller's request, whole launches that hold
 // too few jobs to be anything but a wavefront's latency (bbmsa_set_latency_jobs).
@@ -95,13 +67,13 @@ static int setup_wide_pass(bbmsa_ctx *c) {
     c->wideLdsBytes = (bbmsa::lds_table_ints(c->wideTableLen) + perJob) * 4;
     const void *wfn = bbmsa::fast_kernel_for(c->wideR, c->banded);
     if (wfn && c->wideLdsBytes <= 160 * 1024) {
-        if (c->wideLdsBytes > 64 * 1024) HIP_TRY(hipFuncSetAttribute(wfn, hipFuncAttributeMaxDynamicSharedMemorySize, c->wideLdsBytes));
+        if (c->wideLdsBytes > 64 * 1024) BBHIP(hipFuncSetAttribute(wfn, hipFuncAttributeMaxDynamicSharedMemorySize, c->wideLdsBytes));
         int per = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, wfn, 64, c->wideLdsBytes));
+        BBHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, wfn, 64, c->wideLdsBytes));
         if (per < 1) per = 1;
         if (per > 8) per = 8;
         const long long slotDwords = (long long)(((c->wideCols + 64 - 1) >> 3) + 1) * c->wideR * 64;
-        HIP_TRY(hipMalloc(&c->d_wideDir, (size_t)((long long)c->numCUs * per * slotDwords * 4)));
+        BBHIP(hipMalloc(&c->d_wideDir, (size_t)((long long)c->numCUs * per * slotDwords * 4)));
         c->wideDirSlotDwords = slotDwords;
         c->wideBlocks = c->numCUs * per;
     }
@@ -109,28 +81,20 @@ static int setup_wide_pass(bbmsa_ctx *c) {
 }
 
 extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
-    if (!cfg || !out) return fail(BBMAP_E_ARG, "bbmsa_create: null argument");
+    if (!cfg || !out) return bbfail(BBMAP_E_ARG, "bbmsa_create: null argument");
     *out = nullptr;
     const int scheme = cfg->reserved[2] & 0xFF;
     const bool legacyOnly = (cfg->reserved[2] & BBMSA_LEGACY_ONLY) != 0;
-    if (scheme != BBMSA_SCHEME_11TS && scheme != BBMSA_SCHEME_9PACBIO) return fail(BBMAP_E_ARG, "bbmsa_create: unknown scoring scheme");
+    if (scheme != BBMSA_SCHEME_11TS && scheme != BBMSA_SCHEME_9PACBIO) return bbfail(BBMAP_E_ARG, "bbmsa_create: unknown scoring scheme");
     if (scheme == BBMSA_SCHEME_11TS && (cfg->maxRows < 1 || cfg->maxRows > 640 || cfg->maxColumns < 1 || cfg->maxColumns > 4096))
-        return fail(BBMAP_E_ARG, "bbmsa_create: maxRows must be 1..640 and maxColumns 1..4096");
+        return bbfail(BBMAP_E_ARG, "bbmsa_create: maxRows must be 1..640 and maxColumns 1..4096");
     if (scheme == BBMSA_SCHEME_9PACBIO && (cfg->maxRows < 1 || cfg->maxRows > 6100 || cfg->maxColumns < 1 || cfg->maxColumns > 8192))
-        return fail(BBMAP_E_ARG, "bbmsa_create: the PacBio scheme takes maxRows 1..6100 and maxColumns 1..8192");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(BBMAP_E_NODEVICE, "bbmsa_create: no HIP device (this library has no CPU path)");
-    if (cfg->device < 0 || cfg->device >= ndev) return fail(BBMAP_E_ARG, "bbmsa_create: bad device ordinal");
-    HIP_TRY(hipSetDevice(cfg->device));
+        return bbfail(BBMAP_E_ARG, "bbmsa_create: the PacBio scheme takes maxRows 1..6100 and maxColumns 1..8192");
     hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, cfg->device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(BBMAP_E_NODEVICE, "bbmsa_create: device is %s, this build targets gfx950 only", prop.gcnArchName);
+    BBTRY(bb_use_gfx950("bbmsa_create", cfg->device, &prop));
 
     bbmsa_ctx *c = new (std::nothrow) bbmsa_ctx();
-    if (!c) return fail(BBMAP_E_NOMEM, "bbmsa_create: out of host memory");
-    memset(c, 0, sizeof *c);
+    if (!c) return bbfail(BBMAP_E_NOMEM, "bbmsa_create: out of host memory");
     c->cfg = *cfg;
     c->device = cfg->device;
     c->numCUs = prop.multiProcessorCount;
@@ -141,14 +105,14 @@ extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
     struct Guard { bbmsa_ctx *c; ~Guard() { if (c) bbmsa_destroy(c); } } guard{c};
     if (legacyOnly) {
         // a context for bbmsa_fill_packed only (the per-call JNI shape): one scratch matrix, no batch buffers
-        HIP_TRY(hipMalloc(&c->d_counters, 64));
-        HIP_TRY(hipMemset(c->d_counters, 0, 64));
+        BBHIP(hipMalloc(&c->d_counters, 64));
+        BBHIP(hipMemset(c->d_counters, 0, 64));
         const long long planeInts = (long long)(cfg->maxRows + 1) * (cfg->maxColumns + 2);
         c->genThreads = 1;
-        HIP_TRY(hipMalloc(&c->d_matrix, (size_t)(3 * planeInts * 4)));
-        HIP_TRY(hipMalloc(&c->d_limits, (size_t)((cfg->maxRows + cfg->maxColumns + 4) * 4)));
-        for (int i = 0; i < 4; i++) HIP_TRY(hipEventCreate(&c->ev[i]));
-        { const int rc = bbmsa_legacy_create(c); if (rc != BBMAP_OK) return rc; }
+        BBHIP(hipMalloc(&c->d_matrix, (size_t)(3 * planeInts * 4)));
+        BBHIP(hipMalloc(&c->d_limits, (size_t)((cfg->maxRows + cfg->maxColumns + 4) * 4)));
+        for (int i = 0; i < 4; i++) BBHIP(hipEventCreate(&c->ev[i]));
+        BBTRY(bbmsa_legacy_create(c));
         guard.c = nullptr;
         *out = c;
         return BBMAP_OK;
@@ -156,23 +120,23 @@ extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
     if (scheme != BBMSA_SCHEME_11TS) {
         // 9PacBio: the strip-tiled wavefront kernel (msa_fill_strip.hip), one alignment per wavefront; banded fills and windows
         // narrower than the read are handed to the one-job-per-thread kernel
-        HIP_TRY(hipMalloc(&c->d_counters, 64));
-        HIP_TRY(hipMemset(c->d_counters, 0, 64));
+        BBHIP(hipMalloc(&c->d_counters, 64));
+        BBHIP(hipMemset(c->d_counters, 0, 64));
         const long long planeInts = (long long)(cfg->maxRows + 1) * (cfg->maxColumns + 2);
         const long long perThread = 3 * planeInts * 4;
         long long budget = (long long)env_int("BBMSA_GENERIC_SCRATCH_MB", 40960) << 20;   // 6019 x 7600 (mapPacBio) needs 35 GB for one wavefront of matrices
         long long threads = budget / perThread;
         if (threads > 4096) threads = 4096;
         threads = (threads / 64) * 64;
-        if (threads < 64) return fail(BBMAP_E_NOMEM, "bbmsa_create: BBMSA_GENERIC_SCRATCH_MB cannot hold one wavefront of scratch matrices for this maxRows x maxColumns");
+        if (threads < 64) return bbfail(BBMAP_E_NOMEM, "bbmsa_create: BBMSA_GENERIC_SCRATCH_MB cannot hold one wavefront of scratch matrices for this maxRows x maxColumns");
         c->genThreads = (int)threads;
-        HIP_TRY(hipMalloc(&c->d_matrix, (size_t)(threads * perThread)));
-        HIP_TRY(hipMalloc(&c->d_limits, (size_t)(threads * (cfg->maxRows + cfg->maxColumns + 4) * 4)));
+        BBHIP(hipMalloc(&c->d_matrix, (size_t)(threads * perThread)));
+        BBHIP(hipMalloc(&c->d_limits, (size_t)(threads * (cfg->maxRows + cfg->maxColumns + 4) * 4)));
         {
             const int R = bbmsa::strip_rows_per_lane();
             c->stripLds = (cfg->maxColumns + 2) * 4 + ((cfg->maxColumns + 2 + 7) & ~7);     // horizLimit ints + reference bytes
             const void *kfn = bbmsa::strip_kernel_pacbio();
-            if (c->stripLds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, c->stripLds));
+            if (c->stripLds > 64 * 1024) BBHIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, c->stripLds));
             // Resident wavefronts per CU, from the LDS a wavefront takes (160 KB per CU; the kernel holds ~128 VGPRs, up to 4 waves per
             // SIMD, so LDS is what limits it).  Not asked of hipOccupancyMaxActiveBlocksPerMultiprocessor: that query was seen to fail with
             // hipErrorUnknown depending on what the process had done before (after the CPU oracle had run in it), for reasons the
@@ -190,7 +154,7 @@ extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
             while (c->stripBlocks > 1 && (long long)c->stripBlocks * c->stripSlotDwords * 4 > dirBudget) c->stripBlocks /= 2;
             {   // the pipelined form for launches with few jobs: the strips of one job in `strips` wavefronts
                 const void *kp = bbmsa::strip_kernel_pacbio_pipelined();
-                if (c->stripLds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, c->stripLds));
+                if (c->stripLds > 64 * 1024) BBHIP(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, c->stripLds));
                 int perP = (160 * 1024) / (c->stripLds + 512);
                 if (perP < 1) perP = 1;
                 if (perP > 8) perP = 8;
@@ -201,15 +165,15 @@ extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
                 c->pipeJobsMax = env_int("BBMSA_STRIP_PIPE_JOBS", 512);      // launches with at most this many jobs take the pipelined form
                 if (strips < 2 || c->pipeSlots < 1) c->pipeJobsMax = 0;
                 if (c->pipeJobsMax > 0) {
-                    HIP_TRY(hipMalloc(&c->d_pipeBoundary, (size_t)((long long)c->pipeSlots * strips * 3 * (cfg->maxColumns + 2) * 4)));
-                    HIP_TRY(hipMalloc(&c->d_pipeSync, (size_t)((long long)c->pipeSlots * bbmsa::strip_pipe_sync_ints(strips) * 4)));
+                    BBHIP(hipMalloc(&c->d_pipeBoundary, (size_t)((long long)c->pipeSlots * strips * 3 * (cfg->maxColumns + 2) * 4)));
+                    BBHIP(hipMalloc(&c->d_pipeSync, (size_t)((long long)c->pipeSlots * bbmsa::strip_pipe_sync_ints(strips) * 4)));
                 }
             }
-            HIP_TRY(hipMalloc(&c->d_dir, (size_t)((long long)c->stripBlocks * c->stripSlotDwords * 4)));
-            HIP_TRY(hipMalloc(&c->d_stripBoundary, (size_t)((long long)c->stripBlocks * 6 * (cfg->maxColumns + 2) * 4)));
-            HIP_TRY(hipMalloc(&c->d_stripTmp, (size_t)((long long)c->stripBlocks * (cfg->maxRows + cfg->maxColumns + 8))));
+            BBHIP(hipMalloc(&c->d_dir, (size_t)((long long)c->stripBlocks * c->stripSlotDwords * 4)));
+            BBHIP(hipMalloc(&c->d_stripBoundary, (size_t)((long long)c->stripBlocks * 6 * (cfg->maxColumns + 2) * 4)));
+            BBHIP(hipMalloc(&c->d_stripTmp, (size_t)((long long)c->stripBlocks * (cfg->maxRows + cfg->maxColumns + 8))));
         }
-        for (int i = 0; i < 4; i++) HIP_TRY(hipEventCreate(&c->ev[i]));
+        for (int i = 0; i < 4; i++) BBHIP(hipEventCreate(&c->ev[i]));
         guard.c = nullptr;
         *out = c;
         return BBMAP_OK;
@@ -241,15 +205,15 @@ extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
     if (c->wideTableLen > bbmsa::kTableLen) c->wideTableLen = bbmsa::kTableLen;
     c->tableLen = (c->tableLen + 3) & ~3; c->wideTableLen = (c->wideTableLen + 3) & ~3;
     c->ldsBytes = (bbmsa::lds_table_ints(c->tableLen) + 4 * jobsPerWave * perJobInts) * 4;
-    if (c->ldsBytes > 160 * 1024) return fail(BBMAP_E_ARG, "bbmsa_create: fast-path LDS budget exceeded; lower reserved[1] (fastCols)");
+    if (c->ldsBytes > 160 * 1024) return bbfail(BBMAP_E_ARG, "bbmsa_create: fast-path LDS budget exceeded; lower reserved[1] (fastCols)");
 
     c->banded = !(cfg->bandwidth < 1 && cfg->bandwidthRatio <= 0.0f);
     const void *kfn = bbmsa::fast_kernel_for(c->R, c->banded);
-    if (!kfn) return fail(BBMAP_E_ARG, "bbmsa_create: no kernel for this rows-per-lane");
+    if (!kfn) return bbfail(BBMAP_E_ARG, "bbmsa_create: no kernel for this rows-per-lane");
     if (c->ldsBytes > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, c->ldsBytes));
+        BBHIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, c->ldsBytes));
     int blocksPerCU = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, kfn, 256, c->ldsBytes));
+    BBHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, kfn, 256, c->ldsBytes));
     if (blocksPerCU < 1) blocksPerCU = 1;
     const int capBlocks = env_int("BBMSA_BLOCKS_PER_CU", 0);
     if (capBlocks > 0 && capBlocks < blocksPerCU) blocksPerCU = capBlocks;
@@ -258,9 +222,9 @@ extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
     const int maxSteps = fastCols + G - 1;
     c->dirSlotDwords = (long long)((maxSteps >> 3) + 1) * c->R * G;
     const long long slots = (long long)c->blocks * 4 * jobsPerWave;
-    HIP_TRY(hipMalloc(&c->d_dir, (size_t)(slots * c->dirSlotDwords * 4)));
-    HIP_TRY(hipMalloc(&c->d_counters, 64));
-    HIP_TRY(hipMemset(c->d_counters, 0, 64));
+    BBHIP(hipMalloc(&c->d_dir, (size_t)(slots * c->dirSlotDwords * 4)));
+    BBHIP(hipMalloc(&c->d_counters, 64));
+    BBHIP(hipMemset(c->d_counters, 0, 64));
 
     // generic kernel scratch: as many threads as a 2 GiB matrix budget allows (at least one wave)
     const long long planeInts = (long long)(cfg->maxRows + 1) * (cfg->maxColumns + 2);
@@ -269,29 +233,26 @@ extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
     long long threads = budget / perThread;
     if (threads > 16384) threads = 16384;
     threads = (threads / 64) * 64;
-    if (threads < 64) return fail(BBMAP_E_NOMEM, "bbmsa_create: BBMSA_GENERIC_SCRATCH_MB cannot hold one wavefront of scratch matrices for this maxRows x maxColumns");
+    if (threads < 64) return bbfail(BBMAP_E_NOMEM, "bbmsa_create: BBMSA_GENERIC_SCRATCH_MB cannot hold one wavefront of scratch matrices for this maxRows x maxColumns");
     c->genThreads = (int)threads;
-    HIP_TRY(hipMalloc(&c->d_matrix, (size_t)(threads * perThread)));
-    HIP_TRY(hipMalloc(&c->d_limits, (size_t)(threads * (cfg->maxRows + cfg->maxColumns + 4) * 4)));
+    BBHIP(hipMalloc(&c->d_matrix, (size_t)(threads * perThread)));
+    BBHIP(hipMalloc(&c->d_limits, (size_t)(threads * (cfg->maxRows + cfg->maxColumns + 4) * 4)));
     // wide pass geometry (only when some windows can exceed the first pass's column buffer)
-    c->wideBlocks = 0; c->latencyJobs = 0;
-    if (cfg->maxColumns > fastCols) { const int rc = setup_wide_pass(c); if (rc != BBMAP_OK) return rc; }
+    if (cfg->maxColumns > fastCols) BBTRY(setup_wide_pass(c));
     // narrow-window kernel: only without a band (a band changes the window rule); BBMSA_NARROW=0 disables it
-    c->narrowBlocks = 0; c->narrowOff = false; c->narrowUsed = false;
-    c->sortByWidth = false; c->d_widthHist = nullptr;
     c->narrowSlack = env_int("BBMSA_NARROW_SLACK", 2000);
     if (!c->banded && env_int("BBMSA_NARROW", 1) != 0) {
         int perCU = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (const void *)bbmsa::msa_fill_narrow_kernel, 64, 0));
+        BBHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (const void *)bbmsa::msa_fill_narrow_kernel, 64, 0));
         if (perCU < 1) perCU = 1;
         if (perCU > 16) perCU = 16;
         c->narrowBlocks = c->numCUs * perCU;
-        HIP_TRY(hipMalloc(&c->d_narrowDir, (size_t)c->narrowBlocks * (size_t)(cfg->maxRows + 1) * 64 * 8));
+        BBHIP(hipMalloc(&c->d_narrowDir, (size_t)c->narrowBlocks * (size_t)(cfg->maxRows + 1) * 64 * 8));
     }
     // route switches of the environment (msa_ctx.h): defaults off, as the functions they mirror leave a context
     c->sortByWidth = env_int("BBMSA_SORT_BY_WIDTH", 0) != 0;
-    { const int lat = env_int("BBMSA_LATENCY_JOBS", 0); if (lat > 0) { const int rc = bbmsa_set_latency_jobs(c, lat); if (rc != BBMAP_OK) return rc; } }
-    for (int i = 0; i < 4; i++) HIP_TRY(hipEventCreate(&c->ev[i]));
+    { const int lat = env_int("BBMSA_LATENCY_JOBS", 0); if (lat > 0) BBTRY(bbmsa_set_latency_jobs(c, lat)); }
+    for (int i = 0; i < 4; i++) BBHIP(hipEventCreate(&c->ev[i]));
     guard.c = nullptr;
     *out = c;
     return BBMAP_OK;
@@ -304,17 +265,11 @@ extern "C" void bbmsa_destroy(bbmsa_ctx *c) {
     if (c->d_dir) (void)hipFree(c->d_dir);
     if (c->d_counters) (void)hipFree(c->d_counters);
     if (c->d_widthHist) (void)hipFree(c->d_widthHist);
-
-    if (c->d_slowList) (void)hipFree(c->d_slowList);
+    for (DevBuf *b : {&c->slowList, &c->slowList2, &c->fastList, &c->gref, &c->gaux, &c->gjobs}) b->release();
     if (c->d_matrix) (void)hipFree(c->d_matrix);
     if (c->d_limits) (void)hipFree(c->d_limits);
     if (c->d_wideDir) (void)hipFree(c->d_wideDir);
-    if (c->d_slowList2) (void)hipFree(c->d_slowList2);
     if (c->d_narrowDir) (void)hipFree(c->d_narrowDir);
-    if (c->d_fastList) (void)hipFree(c->d_fastList);
-    if (c->d_gref) (void)hipFree(c->d_gref);
-    if (c->d_gaux) (void)hipFree(c->d_gaux);
-    if (c->d_gjobs) (void)hipFree(c->d_gjobs);
     if (c->d_stripBoundary) (void)hipFree(c->d_stripBoundary);
     if (c->d_stripTmp) (void)hipFree(c->d_stripTmp);
     if (c->d_pipeBoundary) (void)hipFree(c->d_pipeBoundary);
@@ -332,39 +287,60 @@ extern "C" int bbmsa_align_batch_device(bbmsa_ctx *c, void *stream_, int64_t n_j
 extern "C" int bbmsa_align_batch_device_indirect(bbmsa_ctx *c, void *stream_, const uint32_t *n_jobs_dev, int64_t max_jobs,
                                                  const bbmsa_job *jobs, const uint8_t *reads, const uint8_t *refs,
                                                  bbmsa_result *results, uint8_t *match, int32_t match_stride) {
-    if (!n_jobs_dev) return fail(BBMAP_E_ARG, "bbmsa_align_batch_device_indirect: null counter");
+    if (!n_jobs_dev) return bbfail(BBMAP_E_ARG, "bbmsa_align_batch_device_indirect: null counter");
     return bbmsa_align_impl(c, stream_, max_jobs, n_jobs_dev, jobs, reads, refs, results, match, match_stride);
 }
 
-// n_jobs_dev == NULL: n_jobs jobs.  Otherwise n_jobs is the capacity of the buffers and the kernels read the real count
-// from *n_jobs_dev when they run.
+namespace {
+// the caller's arguments of one launch
+struct Batch {
+    int64_t n_jobs; const uint32_t *n_jobs_dev; const bbmsa_job *jobs; const uint8_t *reads, *refs; bbmsa_result *results; uint8_t *match;
+    int32_t match_stride;
+};
+// what every kernel's parameter struct takes from the batch and the context
+template <class P> void set_batch(P &p, const bbmsa_ctx *c, const Batch &B) {
+    p.jobs = B.jobs; p.reads = B.reads; p.refs = B.refs; p.results = B.results; p.match = B.match;
+    p.njobs = B.n_jobs; p.njobs_dev = B.n_jobs_dev; p.match_stride = B.match_stride;
+    p.maxRows = c->cfg.maxRows; p.maxColumns = c->cfg.maxColumns; p.bandwidth = c->cfg.bandwidth; p.bandwidthRatio = c->cfg.bandwidthRatio;
+}
+// the last kernel of every launch: the one-job-per-thread kernel over the jobs the passes before it handed on
+template <class S> int launch_generic(bbmsa_ctx *c, const Batch &B, hipStream_t stream, const int *list, const unsigned int *count) {
+    bbmsa::GenericParams gp;
+    set_batch(gp, c, B);
+    gp.list = list; gp.list_count = count;
+    gp.matrix = c->d_matrix; gp.limits = c->d_limits; gp.queue = c->d_counters + 2;
+    hipLaunchKernelGGL(bbmsa::msa_fill_generic_kernel<S>, dim3(c->genThreads / 64), dim3(64), 0, stream, gp);
+    BBHIP(hipGetLastError());
+    BBHIP(hipEventRecord(c->ev[2], stream));
+    c->timed = true;
+    return BBMAP_OK;
+}
+}  // namespace
+
 int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t *n_jobs_dev,
                      const bbmsa_job *jobs, const uint8_t *reads, const uint8_t *refs,
                      bbmsa_result *results, uint8_t *match, int32_t match_stride) {
-    if (!c) return fail(BBMAP_E_ARG, "bbmsa_align_batch_device: null context");
-    if (n_jobs < 0 || n_jobs > 0x7fffffffLL) return fail(BBMAP_E_ARG, "bbmsa_align_batch_device: n_jobs out of range");
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmsa_align_batch_device: null context");
+    if (n_jobs < 0 || n_jobs > 0x7fffffffLL) return bbfail(BBMAP_E_ARG, "bbmsa_align_batch_device: n_jobs out of range");
     if (n_jobs == 0) return BBMAP_OK;
-    if (!jobs || !reads || !refs || !results) return fail(BBMAP_E_ARG, "bbmsa_align_batch_device: null buffer");
-    if (match && match_stride < 1) return fail(BBMAP_E_ARG, "bbmsa_align_batch_device: match_stride must be positive");
+    if (!jobs || !reads || !refs || !results) return bbfail(BBMAP_E_ARG, "bbmsa_align_batch_device: null buffer");
+    if (match && match_stride < 1) return bbfail(BBMAP_E_ARG, "bbmsa_align_batch_device: match_stride must be positive");
     hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->legacyOnly) return fail(BBMAP_E_ARG, "bbmsa_align_batch_device: this context was created for bbmsa_fill_packed only (BBMSA_LEGACY_ONLY)");
+    BBHIP(hipSetDevice(c->device));
+    if (c->legacyOnly) return bbfail(BBMAP_E_ARG, "bbmsa_align_batch_device: this context was created for bbmsa_fill_packed only (BBMSA_LEGACY_ONLY)");
+    const Batch B = {n_jobs, n_jobs_dev, jobs, reads, refs, results, match, match_stride};
+    const size_t listBytes = (size_t)n_jobs * 4;
+    BBHIP(c->slowList.grow(listBytes, 0, &stream));
+    int *const slowList = c->slowList.as<int>();
     if (c->scheme != BBMSA_SCHEME_11TS) {
-        if (n_jobs > c->slowCap) {
-            if (c->d_slowList) { HIP_TRY(hipStreamSynchronize(stream)); HIP_TRY(hipFree(c->d_slowList)); c->d_slowList = nullptr; }
-            HIP_TRY(hipMalloc(&c->d_slowList, (size_t)n_jobs * 4));
-            c->slowCap = n_jobs;
-        }
-        HIP_TRY(hipMemsetAsync(c->d_counters, 0, 64, stream));
+        BBHIP(hipMemsetAsync(c->d_counters, 0, 64, stream));
         c->narrowUsed = false; c->lastSorted = false; c->lastLatency = false; c->lastIndirect = n_jobs_dev != nullptr;
-        HIP_TRY(hipEventRecord(c->ev[0], stream));
-        HIP_TRY(hipEventRecord(c->ev[3], stream));
+        BBHIP(hipEventRecord(c->ev[0], stream));
+        BBHIP(hipEventRecord(c->ev[3], stream));
         bbmsa::StripParams sp;
-        sp.jobs = jobs; sp.reads = reads; sp.refs = refs; sp.results = results; sp.match = match; sp.njobs = n_jobs; sp.njobs_dev = n_jobs_dev;
+        set_batch(sp, c, B);
         sp.queue = c->d_counters; sp.dirbuf = c->d_dir; sp.dir_slot_dwords = c->stripSlotDwords; sp.dir_strip_dwords = c->stripDwords;
-        sp.boundary = c->d_stripBoundary; sp.tmpbuf = c->d_stripTmp; sp.slow_list = c->d_slowList; sp.slow_count = c->d_counters + 1;
-        sp.match_stride = match_stride; sp.maxRows = c->cfg.maxRows; sp.maxColumns = c->cfg.maxColumns;
-        sp.bandwidth = c->cfg.bandwidth; sp.bandwidthRatio = c->cfg.bandwidthRatio;
+        sp.boundary = c->d_stripBoundary; sp.tmpbuf = c->d_stripTmp; sp.slow_list = slowList; sp.slow_count = c->d_counters + 1;
         long long sblocks = n_jobs < c->stripBlocks ? n_jobs : c->stripBlocks;
         sp.pipeK = 0; sp.pipeSlots = 0; sp.pipeBoundary = nullptr; sp.pipeSync = nullptr;
         sp.pipeSpinLimit = env_int("BBMSA_PIPE_SPIN_LIMIT", 1 << 21);          // polls before a wave of the pipelined form gives up (~3 s; tests force timeouts)
@@ -375,74 +351,50 @@ int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t
             // with its strips pipelined over `pipeK` wavefronts it is ~50
             const long long slots = n_jobs < c->pipeSlots ? n_jobs : c->pipeSlots;
             sp.pipeK = c->pipeK; sp.pipeSlots = (int)slots; sp.pipeBoundary = c->d_pipeBoundary; sp.pipeSync = c->d_pipeSync;
-            HIP_TRY(hipMemsetAsync(c->d_pipeSync, 0, (size_t)(slots * bbmsa::strip_pipe_sync_ints(c->pipeK) * 4), stream));
-            HIP_TRY(hipLaunchKernel(bbmsa::strip_kernel_pacbio_pipelined(), dim3((unsigned)(slots * c->pipeK)), dim3(64), sargs, (size_t)c->stripLds, stream));
+            BBHIP(hipMemsetAsync(c->d_pipeSync, 0, (size_t)(slots * bbmsa::strip_pipe_sync_ints(c->pipeK) * 4), stream));
+            BBHIP(hipLaunchKernel(bbmsa::strip_kernel_pacbio_pipelined(), dim3((unsigned)(slots * c->pipeK)), dim3(64), sargs, (size_t)c->stripLds, stream));
         } else
-        HIP_TRY(hipLaunchKernel(bbmsa::strip_kernel_pacbio(), dim3((unsigned)sblocks), dim3(64), sargs, (size_t)c->stripLds, stream));
-        HIP_TRY(hipEventRecord(c->ev[1], stream));
-        bbmsa::GenericParams gp;
-        gp.jobs = jobs; gp.reads = reads; gp.refs = refs; gp.results = results; gp.match = match;
-        gp.list = c->d_slowList; gp.list_count = c->d_counters + 1; gp.njobs = n_jobs; gp.njobs_dev = n_jobs_dev;
-        gp.matrix = c->d_matrix; gp.limits = c->d_limits; gp.queue = c->d_counters + 2;
-        gp.match_stride = match_stride; gp.maxRows = c->cfg.maxRows; gp.maxColumns = c->cfg.maxColumns;
-        gp.bandwidth = c->cfg.bandwidth; gp.bandwidthRatio = c->cfg.bandwidthRatio;
-        hipLaunchKernelGGL(bbmsa::msa_fill_generic_kernel<bbmsa::Scheme9PacBio>, dim3(c->genThreads / 64), dim3(64), 0, stream, gp);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->ev[2], stream));
-        c->timed = true;
-        return BBMAP_OK;
+        BBHIP(hipLaunchKernel(bbmsa::strip_kernel_pacbio(), dim3((unsigned)sblocks), dim3(64), sargs, (size_t)c->stripLds, stream));
+        BBHIP(hipEventRecord(c->ev[1], stream));
+        return launch_generic<bbmsa::Scheme9PacBio>(c, B, stream, slowList, c->d_counters + 1);
     }
-    if (n_jobs > c->slowCap) {
-        if (c->d_slowList) { HIP_TRY(hipStreamSynchronize(stream)); HIP_TRY(hipFree(c->d_slowList)); c->d_slowList = nullptr; }
-        if (c->d_slowList2) { HIP_TRY(hipFree(c->d_slowList2)); c->d_slowList2 = nullptr; }
-        HIP_TRY(hipMalloc(&c->d_slowList, (size_t)n_jobs * 4));
-        if (c->wideBlocks > 0) HIP_TRY(hipMalloc(&c->d_slowList2, (size_t)n_jobs * 4));
-        c->slowCap = n_jobs;
-    }
+    if (c->wideBlocks > 0) BBHIP(c->slowList2.grow(listBytes, 0, &stream));
     const bool sortJobs = c->sortByWidth && !n_jobs_dev && n_jobs >= 256 && n_jobs > c->latencyJobs && !(c->narrowBlocks > 0 && !c->narrowOff);
-    if ((c->narrowBlocks > 0 || sortJobs) && n_jobs > c->fastCap) {
-        if (c->d_fastList) { HIP_TRY(hipStreamSynchronize(stream)); HIP_TRY(hipFree(c->d_fastList)); c->d_fastList = nullptr; }
-        HIP_TRY(hipMalloc(&c->d_fastList, (size_t)n_jobs * 4));
-        c->fastCap = n_jobs;
-    }
+    if (c->narrowBlocks > 0 || sortJobs) BBHIP(c->fastList.grow(listBytes, 0, &stream));
+    int *const fastList = c->fastList.as<int>();
     // counters: [0] fast queue, [1] slow count, [2] generic queue, [3] narrow queue, [4] fast-list count,
     //           [5] jobs finished by the narrow kernel, [6] candidates it handed on
-    HIP_TRY(hipMemsetAsync(c->d_counters, 0, 64, stream));
-    HIP_TRY(hipEventRecord(c->ev[0], stream));
+    BBHIP(hipMemsetAsync(c->d_counters, 0, 64, stream));
+    BBHIP(hipEventRecord(c->ev[0], stream));
     const bool useNarrow = c->narrowBlocks > 0 && !c->narrowOff;
     c->narrowUsed = useNarrow;
     if (useNarrow) {
         bbmsa::NarrowParams np;
-        np.jobs = jobs; np.reads = reads; np.refs = refs; np.results = results; np.match = match; np.njobs = n_jobs; np.njobs_dev = n_jobs_dev;
-        np.queue = c->d_counters + 3; np.fast_list = c->d_fastList; np.fast_count = c->d_counters + 4;
-        np.dirbuf = c->d_narrowDir; np.stats = c->d_counters + 5;
-        np.match_stride = match_stride; np.maxRows = c->cfg.maxRows; np.maxColumns = c->cfg.maxColumns;
-        np.bandwidth = c->cfg.bandwidth; np.bandwidthRatio = c->cfg.bandwidthRatio; np.maxSlack = c->narrowSlack;
+        set_batch(np, c, B);
+        np.queue = c->d_counters + 3; np.fast_list = fastList; np.fast_count = c->d_counters + 4;
+        np.dirbuf = c->d_narrowDir; np.stats = c->d_counters + 5; np.maxSlack = c->narrowSlack;
         long long nb = (n_jobs + 63) / 64;
         if (nb > c->narrowBlocks) nb = c->narrowBlocks;
         hipLaunchKernelGGL(bbmsa::msa_fill_narrow_kernel, dim3((unsigned)nb), dim3(64), 0, stream, np);
-        HIP_TRY(hipGetLastError());
+        BBHIP(hipGetLastError());
     }
     if (sortJobs) {                    // (never together with the narrow kernel: both write the wavefront kernel's list)
-        if (!c->d_widthHist) HIP_TRY(hipMalloc(&c->d_widthHist, bbmsa::WIDTH_BUCKETS * 4));
-        HIP_TRY(hipMemsetAsync(c->d_widthHist, 0, bbmsa::WIDTH_BUCKETS * 4, stream));
+        if (!c->d_widthHist) BBHIP(hipMalloc(&c->d_widthHist, bbmsa::WIDTH_BUCKETS * 4));
+        BBHIP(hipMemsetAsync(c->d_widthHist, 0, bbmsa::WIDTH_BUCKETS * 4, stream));
         const unsigned sb = (unsigned)((n_jobs + 255) / 256);
         hipLaunchKernelGGL(bbmsa::width_hist_kernel, dim3(sb), dim3(256), 0, stream, jobs, (long long)n_jobs, c->cfg.maxColumns, c->d_widthHist);
         hipLaunchKernelGGL(bbmsa::width_scan_kernel, dim3(1), dim3(bbmsa::WIDTH_BUCKETS), 0, stream, c->d_widthHist, c->d_counters + 4, (unsigned)n_jobs);
-        hipLaunchKernelGGL(bbmsa::width_scatter_kernel, dim3(sb), dim3(256), 0, stream, jobs, (long long)n_jobs, c->cfg.maxColumns, c->d_widthHist, c->d_fastList);
-        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(bbmsa::width_scatter_kernel, dim3(sb), dim3(256), 0, stream, jobs, (long long)n_jobs, c->cfg.maxColumns, c->d_widthHist, fastList);
+        BBHIP(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(c->ev[3], stream));
+    BBHIP(hipEventRecord(c->ev[3], stream));
 
-    bbmsa::FillParams fp;
-    fp.jobs = jobs; fp.reads = reads; fp.refs = refs; fp.results = results; fp.match = match;
-    fp.njobs = n_jobs; fp.njobs_dev = n_jobs_dev;
+    bbmsa::FillParams fp = {};
+    set_batch(fp, c, B);
     fp.queue = c->d_counters; fp.dirbuf = c->d_dir; fp.dir_slot_dwords = c->dirSlotDwords;
-    fp.list = (useNarrow || sortJobs) ? c->d_fastList : nullptr; fp.list_count = c->d_counters + 4; fp.priority = 0;
-    fp.slow_list = c->d_slowList; fp.slow_count = c->d_counters + 1;
-    fp.match_stride = match_stride; fp.lanesPerJob = c->G; fp.fastCols = c->fastCols; fp.tmpBytes = c->tmpBytes; fp.tableLen = c->tableLen;
-    fp.maxRows = c->cfg.maxRows; fp.maxColumns = c->cfg.maxColumns;
-    fp.bandwidth = c->cfg.bandwidth; fp.bandwidthRatio = c->cfg.bandwidthRatio;
+    fp.list = (useNarrow || sortJobs) ? fastList : nullptr; fp.list_count = c->d_counters + 4; fp.priority = 0;
+    fp.slow_list = slowList; fp.slow_count = c->d_counters + 1;
+    fp.lanesPerJob = c->G; fp.fastCols = c->fastCols; fp.tmpBytes = c->tmpBytes; fp.tableLen = c->tableLen;
 
     // A launch with few jobs is a wavefront's latency, not throughput: (columns + lanes - 1) steps of one dependent chain.  The wide
     // pass's geometry (64 lanes x 3 rows, one job per block) has the shorter chain per step (3 rows instead of 5: ~450 instead of
@@ -454,84 +406,73 @@ int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t
     if (blocks > c->blocks) blocks = c->blocks;
     void *args[] = {&fp};
     if (!latency)
-        HIP_TRY(hipLaunchKernel(bbmsa::fast_kernel_for(c->R, c->banded), dim3((unsigned)blocks), dim3(256), args, (size_t)c->ldsBytes, stream));
-    const int *genList = c->d_slowList;
+        BBHIP(hipLaunchKernel(bbmsa::fast_kernel_for(c->R, c->banded), dim3((unsigned)blocks), dim3(256), args, (size_t)c->ldsBytes, stream));
+    const int *genList = slowList;
     const unsigned int *genCount = c->d_counters + 1;
     if (c->wideBlocks > 0) {
         // wide pass over the first pass's hand-overs; what it cannot take either (banded rows with holes) goes on to the
         // generic kernel through the second list ([7] = its count, [8] = wide queue)
         bbmsa::FillParams wp = fp;
         wp.queue = c->d_counters + 8; wp.dirbuf = c->d_wideDir; wp.dir_slot_dwords = c->wideDirSlotDwords;
-        wp.list = c->d_slowList; wp.list_count = c->d_counters + 1;
+        wp.list = slowList; wp.list_count = c->d_counters + 1;
         if (latency) { wp.list = nullptr; wp.list_count = nullptr; }          // every job of the launch
-        wp.slow_list = c->d_slowList2; wp.slow_count = c->d_counters + 7;
+        wp.slow_list = c->slowList2.as<int>(); wp.slow_count = c->d_counters + 7;
         wp.lanesPerJob = 64; wp.fastCols = c->wideCols; wp.tmpBytes = c->wideTmpBytes; wp.tableLen = c->wideTableLen;
         static const int widePrio = env_int("BBMSA_WIDE_PRIORITY", 2);
         wp.priority = widePrio;
         void *wargs[] = {&wp};
         const long long wblocks = latency && n_jobs < c->wideBlocks ? n_jobs : c->wideBlocks;
-        HIP_TRY(hipLaunchKernel(bbmsa::fast_kernel_for(c->wideR, c->banded), dim3((unsigned)wblocks), dim3(64), wargs, (size_t)c->wideLdsBytes, stream));
-        genList = c->d_slowList2; genCount = c->d_counters + 7;
+        BBHIP(hipLaunchKernel(bbmsa::fast_kernel_for(c->wideR, c->banded), dim3((unsigned)wblocks), dim3(64), wargs, (size_t)c->wideLdsBytes, stream));
+        genList = wp.slow_list; genCount = c->d_counters + 7;
     }
-    HIP_TRY(hipEventRecord(c->ev[1], stream));
-
-    bbmsa::GenericParams gp;
-    gp.jobs = jobs; gp.reads = reads; gp.refs = refs; gp.results = results; gp.match = match;
-    gp.list = genList; gp.list_count = genCount; gp.njobs = n_jobs; gp.njobs_dev = n_jobs_dev;
-    gp.matrix = c->d_matrix; gp.limits = c->d_limits; gp.queue = c->d_counters + 2;
-    gp.match_stride = match_stride; gp.maxRows = c->cfg.maxRows; gp.maxColumns = c->cfg.maxColumns;
-    gp.bandwidth = c->cfg.bandwidth; gp.bandwidthRatio = c->cfg.bandwidthRatio;
-    hipLaunchKernelGGL(bbmsa::msa_fill_generic_kernel<bbmsa::Scheme11ts>, dim3(c->genThreads / 64), dim3(64), 0, stream, gp);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev[2], stream));
-    c->timed = true;
-    return BBMAP_OK;
+    BBHIP(hipEventRecord(c->ev[1], stream));
+    return launch_generic<bbmsa::Scheme11ts>(c, B, stream, genList, genCount);
 }
 
 void bbmsa_use_narrow(bbmsa_ctx *c, bool on) { if (c) c->narrowOff = !on; }
 void bbmsa_sort_by_width(bbmsa_ctx *c, bool on) { if (c) c->sortByWidth = on; }
 int bbmsa_set_latency_jobs(bbmsa_ctx *c, int64_t n) {
     if (!c || c->scheme != BBMSA_SCHEME_11TS || c->legacyOnly) return BBMAP_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    if (n > 0) { const int rc = setup_wide_pass(c); if (rc != BBMAP_OK) return rc; }
-    if (n > 0 && c->slowCap > 0 && !c->d_slowList2) HIP_TRY(hipMalloc(&c->d_slowList2, (size_t)c->slowCap * 4));   // (its hand-over list)
+    BBHIP(hipSetDevice(c->device));
+    if (n > 0) BBTRY(setup_wide_pass(c));
+    if (n > 0 && !c->slowList2.p) BBHIP(c->slowList2.grow(c->slowList.cap));   // (its hand-over list, late: as long as the first)
     c->latencyJobs = c->wideBlocks > 0 ? n : 0;
     return BBMAP_OK;
 }
 int bbmsa_wait_first_pass(bbmsa_ctx *c, void *waiter) {
     if (!c || !c->timed) return BBMAP_OK;
-    HIP_TRY(hipStreamWaitEvent((hipStream_t)waiter, c->ev[3], 0));       // recorded right in front of the last launch's first pass
+    BBHIP(hipStreamWaitEvent((hipStream_t)waiter, c->ev[3], 0));       // recorded right in front of the last launch's first pass
     return BBMAP_OK;
 }
 
 extern "C" int bbmsa_last_kernel_ms(bbmsa_ctx *c, float *ms_fast, float *ms_slow) {
-    if (!c || !c->timed) return fail(BBMAP_E_ARG, "bbmsa_last_kernel_ms: nothing launched yet");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventSynchronize(c->ev[2]));
+    if (!c || !c->timed) return bbfail(BBMAP_E_ARG, "bbmsa_last_kernel_ms: nothing launched yet");
+    BBHIP(hipSetDevice(c->device));
+    BBHIP(hipEventSynchronize(c->ev[2]));
     float a = 0, b = 0;
-    HIP_TRY(hipEventElapsedTime(&a, c->ev[0], c->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&b, c->ev[1], c->ev[2]));
+    BBHIP(hipEventElapsedTime(&a, c->ev[0], c->ev[1]));
+    BBHIP(hipEventElapsedTime(&b, c->ev[1], c->ev[2]));
     if (ms_fast) *ms_fast = a;
     if (ms_slow) *ms_slow = b;
     return BBMAP_OK;
 }
 
 extern "C" int bbmsa_last_kernel_ms3(bbmsa_ctx *c, float *ms3) {
-    if (!c || !c->timed || !ms3) return fail(BBMAP_E_ARG, "bbmsa_last_kernel_ms3: nothing launched yet");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventSynchronize(c->ev[2]));
-    HIP_TRY(hipEventElapsedTime(&ms3[0], c->ev[0], c->ev[3]));
-    HIP_TRY(hipEventElapsedTime(&ms3[1], c->ev[3], c->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&ms3[2], c->ev[1], c->ev[2]));
+    if (!c || !c->timed || !ms3) return bbfail(BBMAP_E_ARG, "bbmsa_last_kernel_ms3: nothing launched yet");
+    BBHIP(hipSetDevice(c->device));
+    BBHIP(hipEventSynchronize(c->ev[2]));
+    BBHIP(hipEventElapsedTime(&ms3[0], c->ev[0], c->ev[3]));
+    BBHIP(hipEventElapsedTime(&ms3[1], c->ev[3], c->ev[1]));
+    BBHIP(hipEventElapsedTime(&ms3[2], c->ev[1], c->ev[2]));
     return BBMAP_OK;
 }
 
 extern "C" int bbmsa_last_counts(bbmsa_ctx *c, int64_t *counts4) {
-    if (!c || !c->timed || !counts4) return fail(BBMAP_E_ARG, "bbmsa_last_counts: nothing launched yet");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventSynchronize(c->ev[2]));
+    if (!c || !c->timed || !counts4) return bbfail(BBMAP_E_ARG, "bbmsa_last_counts: nothing launched yet");
+    BBHIP(hipSetDevice(c->device));
+    BBHIP(hipEventSynchronize(c->ev[2]));
     unsigned h[16];
-    HIP_TRY(hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
+    BBHIP(hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
     counts4[0] = h[5]; counts4[1] = h[6]; counts4[2] = c->narrowUsed ? h[4] : 0; counts4[3] = c->wideBlocks > 0 ? h[7] : h[1];
     if (getenv("BBMAP_DP_COUNTS") && c->wideBlocks > 0) fprintf(stderr, "   (first pass handed %u jobs to the wide pass)\n", h[1]);
     return BBMAP_OK;
@@ -543,11 +484,11 @@ int bbmsa_last_route_flags(const bbmsa_ctx *c) {
 }
 
 extern "C" int bbmsa_last_route(bbmsa_ctx *c, int64_t *route8) {
-    if (!c || !c->timed || !route8) return fail(BBMAP_E_ARG, "bbmsa_last_route: nothing launched yet");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventSynchronize(c->ev[2]));
+    if (!c || !c->timed || !route8) return bbfail(BBMAP_E_ARG, "bbmsa_last_route: nothing launched yet");
+    BBHIP(hipSetDevice(c->device));
+    BBHIP(hipEventSynchronize(c->ev[2]));
     unsigned h[16];
-    HIP_TRY(hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
+    BBHIP(hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
     const bool wide = c->scheme == BBMSA_SCHEME_11TS && c->wideBlocks > 0;
     route8[0] = c->narrowUsed; route8[1] = c->lastSorted; route8[2] = c->lastLatency; route8[3] = wide; route8[4] = c->lastIndirect;
     route8[5] = h[1]; route8[6] = wide ? h[7] : 0; route8[7] = c->narrowUsed ? h[5] : 0;
@@ -558,44 +499,31 @@ extern "C" int bbmsa_align_batch(bbmsa_ctx *c, int64_t n_jobs, const bbmsa_job *
                                  const uint8_t *reads, int64_t reads_bytes,
                                  const uint8_t *refs, int64_t refs_bytes,
                                  bbmsa_result *results, uint8_t *match, int32_t match_stride) {
-    if (!c) return fail(BBMAP_E_ARG, "bbmsa_align_batch: null context");
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmsa_align_batch: null context");
     if (n_jobs == 0) return BBMAP_OK;
     if (n_jobs < 0 || !jobs || !reads || !refs || !results || reads_bytes < 0 || refs_bytes < 0)
-        return fail(BBMAP_E_ARG, "bbmsa_align_batch: bad argument");
-    HIP_TRY(hipSetDevice(c->device));
+        return bbfail(BBMAP_E_ARG, "bbmsa_align_batch: bad argument");
+    BBHIP(hipSetDevice(c->device));
     // every job must stay inside the buffers it was given
     for (int64_t i = 0; i < n_jobs; i++) {
         const bbmsa_job &j = jobs[i];
         if (j.read_len < 0 || j.read_off < 0 || j.read_off + j.read_len > reads_bytes)
-            return fail(BBMAP_E_ARG, "bbmsa_align_batch: a read lies outside the reads buffer");
+            return bbfail(BBMAP_E_ARG, "bbmsa_align_batch: a read lies outside the reads buffer");
         if (j.ref_len < 0 || j.ref_off < 0 || j.ref_off + j.ref_len > refs_bytes)
-            return fail(BBMAP_E_ARG, "bbmsa_align_batch: a reference array lies outside the refs buffer");
+            return bbfail(BBMAP_E_ARG, "bbmsa_align_batch: a reference array lies outside the refs buffer");
         if (!(j.flags & BBMSA_CLAMP_WINDOW) && (j.refStartLoc < 0 || j.refEndLoc >= j.ref_len))
-            return fail(BBMAP_E_ARG, "bbmsa_align_batch: window outside its reference array (set BBMSA_CLAMP_WINDOW to clamp)");
+            return bbfail(BBMAP_E_ARG, "bbmsa_align_batch: window outside its reference array (set BBMSA_CLAMP_WINDOW to clamp)");
     }
-    bbmsa_job *d_jobs = nullptr; uint8_t *d_reads = nullptr, *d_refs = nullptr, *d_match = nullptr; bbmsa_result *d_res = nullptr;
-    int rc = BBMAP_OK;
-#define TRY_GOTO(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { snprintf(g_err, sizeof g_err, "%s failed: %s", #expr, hipGetErrorString(e_)); rc = BBMAP_E_HIP; goto done; } } while (0)
-    TRY_GOTO(hipMalloc(&d_jobs, (size_t)n_jobs * sizeof(bbmsa_job)));
-    TRY_GOTO(hipMalloc(&d_reads, (size_t)(reads_bytes > 0 ? reads_bytes : 1)));
-    TRY_GOTO(hipMalloc(&d_refs, (size_t)(refs_bytes > 0 ? refs_bytes : 1)));
-    TRY_GOTO(hipMalloc(&d_res, (size_t)n_jobs * sizeof(bbmsa_result)));
-    if (match) TRY_GOTO(hipMalloc(&d_match, (size_t)n_jobs * (size_t)match_stride));
-    TRY_GOTO(hipMemcpy(d_jobs, jobs, (size_t)n_jobs * sizeof(bbmsa_job), hipMemcpyHostToDevice));
-    TRY_GOTO(hipMemcpy(d_reads, reads, (size_t)reads_bytes, hipMemcpyHostToDevice));
-    TRY_GOTO(hipMemcpy(d_refs, refs, (size_t)refs_bytes, hipMemcpyHostToDevice));
-    TRY_GOTO(hipMemset(d_res, 0xff, (size_t)n_jobs * sizeof(bbmsa_result)));
-    rc = bbmsa_align_batch_device(c, nullptr, n_jobs, d_jobs, d_reads, d_refs, d_res, d_match, match_stride);
-    if (rc != BBMAP_OK) goto done;
-    TRY_GOTO(hipStreamSynchronize(nullptr));
-    TRY_GOTO(hipMemcpy(results, d_res, (size_t)n_jobs * sizeof(bbmsa_result), hipMemcpyDeviceToHost));
-    if (match) TRY_GOTO(hipMemcpy(match, d_match, (size_t)n_jobs * (size_t)match_stride, hipMemcpyDeviceToHost));
-done:
-    if (d_jobs) (void)hipFree(d_jobs);
-    if (d_reads) (void)hipFree(d_reads);
-    if (d_refs) (void)hipFree(d_refs);
-    if (d_res) (void)hipFree(d_res);
-    if (d_match) (void)hipFree(d_match);
-    return rc;
-#undef TRY_GOTO
+    DevTmp<bbmsa_job> d_jobs; DevTmp<uint8_t> d_reads, d_refs, d_match; DevTmp<bbmsa_result> d_res;
+    BBTRY(d_jobs.upload(jobs, (size_t)n_jobs));
+    BBTRY(d_reads.upload(reads, (size_t)reads_bytes));
+    BBTRY(d_refs.upload(refs, (size_t)refs_bytes));
+    BBTRY(d_res.alloc((size_t)n_jobs));
+    if (match) BBTRY(d_match.alloc((size_t)n_jobs * (size_t)match_stride));
+    BBHIP(hipMemset(d_res, 0xff, (size_t)n_jobs * sizeof(bbmsa_result)));
+    BBTRY(bbmsa_align_batch_device(c, nullptr, n_jobs, d_jobs, d_reads, d_refs, d_res, d_match, match_stride));
+    BBHIP(hipStreamSynchronize(nullptr));
+    BBHIP(hipMemcpy(results, d_res, (size_t)n_jobs * sizeof(bbmsa_result), hipMemcpyDeviceToHost));
+    if (match) BBHIP(hipMemcpy(match, d_match, (size_t)n_jobs * (size_t)match_stride, hipMemcpyDeviceToHost));
+    return BBMAP_OK;
 }

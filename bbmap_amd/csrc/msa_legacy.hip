@@ -20,15 +20,13 @@
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <new>
 
+#include "host_common.h"
 #include "msa_common.h"
 #include "msa_ctx.h"
-
-void bbmap_set_error(const char *msg);
 
 namespace bbmsa {
 const void *fast_kernel_mat_for(int R, bool banded);
@@ -36,22 +34,6 @@ template <class S> __global__ void msa_fill_generic_kernel(const GenericParams p
 }  // namespace bbmsa
 
 namespace {
-
-int lfail(int code, const char *msg) { bbmap_set_error(msg); return code; }
-#define L_TRY(expr)                                                                               \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            char b_[400]; snprintf(b_, sizeof b_, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            bbmap_set_error(b_);                                                                  \
-            return BBMAP_E_HIP;                                                                   \
-        }                                                                                         \
-    } while (0)
-
-int env_int(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
-}
 
 enum { OPEN = 0, RUNNING = 1, DONE = 2 };
 
@@ -101,18 +83,18 @@ namespace {
 int alloc_batch(bbmsa_legacy *S, Batch &b) {
     memset(&b, 0, sizeof b);
     const size_t inBytes = (size_t)(S->offBytes + S->capBytes);
-    L_TRY(hipHostMalloc((void **)&b.h_in, inBytes, hipHostMallocDefault));
-    L_TRY(hipMalloc((void **)&b.d_in, inBytes));
-    L_TRY(hipMalloc((void **)&b.d_planes, (size_t)S->capInts * 4));
-    L_TRY(hipHostMalloc((void **)&b.h_planes, (size_t)S->capInts * 4, hipHostMallocDefault));
-    L_TRY(hipMalloc((void **)&b.d_limits, (size_t)S->capLimits * 4));
-    L_TRY(hipHostMalloc((void **)&b.h_limits, (size_t)S->capLimits * 4, hipHostMallocDefault));
-    L_TRY(hipMalloc((void **)&b.d_results, (size_t)S->capJobs * sizeof(bbmsa_result)));
-    L_TRY(hipHostMalloc((void **)&b.h_results, (size_t)S->capJobs * sizeof(bbmsa_result), hipHostMallocDefault));
-    L_TRY(hipMalloc((void **)&b.d_counters, 64));
-    L_TRY(hipHostMalloc((void **)&b.h_counters, 64, hipHostMallocDefault));
-    L_TRY(hipMalloc((void **)&b.d_slow, (size_t)S->capJobs * 4));
-    L_TRY(hipHostMalloc((void **)&b.h_slow, (size_t)S->capJobs * 4, hipHostMallocDefault));
+    BBHIP(hipHostMalloc((void **)&b.h_in, inBytes, hipHostMallocDefault));
+    BBHIP(hipMalloc((void **)&b.d_in, inBytes));
+    BBHIP(hipMalloc((void **)&b.d_planes, (size_t)S->capInts * 4));
+    BBHIP(hipHostMalloc((void **)&b.h_planes, (size_t)S->capInts * 4, hipHostMallocDefault));
+    BBHIP(hipMalloc((void **)&b.d_limits, (size_t)S->capLimits * 4));
+    BBHIP(hipHostMalloc((void **)&b.h_limits, (size_t)S->capLimits * 4, hipHostMallocDefault));
+    BBHIP(hipMalloc((void **)&b.d_results, (size_t)S->capJobs * sizeof(bbmsa_result)));
+    BBHIP(hipHostMalloc((void **)&b.h_results, (size_t)S->capJobs * sizeof(bbmsa_result), hipHostMallocDefault));
+    BBHIP(hipMalloc((void **)&b.d_counters, 64));
+    BBHIP(hipHostMalloc((void **)&b.h_counters, 64, hipHostMallocDefault));
+    BBHIP(hipMalloc((void **)&b.d_slow, (size_t)S->capJobs * 4));
+    BBHIP(hipHostMalloc((void **)&b.h_slow, (size_t)S->capJobs * 4, hipHostMallocDefault));
     b.state = OPEN;
     return BBMAP_OK;
 }
@@ -137,13 +119,13 @@ void free_batch(Batch &b) {
 // the single synchronisation is the last line.
 int run_batch(bbmsa_ctx *c, Batch &b) {
     bbmsa_legacy *S = c->legacy;
-    L_TRY(hipSetDevice(c->device));
+    BBHIP(hipSetDevice(c->device));
     hipStream_t st = S->stream;
     const int n = b.njobs;
     const auto t0 = std::chrono::steady_clock::now();
     auto since = [](std::chrono::steady_clock::time_point a) { return (long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - a).count(); };
-    L_TRY(hipMemcpyAsync(b.d_in, b.h_in, (size_t)(S->offBytes + b.usedBytes), hipMemcpyHostToDevice, st));
-    L_TRY(hipMemsetAsync(b.d_counters, 0, 64, st));
+    BBHIP(hipMemcpyAsync(b.d_in, b.h_in, (size_t)(S->offBytes + b.usedBytes), hipMemcpyHostToDevice, st));
+    BBHIP(hipMemsetAsync(b.d_counters, 0, 64, st));
     const bbmsa_job *d_jobs = (const bbmsa_job *)b.d_in;
     const long long *d_planeOff = (const long long *)(b.d_in + S->offPlaneOff);
     const long long *d_limitsOff = (const long long *)(b.d_in + S->offLimitsOff);
@@ -151,9 +133,9 @@ int run_batch(bbmsa_ctx *c, Batch &b) {
     const long long *h_planeOff = (const long long *)(b.h_in + S->offPlaneOff);
     const long long *h_limitsOff = (const long long *)(b.h_in + S->offLimitsOff);
     auto download = [&]() -> int {
-        L_TRY(hipMemcpyAsync(b.h_planes, b.d_planes, (size_t)b.usedInts * 4, hipMemcpyDeviceToHost, st));
-        L_TRY(hipMemcpyAsync(b.h_limits, b.d_limits, (size_t)b.usedLimits * 4, hipMemcpyDeviceToHost, st));
-        L_TRY(hipMemcpyAsync(b.h_results, b.d_results, (size_t)n * sizeof(bbmsa_result), hipMemcpyDeviceToHost, st));
+        BBHIP(hipMemcpyAsync(b.h_planes, b.d_planes, (size_t)b.usedInts * 4, hipMemcpyDeviceToHost, st));
+        BBHIP(hipMemcpyAsync(b.h_limits, b.d_limits, (size_t)b.usedLimits * 4, hipMemcpyDeviceToHost, st));
+        BBHIP(hipMemcpyAsync(b.h_results, b.d_results, (size_t)n * sizeof(bbmsa_result), hipMemcpyDeviceToHost, st));
         return BBMAP_OK;
     };
     int nslow = n;
@@ -176,11 +158,11 @@ int run_batch(bbmsa_ctx *c, Batch &b) {
         int maxLen = 1;
         for (int i = 0; i < n; i++) if (b.jobs()[i].read_len > maxLen) maxLen = b.jobs()[i].read_len;
         const int R = (maxLen + 63) / 64;
-        L_TRY(hipLaunchKernel(bbmsa::fast_kernel_mat_for(R, c->banded), dim3((unsigned)blocks), dim3(64), args, (size_t)S->ldsBytes, st));
-        L_TRY(hipMemcpyAsync(b.h_counters, b.d_counters, 64, hipMemcpyDeviceToHost, st));
-        L_TRY(hipMemcpyAsync(b.h_slow, b.d_slow, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        BBHIP(hipLaunchKernel(bbmsa::fast_kernel_mat_for(R, c->banded), dim3((unsigned)blocks), dim3(64), args, (size_t)S->ldsBytes, st));
+        BBHIP(hipMemcpyAsync(b.h_counters, b.d_counters, 64, hipMemcpyDeviceToHost, st));
+        BBHIP(hipMemcpyAsync(b.h_slow, b.d_slow, (size_t)n * 4, hipMemcpyDeviceToHost, st));
         { const int rc = download(); if (rc != BBMAP_OK) return rc; }
-        L_TRY(hipStreamSynchronize(st));
+        BBHIP(hipStreamSynchronize(st));
         nslow = (int)b.h_counters[1];
         S->nsWave += since(t0);
         if (nslow == 0) return BBMAP_OK;             // the usual case: one launch, one synchronisation
@@ -194,14 +176,14 @@ int run_batch(bbmsa_ctx *c, Batch &b) {
         const int j = b.h_slow[k];
         const bbmsa_job &jb = b.jobs()[j];
         const int rows = jb.read_len, columns = jb.refEndLoc - jb.refStartLoc + 1;
-        L_TRY(hipMemsetAsync(b.d_counters + 2, 0, 4, st));
+        BBHIP(hipMemsetAsync(b.d_counters + 2, 0, 4, st));
         if (c->scheme == BBMSA_SCHEME_11TS) {   // the scratch matrix keeps cells of earlier fills (as the reference's `packed` does); cells this fill does not visit
             // are handed out as subfloor, like the wavefront kernel's, so that a fill's planes do not depend on what ran before it
             const long long maxGain = (long long)(rows - 1) * bbmsa::P_MATCH2 + bbmsa::P_MATCH;
             const bool lim = (jb.flags & BBMSA_MODE_MASK) == BBMSA_FILL_LIMITED_RAW;
             const long long subfloor = lim ? (long long)jb.minScore * 2048 - maxGain - 5LL * bbmsa::P_MATCH2 : -2 * maxGain;
             for (int s = 0; s < 3; s++)
-                L_TRY(hipMemsetD32Async((hipDeviceptr_t)(c->d_matrix + (long long)s * fullPlane), (int)subfloor,
+                BBHIP(hipMemsetD32Async((hipDeviceptr_t)(c->d_matrix + (long long)s * fullPlane), (int)subfloor,
                                         (size_t)(rows + 1) * (size_t)(columns + 2), st));
         }
         bbmsa::GenericParams gp;
@@ -214,19 +196,19 @@ int run_batch(bbmsa_ctx *c, Batch &b) {
             hipLaunchKernelGGL(bbmsa::msa_fill_generic_kernel<bbmsa::Scheme9PacBio>, dim3(1), dim3(1), 0, st, gp);
         else
             hipLaunchKernelGGL(bbmsa::msa_fill_generic_kernel<bbmsa::Scheme11ts>, dim3(1), dim3(1), 0, st, gp);
-        L_TRY(hipGetLastError());
+        BBHIP(hipGetLastError());
         const size_t W = (size_t)columns + 2;                       // the generic kernel's row stride for this fill
         for (int s = 0; s < 3; s++)
-            L_TRY(hipMemcpy2DAsync(b.d_planes + h_planeOff[j] + (long long)s * rows * columns, (size_t)columns * 4,
+            BBHIP(hipMemcpy2DAsync(b.d_planes + h_planeOff[j] + (long long)s * rows * columns, (size_t)columns * 4,
                                    c->d_matrix + (long long)s * fullPlane + W + 1, W * 4, (size_t)columns * 4, (size_t)rows,
                                    hipMemcpyDeviceToDevice, st));
-        L_TRY(hipMemcpyAsync(b.d_limits + h_limitsOff[j], c->d_limits, (size_t)(rows + 1) * 4, hipMemcpyDeviceToDevice, st));
-        L_TRY(hipMemcpyAsync(b.d_limits + h_limitsOff[j] + rows + 1, c->d_limits + c->cfg.maxRows + 2, (size_t)(columns + 1) * 4,
+        BBHIP(hipMemcpyAsync(b.d_limits + h_limitsOff[j], c->d_limits, (size_t)(rows + 1) * 4, hipMemcpyDeviceToDevice, st));
+        BBHIP(hipMemcpyAsync(b.d_limits + h_limitsOff[j] + rows + 1, c->d_limits + c->cfg.maxRows + 2, (size_t)(columns + 1) * 4,
                              hipMemcpyDeviceToDevice, st));
     }
     S->handed += nslow;
     { const int rc = download(); if (rc != BBMAP_OK) return rc; }
-    L_TRY(hipStreamSynchronize(st));
+    BBHIP(hipStreamSynchronize(st));
     S->nsHanded += since(t1);
     return BBMAP_OK;
 }
@@ -262,7 +244,7 @@ void lead(bbmsa_ctx *c, std::unique_lock<std::mutex> &lk) {
 
 int bbmsa_legacy_create(bbmsa_ctx *c) {
     bbmsa_legacy *S = new (std::nothrow) bbmsa_legacy();
-    if (!S) return lfail(BBMAP_E_NOMEM, "bbmsa_create: out of host memory");
+    if (!S) return bbfail(BBMAP_E_NOMEM, "bbmsa_create: out of host memory");
     c->legacy = S;
     S->open = 0; S->leaderActive = false; S->nextGen = 1; S->calls = S->launches = S->handed = 0; S->nsWave = S->nsHanded = S->nsWaitReaders = 0;
     S->stream = nullptr; S->d_dir = nullptr;
@@ -281,7 +263,7 @@ int bbmsa_legacy_create(bbmsa_ctx *c) {
     S->offPlaneOff = (long long)S->capJobs * sizeof(bbmsa_job);
     S->offLimitsOff = S->offPlaneOff + (long long)S->capJobs * 8;
     S->offBytes = S->offLimitsOff + (long long)S->capJobs * 8;
-    L_TRY(hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking));
+    BBHIP(hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking));
     for (int i = 0; i < 2; i++) { const int rc = alloc_batch(S, S->B[i]); if (rc != BBMAP_OK) return rc; }
     S->B[0].gen = S->nextGen;
     // geometry of the matrix-materialising wavefront launch
@@ -301,15 +283,15 @@ int bbmsa_legacy_create(bbmsa_ctx *c) {
         if (kfn && S->ldsBytes <= 160 * 1024) {
             if (S->ldsBytes > 64 * 1024)
                 for (int r = 1; r <= S->R; r++)
-                    L_TRY(hipFuncSetAttribute(bbmsa::fast_kernel_mat_for(r, c->banded), hipFuncAttributeMaxDynamicSharedMemorySize, S->ldsBytes));
+                    BBHIP(hipFuncSetAttribute(bbmsa::fast_kernel_mat_for(r, c->banded), hipFuncAttributeMaxDynamicSharedMemorySize, S->ldsBytes));
             int per = 0;
-            L_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kfn, 64, S->ldsBytes));
+            BBHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kfn, 64, S->ldsBytes));
             if (per < 1) per = 1;
             if (per > 8) per = 8;
             S->blocks = c->numCUs * per;
             if (S->blocks > S->capJobs) S->blocks = S->capJobs;
             S->dirSlotDwords = (long long)(((S->cols + 64 - 1) >> 3) + 1) * S->R * 64;
-            L_TRY(hipMalloc((void **)&S->d_dir, (size_t)((long long)S->blocks * S->dirSlotDwords * 4)));
+            BBHIP(hipMalloc((void **)&S->d_dir, (size_t)((long long)S->blocks * S->dirSlotDwords * 4)));
             S->wave = true;
         }
     }
@@ -329,13 +311,13 @@ void bbmsa_legacy_destroy(bbmsa_ctx *c) {
 extern "C" int bbmsa_fill_submit(bbmsa_ctx *c, const uint8_t *read, int32_t read_len, const uint8_t *ref, int32_t ref_len,
                                  int32_t refStartLoc, int32_t refEndLoc, int32_t minScore, int32_t mode,
                                  int32_t *result5, int64_t *iterations, bbmsa_ticket *ticket) {
-    if (!c || !read || !ref || !result5 || !ticket) return lfail(BBMAP_E_ARG, "bbmsa_fill_submit: null argument");
-    if (!c->legacy) return lfail(BBMAP_E_ARG, "bbmsa_fill_submit: the context was not created with BBMSA_LEGACY_ONLY");
-    if (mode != BBMSA_FILL_LIMITED_RAW && mode != BBMSA_FILL_UNLIMITED_RAW) return lfail(BBMAP_E_ARG, "bbmsa_fill_submit: mode must be one of the two raw fills");
+    if (!c || !read || !ref || !result5 || !ticket) return bbfail(BBMAP_E_ARG, "bbmsa_fill_submit: null argument");
+    if (!c->legacy) return bbfail(BBMAP_E_ARG, "bbmsa_fill_submit: the context was not created with BBMSA_LEGACY_ONLY");
+    if (mode != BBMSA_FILL_LIMITED_RAW && mode != BBMSA_FILL_UNLIMITED_RAW) return bbfail(BBMAP_E_ARG, "bbmsa_fill_submit: mode must be one of the two raw fills");
     const int rows = read_len;
     const long long columns = (long long)refEndLoc - refStartLoc + 1;
     if (rows < 1 || columns < 1 || rows > c->cfg.maxRows || columns > c->cfg.maxColumns || refStartLoc < 0 || refEndLoc >= ref_len)
-        return lfail(BBMAP_E_SHAPE, "bbmsa_fill_submit: problem exceeds the context limits or its reference array");
+        return bbfail(BBMAP_E_SHAPE, "bbmsa_fill_submit: problem exceeds the context limits or its reference array");
     bbmsa_legacy *S = c->legacy;
     const long long needBytes = ((long long)rows + columns + 7) & ~7LL;
     const long long needInts = 3LL * rows * columns;
@@ -383,8 +365,8 @@ extern "C" int bbmsa_fill_submit(bbmsa_ctx *c, const uint8_t *read, int32_t read
 }
 
 extern "C" int bbmsa_fill_collect(bbmsa_ctx *c, bbmsa_ticket *ticket, int32_t *packed, int32_t *vertLimit, int32_t *horizLimit) {
-    if (!c || !c->legacy || !ticket) return lfail(BBMAP_E_ARG, "bbmsa_fill_collect: null argument");
-    if (ticket->gen < 0 || ticket->batch < 0 || ticket->batch > 1) return lfail(BBMAP_E_ARG, "bbmsa_fill_collect: the ticket holds no finished fill");
+    if (!c || !c->legacy || !ticket) return bbfail(BBMAP_E_ARG, "bbmsa_fill_collect: null argument");
+    if (ticket->gen < 0 || ticket->batch < 0 || ticket->batch > 1) return bbfail(BBMAP_E_ARG, "bbmsa_fill_collect: the ticket holds no finished fill");
     bbmsa_legacy *S = c->legacy;
     Batch &b = S->B[ticket->batch];
     // no lock needed to read: the batch cannot be reopened while this reader is counted
@@ -416,7 +398,7 @@ extern "C" int bbmsa_fill_collect(bbmsa_ctx *c, bbmsa_ticket *ticket, int32_t *p
 extern "C" int bbmsa_fill_packed(bbmsa_ctx *c, const uint8_t *read, int32_t read_len, const uint8_t *ref, int32_t ref_len,
                                  int32_t refStartLoc, int32_t refEndLoc, int32_t minScore, int32_t mode,
                                  int32_t *result5, int64_t *iterations, int32_t *packed) {
-    if (!packed) return lfail(BBMAP_E_ARG, "bbmsa_fill_packed: null argument");
+    if (!packed) return bbfail(BBMAP_E_ARG, "bbmsa_fill_packed: null argument");
     bbmsa_ticket t;
     const int rc = bbmsa_fill_submit(c, read, read_len, ref, ref_len, refStartLoc, refEndLoc, minScore, mode, result5, iterations, &t);
     if (rc != BBMAP_OK) return rc;
@@ -424,7 +406,7 @@ extern "C" int bbmsa_fill_packed(bbmsa_ctx *c, const uint8_t *read, int32_t read
 }
 
 extern "C" int bbmsa_legacy_stats(bbmsa_ctx *c, int64_t *stats6) {
-    if (!c || !c->legacy || !stats6) return lfail(BBMAP_E_ARG, "bbmsa_legacy_stats: null argument");
+    if (!c || !c->legacy || !stats6) return bbfail(BBMAP_E_ARG, "bbmsa_legacy_stats: null argument");
     std::lock_guard<std::mutex> g(c->legacy->mu);
     stats6[0] = c->legacy->calls; stats6[1] = c->legacy->launches; stats6[2] = c->legacy->handed;
     stats6[3] = c->legacy->nsWave; stats6[4] = c->legacy->nsHanded; stats6[5] = c->legacy->nsWaitReaders;

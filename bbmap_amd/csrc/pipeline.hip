@@ -3,12 +3,10 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cstdio>
 
 #include "bbmap_amd.h"
+#include "host_common.h"
 #include "wave_prims.h"
-
-void bbmap_set_error(const char *msg);
 
 namespace bbpipe {
 using namespace wavep;
@@ -168,16 +166,13 @@ __global__ __launch_bounds__(64 * RESC_WAVES) void quick_rescue_kernel(const Res
 
 }  // namespace bbpipe
 
-static thread_local char g_perr[256];
-#define PHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { snprintf(g_perr, sizeof g_perr, "%s failed: %s", #expr, hipGetErrorString(e_)); bbmap_set_error(g_perr); return BBMAP_E_HIP; } } while (0)
-
 extern "C" int bbpipe_revcomp_device(void *stream_, int64_t n_reads, const bbidx_read *reads, const uint8_t *bases_in, uint8_t *bases_out) {
-    if (n_reads < 0) { bbmap_set_error("bbpipe_revcomp_device: bad size"); return BBMAP_E_ARG; }
+    if (n_reads < 0) return bbfail(BBMAP_E_ARG, "bbpipe_revcomp_device: bad size");
     if (n_reads == 0) return BBMAP_OK;
-    if (!reads || !bases_in || !bases_out) { bbmap_set_error("bbpipe_revcomp_device: null buffer"); return BBMAP_E_ARG; }
+    if (!reads || !bases_in || !bases_out) return bbfail(BBMAP_E_ARG, "bbpipe_revcomp_device: null buffer");
     const long long blocks = (n_reads + 3) / 4;
     hipLaunchKernelGGL(bbpipe::revcomp_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, reads, (long long)n_reads, bases_in, bases_out);
-    PHIP(hipGetLastError());
+    BBHIP(hipGetLastError());
     return BBMAP_OK;
 }
 
@@ -185,17 +180,15 @@ extern "C" int bbpipe_quick_rescue_device(void *stream_, int64_t n_jobs, const b
                                           const int64_t *chrom_off, const int32_t *chrom_len, const int32_t *chrom_min_index,
                                           const uint8_t *refs, bbresc_result *results,
                                           int32_t points_match, int32_t points_match2, int32_t use_affine, int32_t base_hit_score) {
-    if (n_jobs < 0) { bbmap_set_error("bbpipe_quick_rescue_device: bad size"); return BBMAP_E_ARG; }
+    if (n_jobs < 0) return bbfail(BBMAP_E_ARG, "bbpipe_quick_rescue_device: bad size");
     if (n_jobs == 0) return BBMAP_OK;
-    if (!jobs || !reads || !chrom_off || !chrom_len || !chrom_min_index || !refs || !results) {
-        bbmap_set_error("bbpipe_quick_rescue_device: null buffer"); return BBMAP_E_ARG;
-    }
+    if (!jobs || !reads || !chrom_off || !chrom_len || !chrom_min_index || !refs || !results) return bbfail(BBMAP_E_ARG, "bbpipe_quick_rescue_device: null buffer");
     bbpipe::RescueParams P;
     P.jobs = jobs; P.reads = reads; P.chromOff = (const long long *)chrom_off; P.chromLen = chrom_len; P.chromMin = chrom_min_index;
     P.refs = refs; P.results = results; P.njobs = n_jobs;
     P.pointsMatch = points_match; P.pointsMatch2 = points_match2; P.useAffine = use_affine; P.baseHitScore = base_hit_score;
     const long long blocks = (n_jobs + bbpipe::RESC_WAVES - 1) / bbpipe::RESC_WAVES;
     hipLaunchKernelGGL(bbpipe::quick_rescue_kernel, dim3((unsigned)blocks), dim3(64 * bbpipe::RESC_WAVES), 0, (hipStream_t)stream_, P);
-    PHIP(hipGetLastError());
+    BBHIP(hipGetLastError());
     return BBMAP_OK;
 }

@@ -21,6 +21,7 @@
 
 #include <climits>
 
+#include "host_common.h"
 #include "wave_prims.h"
 
 namespace bbrunstats {
@@ -254,24 +255,19 @@ hipError_t launch(const Args &a, unsigned long long *counters, unsigned long lon
 
 }  // namespace bbrunstats
 
-void bbmap_set_error(const char *msg);
-
 // The raw form over arrays the caller owns (include/bbmap_amd.h).
 extern "C" int bbpipe_run_stats_device(void *stream, int64_t n_reads, int32_t paired, int32_t scheme, int32_t thresh, const bbidx_read *reads,
                                        const bbmap_final *finals, const uint8_t *pool, const bbmap_msite *sites, const int32_t *nsites,
                                        int32_t cap, const bbmap_truth *truth, bbmap_runstats *counters, int64_t *ihist) {
     if (n_reads < 0 || (paired && (n_reads & 1)) || thresh < 0 || cap < 1 || cap > BBMAP_MAX_SITES_LIMIT ||
-        (scheme != BBMSA_SCHEME_11TS && scheme != BBMSA_SCHEME_9PACBIO)) {
-        bbmap_set_error("bbpipe_run_stats_device: bad argument"); return BBMAP_E_ARG;
-    }
+        (scheme != BBMSA_SCHEME_11TS && scheme != BBMSA_SCHEME_9PACBIO)) return bbfail(BBMAP_E_ARG, "bbpipe_run_stats_device: bad argument");
     if (n_reads == 0) return BBMAP_OK;
-    if (!reads || !finals || !pool || !sites || !nsites || !counters) { bbmap_set_error("bbpipe_run_stats_device: null buffer"); return BBMAP_E_ARG; }
+    if (!reads || !finals || !pool || !sites || !nsites || !counters) return bbfail(BBMAP_E_ARG, "bbpipe_run_stats_device: null buffer");
     bbrunstats::Args a = {};
     a.reads = reads; a.fin = finals; a.pool = pool; a.sites = sites; a.nsites = nsites; a.cap = cap;
     a.truth = truth; a.n = n_reads; a.paired = paired ? 1 : 0;
     a.ptsMatch = scheme == BBMSA_SCHEME_9PACBIO ? 90 : 70; a.ptsMatch2 = 100;     // POINTS_MATCH / POINTS_MATCH2 of the two aligner classes
     a.thresh = thresh; a.maxPairDist = 32000;                                      // MAX_PAIR_DIST (AbstractMapThread.java:2975)
-    const hipError_t e = bbrunstats::launch(a, (unsigned long long *)counters, (unsigned long long *)ihist, (hipStream_t)stream);
-    if (e != hipSuccess) { bbmap_set_error(hipGetErrorString(e)); return BBMAP_E_HIP; }
+    BBHIP(bbrunstats::launch(a, (unsigned long long *)counters, (unsigned long long *)ihist, (hipStream_t)stream));
     return BBMAP_OK;
 }
