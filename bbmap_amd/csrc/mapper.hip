@@ -17,6 +17,7 @@
 // Every function names the reference lines it follows.
 #include <hip/hip_runtime.h>
 
+#include "index_common.h"
 #include "mapper_dev.h"
 
 namespace bbmapper {
@@ -915,6 +916,18 @@ __global__ __launch_bounds__(128) void rescue_finish_kernel(const Dev D) {
 }
 
 #include "mapper_final.h"
+
+// ---------------------------------------------------------------------------------------------- reads the probe leaves alone
+// The probe writes the reverse complement of the reads it probes.  A read shorter than k or without a key is not probed (quickMap's
+// `basesP.length < KEYLEN` return, current/align2/AbstractMapThread.java:646), but its mate may anchor a rescue that searches for it
+// on either strand (basesM1 / basesM2 exist for every read, :501-503).  One thread per read: such reads are few and, as a rule, short.
+__global__ __launch_bounds__(128) void revcomp_unprobed_kernel(const bbidx_read *reads, long long n, int k, const uint8_t *in, uint8_t *out) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const bbidx_read rr = reads[r];
+    if (rr.nkeys >= 1 && rr.len >= k) return;
+    for (int i = 0; i < rr.len; i++) out[rr.bases_off + i] = (uint8_t)bbidx::complement_extended(in[rr.bases_off + rr.len - 1 - i]);
+}
 
 // ---------------------------------------------------------------------------------------------- overflow tier
 // units (reads, or pairs in paired mode) whose site list did not fit: appended in any order, sorted on the host

@@ -150,6 +150,7 @@ __global__ void final_begin_kernel(const Dev D);
 __global__ void final_round_kernel(const Dev D);
 __global__ void final_end_kernel(const Dev D);
 __global__ void final_local_kernel(const Dev D);
+__global__ void revcomp_unprobed_kernel(const bbidx_read *reads, long long n, int k, const uint8_t *in, uint8_t *out);
 __global__ void collect_overflow_kernel(const int *mcount, long long nunits, int paired, int *ids, unsigned *count);
 __global__ void gather_reads_kernel(const bbidx_read *reads, const int *ids, int nunits, int paired, bbidx_read *sub, int *readIds);
 __global__ void mark_tier_kernel(int *mcount, const int *tierCount, const int *readIds, int n, unsigned *resolved);

@@ -477,6 +477,7 @@ static int map_records(bbmap_ctx *c, hipStream_t stream, int64_t n_reads, const 
     // ---- probe (BBIndex.findAdvanced); reverse complements are written on the way
     BBTRY(bbidx_find_batch_device_with(c->index, &c->probeLs, stream, n_reads, reads, bases, baseScores, keyinfo, c->d_psites, c->cfg.max_sites,
                                       c->d_pnsites, writeRc ? bases + minus_delta : nullptr));
+    if (writeRc) BBTRY(launch<128>(revcomp_unprobed_kernel, n_reads, stream, reads, (long long)n_reads, (int)c->index->dev.p.k, (const uint8_t *)bases, bases + minus_delta));
     BBHIP(hipEventRecord(c->ev[EV_PROBE_END], stream));
     Dev D;
     fill_dev(c, D, n_reads, reads, bases, minus_delta);

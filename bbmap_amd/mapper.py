@@ -120,7 +120,9 @@ def _copy(ptr, nbytes, dev=None):
 
 
 class Mapper:
-    """One bbmap_ctx over a DeviceIndex.  Reads of one fixed length, all with the same key offsets / key scores."""
+    """One bbmap_ctx over a DeviceIndex.  Mapper(...) is the fixed-length form: reads of one length, all with the same key offsets /
+    key scores.  from_records / from_reads take reads of any lengths with keys of their own; in paired mode the mates of a pair may
+    differ in length (each stage uses the length of the mate it works on, as BBMapThread.processReadPair does)."""
 
     def __init__(self, di, n_reads, read_len, offsets, key_scores, paired=False, device=0, max_sites=32, **cfg_kw):
         self.L = _lib.load()

@@ -671,7 +671,8 @@ void bbmap_destroy(bbmap_ctx *ctx);
  * INITIAL_AVERAGE_PAIR_DIST).  It enters pairSiteScoresInitial / Final and the rescue search (:1086, :1093). */
 int bbmap_set_average_pair_dist(bbmap_ctx *ctx, int32_t average_pair_dist);
 /* Maps a batch that is resident on the device.  reads[i].bases_off addresses the plus strand inside `bases`; the call writes
- * every read's reverse complement at bases_off + minus_delta.  Enqueues on `stream` and waits for it: the call returns when the
+ * every read's reverse complement at bases_off + minus_delta (also a read's that the probe leaves alone for having no key: rescue
+ * may still place it beside its mate).  In paired mode the mates of a pair (reads 2p, 2p + 1) may differ in length.  Enqueues on `stream` and waits for it: the call returns when the
  * batch is done (the rounds of scoreSlow need the job counts on the host). */
 int bbmap_map_batch_device(bbmap_ctx *ctx, void *stream, int64_t n_reads, const bbidx_read *reads, uint8_t *bases,
                            int64_t minus_delta, const int8_t *baseScores, const int32_t *keyinfo);

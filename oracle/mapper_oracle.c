@@ -683,65 +683,69 @@ static void process_read(mapper *M, const readin *in, slist *l, orc_final *fin, 
 }
 
 /* ------------------------------------------------------------------ processReadPair (BBMapThread.java:943-1098) */
-static void process_pair_tail(mapper *M, const uint8_t *bp1, const uint8_t *bm1, const uint8_t *bp2, const uint8_t *bm2, int L, slist *l1, slist *l2);
+static void process_pair_tail(mapper *M, const uint8_t *bp1, const uint8_t *bm1, int L1, const uint8_t *bp2, const uint8_t *bm2, int L2,
+                              slist *l1, slist *l2);
 static void process_pair(mapper *M, const readin *in1, const readin *in2, slist *l1, slist *l2, orc_final *fin1, orc_final *fin2,
                          uint8_t *fmatch1, uint8_t *fmatch2, int fstride) {
     const orc_map_params *P = M->P;
     const uint8_t *bp1 = in1->bp, *bp2 = in2->bp;
-    const int L = in1->L;                                   /* both mates have one length in every caller of this restatement */
-    uint8_t *bm1 = (uint8_t *)malloc((size_t)L + 1), *bm2 = (uint8_t *)malloc((size_t)L + 1);
-    complement_into(bm1, bp1, L); complement_into(bm2, bp2, L);
+    const int L1 = in1->L, L2 = in2->L;                     /* len1, len2 (:948): the mates need not be equally long */
+    uint8_t *bm1 = (uint8_t *)malloc((size_t)L1 + 1), *bm2 = (uint8_t *)malloc((size_t)L2 + 1);
+    complement_into(bm1, bp1, L1); complement_into(bm2, bp2, L2);
     quick_map(M, in1, bm1, l1);
     quick_map(M, in2, bm2, l2);
-    const int maxSw = orc_max_quality(L), maxImp = orc_max_imperfect_score(L);
-    pair_site_scores_initial(M, l1, l2, L, L, P->trimList);
+    const int maxSw1 = orc_max_quality(L1), maxImp1 = orc_max_imperfect_score(L1);          /* :983-986 */
+    const int maxSw2 = orc_max_quality(L2), maxImp2 = orc_max_imperfect_score(L2);
+    pair_site_scores_initial(M, l1, l2, L1, L2, P->trimList);
     if (P->trimList) {
         if (l1->n > MIN_TRIM_SITES_TO_RETAIN_PAIRED) sort_list(l1, cmp_score);
         if (l2->n > MIN_TRIM_SITES_TO_RETAIN_PAIRED) sort_list(l2, cmp_score);
-        trim_list(l1, 1, maxSw, 0, MIN_TRIM_SITES_TO_RETAIN_PAIRED, P->maxTrimSitesToRetain);
-        trim_list(l2, 1, maxSw, 0, MIN_TRIM_SITES_TO_RETAIN_PAIRED, P->maxTrimSitesToRetain);
+        trim_list(l1, 1, maxSw1, 0, MIN_TRIM_SITES_TO_RETAIN_PAIRED, P->maxTrimSitesToRetain);      /* :998-999 */
+        trim_list(l2, 1, maxSw2, 0, MIN_TRIM_SITES_TO_RETAIN_PAIRED, P->maxTrimSitesToRetain);
     }
     for (int i = 0; i < l1->n; i++) l1->s[i].score = l1->s[i].quickScore;
     for (int i = 0; i < l2->n; i++) l2->s[i].score = l2->s[i].quickScore;
     slist *ls[2] = {l1, l2}; const uint8_t *bps[2] = {bp1, bp2}, *bms[2] = {bm1, bm2};
-    for (int w = 0; w < 2; w++) {
+    const int Ls[2] = {L1, L2}, maxSws[2] = {maxSw1, maxSw2}, maxImps[2] = {maxImp1, maxImp2};
+    for (int w = 0; w < 2; w++) {                                                                  /* :1025-1059 */
         slist *l = ls[w];
         if (l->n > 0) {
-            const int near = score_no_indels_list(M, l, bps[w], bms[w], L, maxSw, maxImp);
+            const int near = score_no_indels_list(M, l, bps[w], bms[w], Ls[w], maxSws[w], maxImps[w]);
             sort_list(l, cmp_score);
-            if (near < 1 && P->tipSearchDist > 0) find_tip_deletions_list(M, l, bps[w], bms[w], L, maxSw, maxImp);
-            score_slow(M, w, l, bps[w], bms[w], L, maxSw, maxImp, 1);
+            if (near < 1 && P->tipSearchDist > 0) find_tip_deletions_list(M, l, bps[w], bms[w], Ls[w], maxSws[w], maxImps[w]);
+            score_slow(M, w, l, bps[w], bms[w], Ls[w], maxSws[w], maxImps[w], 1);
             merge_duplicate_sites(l);
         }
     }
-    process_pair_tail(M, bp1, bm1, bp2, bm2, L, l1, l2);
+    process_pair_tail(M, bp1, bm1, L1, bp2, bm2, L2, l1, l2);
     if (P->finalStage) {
-        rstate r1, r2; r_init(&r1, bp1, bm1, L, M->readIdx[0]); r_init(&r2, bp2, bm2, L, M->readIdx[1]);
+        rstate r1, r2; r_init(&r1, bp1, bm1, L1, M->readIdx[0]); r_init(&r2, bp2, bm2, L2, M->readIdx[1]);
         final_pair(M, &r1, &r2, l1, l2);
         store_final(M, &r1, l1, fin1, fmatch1, fstride); store_final(M, &r2, l2, fin2, fmatch2, fstride);
         m_reset(M);
     }
     free(bm1); free(bm2);
 }
-static void process_pair_tail(mapper *M, const uint8_t *bp1, const uint8_t *bm1, const uint8_t *bp2, const uint8_t *bm2, int L, slist *l1, slist *l2) {
+static void process_pair_tail(mapper *M, const uint8_t *bp1, const uint8_t *bm1, int L1, const uint8_t *bp2, const uint8_t *bm2, int L2,
+                              slist *l1, slist *l2) {
     const orc_map_params *P = M->P;
-    const int maxSw = orc_max_quality(L);
+    const int maxSw1 = orc_max_quality(L1), maxSw2 = orc_max_quality(L2);
     if (P->doRescue) {
         int unpaired1 = 0, unpaired2 = 0;
         for (int i = 0; i < l1->n; i++) if (l1->s[i].pairedScore == 0) unpaired1++;
         for (int i = 0; i < l2->n; i++) if (l2->s[i].pairedScore == 0) unpaired2++;
         const float pre = orc_ratio_pre_rescue(P->minRatio);
         const int searchDist = imin(P->maxPairDist, 2 * P->averagePairDist + 100);
-        if (unpaired1 > 0 && l1->n > 0) {
+        if (unpaired1 > 0 && l1->n > 0) {                                                          /* :1083-1088: mate 1 anchors, mate 2 is loose */
             sort_list(l1, cmp_score);
-            remove_low_quality_paired(l1, maxSw, pre, pre);
-            rescue(M, 1, l1, l2, L, bp2, bm2, L, searchDist);
+            remove_low_quality_paired(l1, maxSw1, pre, pre);
+            rescue(M, 1, l1, l2, L1, bp2, bm2, L2, searchDist);
             merge_duplicate_sites(l2);
         }
-        if (unpaired2 > 0 && l2->n > 0) {
+        if (unpaired2 > 0 && l2->n > 0) {                                                          /* :1090-1095: mate 2 anchors, mate 1 is loose */
             sort_list(l2, cmp_score);
-            remove_low_quality_paired(l2, maxSw, pre, pre);
-            rescue(M, 0, l2, l1, L, bp1, bm1, L, searchDist);
+            remove_low_quality_paired(l2, maxSw2, pre, pre);
+            rescue(M, 0, l2, l1, L2, bp1, bm1, L1, searchDist);
             merge_duplicate_sites(l1);
         }
     }
@@ -832,7 +836,7 @@ static void *drv_worker(void *p) {
     return NULL;
 }
 
-/* Maps n_reads read records (paired: records 2p and 2p+1 are mates of equal length).  A record addresses its bases (and, when
+/* Maps n_reads read records (paired: records 2p and 2p+1 are mates; their lengths may differ).  A record addresses its bases (and, when
  * baseScores != NULL, its base scores) at bases_off and its keys at keyinfo[keys_off]: offsets[nkeys] then keyScores[nkeys] -- the
  * layout of bbidx_read (include/bbmap_amd.h).  sites: n_reads x cap records (may be NULL: timing only).  log (optional): one record
  * per fillAndScoreLimited call; match: logcap x matchStride bytes.  stats4 = {DP calls, visited cells, quickRescue scans, reads
@@ -854,7 +858,6 @@ double orc_map_reads_final(const orc_index *ix, const orc_map_params *P, const o
     if (threads < 1) threads = 1;
     if (n_reads < 1 || (paired && (n_reads & 1))) return -1.0;
     for (int64_t r = 0; r < n_reads; r++) if (recs[r].len > P->msaMaxRows - 1) return -1.0;      /* maxReadLength() = ALIGN_ROWS - 1 */
-    if (paired) for (int64_t r = 0; r < n_reads; r += 2) if (recs[r].len != recs[r + 1].len) return -1.0;
     pthread_t *th = (pthread_t *)malloc(sizeof(pthread_t) * (size_t)threads);
     drv_arg *wa = (drv_arg *)calloc((size_t)threads, sizeof(drv_arg));
     volatile int64_t next = 0, nl = 0;

@@ -523,7 +523,7 @@ def map_reads(oi, recs, bases, keyinfo, base_scores=None, paired=False, params=N
                                match.ctypes.data if want_log else None, stride, threads, stats.ctypes.data,
                                fin.ctypes.data, fmatch.ctypes.data, fstride)
     if t < 0:
-        raise ValueError("orc_map_reads: bad argument (read longer than the MSA's rows, or mates of different length)")
+        raise ValueError("orc_map_reads: bad argument (no reads, an odd number of mates, or a read longer than the MSA's rows)")
     if want_log and nlog.value > logcap:
         raise RuntimeError("job log overflow")
     return dict(sites=sites, nsites=ns, final=fin, fmatch=fmatch, log=log[:nlog.value] if want_log else None,

@@ -8,6 +8,19 @@ FINAL_FIELDS = ("mapped", "chrom", "strand", "start", "stop", "mapScore", "paire
 GAPPED_BIT = 1 << 30
 TRACE_KEEP_GAPS = 1 << 7
 
+# The DP routes the mapper's launches take.  "latency": the defaults -- launches of up to 4,096 fills go straight to the 64-lane
+# geometry, and the narrow kernel only runs for launches of 32,768 fills or more, so at test sizes nearly every launch takes the
+# latency route.  "throughput": what the benchmark's big launches take -- the narrow kernel in front of the first pass in the plain
+# context, the width-sorted first pass in the second.
+DP_ROUTES = {"latency": {}, "throughput": {"BBMAP_LATENCY_JOBS": "0", "BBMAP_NARROW_MIN_JOBS": "1"}}
+
+
+def set_route(monkeypatch, route):
+    for k_ in ("BBMAP_LATENCY_JOBS", "BBMAP_NARROW_MIN_JOBS", "BBMAP_SORT_WIDE"):
+        monkeypatch.delenv(k_, raising=False)
+    for k_, v in DP_ROUTES[route].items():
+        monkeypatch.setenv(k_, v)
+
 
 def gpu_fills(out):
     """{(read, seq): dict} over both fill logs of a Mapper.fetch()."""

@@ -11,7 +11,7 @@ from bbmap_amd import workload as W
 from bbmap_amd.index import DeviceIndex
 from bbmap_amd.mapper import Mapper
 from oracle import oracle as O
-from tests.mapper_check import compare, gpu_fills
+from tests.mapper_check import DP_ROUTES, compare, gpu_fills, set_route as _set_route  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -37,20 +37,6 @@ def _run(ref, reads, L, k, paired, max_sites=32, cap=64, **cfg):
     mp.close()
     di.close()
     return out, orc, st, n
-
-
-# The DP routes the mapper's launches take.  "latency": the defaults -- launches of up to 4,096 fills go straight to the 64-lane
-# geometry, and the narrow kernel only runs for launches of 32,768 fills or more, so at test sizes nearly every launch takes the
-# latency route.  "throughput": what the benchmark's big launches take -- the narrow kernel in front of the first pass in the plain
-# context, the width-sorted first pass in the second.
-DP_ROUTES = {"latency": {}, "throughput": {"BBMAP_LATENCY_JOBS": "0", "BBMAP_NARROW_MIN_JOBS": "1"}}
-
-
-def _set_route(monkeypatch, route):
-    for k_ in ("BBMAP_LATENCY_JOBS", "BBMAP_NARROW_MIN_JOBS", "BBMAP_SORT_WIDE"):
-        monkeypatch.delenv(k_, raising=False)
-    for k_, v in DP_ROUTES[route].items():
-        monkeypatch.setenv(k_, v)
 
 
 def _single_ended(monkeypatch, route, n_reads=3000, **workload):
