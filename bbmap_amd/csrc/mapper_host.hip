@@ -291,10 +291,10 @@ static int grow_logs(bbmap_ctx *c, hipStream_t stream, Dev &D, long long needJob
 // launches the DP over the fills appended since (jobBase, gjobBase)
 static int run_fills(bbmap_ctx *c, hipStream_t stream, const uint8_t *bases, long long jobBase, long long nNew, long long gBase, long long gNew,
                      bool finalStage = false) {
-    // The one-job-per-lane narrow kernel runs in front of the wavefront kernel on the same stream and is a ~1.5 ms dependent chain
-    // however few jobs there are: worth it only for the big first rounds of scoreSlow (163 k of 459 k fills finish there in 4.8 ms
-    // on the bench workload).  The final stage's fills never fit its band (see msa_ctx.h), nor do the second context's wide windows.
-    bbmsa_use_narrow(c->msa, !finalStage && nNew >= c->narrowMinJobs);
+    // The band kernel (msa_fill_band.hip) runs in front of the wavefront kernel on the same stream and is a dependent chain of
+    // 2 * rows turns however few jobs there are: worth it only for the big first rounds -- of scoreSlow, of rescue and of the final
+    // stage (a third to a half of their fills finish in its 32 diagonals).  The second context's wide windows never fit.
+    bbmsa_use_narrow(c->msa, nNew >= c->narrowMinJobs);
     // (not the first context's: its windows span 162..256 columns, and sorted its pass ends 4 ms earlier -- leaving the second
     // context's latency-bound wide pass to finish on its own: final stage 79.6 -> 85.5 ms)
     bbmsa_sort_by_width(c->msa, false);

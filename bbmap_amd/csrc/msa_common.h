@@ -61,7 +61,7 @@ __host__ __device__ inline bool fully_defined(int b) {
     return b < 128 && (u == 'A' || u == 'C' || u == 'G' || u == 'T' || u == 'U');
 }
 
-// ---- scoring schemes.  The wavefront and narrow kernels are written for the 11ts constants above; the generic kernel is
+// ---- scoring schemes.  The wavefront and band kernels are written for the 11ts constants above; the generic kernel is
 // a template over one of these, so that the PacBio parameter set runs through the same literal statement.
 struct Scheme11ts {      // jni/MultiStateAligner11tsJNI.c:18-98
     static constexpr int OFF = kScoreOffset, TMASK = kTimeMask, SMASK = kScoreMask, MAXT = kMaxTime;
@@ -133,7 +133,7 @@ struct FillParams {
     unsigned int *queue;          // work-queue head (zeroed before launch)
     unsigned int *dirbuf;         // traceback direction nibbles, one slot per resident job
     long long dir_slot_dwords;
-    const int *list;              // job indices to process (NULL = all njobs), filled by the narrow kernel or the width sort
+    const int *list;              // job indices to process (NULL = all njobs), filled by the band kernel or the width sort
     const unsigned int *list_count;
     int priority;                 // s_setprio for the launch's wavefronts (0..3): the one-job-per-block passes are a dependent chain per job
                                   // and share their SIMDs with the throughput passes of the other stream
@@ -156,7 +156,8 @@ struct FillParams {
     const long long *limits_off;
 };
 
-// one job per lane, a band of diagonals in registers (msa_fill_narrow.hip)
+// the band kernel in front of the first pass (msa_fill_band.hip): a job over 8 lanes, 16 jobs per wave.  (The name is its
+// predecessor's, the one-job-per-lane narrow-window kernel, as are the switches and counters of the host side.)
 struct NarrowParams {
     const bbmsa_job *jobs;
     const uint8_t *reads;
@@ -168,13 +169,15 @@ struct NarrowParams {
     unsigned int *queue;          // work-queue head (zeroed before launch)
     int *fast_list;               // jobs left to the wavefront kernel
     unsigned int *fast_count;
-    unsigned long long *dirbuf;   // per resident wave: (maxRows + 1) x 64 lanes x 8 bytes of direction nibbles
     unsigned int *stats;          // [0] jobs finished here, [1] candidates that left the band (handed on)
     int match_stride;
     int maxRows, maxColumns;
     int bandwidth;
     float bandwidthRatio;
     int maxSlack;                 // candidate filter: maxQuality(rows) - minScore (points) at most this
+    unsigned int *dirbuf32;       // per resident wave: (bandRows + 1) x 2 jobs x 64 lanes dwords of records
+    int tableLen;                 // entries of the delC / insC tables (see lds_table_ints)
+    int bandRows;                 // longest read it takes (its LDS areas and record slots are sized for it)
 };
 
 struct GenericParams {

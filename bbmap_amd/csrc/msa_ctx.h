@@ -26,7 +26,8 @@ struct bbmsa_ctx {
     long long wideDirSlotDwords = 0;
     unsigned int *d_wideDir = nullptr;
     DevBuf slowList2;           // the wide pass's own hand-over list (only with a wide pass), as long as slowList
-    // narrow-window kernel (msa_fill_narrow.hip): one job per lane
+    // band kernel (msa_fill_band.hip): a job over 8 lanes, 32 diagonals, in front of the first pass.  Its switches and counters keep the
+    // name of its predecessor, the one-job-per-lane narrow-window kernel.
     int narrowBlocks = 0, narrowSlack = 0;     // 0 blocks = disabled
     bool narrowOff = false;            // switched off by the caller for launches whose jobs it cannot take (bbmsa_use_narrow)
     bool narrowUsed = false;           // whether the last launch ran it
@@ -37,11 +38,12 @@ struct bbmsa_ctx {
     bool sortByWidth = false;
     unsigned int *d_widthHist = nullptr;
     long long latencyJobs = 0;         // launches with at most this many jobs go straight to the 64-lane geometry (bbmsa_set_latency_jobs)
-    unsigned long long *d_narrowDir = nullptr;
-    DevBuf fastList;            // ints: the wavefront kernel's job list when the narrow kernel or the width sort writes one
+    int bandRows = 0, bandLds = 0;     // longest read the band kernel takes, its LDS bytes per block
+    unsigned int *d_bandDir = nullptr; // its records: per resident wave (bandRows + 1) x 2 jobs x 64 lanes dwords
+    DevBuf fastList;            // ints: the wavefront kernel's job list when the band kernel or the width sort writes one
     // gapped-reference scratch (msa_gapped.hip), grown on demand: gapped references, their bookkeeping, the derived jobs
     DevBuf gref, gaux, gjobs;
-    hipEvent_t ev[4] = {};  // start, after wavefront kernel, after generic kernel, after narrow kernel
+    hipEvent_t ev[4] = {};  // start, after wavefront kernel, after generic kernel, after band kernel
     bool timed = false;
     bool banded = false;
     bool legacyOnly = false;    // created with BBMSA_LEGACY_ONLY: bbmsa_fill_submit / _collect / _packed only
@@ -61,9 +63,10 @@ struct bbmsa_ctx {
 int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t *n_jobs_dev, const bbmsa_job *jobs,
                      const uint8_t *reads, const uint8_t *refs, bbmsa_result *results, uint8_t *match, int32_t match_stride);
 
-// Internal (mapper_host.hip, which includes this header through mapper_ctx.h).  The mapper switches the narrow kernel off for launches it cannot help: small ones (one job per lane is a
-// ~1.5 ms dependent chain however few jobs there are, in front of the wavefront kernel on the same stream) and the final alignment
-// stage's (realign_new pads its windows by >= 6 columns and passes minScore - 120: no such fill fits the 16-diagonal band).
+// Internal (mapper_host.hip, which includes this header through mapper_ctx.h).  The mapper switches the band kernel off for launches it
+// cannot help: small ones (its fill is a dependent chain of 2 * rows turns however few jobs there are, in front of the wavefront kernel
+// on the same stream).  The final alignment stage's launches run it since it has 32 diagonals: realign_new pads its windows by >= 6
+// columns and passes minScore - 120, which keeps 17-24 diagonals alive -- a third of those fills finish in the band.
 void bbmsa_use_narrow(bbmsa_ctx *c, bool on);
 // Makes `waiter` (a stream) wait until the context's last launch sequence has reached its first wavefront pass.  The mapper's two
 // contexts run side by side; the second one's sequence begins with make_gref_kernel, and if the first context's persistent blocks

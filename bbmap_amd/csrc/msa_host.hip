@@ -25,7 +25,8 @@ const void *strip_kernel_pacbio_pipelined();
 int strip_pipe_sync_ints(int K);
 const void *fast_kernel_for(int R, bool banded);
 template <class S> __global__ void msa_fill_generic_kernel(const GenericParams p);
-__global__ void msa_fill_narrow_kernel(const NarrowParams p);
+const void *band_kernel();                                     // msa_fill_band.hip
+int band_lds_bytes(int tableLen, int bandRows);
 }  // namespace bbmsa
 
 namespace bbmsa {
@@ -239,15 +240,19 @@ extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
     BBHIP(hipMalloc(&c->d_limits, (size_t)(threads * (cfg->maxRows + cfg->maxColumns + 4) * 4)));
     // wide pass geometry (only when some windows can exceed the first pass's column buffer)
     if (cfg->maxColumns > fastCols) BBTRY(setup_wide_pass(c));
-    // narrow-window kernel: only without a band (a band changes the window rule); BBMSA_NARROW=0 disables it
+    // band kernel (msa_fill_band.hip) in front of the first pass: only without a band (a band changes the window rule);
+    // BBMSA_NARROW=0 disables it (the switches keep the name of its predecessor, the one-job-per-lane narrow-window kernel)
     c->narrowSlack = env_int("BBMSA_NARROW_SLACK", 2000);
     if (!c->banded && env_int("BBMSA_NARROW", 1) != 0) {
         int perCU = 0;
-        BBHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (const void *)bbmsa::msa_fill_narrow_kernel, 64, 0));
+        c->bandRows = cfg->maxRows < 256 ? cfg->maxRows : 256;
+        c->bandLds = bbmsa::band_lds_bytes(c->tableLen, c->bandRows);
+        if (c->bandLds > 64 * 1024) BBHIP(hipFuncSetAttribute(bbmsa::band_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, c->bandLds));
+        BBHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, bbmsa::band_kernel(), 256, c->bandLds));
         if (perCU < 1) perCU = 1;
-        if (perCU > 16) perCU = 16;
+        if (perCU > 4) perCU = 4;
         c->narrowBlocks = c->numCUs * perCU;
-        BBHIP(hipMalloc(&c->d_narrowDir, (size_t)c->narrowBlocks * (size_t)(cfg->maxRows + 1) * 64 * 8));
+        BBHIP(hipMalloc(&c->d_bandDir, (size_t)c->narrowBlocks * 4 * (size_t)(c->bandRows + 1) * 128 * 4));
     }
     // route switches of the environment (msa_ctx.h): defaults off, as the functions they mirror leave a context
     c->sortByWidth = env_int("BBMSA_SORT_BY_WIDTH", 0) != 0;
@@ -269,7 +274,7 @@ extern "C" void bbmsa_destroy(bbmsa_ctx *c) {
     if (c->d_matrix) (void)hipFree(c->d_matrix);
     if (c->d_limits) (void)hipFree(c->d_limits);
     if (c->d_wideDir) (void)hipFree(c->d_wideDir);
-    if (c->d_narrowDir) (void)hipFree(c->d_narrowDir);
+    if (c->d_bandDir) (void)hipFree(c->d_bandDir);
     if (c->d_stripBoundary) (void)hipFree(c->d_stripBoundary);
     if (c->d_stripTmp) (void)hipFree(c->d_stripTmp);
     if (c->d_pipeBoundary) (void)hipFree(c->d_pipeBoundary);
@@ -363,7 +368,7 @@ int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t
     if (c->narrowBlocks > 0 || sortJobs) BBHIP(c->fastList.grow(listBytes, 0, &stream));
     int *const fastList = c->fastList.as<int>();
     // counters: [0] fast queue, [1] slow count, [2] generic queue, [3] narrow queue, [4] fast-list count,
-    //           [5] jobs finished by the narrow kernel, [6] candidates it handed on
+    //           [5] jobs finished by the band kernel (the "narrow" slots), [6] candidates it handed on
     BBHIP(hipMemsetAsync(c->d_counters, 0, 64, stream));
     BBHIP(hipEventRecord(c->ev[0], stream));
     const bool useNarrow = c->narrowBlocks > 0 && !c->narrowOff;
@@ -372,11 +377,12 @@ int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t
         bbmsa::NarrowParams np;
         set_batch(np, c, B);
         np.queue = c->d_counters + 3; np.fast_list = fastList; np.fast_count = c->d_counters + 4;
-        np.dirbuf = c->d_narrowDir; np.stats = c->d_counters + 5; np.maxSlack = c->narrowSlack;
+        np.stats = c->d_counters + 5; np.maxSlack = c->narrowSlack;
+        np.dirbuf32 = c->d_bandDir; np.tableLen = c->tableLen; np.bandRows = c->bandRows;
         long long nb = (n_jobs + 63) / 64;
         if (nb > c->narrowBlocks) nb = c->narrowBlocks;
-        hipLaunchKernelGGL(bbmsa::msa_fill_narrow_kernel, dim3((unsigned)nb), dim3(64), 0, stream, np);
-        BBHIP(hipGetLastError());
+        void *nargs[] = {&np};
+        BBHIP(hipLaunchKernel(bbmsa::band_kernel(), dim3((unsigned)nb), dim3(256), nargs, (size_t)c->bandLds, stream));
     }
     if (sortJobs) {                    // (never together with the narrow kernel: both write the wavefront kernel's list)
         if (!c->d_widthHist) BBHIP(hipMalloc(&c->d_widthHist, bbmsa::WIDTH_BUCKETS * 4));

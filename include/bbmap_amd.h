@@ -195,17 +195,17 @@ int bbmsa_align_gapped_batch(bbmsa_ctx *ctx, int64_t n_jobs, const bbmsa_job *jo
 /* Timing of the last bbmsa_align_batch_device launch sequence on this context, measured with
  * HIP events on the launch stream.  Valid after the stream has been synchronised. */
 int bbmsa_last_kernel_ms(bbmsa_ctx *ctx, float *ms_fast, float *ms_slow);
-/* The same per kernel: ms3 = {narrow-window kernel, wavefront kernel, generic kernel}. */
+/* The same per kernel: ms3 = {band kernel, wavefront kernel, generic kernel}. */
 int bbmsa_last_kernel_ms3(bbmsa_ctx *ctx, float *ms3);
-/* Which kernel took how many jobs of the last launch sequence: counts4 = {finished by the narrow-window kernel (one job
- * per lane, a band of diagonals in registers), candidates it handed on because their window left the band, jobs given
+/* Which kernel took how many jobs of the last launch sequence: counts4 = {finished by the band kernel (a job over
+ * 8 lanes, a band of 32 diagonals in registers), candidates it handed on because their window left the band, jobs given
  * to the wavefront kernel in total, jobs the wavefront kernel handed to the generic kernel}. */
 int bbmsa_last_counts(bbmsa_ctx *ctx, int64_t *counts4);
 /* The route the last launch sequence took (host flags recorded at launch, then the device counters):
- * route8 = {narrow-window kernel ran (0/1), first pass in descending window width (0/1), latency route: no first pass, the
+ * route8 = {band kernel ran (0/1), first pass in descending window width (0/1), latency route: no first pass, the
  * wide pass took every job (0/1), the context has a wide pass (0/1), job count read on the device (an _indirect entry, 0/1),
  * jobs the first pass handed on (9PacBio: the strip kernel to the generic kernel), jobs the wide pass handed to the generic
- * kernel, jobs the narrow-window kernel finished}.  Waits for the launch sequence to finish. */
+ * kernel, jobs the band kernel finished}.  Waits for the launch sequence to finish. */
 int bbmsa_last_route(bbmsa_ctx *ctx, int64_t *route8);
 
 /* =====================================================================================
@@ -644,7 +644,7 @@ typedef struct bbmap_stats {
                                     * ms_dp_wave is the sum over all rounds and rescue passes */
     float ms_final;                /* the final alignment stage (included in ms_total) */
     int64_t final_fills, final_rounds, final_local;   /* its fills, rounds, reads that went through toLocalAlignment */
-    int64_t dp_narrow_launches;    /* DP launches that ran the narrow-window kernel (bbmsa_last_route: route8[0]) */
+    int64_t dp_narrow_launches;    /* DP launches that ran the band kernel (bbmsa_last_route: route8[0]) */
     int64_t dp_sorted_launches;    /* DP launches whose first pass took the jobs widest first (route8[1]) */
     int64_t sites_cross_scaffold;  /* probe sites quickMap's tail removed for spanning two scaffolds (bbidx_set_scaffolds; 0 without a
                                     * table).  The overflow tier's pass adds its own: a pair one of whose mates overflowed the probe is
