@@ -28,6 +28,8 @@ EXPORTS = [
     "bbkeys_device_workspace_bytes", "bbkeys_make_batch_device",
     "bbpipe_run_stats_device", "bbmap_add_run_stats", "bbmap_get_run_stats", "bbmap_reset_run_stats", "bbmap_set_adaptive", "bbmap_set_truth",
     "bbmap_get_adaptive_state",
+    "bbpipe_coverage_layout", "bbpipe_coverage_workspace_bytes", "bbpipe_coverage_add_device", "bbpipe_coverage_finalize_device",
+    "bbmap_cov_enable", "bbmap_add_coverage", "bbmap_cov_finalize", "bbmap_get_coverage", "bbmap_reset_coverage",
 ]
 
 

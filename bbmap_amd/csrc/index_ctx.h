@@ -44,6 +44,7 @@ struct bbidx_ctx {
     bbscaf::Table scaf = {};
     bool scafFilter = false;
     void *scafBuf = nullptr;
+    long long scafGen = 0;  // moves whenever the table is set or cleared (the coverage state of a mapper is sized by one table)
 };
 
 // BBIDX_MAX_GROUPS, read once per context (bbidx_create / bbidx_build): unset or 0 = no cap

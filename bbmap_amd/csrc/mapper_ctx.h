@@ -79,6 +79,25 @@ struct bbmap_ctx {
     long long numMatedSeen = 0;     // numMated after the last accumulation the insert-length rule looked at
     const bbmap_truth *truthNext = nullptr;     // bbmap_set_truth: for the next batch's own accumulation
     hipStream_t statsStream = nullptr;          // the stream of the last accumulation: the only work that writes the counters
+    // coverage (bbmap_cov_enable): null until enabled
+    struct CovState *cov = nullptr;
+    bool covCounted = false;        // the last batch is in the coverage state already
+};
+
+// Coverage state of a context: everything is sized by the index's scaffold table as it was at bbmap_cov_enable (`gen`).
+struct CovState {
+    int flags = 0, nscaf = 0, binsize = -1;
+    long long slots = 0, nbins = 0, gen = 0;
+    hipStream_t stream = nullptr;   // of the last accumulation or finalize
+    DevBuf covoff, len, diff[2], depth[2], recs, hist[2], totals, ws, refgc, binoff, bins[2];
+    std::vector<int> hostLen;
+    CovState() = default;
+    CovState(const CovState &) = delete;
+    ~CovState() {
+        for (DevBuf *b : {&covoff, &len, &diff[0], &diff[1], &depth[0], &depth[1], &recs, &hist[0], &hist[1], &totals, &ws, &refgc, &binoff,
+                          &bins[0], &bins[1]})
+            b->release();
+    }
 };
 
 // a device array of the context's that lives until bbmap_destroy

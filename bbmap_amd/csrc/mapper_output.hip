@@ -1,5 +1,5 @@
 // What reads a finished batch of the mapper (mapper_host.hip maps it): packed site lists, the host-buffer form of the batch call, the
-// log and final records, scaffold records, SAM records, run statistics.
+// log and final records, scaffold records, SAM records, run statistics, coverage.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -7,6 +7,9 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include <memory>
+
+#include "coverage.h"
 #include "mapper_ctx.h"
 #include "run_stats.h"
 #include "sam_records.h"
@@ -356,6 +359,157 @@ extern "C" int bbmap_set_adaptive(bbmap_ctx *c, int32_t flags) {
 extern "C" int bbmap_set_truth(bbmap_ctx *c, const bbmap_truth *truth) {
     if (!c) return bbfail(BBMAP_E_ARG, "bbmap_set_truth: null context");
     c->truthNext = truth;
+    return BBMAP_OK;
+}
+
+// ---- coverage (coverage.hip): thin wrappers over the raw calls' launches
+static const int COV_FLAGS = BBMAP_COV_START_ONLY | BBMAP_COV_EXCLUDE_DELETIONS | BBMAP_COV_STRANDED | BBMAP_COV_32BIT;
+
+extern "C" int bbmap_cov_enable(bbmap_ctx *c, int32_t flags) {
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_cov_enable: null context");
+    if (!c->S.finalStage) return bbfail(BBMAP_E_ARG, "bbmap_cov_enable: the context runs without the final stage (bbmap_config.finalStage)");
+    const bbscaf::Table T = c->index->scaf;
+    if (!T.off) return bbfail(BBMAP_E_ARG, "bbmap_cov_enable: the index has no scaffold table (bbidx_set_scaffolds)");
+    if (flags & ~COV_FLAGS) return bbfail(BBMAP_E_ARG, "bbmap_cov_enable: unknown flag bits");
+    if (c->cov) {
+        if (c->cov->flags != flags) return bbfail(BBMAP_E_ARG, "bbmap_cov_enable: coverage is enabled already with other flags");
+        if (c->cov->gen != c->index->scafGen) return bbfail(BBMAP_E_ARG, "bbmap_cov_enable: the scaffold table has been replaced since coverage was enabled");
+        return BBMAP_OK;
+    }
+    BBHIP(hipSetDevice(c->cfg.device));
+    std::unique_ptr<CovState> v(new CovState);
+    v->flags = flags; v->gen = c->index->scafGen;
+    std::vector<int> off((size_t)T.nchroms + 2);
+    BBHIP(hipMemcpy(off.data(), T.off, off.size() * 4, hipMemcpyDeviceToHost));
+    v->nscaf = off[(size_t)T.nchroms + 1];
+    const size_t ns = (size_t)v->nscaf;
+    v->hostLen.resize(ns);
+    BBHIP(hipMemcpy(v->hostLen.data(), T.len, ns * 4, hipMemcpyDeviceToHost));
+    std::vector<int64_t> covoff(ns + 1);
+    BBTRY(bbpipe_coverage_layout(v->nscaf, v->hostLen.data(), 0, covoff.data(), nullptr));
+    v->slots = covoff[ns];
+    if (v->slots > (1ll << 32)) return bbfail(BBMAP_E_ARG, "bbmap_cov_enable: more than 2^32 reference bases");
+    const int strands = flags & BBMAP_COV_STRANDED ? 2 : 1;
+    const size_t slots = (size_t)v->slots, hb = (size_t)bbcov::hist_bins(flags);
+    if (v->covoff.grow((ns + 1) * 8) != hipSuccess || v->binoff.grow((ns + 1) * 8) != hipSuccess || v->recs.grow(ns * sizeof(bbmap_covrec)) != hipSuccess ||
+        v->refgc.grow(ns * 32) != hipSuccess || v->totals.grow(sizeof(bbmap_covtotals)) != hipSuccess ||
+        v->ws.grow((size_t)bbcov::workspace_bytes(v->nscaf, v->slots)) != hipSuccess)
+        return bbfail(BBMAP_E_NOMEM, "bbmap_cov_enable: device allocation failed");
+    for (int t = 0; t < strands; t++)
+        if (v->diff[t].grow(slots * 4) != hipSuccess || v->depth[t].grow(slots * (flags & BBMAP_COV_32BIT ? 4 : 2)) != hipSuccess ||
+            v->hist[t].grow(hb * 8) != hipSuccess)
+            return bbfail(BBMAP_E_NOMEM, "bbmap_cov_enable: device allocation failed (4 + 2 or 4 bytes per reference base and strand)");
+    BBHIP(hipMemcpy(v->covoff.p, covoff.data(), (ns + 1) * 8, hipMemcpyHostToDevice));
+    for (int t = 0; t < strands; t++) BBHIP(hipMemset(v->diff[t].p, 0, slots * 4));
+    BBHIP(hipMemset(v->recs.p, 0, ns * sizeof(bbmap_covrec)));
+    BBHIP(hipMemset(v->totals.p, 0, sizeof(bbmap_covtotals)));
+    BBHIP(bbcov::launch_refgc(T, v->nscaf, c->d_chromArr, v->refgc.as<long long>(), nullptr));      // once per enable, not per finalize
+    BBHIP(hipStreamSynchronize(nullptr));
+    c->cov = v.release();
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_add_coverage(bbmap_ctx *c, void *stream_) {
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_add_coverage: null context");
+    if (!c->cov) return bbfail(BBMAP_E_ARG, "bbmap_add_coverage: coverage is not enabled (bbmap_cov_enable)");
+    if (!c->ran) return bbfail(BBMAP_E_ARG, "bbmap_add_coverage: no batch has been mapped yet");
+    if (c->covCounted) return bbfail(BBMAP_E_ARG, "bbmap_add_coverage: the last batch has been counted already");
+    if (!c->batch.reads || !c->batch.bases || c->batch.n_reads != c->stats.reads)
+        return bbfail(BBMAP_E_ARG, "bbmap_add_coverage: the context does not hold the last batch's reads");
+    CovState *v = c->cov;
+    if (v->gen != c->index->scafGen || !c->index->scaf.off)
+        return bbfail(BBMAP_E_ARG, "bbmap_add_coverage: the scaffold table has been replaced since coverage was enabled");
+    hipStream_t stream = (hipStream_t)stream_;
+    BBHIP(hipSetDevice(c->cfg.device));
+    const long long n = c->stats.reads;
+    bbcov::AddArgs a = {};
+    a.reads = c->batch.reads; a.bases = c->batch.bases; a.fin = c->d_final; a.pool = c->d_pool;
+    BBTRY(tier_index(c, stream, n, &a.tierIdx));
+    if (a.tierIdx) { a.tfin = c->tier->d_final; a.tpool = c->tier->d_pool; a.nsites = c->d_mcount; }
+    a.n = n; a.paired = c->cfg.paired; a.flags = v->flags;
+    a.T = c->index->scaf; a.nscaf = v->nscaf; a.covoff = v->covoff.as<long long>();
+    a.diff[0] = v->diff[0].as<int>(); a.diff[1] = v->diff[1].as<int>();
+    a.recs = v->recs.as<unsigned long long>(); a.totals = v->totals.as<unsigned long long>();
+    BBHIP(bbcov::launch_add(a, stream));
+    c->covCounted = true; v->stream = stream;
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_cov_finalize(bbmap_ctx *c, void *stream_, int32_t binsize, bbmap_cov_view *out) {
+    if (!c || !out) return bbfail(BBMAP_E_ARG, "bbmap_cov_finalize: null argument");
+    if (!c->cov) return bbfail(BBMAP_E_ARG, "bbmap_cov_finalize: coverage is not enabled (bbmap_cov_enable)");
+    if (binsize < 0) return bbfail(BBMAP_E_ARG, "bbmap_cov_finalize: binsize must be >= 0");
+    CovState *v = c->cov;
+    if (v->gen != c->index->scafGen || !c->index->scaf.off)
+        return bbfail(BBMAP_E_ARG, "bbmap_cov_finalize: the scaffold table has been replaced since coverage was enabled");
+    hipStream_t stream = (hipStream_t)stream_;
+    BBHIP(hipSetDevice(c->cfg.device));
+    const int strands = v->flags & BBMAP_COV_STRANDED ? 2 : 1;
+    const size_t ns = (size_t)v->nscaf;
+    if (stream != v->stream) BBHIP(hipStreamSynchronize(v->stream));       // behind everything added so far
+    if (binsize != v->binsize) {
+        std::vector<int64_t> binoff(ns + 1, 0);
+        BBTRY(bbpipe_coverage_layout(v->nscaf, v->hostLen.data(), binsize, nullptr, binoff.data()));
+        BBHIP(hipStreamSynchronize(stream));                               // an earlier finalize may still read the old offsets
+        for (int t = 0; t < strands; t++) BBHIP(v->bins[t].grow((size_t)binoff[ns] * 8));
+        BBHIP(hipMemcpy(v->binoff.p, binoff.data(), (ns + 1) * 8, hipMemcpyHostToDevice));
+        v->binsize = binsize; v->nbins = binoff[ns];
+    }
+    bbcov::FinArgs a = {};
+    a.flags = v->flags; a.nscaf = v->nscaf; a.slots = v->slots; a.len = c->index->scaf.len; a.covoff = v->covoff.as<long long>();
+    for (int t = 0; t < strands; t++) {
+        a.diff[t] = v->diff[t].as<int>(); a.depth[t] = v->depth[t].p;
+        a.hist[t] = v->hist[t].as<unsigned long long>(); a.bins[t] = v->bins[t].as<unsigned long long>();
+    }
+    a.recs = v->recs.as<unsigned long long>(); a.refgc = v->refgc.as<long long>();
+    a.binsize = binsize; a.binoff = v->binoff.as<long long>(); a.nbins = v->nbins;
+    a.totals = v->totals.as<unsigned long long>(); a.ws = v->ws.p;
+    BBHIP(bbcov::launch_finalize(a, stream));
+    v->stream = stream;
+    memset(out, 0, sizeof *out);
+    out->flags = v->flags; out->nscaf = v->nscaf; out->binsize = binsize; out->depth_bytes = v->flags & BBMAP_COV_32BIT ? 4 : 2;
+    out->slots = v->slots; out->hist_bins = bbcov::hist_bins(v->flags); out->nbins = v->nbins;
+    out->covoff = v->covoff.as<int64_t>(); out->recs = v->recs.as<bbmap_covrec>();
+    out->binoff = v->binoff.as<int64_t>(); out->totals = v->totals.as<bbmap_covtotals>();
+    for (int t = 0; t < strands; t++) { out->depth[t] = v->depth[t].p; out->hist[t] = v->hist[t].as<int64_t>(); out->bins[t] = v->bins[t].as<int64_t>(); }
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_get_coverage(bbmap_ctx *c, int32_t binsize, bbmap_covrec *recs_out, int64_t nscaf_cap, bbmap_covtotals *totals_out,
+                                  int64_t *hist_out, int64_t hist_cap, void *depth_out, int64_t depth_cap, int64_t *bins_out, int64_t bins_cap,
+                                  bbmap_cov_view *view_out) {
+    if (!c || !recs_out || !totals_out) return bbfail(BBMAP_E_ARG, "bbmap_get_coverage: null argument");
+    if (nscaf_cap < 0 || hist_cap < 0 || depth_cap < 0 || bins_cap < 0 || (hist_cap > 0 && !hist_out) || (depth_cap > 0 && !depth_out) ||
+        (bins_cap > 0 && !bins_out))
+        return bbfail(BBMAP_E_ARG, "bbmap_get_coverage: bad buffer");
+    if (c->cov && nscaf_cap < c->cov->nscaf) return bbfail(BBMAP_E_ARG, "bbmap_get_coverage: recs_out holds fewer records than the table has scaffolds");
+    bbmap_cov_view w;
+    BBTRY(bbmap_cov_finalize(c, nullptr, binsize, &w));
+    BBHIP(hipStreamSynchronize(nullptr));
+    if (view_out) *view_out = w;
+    const int strands = w.flags & BBMAP_COV_STRANDED ? 2 : 1;
+    BBHIP(hipMemcpy(recs_out, w.recs, (size_t)w.nscaf * sizeof(bbmap_covrec), hipMemcpyDeviceToHost));
+    BBHIP(hipMemcpy(totals_out, w.totals, sizeof(bbmap_covtotals), hipMemcpyDeviceToHost));
+    const size_t db = (size_t)w.slots * (size_t)w.depth_bytes;
+    for (int t = 0; t < strands; t++) {
+        if (hist_cap >= w.hist_bins) BBHIP(hipMemcpy(hist_out + (size_t)t * (size_t)hist_cap, w.hist[t], (size_t)w.hist_bins * 8, hipMemcpyDeviceToHost));
+        if ((size_t)depth_cap >= db && db > 0) BBHIP(hipMemcpy((char *)depth_out + (size_t)t * (size_t)depth_cap, w.depth[t], db, hipMemcpyDeviceToHost));
+        if (w.nbins > 0 && bins_cap >= w.nbins) BBHIP(hipMemcpy(bins_out + (size_t)t * (size_t)bins_cap, w.bins[t], (size_t)w.nbins * 8, hipMemcpyDeviceToHost));
+    }
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_reset_coverage(bbmap_ctx *c) {
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_reset_coverage: null context");
+    CovState *v = c->cov;
+    if (!v) return BBMAP_OK;
+    BBHIP(hipSetDevice(c->cfg.device));
+    const int strands = v->flags & BBMAP_COV_STRANDED ? 2 : 1;
+    for (int t = 0; t < strands; t++) BBHIP(hipMemsetAsync(v->diff[t].p, 0, (size_t)v->slots * 4, v->stream));      // behind the last accumulation
+    BBHIP(hipMemsetAsync(v->recs.p, 0, (size_t)v->nscaf * sizeof(bbmap_covrec), v->stream));
+    BBHIP(hipMemsetAsync(v->totals.p, 0, sizeof(bbmap_covtotals), v->stream));
+    BBHIP(hipStreamSynchronize(v->stream));
+    c->covCounted = false;          // the state no longer holds the batch the context still has
     return BBMAP_OK;
 }
 

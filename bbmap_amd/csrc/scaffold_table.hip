@@ -14,6 +14,7 @@ static void clear_table(bbidx_ctx *c) {
     c->scafBuf = nullptr;
     c->scaf = bbscaf::Table{};
     c->scafFilter = false;
+    c->scafGen++;
 }
 
 extern "C" int bbidx_set_scaffolds(bbidx_ctx *c, int32_t nchroms, const int32_t *counts, const int32_t *const *locs,

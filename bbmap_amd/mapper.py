@@ -388,6 +388,64 @@ class Mapper:
         _lib.check(self.L.bbmap_get_adaptive_state(self.h, C.byref(a), C.byref(r)), "bbmap_get_adaptive_state")
         return a.value, r.value
 
+    def enable_coverage(self, flags=0):
+        """bbmap_cov_enable: allocates the coverage state for the index's scaffold table (flags: bbmap_amd.coverage.COV_*)."""
+        self.L.bbmap_cov_enable.argtypes = [C.c_void_p, C.c_int32]
+        self.L.bbmap_cov_enable.restype = C.c_int
+        _lib.check(self.L.bbmap_cov_enable(self.h, int(flags)), "bbmap_cov_enable")
+
+    def add_coverage(self):
+        """bbmap_add_coverage: adds the last step, overflow tier included.  A second call for one step raises."""
+        self.L.bbmap_add_coverage.argtypes = [C.c_void_p, C.c_void_p]
+        self.L.bbmap_add_coverage.restype = C.c_int
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(self.L.bbmap_add_coverage(self.h, C.c_void_p(stream)), "bbmap_add_coverage")
+
+    def coverage(self, binsize=1000):
+        """bbmap_cov_finalize: a snapshot of everything added so far as a bbmap_amd.coverage.Coverage (numpy arrays)."""
+        from . import coverage as V
+        self.L.bbmap_cov_finalize.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(V.bbmap_cov_view)]
+        self.L.bbmap_cov_finalize.restype = C.c_int
+        w = V.bbmap_cov_view()
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(self.L.bbmap_cov_finalize(self.h, C.c_void_p(stream), int(binsize), C.byref(w)), "bbmap_cov_finalize")
+        torch.cuda.current_stream().synchronize()
+        strands = 2 if w.flags & V.COV_STRANDED else 1
+        ddt = np.int32 if w.depth_bytes == 4 else np.uint16
+        arr = lambda p, count, dt: _copy(p, count * np.dtype(dt).itemsize, self.dev).view(dt)
+        return V.Coverage(w.flags, arr(w.recs, w.nscaf, V.COVREC_DTYPE), arr(w.totals, 1, V.COVTOTALS_DTYPE)[0], arr(w.covoff, w.nscaf + 1, np.int64),
+                          [arr(w.depth[t], w.slots, ddt) for t in range(strands)], [arr(w.hist[t], w.hist_bins, np.int64) for t in range(strands)],
+                          int(binsize), arr(w.binoff, w.nscaf + 1, np.int64) if binsize > 0 else None,
+                          [arr(w.bins[t], w.nbins, np.int64) for t in range(strands)] if binsize > 0 else None,
+                          getattr(self.di, "scaffold_names", None))
+
+    def coverage_host(self, binsize=1000):
+        """bbmap_get_coverage, the host-buffer form: sizes first, then everything into buffers that hold it.  Returns a Coverage
+        without covoff-independent extras (covoff and binoff are bbmap_amd.coverage.layout's)."""
+        from . import coverage as V
+        self.L.bbmap_get_coverage.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                              C.c_int64, C.c_void_p, C.c_int64, C.POINTER(V.bbmap_cov_view)]
+        self.L.bbmap_get_coverage.restype = C.c_int
+        nscaf = len(self.di.scaffold_names)
+        recs, totals, w = np.zeros(nscaf, V.COVREC_DTYPE), np.zeros(1, V.COVTOTALS_DTYPE), V.bbmap_cov_view()
+        _lib.check(self.L.bbmap_get_coverage(self.h, int(binsize), recs.ctypes.data, nscaf, totals.ctypes.data, None, 0, None, 0, None, 0,
+                                             C.byref(w)), "bbmap_get_coverage")
+        strands = 2 if w.flags & V.COV_STRANDED else 1
+        hist = np.zeros((strands, w.hist_bins), np.int64)
+        depth = np.zeros((strands, w.slots), np.int32 if w.depth_bytes == 4 else np.uint16)
+        bins = np.zeros((strands, max(1, w.nbins)), np.int64)
+        _lib.check(self.L.bbmap_get_coverage(self.h, int(binsize), recs.ctypes.data, nscaf, totals.ctypes.data, hist.ctypes.data, hist.shape[1],
+                                             depth.ctypes.data, depth.shape[1] * depth.itemsize, bins.ctypes.data, bins.shape[1], C.byref(w)),
+                   "bbmap_get_coverage")
+        covoff, binoff = V.layout(recs["length"].astype(np.int32), binsize)
+        return V.Coverage(w.flags, recs, totals[0], covoff, list(depth), list(hist), int(binsize), binoff,
+                          [b[:w.nbins] for b in bins] if binsize > 0 else None, self.di.scaffold_names)
+
+    def reset_coverage(self):
+        self.L.bbmap_reset_coverage.argtypes = [C.c_void_p]
+        self.L.bbmap_reset_coverage.restype = C.c_int
+        _lib.check(self.L.bbmap_reset_coverage(self.h), "bbmap_reset_coverage")
+
     def pack_sites(self, counts, offsets, packed):
         """The last step's site lists without their empty slots (bbmap_pack_sites_device), enqueued on the current stream:
         counts int32[n+1], offsets int64[n+1], packed uint8[cap_records * 128] -- device tensors of the caller's."""

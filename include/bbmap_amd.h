@@ -933,6 +933,119 @@ int bbmap_set_truth(bbmap_ctx *ctx, const bbmap_truth *truth);
  * rule on the running counters, BBMAP_ADAPT_RESCUE_SKIP set; waits for the stream of the last accumulation, as bbmap_get_run_stats
  * does).  Either pointer may be NULL. */
 int bbmap_get_adaptive_state(bbmap_ctx *ctx, int32_t *averagePairDist, int32_t *rescueSkipped);
+/* =====================================================================================
+ * Coverage: covstats= / covhist= / basecov= / bincov=
+ *   The tail of AbstractMapThread.run (current/align2/AbstractMapThread.java:552-558) feeds every read to a jgi.CoveragePileup
+ *   (created in BBMap.java:401-409): CoveragePileup.processRead (current/jgi/CoveragePileup.java:784-813) -> ScaffoldCoordinates.
+ *   setFromIndex (current/stream/ScaffoldCoordinates.java:37-56) -> addCoverage (:600-663) / addCoverageIgnoringDeletions (:665-722)
+ *   -> CoverageArray2/3.incrementRange (current/dna/CoverageArray2.java:145-164, CoverageArray3.java:155-174).  Here a batch is added
+ *   on the device from its final records, match strings and reads (coverage.hip), and a finalize call turns the running state into
+ *   what writeStats (:991-1106), writeHist (:1113-1132), writeCoveragePerBase (:1143-1177), writeCoveragePerBaseBinned2 (:1276-1315),
+ *   standardDeviation (:1405-1438) and standardDeviationBinned (:1349-1402) read: depths, per-scaffold integers, the depth histogram
+ *   and bin sums.  Every figure is an integer; the float columns are the host's (bbmap_amd/coverage.py).
+ *   A read counts when it is mapped and Data.isSingleScaffold(chrom, start, stop) holds; its scaffold is
+ *   scaffoldIndex(chrom, (start + stop) / 2), start and stop become scaffold-relative and are clamped to [0, length - 1].  Java's
+ *   assertions are off in a BBMap run: a record wholly left of its scaffold moves basehits by stop - start + 1 (negative) and no depth.
+ *   Flags:
+ *     default                       INCLUDE_DELETIONS = true, what bbmap.sh always runs: +1 on [start, stop], basehits += stop - start + 1
+ *     BBMAP_COV_START_ONLY          startcov=t: +1 at start only (wins over EXCLUDE_DELETIONS, :626).  A start at or past the scaffold's
+ *                                   end adds no depth (Java: the extra slot for start == length, an exception beyond).
+ *     BBMAP_COV_EXCLUDE_DELETIONS   the class's delcov=f path (pileup.sh); bbmap.sh's own command line never reaches it, it is opt-in
+ *                                   here: the match string is walked from the CLAMPED start, m / S / N cover a base, D skips one,
+ *                                   I / X / Y / C do nothing; a record without a string adds the read counters and no depth.
+ *     BBMAP_COV_STRANDED            strand-1 reads go to a second array (the per-scaffold read counters are shared, as in writeStats)
+ *     BBMAP_COV_32BIT               depths saturate at Integer.MAX_VALUE instead of 65,535, histogram bins 0..1,000,000 instead of
+ *                                   0..65,535
+ *   Every increment is +1, so saturating at read-out, min(count, cap), equals CoverageArray's cap per increment.
+ *   Layout: global scaffold s (FASTA order, as in bbmap_scafrec) owns length[s] + 1 slots at covoff[s] (the class's arrays have
+ *   length + 1 elements too; the extra one is always 0 here and takes part in Median_fold and Std_Dev as it does there).
+ *   Out of scope: physcov, secondary-site coverage (USE_SECONDARY; BBMap passes secondary=f, BBMap.java:403), bitset mode, normcov /
+ *   normcovo, rpkm=, the low-coverage window column (USE_WINDOW), twocolumn, the concise and delta-only basecov forms, and a JNI native
+ *   for BBMapHIP.
+ * ===================================================================================== */
+enum { BBMAP_COV_START_ONLY = 1, BBMAP_COV_EXCLUDE_DELETIONS = 2, BBMAP_COV_STRANDED = 4, BBMAP_COV_32BIT = 8 };
+enum { BBMAP_COV_MAX_WAVES = 8192 };        /* wavefronts of the accumulate kernel's persistent grid (one read per wavefront and turn) */
+enum { BBMAP_COV_SCAN_TILE = 2048 };        /* slots per workgroup of the prefix sum (tile sums, scan, apply) */
+enum { BBMAP_COV_STATS_CHUNK = 65536 };     /* slots per workgroup of the passes that only read the depths: statistics, the long median's counts */
+enum { BBMAP_COV_MEDIAN_SHORT = 65536 };    /* scaffolds up to this length take the one-workgroup median, longer ones the many-workgroup one */
+enum { BBMAP_COV_HIST_LDS_BINS = 1024 };    /* depths below this are counted in a workgroup's LDS sub-histogram first */
+enum { BBMAP_COV_LDS_SCAFFOLDS = 512 };     /* tables of up to this many scaffolds: the accumulate kernel sums a workgroup's per-scaffold counters in LDS */
+typedef struct bbmap_covstrand {
+    int64_t covered;               /* positions < length with depth > 0 */
+    int64_t median;                /* element length / 2 of the length + 1 slots sorted descending (writeStats :1033-1042) */
+    int64_t max;
+    int64_t sumDepth;              /* over positions < length, of the saturated depths */
+    uint64_t sumSqLo, sumSqHi;     /* the same of their squares, a 128-bit integer */
+} bbmap_covstrand;                 /* 48 bytes */
+typedef struct bbmap_covrec {
+    int64_t length;
+    int64_t basehits, readhits, readhitsMinus, fraghits;   /* Scaffold's counters (:612-632, :719) */
+    int64_t readBases[4];          /* A C G T of the counted reads (basecount[0..3], charToNum: jgi/AssemblyStats2.java:1667-1683) */
+    int64_t refBases[4];           /* A C G T of the scaffold's own bases (ChromosomeArray.calcGC, current/dna/ChromosomeArray.java:204-209) */
+    bbmap_covstrand strand[2];     /* [1] is filled under BBMAP_COV_STRANDED */
+} bbmap_covrec;                    /* 200 bytes */
+typedef struct bbmap_covtotals { int64_t readsProcessed, mappedReads, mappedBases, refBases; } bbmap_covtotals;   /* 32 bytes */
+typedef struct bbmap_cov_view {    /* device pointers, valid until the next bbmap_cov_finalize, bbmap_reset_coverage or bbmap_destroy */
+    int32_t flags, nscaf;
+    int32_t binsize, depth_bytes;  /* bytes per depth: 2 (uint16) or 4 (int32) */
+    int64_t slots;                 /* covoff[nscaf] */
+    int64_t hist_bins;             /* 65,536 or 1,000,001 */
+    int64_t nbins;                 /* binoff[nscaf] */
+    const int64_t *covoff;         /* [nscaf + 1] */
+    const void *depth[2];          /* [slots] each; [1] NULL without BBMAP_COV_STRANDED */
+    const bbmap_covrec *recs;      /* [nscaf] */
+    const int64_t *hist[2];        /* [hist_bins] each: positions < length of EVERY scaffold by min(depth, hist_bins - 1) (writeStats leaves
+                                      out the scaffolds no read touched, whose arrays it never made: the host subtracts their lengths
+                                      from bin 0) */
+    const int64_t *binoff;         /* [nscaf + 1]: scaffold s has ceil(length / binsize) bins, the last one short */
+    const int64_t *bins[2];        /* [nbins] each: sums of the depths of a bin's positions */
+    const bbmap_covtotals *totals;
+} bbmap_cov_view;
+/* Host-side layout arithmetic: covoff (nscaf + 1 entries, covoff[s + 1] = covoff[s] + lengths[s] + 1) and, when binsize > 0 and
+ * binoff is given, binoff (nscaf + 1 entries).  Either output may be NULL.  BBMAP_E_ARG: a length < 1, nscaf < 0, binsize < 0. */
+int bbpipe_coverage_layout(int32_t nscaf, const int32_t *lengths, int32_t binsize, int64_t *covoff, int64_t *binoff);
+/* Bytes of device workspace bbpipe_coverage_finalize_device needs for a table of nscaf scaffolds and `slots` slots (< 0: bad argument). */
+int64_t bbpipe_coverage_workspace_bytes(int32_t nscaf, int64_t slots);
+/* The raw accumulate over device arrays the caller owns: reads (bases_off and len are used) with their plus-strand `bases`, one
+ * final record per read with its string in `pool` at match_off; paired: every read has a mate (fraghits moves by 1, else by 2).  The
+ * scaffold table as bbidx_set_scaffolds lays it out: scaf_off[nchroms + 2] (chromosome c's scaffolds are scaf_off[c] .. scaf_off[c + 1],
+ * c from 1), scaf_loc / scaf_len by global scaffold number, pad = interScaffoldPadding.  covoff as bbpipe_coverage_layout gives it for
+ * scaf_len; diff0 / diff1: int32[slots] difference arrays (diff1 only under BBMAP_COV_STRANDED), recs[nscaf] and totals are ADDED to
+ * (zero them first).  A mapped record whose chromosome is not 1..nchroms is not counted.  Enqueues on `stream`. */
+int bbpipe_coverage_add_device(void *stream, int64_t n_reads, int32_t paired, int32_t flags, const bbidx_read *reads, const uint8_t *bases,
+                               const bbmap_final *finals, const uint8_t *pool, int32_t nchroms, int32_t nscaf, const int32_t *scaf_off,
+                               const int32_t *scaf_loc, const int32_t *scaf_len, int32_t pad, const int64_t *covoff, int32_t *diff0,
+                               int32_t *diff1, bbmap_covrec *recs, bbmap_covtotals *totals);
+/* The raw finalize over the same arrays: a snapshot (the difference arrays and the counters in recs are only read; accumulation may go
+ * on afterwards).  Writes depth0 / depth1 (uint16[slots], or int32[slots] under BBMAP_COV_32BIT), length / refBases / strand[] of every
+ * record (refgc: int64[nscaf][4], or NULL for zeros), hist0 / hist1 (65,536 or 1,000,001 entries) and, when binsize > 0, bins0 / bins1
+ * at binoff.  totals->refBases is set.  workspace: bbpipe_coverage_workspace_bytes.  Enqueues on `stream`. */
+int bbpipe_coverage_finalize_device(void *stream, int32_t flags, int32_t nscaf, int64_t slots, const int32_t *scaf_len, const int64_t *covoff,
+                                    const int32_t *diff0, const int32_t *diff1, void *depth0, void *depth1, bbmap_covrec *recs,
+                                    const int64_t *refgc, int64_t *hist0, int64_t *hist1, int32_t binsize, const int64_t *binoff,
+                                    int64_t nbins, int64_t *bins0, int64_t *bins1, bbmap_covtotals *totals, void *workspace,
+                                    int64_t workspace_bytes);
+/* Allocates the coverage state for the index's scaffold table as it is now (4 + 2 or 4 bytes per slot and strand) and counts the
+ * reference's bases per scaffold.  A second call with the same flags over the same table changes nothing.  BBMAP_E_ARG: the context
+ * runs without the final stage, the index has no scaffold table, unknown flag bits, or coverage is enabled already with other flags
+ * or over a table that bbidx_set_scaffolds has replaced since. */
+int bbmap_cov_enable(bbmap_ctx *ctx, int32_t flags);
+/* Adds the last batch, overflow tier included; enqueues on `stream`.  BBMAP_E_ARG: coverage is not enabled, no batch has been mapped,
+ * this batch has been counted already (a second call changes nothing), or the scaffold table has been replaced. */
+int bbmap_add_coverage(bbmap_ctx *ctx, void *stream);
+/* Runs the finalize kernels on `stream` behind everything added so far; binsize 0 = no bins.  *out is filled at once, its arrays are
+ * complete when `stream` has run. */
+int bbmap_cov_finalize(bbmap_ctx *ctx, void *stream, int32_t binsize, bbmap_cov_view *out);
+/* Host form: finalizes on the null stream, waits, and copies records (nscaf_cap >= nscaf), totals and histogram(s) (hist_cap entries
+ * per strand, all or nothing) always, depths and bins only into buffers that hold them (depth_cap bytes / bins_cap entries per strand;
+ * the strands follow each other).  *view_out (optional) reports the sizes that were needed; its pointers are the device's. */
+int bbmap_get_coverage(bbmap_ctx *ctx, int32_t binsize, bbmap_covrec *recs_out, int64_t nscaf_cap, bbmap_covtotals *totals_out,
+                       int64_t *hist_out, int64_t hist_cap, void *depth_out, int64_t depth_cap, int64_t *bins_out, int64_t bins_cap,
+                       bbmap_cov_view *view_out);
+/* Zeroes everything accumulated (the reference's base counts stay); waits for the stream of the last accumulation.  The batch the
+ * context still holds counts as not added again: a bbmap_add_coverage for it is accepted. */
+int bbmap_reset_coverage(bbmap_ctx *ctx);
+
 /* The last batch's site lists without their empty slots, for a host that copies them back: counts (n_reads + 1 ints), offsets
  * (n_reads + 1 int64: exclusive prefix sums, offsets[n_reads] = total) and packed (packed_cap records) are device buffers of the
  * caller's; read r's counts[r] sites are packed[offsets[r] ...] (0 for a read without a list, a flagged one, or one the overflow
