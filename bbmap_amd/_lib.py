@@ -30,6 +30,8 @@ EXPORTS = [
     "bbmap_get_adaptive_state",
     "bbpipe_coverage_layout", "bbpipe_coverage_workspace_bytes", "bbpipe_coverage_add_device", "bbpipe_coverage_finalize_device",
     "bbmap_cov_enable", "bbmap_add_coverage", "bbmap_cov_finalize", "bbmap_get_coverage", "bbmap_reset_coverage",
+    "bbpipe_read_hist_bytes", "bbpipe_read_hist_view", "bbpipe_read_hist_add_device",
+    "bbmap_hist_enable", "bbmap_add_read_hist", "bbmap_get_read_hist_view", "bbmap_get_read_hist", "bbmap_reset_read_hist",
 ]
 
 

@@ -82,6 +82,11 @@ struct bbmap_ctx {
     // coverage (bbmap_cov_enable): null until enabled
     struct CovState *cov = nullptr;
     bool covCounted = false;        // the last batch is in the coverage state already
+    // read histograms (bbmap_hist_enable): null until enabled
+    unsigned long long *d_readHist = nullptr;
+    int rhFlags = 0;
+    bool rhCounted = false;         // the last batch is in the histograms already
+    hipStream_t rhStream = nullptr; // the stream of the last accumulation: the only work that writes the state
 };
 
 // Coverage state of a context: everything is sized by the index's scaffold table as it was at bbmap_cov_enable (`gen`).

@@ -1,5 +1,5 @@
 // What reads a finished batch of the mapper (mapper_host.hip maps it): packed site lists, the host-buffer form of the batch call, the
-// log and final records, scaffold records, SAM records, run statistics, coverage.
+// log and final records, scaffold records, SAM records, run statistics, coverage, read histograms.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -11,6 +11,7 @@
 
 #include "coverage.h"
 #include "mapper_ctx.h"
+#include "read_hist.h"
 #include "run_stats.h"
 #include "sam_records.h"
 
@@ -510,6 +511,77 @@ extern "C" int bbmap_reset_coverage(bbmap_ctx *c) {
     BBHIP(hipMemsetAsync(v->totals.p, 0, sizeof(bbmap_covtotals), v->stream));
     BBHIP(hipStreamSynchronize(v->stream));
     c->covCounted = false;          // the state no longer holds the batch the context still has
+    return BBMAP_OK;
+}
+
+// ---- read histograms (read_hist.hip): thin wrappers over the raw calls' launch
+extern "C" int bbmap_hist_enable(bbmap_ctx *c, int32_t flags) {
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_hist_enable: null context");
+    if (!c->S.finalStage) return bbfail(BBMAP_E_ARG, "bbmap_hist_enable: the context runs without the final stage (bbmap_config.finalStage)");
+    if (flags & ~BBMAP_RH_ALL) return bbfail(BBMAP_E_ARG, "bbmap_hist_enable: unknown flag bits");
+    if (!flags) return bbfail(BBMAP_E_ARG, "bbmap_hist_enable: no histogram group selected");
+    if (c->d_readHist) {
+        if (c->rhFlags != flags) return bbfail(BBMAP_E_ARG, "bbmap_hist_enable: the histograms are enabled already with other flags");
+        return BBMAP_OK;
+    }
+    BBHIP(hipSetDevice(c->cfg.device));
+    const size_t words = (size_t)bbrh::layout_of(flags).words;
+    unsigned long long *p = nullptr;
+    BBTRY(dalloc(c, &p, words));
+    BBHIP(hipMemset(p, 0, 8 * words));
+    BBHIP(hipStreamSynchronize(nullptr));                   // a first add on a non-blocking stream finds the state zeroed
+    c->d_readHist = p; c->rhFlags = flags;
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_add_read_hist(bbmap_ctx *c, void *stream_, const uint8_t *quality) {
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_add_read_hist: null context");
+    if (!c->d_readHist) return bbfail(BBMAP_E_ARG, "bbmap_add_read_hist: the histograms are not enabled (bbmap_hist_enable)");
+    if (!c->ran) return bbfail(BBMAP_E_ARG, "bbmap_add_read_hist: no batch has been mapped yet");
+    if (c->rhCounted) return bbfail(BBMAP_E_ARG, "bbmap_add_read_hist: the last batch has been counted already");
+    if (!c->batch.reads || !c->batch.bases || c->batch.n_reads != c->stats.reads)
+        return bbfail(BBMAP_E_ARG, "bbmap_add_read_hist: the context does not hold the last batch's reads");
+    hipStream_t stream = (hipStream_t)stream_;
+    BBHIP(hipSetDevice(c->cfg.device));
+    const long long n = c->stats.reads;
+    bbrh::Args a = {};
+    a.reads = c->batch.reads; a.bases = c->batch.bases; a.qual = quality; a.fin = c->d_final; a.pool = c->d_pool;
+    BBTRY(tier_index(c, stream, n, &a.tierIdx));
+    if (a.tierIdx) { a.tfin = c->tier->d_final; a.tpool = c->tier->d_pool; a.nsites = c->d_mcount; }
+    a.n = n; a.paired = c->cfg.paired; a.flags = c->rhFlags;
+    a.state = c->d_readHist;
+    BBHIP(bbrh::launch_add(a, stream));
+    c->rhCounted = true; c->rhStream = stream;
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_get_read_hist_view(bbmap_ctx *c, bbmap_readhist_view *out) {
+    if (!c || !out) return bbfail(BBMAP_E_ARG, "bbmap_get_read_hist_view: null argument");
+    if (!c->d_readHist) return bbfail(BBMAP_E_ARG, "bbmap_get_read_hist_view: the histograms are not enabled (bbmap_hist_enable)");
+    return bbpipe_read_hist_view(c->rhFlags, c->d_readHist, out);
+}
+
+extern "C" int bbmap_get_read_hist(bbmap_ctx *c, int64_t *out, int64_t cap_words, bbmap_readhist_view *view_out) {
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_get_read_hist: null context");
+    if (!c->d_readHist) return bbfail(BBMAP_E_ARG, "bbmap_get_read_hist: the histograms are not enabled (bbmap_hist_enable)");
+    if (cap_words < 0 || (cap_words > 0 && !out)) return bbfail(BBMAP_E_ARG, "bbmap_get_read_hist: bad buffer");
+    bbmap_readhist_view w;
+    BBTRY(bbpipe_read_hist_view(c->rhFlags, c->d_readHist, &w));
+    if (view_out) *view_out = w;
+    if (cap_words < w.words) return BBMAP_OK;
+    BBHIP(hipSetDevice(c->cfg.device));
+    BBHIP(hipStreamSynchronize(c->rhStream));               // the state is written on that stream only
+    BBHIP(hipMemcpy(out, c->d_readHist, 8 * (size_t)w.words, hipMemcpyDeviceToHost));
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_reset_read_hist(bbmap_ctx *c) {
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_reset_read_hist: null context");
+    if (!c->d_readHist) return BBMAP_OK;
+    BBHIP(hipSetDevice(c->cfg.device));
+    BBHIP(hipMemsetAsync(c->d_readHist, 0, 8 * (size_t)bbrh::layout_of(c->rhFlags).words, c->rhStream));      // behind the last accumulation
+    BBHIP(hipStreamSynchronize(c->rhStream));
+    c->rhCounted = false;           // the state no longer holds the batch the context still has
     return BBMAP_OK;
 }
 

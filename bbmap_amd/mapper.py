@@ -225,6 +225,7 @@ class Mapper:
             qblob = np.ascontiguousarray(quality, np.uint8).reshape(-1)
             assert qblob.size == blob.size
             q = torch.from_numpy(qblob).to(self.dev)
+        self.quality = q                    # add_read_hist()'s default
         self.reads = torch.from_numpy(recs.view(np.uint8).reshape(-1).copy()).to(self.dev)
         _, keyinfo, self.base_scores = K.make_batch_device(self.reads, self.bases[: self.total_bytes], q, kcfg or K.default_config(profile))
         self.keyinfo = keyinfo if keyinfo.numel() else torch.zeros(1, dtype=torch.int32, device=self.dev)
@@ -244,6 +245,7 @@ class Mapper:
     def load_reads(self, reads_u8):
         """reads_u8: n_reads x read_len bases; paired mode: mates interleaved (read 2p, 2p+1)."""
         assert reads_u8.size == self.total_bytes
+        self.quality = None                 # (the qualities from_reads uploaded belong to the reads it was given)
         self.bases[: self.total_bytes].copy_(torch.from_numpy(np.ascontiguousarray(reads_u8).reshape(-1)))
 
     def load_records(self, recs, bases, base_scores, keyinfo):
@@ -253,6 +255,7 @@ class Mapper:
         assert 0 < len(recs) <= self.cfg.max_reads and int(recs["len"].max()) <= self.cfg.max_read_len
         blob = np.ascontiguousarray(bases, np.uint8)
         self.n, self.total_bytes = len(recs), int(blob.size)
+        self.quality = None                 # (the qualities from_reads uploaded belong to the reads it was given)
         self.bases = torch.zeros(2 * self.total_bytes, dtype=torch.uint8, device=self.dev)
         self.bases[: self.total_bytes].copy_(torch.from_numpy(blob))
         self.base_scores = torch.from_numpy(np.ascontiguousarray(base_scores, np.int8)).to(self.dev)
@@ -266,6 +269,7 @@ class Mapper:
         batches uploads the next one while this one is mapped)."""
         stream = torch.cuda.current_stream().cuda_stream
         b = self.bases if bases is None else bases
+        self._stepped_own_bases = b is self.bases
         assert b.numel() == 2 * self.total_bytes and b.dtype == torch.uint8
         _lib.check(self.L.bbmap_map_batch_device(self.h, C.c_void_p(stream), self.n, self.reads.data_ptr(), b.data_ptr(),
                                                  self.total_bytes, self.base_scores.data_ptr(), self.keyinfo.data_ptr()),
@@ -503,3 +507,40 @@ class Mapper:
         if self.cfg.finalStage and rows is None:
             out["final"], out["final_match"] = self.final(with_match)
         return out
+
+    def enable_read_hist(self, flags=None):
+        """bbmap_hist_enable: allocates the zeroed histogram state (flags: bbmap_amd.readstats.RH_*, default all groups)."""
+        from . import readstats as R
+        self.L.bbmap_hist_enable.argtypes = [C.c_void_p, C.c_int32]
+        self.L.bbmap_hist_enable.restype = C.c_int
+        _lib.check(self.L.bbmap_hist_enable(self.h, int(R.RH_ALL if flags is None else flags)), "bbmap_hist_enable")
+
+    def add_read_hist(self, quality=None):
+        """bbmap_add_read_hist: adds the last step, overflow tier included.  quality: a device uint8 tensor laid out like the
+        batch's bases (numeric phred); default: the one from_reads uploaded, as long as the batch is still the one it was uploaded
+        with (load_reads / load_records forget it, a step over another bases buffer does not use it), else none: the
+        quality-dependent histograms then do not move.  A second call for one step raises."""
+        if quality is None and getattr(self, "_stepped_own_bases", True):
+            quality = getattr(self, "quality", None)        # (cleared by load_reads / load_records; not used for step(bases=other))
+        assert quality is None or (quality.dtype == torch.uint8 and quality.numel() >= self.total_bytes)
+        self.L.bbmap_add_read_hist.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self.L.bbmap_add_read_hist.restype = C.c_int
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(self.L.bbmap_add_read_hist(self.h, C.c_void_p(stream), None if quality is None else C.c_void_p(quality.data_ptr())),
+                   "bbmap_add_read_hist")
+
+    def read_hist(self):
+        """bbmap_get_read_hist: a host copy of everything added so far as a bbmap_amd.readstats.ReadHist."""
+        from . import readstats as R
+        self.L.bbmap_get_read_hist.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(R.bbmap_readhist_view)]
+        self.L.bbmap_get_read_hist.restype = C.c_int
+        w = R.bbmap_readhist_view()
+        _lib.check(self.L.bbmap_get_read_hist(self.h, None, 0, C.byref(w)), "bbmap_get_read_hist")
+        block = np.zeros(w.words, np.int64)
+        _lib.check(self.L.bbmap_get_read_hist(self.h, block.ctypes.data, block.size, C.byref(w)), "bbmap_get_read_hist")
+        return R.ReadHist(w.flags, block)
+
+    def reset_read_hist(self):
+        self.L.bbmap_reset_read_hist.argtypes = [C.c_void_p]
+        self.L.bbmap_reset_read_hist.restype = C.c_int
+        _lib.check(self.L.bbmap_reset_read_hist(self.h), "bbmap_reset_read_hist")

@@ -1046,6 +1046,90 @@ int bbmap_get_coverage(bbmap_ctx *ctx, int32_t binsize, bbmap_covrec *recs_out, 
  * context still holds counts as not added again: a bbmap_add_coverage for it is accepted. */
 int bbmap_reset_coverage(bbmap_ctx *ctx);
 
+/* =====================================================================================
+ * Read histograms: mhist= / qhist= / bqhist= / qchist= / bhist= / qahist= / ehist= / indelhist= / lhist= / gchist= / idhist=
+ *   align2.ReadStats as AbstractMapThread.run feeds it (current/align2/AbstractMapThread.java:478-482 before mapping, :523-529
+ *   after it): addToMatchHistogram2 (current/align2/ReadStats.java:516-576), addToQualityAccuracy (:336-387), addToErrorHistogram
+ *   (:395-399), addToIndelHistogram (:472-508), addToIdentityHistogram (:446-452, Read.identityFlat, current/stream/Read.java:
+ *   1529-1596), addToQualityHistogram2 / addToBQualityHistogram / addToQCountHistogram (:273-328), addToBaseHistogram2 (:648-664),
+ *   addToLengthHistogram (:407-411), addToGCHistogram (:413-438, usePairGC, Read.gc :2530-2542).  Accumulated on the device from
+ *   the batch's reads, their numeric phred qualities, the final records and their match strings (read_hist.hip); every figure is a
+ *   64-bit integer, so the result does not depend on the order of the adds; the float columns and the text are the host's
+ *   (bbmap_amd/readstats.py).  `mate` is the read's index within its pair (reads 2p + 1 of a paired batch are mate 1).
+ *   One flag bit per COLLECT_* switch of the class; a group that is not selected takes no memory and is not counted.
+ *   Stated deviations: a mapped read without a match string takes no part in the match histogram (Java counts its bases as N /
+ *   other); the quality-accuracy walk stops when rpos reaches the read's length (Java would throw on a string that overruns its
+ *   read) and a quality above 98 counts in bin 98; a quality above 126 counts in bin 126; the error histogram has
+ *   BBMAP_RH_MAX_POS + 1 bins and a larger count lands in the last one (Java's list grows); the float sums behind qhist= (qualSum,
+ *   qualSumDouble) are not kept, the host derives them from the position x quality table, so BBMAP_RH_QUALITY always keeps that
+ *   table.  Reads longer than BBMAP_RH_MAX_POS (the library maps none) are counted up to that position.
+ *   Out of scope: aqhist= (a per-read float32 sum in read order through log10: the host holds the qualities it read and can do it
+ *   there), timehist=, ihist= (bbmap_get_run_stats' histogram), ID_BINS_AUTO / GC_BINS_AUTO / GC_PLOT_X, trimming (TrimRead) and
+ *   the SamLine branches of pairnum, and JNI natives for BBMapHIP.
+ * ===================================================================================== */
+enum { BBMAP_RH_MATCH = 1,         /* mhist=: matchSum subSum delSum insSum nSum clipSum otherSum, [7][2][BBMAP_RH_MAXLEN] */
+       BBMAP_RH_QUALITY = 2,       /* qhist= / bqhist= / qchist=: qualLength [2][MAXLEN], bqualHist [2][MAXLEN][127], qcountHist [2][127] */
+       BBMAP_RH_BASE = 4,          /* bhist=: baseHist [2][5][BBMAP_RH_MAX_POS], slot 0 = N or other, 1-4 = A C G T */
+       BBMAP_RH_ACCURACY = 8,      /* qahist=: qualMatch qualSub qualIns qualDel, [4][99] */
+       BBMAP_RH_INDEL = 16,        /* indelhist=: insHist [1001], delHist [1000], delHist2 [10001] */
+       BBMAP_RH_ERROR = 32,        /* ehist=: [BBMAP_RH_MAX_POS + 1] */
+       BBMAP_RH_LENGTH = 64,       /* lhist=: [BBMAP_RH_MAX_POS + 1] */
+       BBMAP_RH_GC = 128,          /* gchist=: gcHist [101], then gcMaxReadLen */
+       BBMAP_RH_IDENTITY = 256,    /* idhist=: idHist [101], idBaseHist [101], then idMaxReadLen */
+       BBMAP_RH_ALL = 511 };
+enum { BBMAP_RH_MAXLEN = 6000, BBMAP_RH_MAXINSLEN = 1000, BBMAP_RH_MAXDELLEN = 1000, BBMAP_RH_MAXDELLEN2 = 1000000, BBMAP_RH_GC_BINS = 100,
+       BBMAP_RH_ID_BINS = 100 };   /* ReadStats.java:1312-1321 */
+enum { BBMAP_RH_MAX_POS = 6016 };          /* the library's longest read (BBIDX_PACBIO_MAX_READ_LEN): positions of bhist, bins of lhist / ehist */
+enum { BBMAP_RH_QUAL_BINS = 127, BBMAP_RH_ACC_BINS = 99, BBMAP_RH_DEL2_BINS = BBMAP_RH_MAXDELLEN2 / 100 + 1 };
+/* the accumulate kernel's tiles: what a workgroup counts in its LDS (32-bit counters) before it adds to the state */
+enum { BBMAP_RH_MAX_BLOCKS = 256 };        /* workgroups of the persistent grid (16 wavefronts each, one pair or single read per wavefront and turn) */
+enum { BBMAP_RH_CHUNK_UNITS = 2048 };      /* pairs (single reads) a workgroup counts between two flushes of its LDS counters */
+enum { BBMAP_RH_POS_TILE = 256 };          /* positions below this: the per-position arrays of mhist / bhist / qualLength / bqualHist */
+enum { BBMAP_RH_QUAL_TILE = 44 };          /* qualities below this (and positions below the tile): bqualHist's LDS sub-table */
+enum { BBMAP_RH_ERR_LDS_BINS = 256, BBMAP_RH_LEN_LDS_BINS = 512, BBMAP_RH_DEL2_LDS_BINS = 64 };
+typedef struct bbmap_readhist_view {       /* device pointers into one block of `words` int64; NULL for a group that is not selected */
+    int32_t flags, reserved;
+    int64_t words;
+    const int64_t *state;                  /* the block: every pointer below is state + an offset that depends on flags only */
+    const int64_t *match;                  /* [7][2][MAXLEN]: match, sub, del, ins, N, clip, other */
+    const int64_t *qual_length;            /* [2][MAXLEN]: reads by min(len, MAXLEN) - 1 (the writer turns it into a suffix sum) */
+    const int64_t *bqual;                  /* [2][MAXLEN][127] */
+    const int64_t *qcount;                 /* [2][127], over ALL bases of a read */
+    const int64_t *base;                   /* [2][5][MAX_POS] */
+    const int64_t *accuracy;               /* [4][99]: match, sub, ins, del */
+    const int64_t *ins, *del, *del2;       /* [1001], [1000], [10001] */
+    const int64_t *error;                  /* [MAX_POS + 1] */
+    const int64_t *length;                 /* [MAX_POS + 1] */
+    const int64_t *gc;                     /* [101], then gcMaxReadLen (0 = nothing counted; the class starts at 1) */
+    const int64_t *identity;               /* idHist [101], idBaseHist [101], then idMaxReadLen */
+} bbmap_readhist_view;
+/* Bytes of the state for these groups (< 0: unknown flag bits). */
+int64_t bbpipe_read_hist_bytes(int32_t flags);
+/* Where the arrays of a state block lie (pure arithmetic, no device call). */
+int bbpipe_read_hist_view(int32_t flags, const void *state, bbmap_readhist_view *out);
+/* The raw form over device arrays the caller owns: reads (bases_off, len), the bases blob in plus-strand form, quality laid out like
+ * bases (numeric phred, one byte per base) or NULL (the quality-dependent histograms then do not move), one final record per read
+ * with its long-format string in `pool` at match_off.  paired: reads 2p and 2p + 1 are mates.  ADDS to `state`
+ * (bbpipe_read_hist_bytes(flags) bytes; zero it first).  Enqueues on `stream`. */
+int bbpipe_read_hist_add_device(void *stream, int64_t n_reads, int32_t paired, int32_t flags, const bbidx_read *reads, const uint8_t *bases,
+                                const uint8_t *quality, const bbmap_final *finals, const uint8_t *pool, void *state);
+/* Allocates the zeroed state.  A second call with the same flags changes nothing.  BBMAP_E_ARG: the context runs without the final
+ * stage, unknown flag bits or none, or the histograms are enabled already with other flags. */
+int bbmap_hist_enable(bbmap_ctx *ctx, int32_t flags);
+/* Adds the last batch, overflow tier included; enqueues on `stream`.  quality: a device array laid out like the batch's bases, or
+ * NULL.  BBMAP_E_ARG: not enabled, no batch has been mapped, or this batch has been added already. */
+int bbmap_add_read_hist(bbmap_ctx *ctx, void *stream, const uint8_t *quality);
+/* The state as it is on the device (not synchronised: order your reads behind the stream of the last accumulation). */
+int bbmap_get_read_hist_view(bbmap_ctx *ctx, bbmap_readhist_view *out);
+/* Host copy: waits for the stream of the last accumulation (which must still exist) and copies the block into out (cap_words int64;
+ * nothing is copied into a buffer that is too small).  *view_out (optional): the device view; an array's offset in `out` is its
+ * pointer minus view_out->state. */
+int bbmap_get_read_hist(bbmap_ctx *ctx, int64_t *out, int64_t cap_words, bbmap_readhist_view *view_out);
+/* Zeroes the state behind the last accumulation, on its stream, and waits for that stream.  The batch the context still holds
+ * counts as not added again.  Only the stream of the LAST add is known: adds between two resets (and before a host copy) go on
+ * one stream, or the caller orders them. */
+int bbmap_reset_read_hist(bbmap_ctx *ctx);
+
 /* The last batch's site lists without their empty slots, for a host that copies them back: counts (n_reads + 1 ints), offsets
  * (n_reads + 1 int64: exclusive prefix sums, offsets[n_reads] = total) and packed (packed_cap records) are device buffers of the
  * caller's; read r's counts[r] sites are packed[offsets[r] ...] (0 for a read without a list, a flagged one, or one the overflow
