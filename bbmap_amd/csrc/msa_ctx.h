@@ -94,3 +94,5 @@ int bbmsa_last_route_flags(const bbmsa_ctx *c);
 // msa_legacy.hip: persistent buffers, stream and the call combiner of a BBMSA_LEGACY_ONLY context (c->d_matrix / d_limits exist)
 int bbmsa_legacy_create(bbmsa_ctx *c);
 void bbmsa_legacy_destroy(bbmsa_ctx *c);
+// rows per lane of the last matrix-materialising launch (0: none yet) and the set of values launched so far (bit r)
+void bbmsa_legacy_rows_per_lane(bbmsa_ctx *c, int *last, int *mask);

@@ -501,6 +501,19 @@ extern "C" int bbmsa_last_route(bbmsa_ctx *c, int64_t *route8) {
     return BBMAP_OK;
 }
 
+extern "C" int bbmsa_geometry(bbmsa_ctx *c, int32_t *geo4) {
+    if (!c || !geo4) return bbfail(BBMAP_E_ARG, "bbmsa_geometry: null argument");
+    geo4[0] = geo4[1] = geo4[2] = geo4[3] = 0;
+    if (c->legacy) {
+        int last = 0, mask = 0;
+        bbmsa_legacy_rows_per_lane(c, &last, &mask);
+        geo4[0] = 64; geo4[1] = last; geo4[2] = c->cfg.maxColumns; geo4[3] = mask;
+    } else if (c->scheme == BBMSA_SCHEME_11TS) {
+        geo4[0] = c->G; geo4[1] = c->R; geo4[2] = c->fastCols; geo4[3] = c->wideBlocks > 0 ? c->wideR : 0;
+    }
+    return BBMAP_OK;
+}
+
 extern "C" int bbmsa_align_batch(bbmsa_ctx *c, int64_t n_jobs, const bbmsa_job *jobs,
                                  const uint8_t *reads, int64_t reads_bytes,
                                  const uint8_t *refs, int64_t refs_bytes,

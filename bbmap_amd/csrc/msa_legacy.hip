@@ -75,6 +75,7 @@ struct bbmsa_legacy {
     bool wave;                                           // false: every fill goes to the generic kernel (9PacBio scheme)
     // statistics
     long long calls, launches, handed;
+    int lastR, rMask;                               // rows per lane of the last wavefront launch, and every value launched so far (bit r)
     long long nsWave, nsHanded, nsWaitReaders;      // leader time: first synchronisation, hand-over pass, waiting for collectors
 };
 
@@ -158,6 +159,7 @@ int run_batch(bbmsa_ctx *c, Batch &b) {
         int maxLen = 1;
         for (int i = 0; i < n; i++) if (b.jobs()[i].read_len > maxLen) maxLen = b.jobs()[i].read_len;
         const int R = (maxLen + 63) / 64;
+        S->lastR = R; S->rMask |= 1 << R;
         BBHIP(hipLaunchKernel(bbmsa::fast_kernel_mat_for(R, c->banded), dim3((unsigned)blocks), dim3(64), args, (size_t)S->ldsBytes, st));
         BBHIP(hipMemcpyAsync(b.h_counters, b.d_counters, 64, hipMemcpyDeviceToHost, st));
         BBHIP(hipMemcpyAsync(b.h_slow, b.d_slow, (size_t)n * 4, hipMemcpyDeviceToHost, st));
@@ -246,7 +248,7 @@ int bbmsa_legacy_create(bbmsa_ctx *c) {
     bbmsa_legacy *S = new (std::nothrow) bbmsa_legacy();
     if (!S) return bbfail(BBMAP_E_NOMEM, "bbmsa_create: out of host memory");
     c->legacy = S;
-    S->open = 0; S->leaderActive = false; S->nextGen = 1; S->calls = S->launches = S->handed = 0; S->nsWave = S->nsHanded = S->nsWaitReaders = 0;
+    S->open = 0; S->leaderActive = false; S->nextGen = 1; S->calls = S->launches = S->handed = 0; S->lastR = S->rMask = 0; S->nsWave = S->nsHanded = S->nsWaitReaders = 0;
     S->stream = nullptr; S->d_dir = nullptr;
     memset(S->B, 0, sizeof S->B);
     const int maxRows = c->cfg.maxRows, maxCols = c->cfg.maxColumns;
@@ -403,6 +405,11 @@ extern "C" int bbmsa_fill_packed(bbmsa_ctx *c, const uint8_t *read, int32_t read
     const int rc = bbmsa_fill_submit(c, read, read_len, ref, ref_len, refStartLoc, refEndLoc, minScore, mode, result5, iterations, &t);
     if (rc != BBMAP_OK) return rc;
     return bbmsa_fill_collect(c, &t, packed, nullptr, nullptr);
+}
+
+void bbmsa_legacy_rows_per_lane(bbmsa_ctx *c, int *last, int *mask) {
+    std::lock_guard<std::mutex> g(c->legacy->mu);
+    *last = c->legacy->lastR; *mask = c->legacy->rMask;
 }
 
 extern "C" int bbmsa_legacy_stats(bbmsa_ctx *c, int64_t *stats6) {

@@ -53,7 +53,7 @@ class MSAContext:
         h = C.c_void_p()
         _lib.check(self.L.bbmsa_create(C.byref(cfg), C.byref(h)), "bbmsa_create")
         self.h = h
-        self.maxRows, self.maxColumns = maxRows, maxColumns
+        self.maxRows, self.maxColumns, self.legacy = maxRows, maxColumns, legacy
 
     def close(self):
         if getattr(self, "h", None):
@@ -162,6 +162,16 @@ class MSAContext:
         _lib.check(self.L.bbmsa_last_route(self.h, r), "bbmsa_last_route")
         return {"narrow": bool(r[0]), "sorted": bool(r[1]), "latency": bool(r[2]), "wide_pass": bool(r[3]), "indirect": bool(r[4]),
                 "first_handed_on": r[5], "wide_handed_on": r[6], "narrow_finished": r[7]}
+
+    def geometry(self):
+        """Which build of the wavefront kernel the context launches (bbmsa_geometry).  A batch context: lanes per job, rows per
+        lane, columns of the first pass's buffer, rows per lane of the wide pass (0: none).  A legacy context: rows per lane of
+        its last launch (0: none yet) and the set of rows-per-lane values it has launched so far."""
+        g = (C.c_int32 * 4)()
+        _lib.check(self.L.bbmsa_geometry(self.h, g), "bbmsa_geometry")
+        if self.legacy:
+            return {"lanes": g[0], "rows_per_lane": g[1], "columns": g[2], "launched": {r for r in range(1, 32) if g[3] >> r & 1}}
+        return {"lanes": g[0], "rows_per_lane": g[1], "fast_cols": g[2], "wide_rows_per_lane": g[3]}
 
     def last_counts(self):
         """{narrow: finished by the one-job-per-lane kernel, narrow_left: its candidates handed on, wave: jobs of the

@@ -207,6 +207,11 @@ int bbmsa_last_counts(bbmsa_ctx *ctx, int64_t *counts4);
  * jobs the first pass handed on (9PacBio: the strip kernel to the generic kernel), jobs the wide pass handed to the generic
  * kernel, jobs the band kernel finished}.  Waits for the launch sequence to finish. */
 int bbmsa_last_route(bbmsa_ctx *ctx, int64_t *route8);
+/* Which build of the wavefront kernel the context launches: geo4 = {lanes per job, rows per lane of the first pass, columns of
+ * the first pass's buffer, rows per lane of the wide pass (0: no wide pass)}.  A BBMSA_LEGACY_ONLY context launches one fill per
+ * wavefront with the rows per lane its longest read of the launch asks for: geo4 = {64, rows per lane of the last launch (0: none
+ * yet), maxColumns, bit r set for every rows-per-lane value r launched so far}.  The 9PacBio scheme has no such geometry: zeros. */
+int bbmsa_geometry(bbmsa_ctx *ctx, int32_t *geo4);
 
 /* =====================================================================================
  * BandedAligner (unit-cost edit distance in a diagonal band)

@@ -54,6 +54,19 @@ static int tables_ready = 0;
 static inline int imax(int a, int b) { return a > b ? a : b; }
 static inline int imin(int a, int b) { return a < b ? a : b; }
 
+/* The reference's arrays hold NTAB entries, enough for the matrices it builds (601 rows for this aligner); an index past them
+ * throws there.  The restatement also serves longer reads (up to 640 rows on the device), so a streak or a count of needed
+ * insertions beyond the table keeps the last tier (INS4 / SUB3) -- what orc_msa_new does for column 0 and what the closed forms of
+ * the deletion costs do anyway -- instead of reading past the array. */
+static inline int32_t ins_off(int i) { return T_INSoff[i < NTAB ? i : NTAB - 1]; }
+static inline int32_t sub_off(int i) { return T_SUBoff[i < NTAB ? i : NTAB - 1]; }
+static inline int32_t sub_pts(int i) { return T_SUB[i < NTAB ? i : NTAB - 1]; }
+static inline int32_t ins_off_c(int i) {
+    if (i < NTAB) return T_INSoff_C[i];
+    const long long s = (long long)T_INSoff_C[NTAB - 1] + (long long)(i - (NTAB - 1)) * SH(PTS_INS4);
+    return s < K_MINOFF_SCORE ? K_MINOFF_SCORE : (int32_t)s;
+}
+
 /* MultiStateAligner11tsJNI.java:1576-1625 ; dna/AminoAcid.java:614-624 */
 static void build_tables(void) {
     if (tables_ready) return;
@@ -141,7 +154,7 @@ int32_t orc_calc_del_score_offset(int len) {
 int32_t orc_calc_ins_score_offset(int len) {
     if (len <= 0) return 0;
     build_tables();
-    return T_INSoff_C[len];               /* AFFINE_ARRAYS==1 branch, :342-343 */
+    return ins_off_c(len);                /* AFFINE_ARRAYS==1 branch, :342-343 */
 }
 
 /* per-step deletion extension cost, jni/...c:229-233 */
@@ -209,7 +222,7 @@ void orc_fill_unlimited_raw(orc_msa *m, const uint8_t *read, int read_len,
                     tA = prevMatch ? streak + 1 : 1;
                 } else {
                     if (ref1 != 'N' && call1 != 'N')
-                        a = dm + (prevMatch ? (streak <= 1 ? SH(PTS_SUBR) : SH(PTS_SUB)) : T_SUBoff[streak + 1]);
+                        a = dm + (prevMatch ? (streak <= 1 ? SH(PTS_SUBR) : SH(PTS_SUB)) : sub_off(streak + 1));
                     else
                         a = dm + SH(PTS_NOCALL);
                     bonus = SH(PTS_SUB);
@@ -241,7 +254,7 @@ void orc_fill_unlimited_raw(orc_msa *m, const uint8_t *read, int read_len,
             } else {
                 const int32_t streak = I[up + col] & ORC_TIMEMASK;
                 const int32_t a = (M[up + col] & ORC_SCOREMASK) + SH(PTS_INS);
-                const int32_t b = (I[up + col] & ORC_SCOREMASK) + T_INSoff[streak + 1];
+                const int32_t b = (I[up + col] & ORC_SCOREMASK) + ins_off(streak + 1);
                 int32_t score, time;
                 if (a >= b) { score = a; time = 1; } else { score = b; time = streak + 1; }
                 I[cur + col] = score | clamp_time(time);
@@ -336,7 +349,7 @@ void orc_fill_limited_raw(orc_msa *m, const uint8_t *read, int read_len,
             const int delNeeded = imax(0, row - col - 1);
             const int insNeeded = imax(0, (rows - row) - (columns - col) - 1);
             const int32_t delPenalty = orc_calc_del_score_offset(delNeeded);
-            const int32_t insPenalty = (insNeeded <= 0) ? 0 : T_INSoff_C[insNeeded];
+            const int32_t insPenalty = (insNeeded <= 0) ? 0 : ins_off_c(insNeeded);
 
             const int32_t dm = M[up + col - 1] & ORC_SCOREMASK;
             const int32_t dd = D[up + col - 1] & ORC_SCOREMASK;
@@ -358,7 +371,7 @@ void orc_fill_limited_raw(orc_msa *m, const uint8_t *read, int read_len,
                     tA = prevMatch ? streak + 1 : 1;
                 } else {
                     if (ref1 != 'N' && call1 != 'N')
-                        a = dm + (prevMatch ? (streak <= 1 ? SH(PTS_SUBR) : SH(PTS_SUB)) : T_SUBoff[streak + 1]);
+                        a = dm + (prevMatch ? (streak <= 1 ? SH(PTS_SUBR) : SH(PTS_SUB)) : sub_off(streak + 1));
                     else
                         a = dm + SH(PTS_NOCALL);
                     bonus = SH(PTS_SUB);
@@ -404,7 +417,7 @@ void orc_fill_limited_raw(orc_msa *m, const uint8_t *read, int read_len,
             } else {
                 const int32_t streak = I[up + col] & ORC_TIMEMASK;
                 const int32_t a = um + SH(PTS_INS);
-                const int32_t b = ui + T_INSoff[streak + 1];
+                const int32_t b = ui + ins_off(streak + 1);
                 int32_t score, time;
                 if (a >= b) { score = a; time = 1; } else { score = b; time = streak + 1; }
                 int32_t limit2;
@@ -701,7 +714,7 @@ static int score_no_indels_core(const uint8_t *read, int read_len, const uint8_t
         } else {
             if (match) match[i] = 'S';
             if (mode == 3) timeInMode++; else timeInMode = 0;
-            score += T_SUB[timeInMode + 1];
+            score += sub_pts(timeInMode + 1);
             mode = 3;
         }
     }
@@ -776,7 +789,7 @@ int orc_calc_affine_score(const int32_t *locArray, int n, const int8_t *baseScor
             }
             lastLoc = loc;
         } else if (loc == -1) {
-            if (lastValue < 0 && timeInMode > 0) { timeInMode++; score += T_SUB[timeInMode]; }
+            if (lastValue < 0 && timeInMode > 0) { timeInMode++; score += sub_pts(timeInMode); }
             else { score += PTS_SUB; timeInMode = 1; }
         } else {
             timeInMode = 0; score += PTS_NOCALL;

@@ -1,6 +1,12 @@
 """Oracle answer of one bbmsa job and the field-by-field check of a kernel's record against it (shared by the GPU parity
-tests of the DP: tests/test_msa_gpu.py, tests/test_msa_routes_gpu.py)."""
+tests of the DP: tests/test_msa_gpu.py, tests/test_msa_routes_gpu.py, tests/test_msa_rows_per_lane_gpu.py), and the check of
+one per-call fill's planes and limits against the oracle's `packed` matrix."""
+import ctypes as C
+
+import numpy as np
+
 from bbmap_amd import msa as M
+from oracle.oracle import OracleMSA
 
 
 def oracle_align(om, read, ref, a, b, ms, flags):
@@ -48,3 +54,61 @@ def check_job(g, exp, ctx):
     assert g["fill_kind"] == exp["fill_kind"], ctx
     assert g["score"] == exp["score"], ctx
     assert g["match"] == exp["match"], ctx
+
+
+MARK = 0x5a5a5a5a                                   # what the oracle's planes hold where its fill wrote nothing
+
+
+def check_packed_fill(maxRows, maxCols, band, rd, ref, a, b, ms, limited, fill, packed=None):
+    """One per-call fill (bbmsa_fill_submit / _collect) against a fresh oracle of the same shape.  `fill(packed)` gets the flat
+    3 x (maxRows + 1) x (maxCols + 1) int32 array in the Java layout, holding what the constructor leaves there, puts the device's
+    planes into it and returns (result5, iterations, vertLimit, horizLimit).  Three checks: (1) every cell the oracle's
+    restatement of the native fill WROTE holds the same int on our side (score, time bits and the subfloor of visited-but-bad
+    cells), and nothing outside rows x columns changed; (2) vertLimit / horizLimit come back as the native code leaves them;
+    (3) score2 / traceback2 (the oracle's restatement of the Java walkers, which read `packed`) run on OUR matrix and give what they
+    give on the oracle's own.  Returns whether the walkers ran (False: a limited fill below minScore, nothing to walk).
+    `packed`: an array to reuse."""
+    om = OracleMSA(maxRows, maxCols, bandwidth=band[0], bandwidthRatio=band[1])
+    view = np.ctypeslib.as_array(om.s.packed, shape=(3, maxRows + 1, maxCols + 1))
+    pristine = view.copy()                              # row 0 / column 0 as the constructor leaves them
+    view[:, 1:, 1:] = MARK
+    if limited:
+        exp, exp_it = om.fill_limited_raw(rd, ref, a, b, ms)
+    else:
+        exp, exp_it = om.fill_unlimited_raw(rd, ref, a, b)
+        exp = exp + [0]
+    if packed is None:
+        packed = np.empty(pristine.size, np.int32)
+    packed[:] = pristine.reshape(-1)
+    got, it, vl, hl = fill(packed)
+    assert got[:4] == exp[:4] and (not limited or got[4] == exp[4]) and it == exp_it
+    rows, cols = len(rd), b - a + 1
+    ours = packed.reshape(3, maxRows + 1, maxCols + 1)
+    o, g = view[:, 1:rows + 1, 1:cols + 1], ours[:, 1:rows + 1, 1:cols + 1]
+    wrote = o != MARK
+    assert wrote.sum() > rows                           # (the oracle did fill something)
+    # "not a score": subfloor (pruned, below the limit, or a row-end sentinel) and the BADoff the native fill spreads over the last
+    # row first (:398-403).  Nothing reads the time bits of such a cell, and the native code itself strips them wherever a
+    # sentinel lands on a computed cell; we keep subfloor there.  Every other cell -- every real score and its time -- is exact.
+    maxGain = (rows - 1) * 100 + 70
+    subfloor = ((ms << 11) - (maxGain << 11) - 5 * (100 << 11)) if limited else -2 * (maxGain << 11)
+    badoff = (-(1 << 20) + 2000) << 11
+    dead = wrote & (((o & ~2047) == subfloor) | (o == badoff))
+    live = wrote & ~dead
+    assert live.sum() > rows
+    assert (g[live] == o[live]).all()
+    assert (((g[dead] & ~2047) == subfloor) | (g[dead] == badoff)).all()
+    assert (ours[:, 0, :] == pristine[:, 0, :]).all() and (ours[:, :, 0] == pristine[:, :, 0]).all()
+    assert (ours[:, rows + 1:, :] == pristine[:, rows + 1:, :]).all() and (ours[:, 1:, cols + 1:] == pristine[:, 1:, cols + 1:]).all()
+    if limited:
+        assert list(vl) == np.ctypeslib.as_array(om.s.vertLimit, shape=(maxRows + 1,))[:rows + 1].tolist()
+        assert list(hl) == np.ctypeslib.as_array(om.s.horizLimit, shape=(maxCols + 1,))[:cols + 1].tolist()
+    if limited and exp[4] == 1:
+        return False
+    want_score = om.score(rd, ref, a, b, exp[0], exp[1], exp[2])
+    want_tb = om.traceback(rd, ref, a, b, exp[0], exp[1], exp[2])
+    # same walkers, our matrix: overwrite the oracle's packed with the planes the GPU produced
+    C.memmove(om.s.packed, packed.ctypes.data, packed.size * 4)
+    assert om.score(rd, ref, a, b, got[0], got[1], got[2]) == want_score
+    assert om.traceback(rd, ref, a, b, got[0], got[1], got[2]) == want_tb
+    return True

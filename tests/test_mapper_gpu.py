@@ -107,6 +107,27 @@ def test_paired_matches_oracle_with_rescue_on_the_throughput_route(monkeypatch):
     print("throughput route: %d narrow launches, %d width-sorted launches" % (st["dp_narrow_launches"], st["dp_sorted_launches"]))
 
 
+@pytest.mark.parametrize("first_pass", ["64_lanes_x_4_rows", "32_lanes_x_8_rows"])
+def test_paired_2x250_matches_oracle(monkeypatch, first_pass):
+    """Reads of 250 bases: both DP contexts hold 256 rows.  As configured the launches of this size go straight to the 64-lane
+    geometry, 4 rows per lane; with BBMAP_LATENCY_JOBS=0 their first pass runs 32 lanes x 8 rows (the 100- and 150-base tests run
+    2 / 3 and 4 / 5 rows per lane).  fastCols = 384: the plain context's default of 256 columns is narrower than any window of
+    a 250-base read, which would leave every fill to the second context."""
+    _set_route(monkeypatch, "latency")
+    if first_pass == "32_lanes_x_8_rows":
+        monkeypatch.setenv("BBMAP_LATENCY_JOBS", "0")
+    L, k = 250, 12
+    ref = W.make_reference(200000, seed=14, pad=2000, repeat_frac=0.15)
+    reads, _ = W.make_pairs(ref, 400, read_len=L, seed=8, pad=2000, hard_frac=0.08)
+    out, orc, st, n = _run(ref, reads, L, k, paired=True, fastCols=384)
+    assert st["reads_overflowed"] == 0
+    bad = compare(out, orc, n, paired=True)
+    assert not bad, "\n".join(bad[:20])
+    print("2 x 250, %s: %d fills, %d in the second context, %d rounds" % (first_pass, st["fills"], st["gapped_fills"], st["rounds"]))
+    assert st["fills"] > 0 and st["gapped_fills"] > 0, st
+    assert st["dp_narrow_launches"] == 0 and st["dp_sorted_launches"] == 0, st
+
+
 def test_paired_without_tip_search_and_trimming():
     L, k = 100, 11
     ref = W.make_reference(120000, seed=8, pad=1000, repeat_frac=0.3)

@@ -6,7 +6,7 @@ import pytest
 
 from bbmap_amd import msa as M
 from oracle.oracle import OracleMSA
-from tests.msa_check import check_job, oracle_align
+from tests.msa_check import check_job, check_packed_fill, oracle_align
 from tests.problems import mixed_problems, survey_problem_stream, max_quality, rand_seq
 
 pytestmark = pytest.mark.gpu
@@ -198,64 +198,21 @@ def _legacy_cases(rng, ref, n):
 
 @pytest.mark.parametrize("band", [(0, 0.0), (40, 0.18)])
 def test_legacy_packed_matrix_feeds_the_java_walkers(band):
-    """bbmsa_fill_submit / _collect: the planes land in the Java layout.  Three checks per fill: (1) every cell the oracle's
-    restatement of the native fill WROTE holds the same int on our side (score, time bits and the subfloor of visited-but-bad cells);
-    (2) score2 / traceback2 (the oracle's restatement of the Java walkers, which read `packed`) run on OUR matrix and give what they
-    give on the oracle's own; (3) vertLimit / horizLimit come back as the native code leaves them."""
-    import ctypes as C
+    """bbmsa_fill_submit / _collect: the planes land in the Java layout.  Three checks per fill (tests/msa_check.py,
+    check_packed_fill): (1) every cell the oracle's restatement of the native fill WROTE holds the same int on our side (score,
+    time bits and the subfloor of visited-but-bad cells); (2) score2 / traceback2 (the oracle's restatement of the Java walkers,
+    which read `packed`) run on OUR matrix and give what they give on the oracle's own; (3) vertLimit / horizLimit come back as
+    the native code leaves them."""
     import random
-    import numpy as np
-    from oracle.oracle import OracleMSA
     rng = random.Random(91)
     maxRows, maxCols = 160, 300
     ctx = M.MSAContext(maxRows=maxRows, maxColumns=maxCols, bandwidth=band[0], bandwidthRatio=band[1], legacy=True)
     ref = bytes(rng.choice(b"ACGT") for _ in range(3000))
-    n_int = 3 * (maxRows + 1) * (maxCols + 1)
-    MARK = 0x5a5a5a5a
     done = 0
     for rd, a, b, limited, ms in _legacy_cases(rng, ref, 48):
-        om = OracleMSA(maxRows, maxCols, bandwidth=band[0], bandwidthRatio=band[1])
-        view = np.ctypeslib.as_array(om.s.packed, shape=(3, maxRows + 1, maxCols + 1))
-        pristine = view.copy()                              # row 0 / column 0 as the constructor leaves them
-        view[:, 1:, 1:] = MARK
-        if limited:
-            exp, exp_it = om.fill_limited_raw(rd, ref, a, b, ms)
-        else:
-            exp, exp_it = om.fill_unlimited_raw(rd, ref, a, b)
-            exp = exp + [0]
-        packed = pristine.copy().reshape(-1)
-        got, it, vl, hl = ctx.fill_packed(rd, ref, a, b, ms, limited, packed, limits=True)
-        assert got[:4] == exp[:4] and (not limited or got[4] == exp[4]) and it == exp_it
-        rows, cols = len(rd), b - a + 1
-        ours = packed.reshape(3, maxRows + 1, maxCols + 1)
-        o, g = view[:, 1:rows + 1, 1:cols + 1], ours[:, 1:rows + 1, 1:cols + 1]
-        wrote = o != MARK
-        assert wrote.sum() > rows                           # (the oracle did fill something)
-        # "not a score": subfloor (pruned, below the limit, or a row-end sentinel) and the BADoff the native fill spreads over the last
-        # row first (:398-403).  Nothing reads the time bits of such a cell, and the native code itself strips them wherever a
-        # sentinel lands on a computed cell; we keep subfloor there.  Every other cell -- every real score and its time -- is exact.
-        maxGain = (rows - 1) * 100 + 70
-        subfloor = ((ms << 11) - (maxGain << 11) - 5 * (100 << 11)) if limited else -2 * (maxGain << 11)
-        badoff = (-(1 << 20) + 2000) << 11
-        dead = wrote & (((o & ~2047) == subfloor) | (o == badoff))
-        live = wrote & ~dead
-        assert live.sum() > rows
-        assert (g[live] == o[live]).all()
-        assert (((g[dead] & ~2047) == subfloor) | (g[dead] == badoff)).all()
-        assert (ours[:, 0, :] == pristine[:, 0, :]).all() and (ours[:, :, 0] == pristine[:, :, 0]).all()
-        assert (ours[:, rows + 1:, :] == pristine[:, rows + 1:, :]).all() and (ours[:, 1:, cols + 1:] == pristine[:, 1:, cols + 1:]).all()
-        if limited:
-            assert vl.tolist() == np.ctypeslib.as_array(om.s.vertLimit, shape=(maxRows + 1,))[:rows + 1].tolist()
-            assert hl.tolist() == np.ctypeslib.as_array(om.s.horizLimit, shape=(maxCols + 1,))[:cols + 1].tolist()
-        if limited and exp[4] == 1:
-            continue
-        want_score = om.score(rd, ref, a, b, exp[0], exp[1], exp[2])
-        want_tb = om.traceback(rd, ref, a, b, exp[0], exp[1], exp[2])
-        # same walkers, our matrix: overwrite the oracle's packed with the planes the GPU produced
-        C.memmove(om.s.packed, packed.ctypes.data, n_int * 4)
-        assert om.score(rd, ref, a, b, got[0], got[1], got[2]) == want_score
-        assert om.traceback(rd, ref, a, b, got[0], got[1], got[2]) == want_tb
-        done += 1
+        def fill(packed):
+            return ctx.fill_packed(rd, ref, a, b, ms, limited, packed, limits=True)
+        done += check_packed_fill(maxRows, maxCols, band, rd, ref, a, b, ms, limited, fill)
     st = ctx.legacy_stats()
     assert st["calls"] == 48 and st["launches"] == 48 and st["handed_on"] >= 4
     assert done > 24

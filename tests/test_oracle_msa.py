@@ -79,6 +79,23 @@ def test_tables_match_java_static_init():
     assert [b2n[ord(c)] for c in "ACGTUacgtuN-"] == [0, 1, 2, 3, 3, 0, 1, 2, 3, 3, -1, -1]
 
 
+def test_rows_beyond_the_references_604_entry_tables_keep_the_last_tier():
+    """The reference's INS / SUB arrays hold 604 entries, enough for its 601-row matrices.  The device takes reads of up to 640
+    bases, so the restatement must not index past them: an insertion streak of 603 or more rows (column 1 of a 640-row fill)
+    goes on costing INS4 per row, and the count of still-needed insertions of a limited fill follows the same closed form."""
+    import numpy as np
+    rng = random.Random(5)
+    ref = bytes(rng.choice(b"ACGT") for _ in range(800))
+    m = OracleMSA(640, 700)
+    m.fill_unlimited_raw(ref[20:660], ref, 16, 671)
+    col1 = np.ctypeslib.as_array(m.s.packed, shape=(3, 641, 701))[2, 1:641, 1].astype(np.int64)
+    col1 = col1[30:638]                                    # (below the tiers' start; above the last two rows, where the insertion barrier rules)
+    assert (np.diff(col1 >> 11) == -8).all() and (np.diff(col1 & 2047) == 1).all()
+    L = lib()
+    assert L.orc_calc_ins_score_offset(603) - L.orc_calc_ins_score_offset(602) == -8 * 2048
+    assert [L.orc_calc_ins_score_offset(n) - L.orc_calc_ins_score_offset(603) for n in (604, 605, 640)] == [-8 * 2048, -16 * 2048, -37 * 8 * 2048]
+
+
 def test_perfect_read_scores_max_quality():
     rng = random.Random(5)
     ref = bytes(rng.choice(b"ACGT") for _ in range(600))
