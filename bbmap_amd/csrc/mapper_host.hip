@@ -329,13 +329,15 @@ static void add_dp_ms(bbmap_ctx *c, bool plain, bool gapped) {
     if (gapped && c->msaGapped != c->msa && bbmsa_last_kernel_ms3(c->msaGapped, k3) == BBMAP_OK) c->stats.ms_dp_gapped += k3[0] + k3[1] + k3[2];
     static const bool show = getenv("BBMAP_DP_COUNTS") != nullptr;      // where the fills of a launch sequence ended up (experiments)
     if (show) {
-        int64_t n4[4];
-        if (plain && bbmsa_last_counts(c->msa, n4) == BBMAP_OK)
-            fprintf(stderr, "dp counts plain : narrow finished %lld, narrow handed on %lld, wavefront list %lld, to the wide/generic pass %lld\n",
-                    (long long)n4[0], (long long)n4[1], (long long)n4[2], (long long)n4[3]);
-        if (gapped && bbmsa_last_counts(c->msaGapped, n4) == BBMAP_OK)
-            fprintf(stderr, "dp counts second: narrow finished %lld, narrow handed on %lld, wavefront list %lld, to the wide/generic pass %lld\n",
-                    (long long)n4[0], (long long)n4[1], (long long)n4[2], (long long)n4[3]);
+        int64_t n4[4], u4[4];
+        if (plain && bbmsa_last_counts(c->msa, n4) == BBMAP_OK && bbmsa_last_unlimited(c->msa, u4) == BBMAP_OK)
+            fprintf(stderr, "dp counts plain : narrow finished %lld, narrow handed on %lld, wavefront list %lld, to the wide/generic pass %lld, "
+                    "unlimited in their own build %lld, in the general build %lld, wavefront steps unlimited %lld of %lld\n",
+                    (long long)n4[0], (long long)n4[1], (long long)n4[2], (long long)n4[3], (long long)u4[0], (long long)u4[1], (long long)u4[2], (long long)u4[3]);
+        if (gapped && bbmsa_last_counts(c->msaGapped, n4) == BBMAP_OK && bbmsa_last_unlimited(c->msaGapped, u4) == BBMAP_OK)
+            fprintf(stderr, "dp counts second: narrow finished %lld, narrow handed on %lld, wavefront list %lld, to the wide/generic pass %lld, "
+                    "unlimited in their own build %lld, in the general build %lld, wavefront steps unlimited %lld of %lld\n",
+                    (long long)n4[0], (long long)n4[1], (long long)n4[2], (long long)n4[3], (long long)u4[0], (long long)u4[1], (long long)u4[2], (long long)u4[3]);
     }
 }
 

@@ -122,14 +122,18 @@ template <class S> struct SpelledPen {
 template <class S> __device__ __forceinline__ int clamp_cell_time(int t) { return t > S::MAXT ? S::MAXT - 3 : t; }
 
 // CLAMP_ALL: clamp the match and insertion planes' times too (their streaks are bounded by the rows: only reads longer than MAXT need it)
-template <class S, bool CLAMP_ALL, class Pen>
+// LIMITED = false: the cell of fillUnlimited (jni/...c:168-300).  No limits and no "still needed" penalties: the match plane is pruned
+// by !act | gap alone, the deletion plane by its barrier rows, the insertion plane by gap and its barriers, and a cell that is not
+// pruned is good.  in.limitP, floorP, rows, row, c and insNeededBase are not read.  (The deletion plane's time clamp stays: a
+// deletion streak passes MAXT in a window of more than MAXT columns, and only unlimited fills get that wide.)
+template <class S, bool CLAMP_ALL, class Pen, bool LIMITED = true>
 __device__ __forceinline__ CellOut cell_update(const Pen &pen, const CellIn &in) {
     constexpr int ONE = S::TMASK + 1;
     CellOut o;
     const int limit = in.limitP - ONE;
     const int delNeeded = max(0, in.row - in.c - 1);
     const int insNeeded = max(0, (in.rows - in.row) - in.insNeededBase);
-    const NeedPen np = pen.need(delNeeded, insNeeded);
+    const NeedPen np = LIMITED ? pen.need(delNeeded, insNeeded) : NeedPen{};
 
     // ---- match / substitution plane (diagonal)
     const int streakM = in.dgM & S::TMASK;
@@ -139,20 +143,20 @@ __device__ __forceinline__ CellOut cell_update(const Pen &pen, const CellIn &in)
     o.mb8 = in.match ? 8 : 0;
     const MEntry me = pen.m_entry(streakM, o.mb8, in.pm8, prevMatch, in.match);
     const int t3 = max(in.floorP, in.limitP - me.t3sub);
-    o.pruneM = !in.act | in.gap | (max(in.dgM, max(in.dgD, in.dgI)) < t3);      // (bitwise: no short-circuit branches)
+    o.pruneM = !in.act | in.gap | (LIMITED && (max(in.dgM, max(in.dgD, in.dgI)) < t3));      // (bitwise: no short-circuit branches; LIMITED is a constant)
     const int addA = (in.refN | (in.cl1 == 'N')) ? 0 : me.addA;                  // (a match has neither base N)
     const int sa = sdm + addA;
     const int sbc = mDI + me.bonus;
     const bool aWinsM = sa >= sbc;
     const int scoreM = max(sa, sbc);
     o.timeM = (aWinsM & (in.match == prevMatch)) ? streakM + 1 : 1;
-    o.goodM = !o.pruneM & (scoreM + np.pen0 >= limit);                           // the offsets are negative: score >= limit - offset
+    o.goodM = !o.pruneM & (!LIMITED || (scoreM + np.pen0 >= limit));             // the offsets are negative: score >= limit - offset
     o.nM = o.goodM ? (scoreM | (CLAMP_ALL ? clamp_cell_time<S>(o.timeM) : o.timeM)) : in.subfloor;
 
     // ---- deletion plane (same row, previous column)
     const int streakD = in.lD & S::TMASK;
     const int slm = in.lM & S::SMASK, sld = in.lD & S::SMASK;
-    o.pruneD = !in.act | (max(in.lM, in.lD) < max(in.limitP, in.delForce));
+    o.pruneD = !in.act | (LIMITED ? (max(in.lM, in.lD) < max(in.limitP, in.delForce)) : (in.delForce > 0));
     const int dsa = slm + S::DEL;
     const int dsb = sld + pen.del_ext(streakD);
     const bool aWinsD = dsa >= dsb;
@@ -162,18 +166,18 @@ __device__ __forceinline__ CellOut cell_update(const Pen &pen, const CellIn &in)
     // ---- insertion plane (row above, same column)
     const int streakI = in.upI & S::TMASK;
     const int sum = in.upM & S::SMASK, sui = in.upI & S::SMASK;
-    o.pruneI = !in.act | in.gap | (max(in.upM, in.upI) < max(in.limitP, in.insForce));
+    o.pruneI = !in.act | in.gap | (LIMITED ? (max(in.upM, in.upI) < max(in.limitP, in.insForce)) : (in.insForce > 0));
     const int isa = sum + S::INS;
     const int isb = sui + pen.ins_ext(streakI);
     const bool aWinsI = isa >= isb;
     const int scoreI = max(isa, isb);
     o.timeI = aWinsI ? 1 : streakI + 1;
 
-    int penD, penI;
-    pen.rest(np, delNeeded, insNeeded, o.timeD, o.timeI, penD, penI);
-    o.goodD = !o.pruneD & (scoreD + penD >= limit);
+    int penD = 0, penI = 0;
+    if (LIMITED) pen.rest(np, delNeeded, insNeeded, o.timeD, o.timeI, penD, penI);
+    o.goodD = !o.pruneD & (!LIMITED || (scoreD + penD >= limit));
     o.nD = o.goodD ? (scoreD | clamp_cell_time<S>(o.timeD)) : in.subfloor;
-    o.goodI = !o.pruneI & (scoreI + penI >= limit);
+    o.goodI = !o.pruneI & (!LIMITED || (scoreI + penI >= limit));
     o.nI = o.goodI ? (scoreI | (CLAMP_ALL ? clamp_cell_time<S>(o.timeI) : o.timeI)) : in.subfloor;
 
     // ---- traceback record (MultiStateAligner11tsJNI.java:389-443): what traceback2 / score2 would decide at this cell (time > 1:

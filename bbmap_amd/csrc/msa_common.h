@@ -115,6 +115,26 @@ struct Scheme9PacBio {   // current/align2/MultiStateAligner9PacBio.java:2359-24
     }
 };
 
+// Which fill a job gets.  halfband: jni/...c:392-393 (0 = the context has no band).
+__host__ __device__ inline int fill_halfband(int rows, int columns, int bandwidth, float bandwidthRatio) {
+    if (bandwidth < 1 && bandwidthRatio <= 0.0f) return 0;
+    const int bwA = bandwidth < 1 ? 9999999 : bandwidth;
+    const int bwB = bandwidthRatio <= 0.0f ? 9999999 : 8 + (int)((float)rows * bandwidthRatio);     // (one rounded multiply: nothing to contract)
+    return max(min(bwA, bwB), columns - rows + 8) / 2;
+}
+// The raw modes say it themselves; BBMSA_FILL_LIMITED goes through MSA.fillLimited's gate (MultiStateAligner11tsJNI.java:137-144),
+// which turns a fill into fillUnlimited when there is no score to prune by, when the matrix is tiny, or when the window is much
+// wider than the read and no band narrows it.  (A limited fill of that mode runs with minScore - 120: the caller's business.)
+// `columns` is the clamped window's.  The wavefront kernel and the width sort in front of it share this; the band, generic and strip
+// kernels have their own copies.
+__host__ __device__ inline bool fill_is_limited(int flags, int minScore, int rows, int columns, int halfband) {
+    const int mode = flags & BBMSA_MODE_MASK;
+    if (mode == BBMSA_FILL_UNLIMITED_RAW) return false;
+    if (mode == BBMSA_FILL_LIMITED_RAW) return true;
+    return !(minScore < 1 || (columns + rows < 90) ||
+             ((halfband < 1 || halfband * 3 > columns) && (columns > rows + min(170, rows + 20))));
+}
+
 // number of jobs of a launch: a host value, or a counter a previous kernel of the same stream left on the device
 __device__ inline long long job_count(long long njobs, const unsigned int *njobs_dev) {
     if (!njobs_dev) return njobs;
@@ -147,6 +167,8 @@ struct FillParams {
     int maxRows, maxColumns;      // context limits (MSA(maxRows_, maxColumns_))
     int bandwidth;
     float bandwidthRatio;
+    unsigned int *unl_stats;      // [0] jobs that ran in the unlimited build, [1] unlimited jobs that ran in the general build,
+                                  // [4] / [5] wavefront steps (columns + lanes in use - 1) of the unlimited jobs / of all jobs; NULL: not counted
     // matrix-materialising mode (the legacy per-call JNI shape, msa_legacy.hip; kernels instantiated with MAT only): job j's three
     // score planes go to planes + plane_off[j], each rows x columns ints (state-major; rows 1..rows, columns 1..columns of the matrix), its
     // vertLimit[0..rows] / horizLimit[0..columns] to limits + limits_off[j] (rows + 1 ints, then columns + 1)

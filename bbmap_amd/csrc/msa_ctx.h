@@ -14,7 +14,7 @@ struct bbmsa_ctx {
     int G = 0, R = 0, fastCols = 0, tmpBytes = 0, blocks = 0, ldsBytes = 0, tableLen = 0, wideTableLen = 0;
     long long dirSlotDwords = 0;
     unsigned int *d_dir = nullptr;
-    unsigned int *d_counters = nullptr;   // [0]=fast queue, [1]=slow count, [2]=generic queue
+    unsigned int *d_counters = nullptr;   // 16 words; [0]=fast queue, [1]=slow count, [2]=generic queue, ... (bbmsa_align_impl has the list)
     DevBuf slowList;            // ints: the jobs the wavefront kernel hands on; as long as the largest launch so far
     // generic kernel
     int genThreads = 0;
@@ -36,6 +36,8 @@ struct bbmsa_ctx {
     // widest windows first (bbmsa_sort_by_width): two jobs share a wavefront and step together, so a 600-column job beside a
     // 200-column one idles half the wave for 400 steps; in width order neighbours are alike, and the longest jobs do not end up last
     bool sortByWidth = false;
+    bool unlimitedLoop = true;         // a width-sorted launch runs its unlimited fills in the wavefront kernel's build for them (BBMSA_UNLIMITED_LOOP=0: no)
+    bool unlimitedStats = false;       // the kernels count for bbmsa_last_unlimited (BBMSA_UNLIMITED_STATS=1 or BBMAP_DP_COUNTS at bbmsa_create)
     unsigned int *d_widthHist = nullptr;
     long long latencyJobs = 0;         // launches with at most this many jobs go straight to the 64-lane geometry (bbmsa_set_latency_jobs)
     int bandRows = 0, bandLds = 0;     // longest read the band kernel takes, its LDS bytes per block
@@ -74,7 +76,7 @@ void bbmsa_use_narrow(bbmsa_ctx *c, bool on);
 // to overlap with) only start when those drain: measured, the final stage 86 -> 93 ms.
 int bbmsa_wait_first_pass(bbmsa_ctx *c, void *waiter);
 // Launches of this context hand their jobs to the wavefront kernel in descending window width (a counting sort by columns / 8 in
-// front of the first pass); results are indexed by job as always.  The mapper asks for it on its second context, whose windows
+// front of the first pass, the unlimited fills in front of the limited ones); results are indexed by job as always.  The mapper asks for it on its second context, whose windows
 // span 170..640+ columns.
 void bbmsa_sort_by_width(bbmsa_ctx *c, bool on);
 // BBMSA_SORT_BY_WIDTH=1 in the environment switches it on for every context bbmsa_create makes (default 0; a caller that sets it,

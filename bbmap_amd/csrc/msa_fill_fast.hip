@@ -70,7 +70,9 @@ __device__ __forceinline__ unsigned load_coherent(const unsigned *p) {
 // code leaves in the Java class's `packed` matrix for score2 / traceback2 to walk (jni/MultiStateAligner11tsJNI.c:124-127, :707-812).
 // A cell that is visited but not "good" is stored as subfloor | time, as the reference stores it (:556-562); cells this schedule
 // computes beyond a row's end are stored as subfloor -- the reference leaves those untouched, and never reads them (its sentinels).
-template <int R, bool BANDED, bool MAT = false>
+// UNL: the build for unlimited fills only (fillUnlimited), launched over the unlimited fills of a width-sorted launch in front of the
+// general build: its step loop has no limits, no prune tests and no good-column extents.  A limited job it met would be handed on.
+template <int R, bool BANDED, bool MAT = false, bool UNL = false>
 __global__ __launch_bounds__(256, BBMSA_MIN_WAVES(R)) void msa_fill_fast_kernel(const FillParams p) {
     extern __shared__ int lds[];
     int *delC = lds;
@@ -144,24 +146,12 @@ __global__ __launch_bounds__(256, BBMSA_MIN_WAVES(R)) void msa_fill_fast_kernel(
         const int columns = b - a + 1;
         const bool shapeOK = valid && rows >= 1 && columns >= 1 && rows <= p.maxRows && columns <= p.maxColumns;
 
-        // halfband: jni/...c:392-393 ; Java gate: MultiStateAligner11tsJNI.java:137-144
-        int halfband = 0;
-        if (!(p.bandwidth < 1 && p.bandwidthRatio <= 0.0f)) {
-            const int bwA = p.bandwidth < 1 ? 9999999 : p.bandwidth;
-            const int bwB = p.bandwidthRatio <= 0.0f ? 9999999 : 8 + (int)__fmul_rn((float)rows, p.bandwidthRatio);
-            halfband = max(min(bwA, bwB), columns - rows + 8) / 2;
-        }
-        int minScore = jb.minScore;
-        bool limited;
-        if (mode == BBMSA_FILL_UNLIMITED_RAW) limited = false;
-        else if (mode == BBMSA_FILL_LIMITED_RAW) limited = true;
-        else {
-            if (minScore < 1 || (columns + rows < 90) ||
-                ((halfband < 1 || halfband * 3 > columns) && (columns > rows + min(170, rows + 20)))) limited = false;
-            else { limited = true; minScore -= 120; }
-        }
+        // the fill kind (msa_common.h); a limited fill that came through the Java gate runs with minScore - 120
+        const int halfband = fill_halfband(rows, columns, p.bandwidth, p.bandwidthRatio);
+        const bool limited = fill_is_limited(jb.flags, jb.minScore, rows, columns, halfband);
+        const int minScore = (limited && mode != BBMSA_FILL_LIMITED_RAW) ? jb.minScore - 120 : jb.minScore;
         const bool fits = rows <= G * R && columns <= p.fastCols && columns >= rows - 2;   // (narrower windows: see the cell)
-        const bool needGeneric = shapeOK && !fits;
+        const bool needGeneric = shapeOK && (!fits || (UNL && limited));
         const bool run = shapeOK && !needGeneric;
         // Banded fill (jni/...c:441-442): a row may only extend one column past the last good column of the
         // row above, which this schedule learns one column late.  The kernel assumes a row's good columns have
@@ -252,7 +242,7 @@ __global__ __launch_bounds__(256, BBMSA_MIN_WAVES(R)) void msa_fill_fast_kernel(
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        if (run && gl == 0) {                                            // jni/...c:427-438
+        if (run && gl == 0 && !UNL) {                                    // jni/...c:427-438 (the prune-free loop reads no horizLimit)
             int h = minScoreOff;
             bool prevDef = false;
             for (int i = columns - 1; i >= 0; i--) {
@@ -280,6 +270,10 @@ __global__ __launch_bounds__(256, BBMSA_MIN_WAVES(R)) void msa_fill_fast_kernel(
         //    own comparison" (extension costs are never below the opening cost), so those two record bits are free.
         const int nl = (rows + R - 1) / R;                               // lanes in use
         int steps = run ? columns + nl - 1 : 0;
+        if (!MAT && p.unl_stats && gl == 0 && run) {                     // bbmsa_last_unlimited
+            if (!limited) { atomicAdd(p.unl_stats + (UNL ? 0 : 1), 1u); atomicAdd(p.unl_stats + 4, (unsigned)steps); }
+            atomicAdd(p.unl_stats + 5, (unsigned)steps);
+        }
         for (int d = 32; d >= 1; d >>= 1) steps = max(steps, __shfl_xor(steps, d, 64));
 
         int pM[R], pD[R], pI[R];         // my rows' cells at the previous column
@@ -312,6 +306,74 @@ __global__ __launch_bounds__(256, BBMSA_MIN_WAVES(R)) void msa_fill_fast_kernel(
         const bool ownerLaneFlag = gl == (max(rows, 1) - 1) / R;
         int bestM = 0, bestD = 0, bestI = 0, bestMc = -1, bestDc = -1, bestIc = -1;
 
+        if constexpr (UNL) {
+        // The step loop of fillUnlimited (jni/...c:134-290): the general loop below without limits, "still needed" penalties and
+        // good-column extents (iterations = rows x columns).  Rows beyond the read: their deletion and insertion planes sit behind
+        // the barrier forces, their match plane computes values nobody reads (each row only feeds the rows below it).
+        for (int t = 1; t <= steps; t++) {
+            const int c = t - gl;
+            if (c >= 1 && run) {
+            const bool inRange = c <= columns;
+            const int ref1 = colRef[min(c, columns)];
+            const int ref0 = c < 2 ? '!' : lastRef;
+            const bool gap = ref1 == '-';
+            const bool refN = ref1 == 'N';
+            const int refPen = refN ? P_DEL_REF_N : (gap ? P_GAP : 0);
+            const bool cGt1 = c > 1;
+            const int cLtLastForce = (c < columns - 1) ? INT_MAX : INT_MIN;
+            const unsigned sh = (unsigned)(t & 7) * 4u;
+
+            int upM = lane_up(pM[R - 1], 0);
+            int upD = lane_up(pD[R - 1], 0);
+            int upI = lane_up(pI[R - 1], 0);
+            upM = groupLead ? 0 : upM; upD = groupLead ? 0 : upD; upI = groupLead ? 0 : upI;
+            int dgM = svM, dgD = svD, dgI = svI;
+            svM = upM; svD = upD; svI = upI;
+            int pm8 = ((call0First == ref0) & (ref0 != 'N')) ? 8 : 0;
+
+#pragma unroll
+            for (int k = 0; k < R; k++) {
+                CellIn ci_;
+                ci_.row = 0; ci_.c = 0; ci_.rows = 0; ci_.insNeededBase = 0; ci_.limitP = 0; ci_.floorP = 0;      // (not read)
+                ci_.cl1 = call1[k]; ci_.ref1 = ref1; ci_.refN = refN; ci_.gap = gap; ci_.match = (call1[k] == ref1) & !refN; ci_.act = inRange;
+                ci_.refPen = refPen; ci_.subfloor = subfloor;
+                ci_.dgM = dgM; ci_.dgD = dgD; ci_.dgI = dgI; ci_.lM = pM[k]; ci_.lD = pD[k]; ci_.upM = upM; ci_.upI = upI;
+                ci_.delForce = delForce[k];
+                ci_.insForce = (k == 0) ? ((rowOne && cGt1) ? INT_MAX : min(insHiForce[k], cLtLastForce)) : min(insHiForce[k], cLtLastForce);
+                ci_.pm8 = pm8;
+                const CellOut co = cell_update<Scheme11ts, false, LdsPen, false>(pen, ci_);
+                dacc[k] |= co.nib << sh;
+                dgM = pM[k]; dgD = pD[k]; dgI = pI[k];
+                pM[k] = co.nM; pD[k] = co.nD; pI[k] = co.nI;
+                upM = co.nM; upI = co.nI;
+                pm8 = mPrev[k];
+                mPrev[k] = co.mb8;
+            }
+            lastRef = ref1;
+
+            {
+                int lm = pM[0], ld = pD[0], li = pI[0];
+#pragma unroll
+                for (int k = 1; k < R; k++) {
+                    lm = (lastSlot == k) ? pM[k] : lm; ld = (lastSlot == k) ? pD[k] : ld; li = (lastSlot == k) ? pI[k] : li;
+                }
+                const bool track = ownerLaneFlag & inRange;
+                const bool um = track & ((bestMc < 0) | ((lm & kScoreMask) > (bestM & kScoreMask)));
+                const bool ud = track & ((bestDc < 0) | ((ld & kScoreMask) > (bestD & kScoreMask)));
+                const bool ui = track & ((bestIc < 0) | ((li & kScoreMask) > (bestI & kScoreMask)));
+                bestM = um ? lm : bestM; bestMc = um ? c : bestMc;
+                bestD = ud ? ld : bestD; bestDc = ud ? c : bestDc;
+                bestI = ui ? li : bestI; bestIc = ui ? c : bestIc;
+            }
+            }   // c >= 1
+
+            if ((t & 7) == 7) {
+                const long long o = (long long)(t >> 3) * R * G + gl;
+#pragma unroll
+                for (int k = 0; k < R; k++) { dir[o + (long long)k * G] = dacc[k]; dacc[k] = 0; }
+            }
+        }
+        } else
         for (int t = 1; t <= steps; t++) {
             const int c = t - gl;
             // Lanes that have not reached column 1 yet sit this step out under EXEC (their registers keep the
@@ -630,6 +692,14 @@ const void *fast_kernel_mat_for(int R, bool banded) {
     switch (R) {
         BBMSA_CASE_MAT(1) BBMSA_CASE_MAT(2) BBMSA_CASE_MAT(3) BBMSA_CASE_MAT(4) BBMSA_CASE_MAT(5)
         BBMSA_CASE_MAT(6) BBMSA_CASE_MAT(7) BBMSA_CASE_MAT(8) BBMSA_CASE_MAT(9) BBMSA_CASE_MAT(10)
+    }
+    return nullptr;
+}
+#define BBMSA_CASE_UNL(R) case R: return (const void *)msa_fill_fast_kernel<R, false, false, true>;
+const void *fast_kernel_unl_for(int R) {            // (an unlimited fill has no band: one build serves banded contexts too)
+    switch (R) {
+        BBMSA_CASE_UNL(1) BBMSA_CASE_UNL(2) BBMSA_CASE_UNL(3) BBMSA_CASE_UNL(4) BBMSA_CASE_UNL(5)
+        BBMSA_CASE_UNL(6) BBMSA_CASE_UNL(7) BBMSA_CASE_UNL(8) BBMSA_CASE_UNL(9) BBMSA_CASE_UNL(10)
     }
     return nullptr;
 }

@@ -24,35 +24,48 @@ const void *strip_kernel_pacbio();
 const void *strip_kernel_pacbio_pipelined();
 int strip_pipe_sync_ints(int K);
 const void *fast_kernel_for(int R, bool banded);
+const void *fast_kernel_unl_for(int R);
 template <class S> __global__ void msa_fill_generic_kernel(const GenericParams p);
 const void *band_kernel();                                     // msa_fill_band.hip
 int band_lds_bytes(int tableLen, int bandRows);
 }  // namespace bbmsa
 
 namespace bbmsa {
-constexpr int WIDTH_BUCKETS = 1024;            // columns / 8, clamped
-__device__ inline int job_width_bucket(const bbmsa_job &t, int maxColumns) {
+constexpr int WIDTH_BUCKETS = 1024;            // fill kind (major) x columns / 8: 512 widths per kind.  Only 11ts contexts sort, and bbmsa_create
+                                               // refuses one of more than 4,096 columns, so only a window of exactly 4,096 shares its bucket (with 4,088..4,095)
+struct SortKey { int maxColumns, bandwidth; float bandwidthRatio; int byKind; };
+// byKind: the unlimited fills in front of the limited ones, each kind in descending width.  The wavefront kernel has a build of its
+// own for unlimited fills, which is launched over them in front of the general build (bbmsa_align_impl); the scatter gives each
+// kind its own list.
+__device__ inline int job_width_bucket(const bbmsa_job &t, const SortKey k) {
     int a = t.refStartLoc, b = t.refEndLoc;
-    if (t.flags & BBMSA_CLAMP_WINDOW) { a = max(0, a); b = min(t.ref_len - 1, b); if (b - a >= maxColumns) b = min(t.ref_len - 1, a + maxColumns - 1); }
+    if (t.flags & BBMSA_CLAMP_WINDOW) { a = max(0, a); b = min(t.ref_len - 1, b); if (b - a >= k.maxColumns) b = min(t.ref_len - 1, a + k.maxColumns - 1); }
     const int cols = max(0, b - a + 1);
-    return WIDTH_BUCKETS - 1 - min(WIDTH_BUCKETS - 1, cols >> 3);            // bucket 0 = the widest
+    const bool limited = fill_is_limited(t.flags, t.minScore, t.read_len, b - a + 1, fill_halfband(t.read_len, b - a + 1, k.bandwidth, k.bandwidthRatio));
+    constexpr int W = WIDTH_BUCKETS / 2;
+    return ((limited || !k.byKind) ? W : 0) + W - 1 - min(W - 1, cols >> 3);  // bucket 0 = the widest unlimited fill, W = the widest limited one
 }
-__global__ void width_hist_kernel(const bbmsa_job *jobs, long long n, int maxColumns, unsigned *hist) {
+__global__ void width_hist_kernel(const bbmsa_job *jobs, long long n, SortKey key, unsigned *hist) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) atomicAdd(&hist[job_width_bucket(jobs[i], maxColumns)], 1u);
+    if (i < n) atomicAdd(&hist[job_width_bucket(jobs[i], key)], 1u);
 }
-__global__ void width_scan_kernel(unsigned *hist, unsigned *listCount, unsigned n) {      // one block of WIDTH_BUCKETS threads: exclusive prefix sums in place
+// one block of WIDTH_BUCKETS threads: exclusive prefix sums in place, each kind's from 0 (the scatter's cursors); the lengths of the two lists
+__global__ void width_scan_kernel(unsigned *hist, unsigned *listCount, unsigned *unlCount, unsigned n) {
     __shared__ unsigned s[WIDTH_BUCKETS];
     const int t = threadIdx.x;
     s[t] = hist[t];
     __syncthreads();
     for (int d = 1; d < WIDTH_BUCKETS; d <<= 1) { const unsigned v = t >= d ? s[t - d] : 0u; __syncthreads(); s[t] += v; __syncthreads(); }
-    hist[t] = s[t] - hist[t];
-    if (t == 0) *listCount = n;
+    const unsigned unl = s[WIDTH_BUCKETS / 2 - 1];
+    hist[t] = s[t] - hist[t] - (t >= WIDTH_BUCKETS / 2 ? unl : 0u);
+    if (t == 0) { *listCount = n - unl; *unlCount = unl; }
 }
-__global__ void width_scatter_kernel(const bbmsa_job *jobs, long long n, int maxColumns, unsigned *cursor, int *list) {
+__global__ void width_scatter_kernel(const bbmsa_job *jobs, long long n, SortKey key, unsigned *cursor, int *list, int *unlList) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) list[atomicAdd(&cursor[job_width_bucket(jobs[i], maxColumns)], 1u)] = (int)i;
+    if (i < n) {
+        const int bucket = job_width_bucket(jobs[i], key);
+        (bucket < WIDTH_BUCKETS / 2 ? unlList : list)[atomicAdd(&cursor[bucket], 1u)] = (int)i;
+    }
 }
 }  // namespace bbmsa
 
@@ -211,8 +224,10 @@ extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
     c->banded = !(cfg->bandwidth < 1 && cfg->bandwidthRatio <= 0.0f);
     const void *kfn = bbmsa::fast_kernel_for(c->R, c->banded);
     if (!kfn) return bbfail(BBMAP_E_ARG, "bbmsa_create: no kernel for this rows-per-lane");
-    if (c->ldsBytes > 64 * 1024)
+    if (c->ldsBytes > 64 * 1024) {
         BBHIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, c->ldsBytes));
+        BBHIP(hipFuncSetAttribute(bbmsa::fast_kernel_unl_for(c->R), hipFuncAttributeMaxDynamicSharedMemorySize, c->ldsBytes));
+    }
     int blocksPerCU = 0;
     BBHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, kfn, 256, c->ldsBytes));
     if (blocksPerCU < 1) blocksPerCU = 1;
@@ -256,6 +271,9 @@ extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
     }
     // route switches of the environment (msa_ctx.h): defaults off, as the functions they mirror leave a context
     c->sortByWidth = env_int("BBMSA_SORT_BY_WIDTH", 0) != 0;
+    c->unlimitedLoop = env_int("BBMSA_UNLIMITED_LOOP", 1) != 0;         // 0: the general build of the wavefront kernel takes every job
+    // bbmsa_last_unlimited's counters cost every fill two or three atomics on the same few words: only on request
+    c->unlimitedStats = env_int("BBMSA_UNLIMITED_STATS", 0) != 0 || getenv("BBMAP_DP_COUNTS") != nullptr;
     { const int lat = env_int("BBMSA_LATENCY_JOBS", 0); if (lat > 0) BBTRY(bbmsa_set_latency_jobs(c, lat)); }
     for (int i = 0; i < 4; i++) BBHIP(hipEventCreate(&c->ev[i]));
     guard.c = nullptr;
@@ -365,10 +383,13 @@ int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t
     }
     if (c->wideBlocks > 0) BBHIP(c->slowList2.grow(listBytes, 0, &stream));
     const bool sortJobs = c->sortByWidth && !n_jobs_dev && n_jobs >= 256 && n_jobs > c->latencyJobs && !(c->narrowBlocks > 0 && !c->narrowOff);
-    if (c->narrowBlocks > 0 || sortJobs) BBHIP(c->fastList.grow(listBytes, 0, &stream));
+    if (c->narrowBlocks > 0 || sortJobs) BBHIP(c->fastList.grow(sortJobs ? 2 * listBytes : listBytes, 0, &stream));   // (sorted: the limited fills' list, then the unlimited fills')
     int *const fastList = c->fastList.as<int>();
     // counters: [0] fast queue, [1] slow count, [2] generic queue, [3] narrow queue, [4] fast-list count,
-    //           [5] jobs finished by the band kernel (the "narrow" slots), [6] candidates it handed on
+    //           [5] jobs finished by the band kernel (the "narrow" slots), [6] candidates it handed on, [7] wide pass's slow count,
+    //           [8] wide queue, [9] jobs the wavefront kernel's unlimited build ran, [10] unlimited jobs its general build ran,
+    //           [11] length of a width-sorted launch's list of unlimited jobs, [12] the unlimited build's queue,
+    //           [13] / [14] wavefront steps of the unlimited jobs / of all jobs (bbmsa_last_unlimited)
     BBHIP(hipMemsetAsync(c->d_counters, 0, 64, stream));
     BBHIP(hipEventRecord(c->ev[0], stream));
     const bool useNarrow = c->narrowBlocks > 0 && !c->narrowOff;
@@ -388,9 +409,10 @@ int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t
         if (!c->d_widthHist) BBHIP(hipMalloc(&c->d_widthHist, bbmsa::WIDTH_BUCKETS * 4));
         BBHIP(hipMemsetAsync(c->d_widthHist, 0, bbmsa::WIDTH_BUCKETS * 4, stream));
         const unsigned sb = (unsigned)((n_jobs + 255) / 256);
-        hipLaunchKernelGGL(bbmsa::width_hist_kernel, dim3(sb), dim3(256), 0, stream, jobs, (long long)n_jobs, c->cfg.maxColumns, c->d_widthHist);
-        hipLaunchKernelGGL(bbmsa::width_scan_kernel, dim3(1), dim3(bbmsa::WIDTH_BUCKETS), 0, stream, c->d_widthHist, c->d_counters + 4, (unsigned)n_jobs);
-        hipLaunchKernelGGL(bbmsa::width_scatter_kernel, dim3(sb), dim3(256), 0, stream, jobs, (long long)n_jobs, c->cfg.maxColumns, c->d_widthHist, fastList);
+        const bbmsa::SortKey key = {c->cfg.maxColumns, c->cfg.bandwidth, c->cfg.bandwidthRatio, c->unlimitedLoop ? 1 : 0};
+        hipLaunchKernelGGL(bbmsa::width_hist_kernel, dim3(sb), dim3(256), 0, stream, jobs, (long long)n_jobs, key, c->d_widthHist);
+        hipLaunchKernelGGL(bbmsa::width_scan_kernel, dim3(1), dim3(bbmsa::WIDTH_BUCKETS), 0, stream, c->d_widthHist, c->d_counters + 4, c->d_counters + 11, (unsigned)n_jobs);
+        hipLaunchKernelGGL(bbmsa::width_scatter_kernel, dim3(sb), dim3(256), 0, stream, jobs, (long long)n_jobs, key, c->d_widthHist, fastList, fastList + n_jobs);
         BBHIP(hipGetLastError());
     }
     BBHIP(hipEventRecord(c->ev[3], stream));
@@ -401,6 +423,7 @@ int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t
     fp.list = (useNarrow || sortJobs) ? fastList : nullptr; fp.list_count = c->d_counters + 4; fp.priority = 0;
     fp.slow_list = slowList; fp.slow_count = c->d_counters + 1;
     fp.lanesPerJob = c->G; fp.fastCols = c->fastCols; fp.tmpBytes = c->tmpBytes; fp.tableLen = c->tableLen;
+    fp.unl_stats = c->unlimitedStats ? c->d_counters + 9 : nullptr;
 
     // A launch with few jobs is a wavefront's latency, not throughput: (columns + lanes - 1) steps of one dependent chain.  The wide
     // pass's geometry (64 lanes x 3 rows, one job per block) has the shorter chain per step (3 rows instead of 5: ~450 instead of
@@ -410,6 +433,13 @@ int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t
     const int jobsPerBlock = 4 * (64 / c->G);
     long long blocks = (n_jobs + jobsPerBlock - 1) / jobsPerBlock;
     if (blocks > c->blocks) blocks = c->blocks;
+    if (sortJobs && c->unlimitedLoop) {
+        // the sort made a list of the unlimited fills: the build without limits and prune tests takes them, the general build the rest
+        bbmsa::FillParams up = fp;
+        up.queue = c->d_counters + 12; up.list = fastList + n_jobs; up.list_count = c->d_counters + 11;
+        void *uargs[] = {&up};
+        BBHIP(hipLaunchKernel(bbmsa::fast_kernel_unl_for(c->R), dim3((unsigned)blocks), dim3(256), uargs, (size_t)c->ldsBytes, stream));
+    }
     void *args[] = {&fp};
     if (!latency)
         BBHIP(hipLaunchKernel(bbmsa::fast_kernel_for(c->R, c->banded), dim3((unsigned)blocks), dim3(256), args, (size_t)c->ldsBytes, stream));
@@ -481,6 +511,18 @@ extern "C" int bbmsa_last_counts(bbmsa_ctx *c, int64_t *counts4) {
     BBHIP(hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
     counts4[0] = h[5]; counts4[1] = h[6]; counts4[2] = c->narrowUsed ? h[4] : 0; counts4[3] = c->wideBlocks > 0 ? h[7] : h[1];
     if (getenv("BBMAP_DP_COUNTS") && c->wideBlocks > 0) fprintf(stderr, "   (first pass handed %u jobs to the wide pass)\n", h[1]);
+    return BBMAP_OK;
+}
+
+extern "C" int bbmsa_last_unlimited(bbmsa_ctx *c, int64_t *counts4) {
+    if (!c || !c->timed || !counts4) return bbfail(BBMAP_E_ARG, "bbmsa_last_unlimited: nothing launched yet");
+    if (c->scheme == BBMSA_SCHEME_11TS && !c->legacyOnly && !c->unlimitedStats) return bbfail(BBMAP_E_ARG, "bbmsa_last_unlimited: the context does not count (create it with BBMSA_UNLIMITED_STATS=1 in the environment)");
+    BBHIP(hipSetDevice(c->device));
+    BBHIP(hipEventSynchronize(c->ev[2]));
+    unsigned h[16];
+    BBHIP(hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
+    const bool wave = c->scheme == BBMSA_SCHEME_11TS && !c->legacyOnly;
+    counts4[0] = wave ? h[9] : 0; counts4[1] = wave ? h[10] : 0; counts4[2] = wave ? h[13] : 0; counts4[3] = wave ? h[14] : 0;
     return BBMAP_OK;
 }
 

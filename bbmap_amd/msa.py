@@ -163,6 +163,14 @@ class MSAContext:
         return {"narrow": bool(r[0]), "sorted": bool(r[1]), "latency": bool(r[2]), "wide_pass": bool(r[3]), "indirect": bool(r[4]),
                 "first_handed_on": r[5], "wide_handed_on": r[6], "narrow_finished": r[7]}
 
+    def last_unlimited(self):
+        """{stripped: fills the wavefront kernel's build for unlimited fills ran, general: unlimited fills its general build ran,
+        unlimited_steps / steps: wavefront steps of the unlimited fills / of all fills} for the last launch sequence
+        (bbmsa_last_unlimited)."""
+        c = (C.c_int64 * 4)()
+        _lib.check(self.L.bbmsa_last_unlimited(self.h, c), "bbmsa_last_unlimited")
+        return {"stripped": c[0], "general": c[1], "unlimited_steps": c[2], "steps": c[3]}
+
     def geometry(self):
         """Which build of the wavefront kernel the context launches (bbmsa_geometry).  A batch context: lanes per job, rows per
         lane, columns of the first pass's buffer, rows per lane of the wide pass (0: none).  A legacy context: rows per lane of

@@ -207,6 +207,15 @@ int bbmsa_last_counts(bbmsa_ctx *ctx, int64_t *counts4);
  * jobs the first pass handed on (9PacBio: the strip kernel to the generic kernel), jobs the wide pass handed to the generic
  * kernel, jobs the band kernel finished}.  Waits for the launch sequence to finish. */
 int bbmsa_last_route(bbmsa_ctx *ctx, int64_t *route8);
+/* How the wavefront kernel ran the unlimited fills (fillUnlimited: the raw mode, or MSA.fillLimited's gate) of the last launch
+ * sequence, first and wide pass together: counts4 = {fills run by the kernel's build for unlimited fills (no limits, no prune
+ * tests: a width-sorted launch sends it the unlimited fills that fit the first pass), unlimited fills run by the general build
+ * (every other route, the wide pass, or BBMSA_UNLIMITED_LOOP=0 in the environment of bbmsa_create), wavefront steps (columns +
+ * lanes in use - 1 per fill) of the unlimited fills, wavefront steps of all fills}.  A fill the first pass hands to the wide pass
+ * counts there only.  The kernels count only in a context created with BBMSA_UNLIMITED_STATS=1 (or BBMAP_DP_COUNTS) in the
+ * environment, since every fill pays atomics for it; otherwise the call fails.  Host only; waits for the launch sequence to
+ * finish.  The 9PacBio scheme: zeros. */
+int bbmsa_last_unlimited(bbmsa_ctx *ctx, int64_t *counts4);
 /* Which build of the wavefront kernel the context launches: geo4 = {lanes per job, rows per lane of the first pass, columns of
  * the first pass's buffer, rows per lane of the wide pass (0: no wide pass)}.  A BBMSA_LEGACY_ONLY context launches one fill per
  * wavefront with the rows per lane its longest read of the launch asks for: geo4 = {64, rows per lane of the last launch (0: none
