@@ -22,7 +22,7 @@ EXPORTS = [
     "bbmap_copy_to_host", "bbidx_get_chrom_table",
     "bbpipe_revcomp_device", "bbpipe_quick_rescue_device",
     "bbidx_build_profile", "bbkeys_default_config", "bbkeys_make", "bbkeys_make_batch", "bbmap_default_config_profile",
-    "bbmap_get_final", "bbmap_set_average_pair_dist", "bbmap_final_batch_device",
+    "bbmap_get_final", "bbmap_set_average_pair_dist", "bbmap_final_batch_device", "bbmap_untrim_batch_device",
     "bbidx_set_scaffolds", "bbmap_get_scaffold_records",
     "bbmap_get_sam_records", "bbmap_get_sam",
     "bbkeys_device_workspace_bytes", "bbkeys_make_batch_device",
@@ -33,6 +33,9 @@ EXPORTS = [
     "bbpipe_read_hist_bytes", "bbpipe_read_hist_view", "bbpipe_read_hist_add_device",
     "bbmap_hist_enable", "bbmap_add_read_hist", "bbmap_get_read_hist_view", "bbmap_get_read_hist", "bbmap_reset_read_hist",
 ]
+# the trim stage's symbols (bbmap_amd.trim); a list of their own: tests/test_abi.py compares EXPORTS with the bbmap_ / bbmsa_ / bbband_ /
+# bbidx_ / bbpipe_ / bbkeys_ names it finds in the header
+TRIM_EXPORTS = ["bbtrim_default_config", "bbtrim_batch", "bbtrim_batch_device"]
 
 
 class bbmsa_job(C.Structure):

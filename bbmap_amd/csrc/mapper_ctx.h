@@ -87,6 +87,13 @@ struct bbmap_ctx {
     int rhFlags = 0;
     bool rhCounted = false;         // the last batch is in the histograms already
     hipStream_t rhStream = nullptr; // the stream of the last accumulation: the only work that writes the state
+    // bbmap_untrim_batch_device (untrim.hip): the second match-string pool (swapped with d_pool by the call), per-read byte counts and
+    // their prefix sums, allocated on first use
+    uint8_t *d_pool2 = nullptr; long long pool2Units = 0;
+    int *d_untrimCounts = nullptr;
+    long long *d_untrimOffsets = nullptr;
+    DevBuf untrimTmp;               // the scan's scratch
+    bool untrimmed = false;         // the last batch has been untrimmed already
 };
 
 // Coverage state of a context: everything is sized by the index's scaffold table as it was at bbmap_cov_enable (`gen`).

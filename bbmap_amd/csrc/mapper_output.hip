@@ -306,6 +306,8 @@ extern "C" int bbmap_add_run_stats(bbmap_ctx *c, void *stream_, const bbmap_trut
     if (!c->S.finalStage) return bbfail(BBMAP_E_ARG, "bbmap_add_run_stats: the context runs without the final stage (bbmap_config.finalStage)");
     if (!c->ran) return bbfail(BBMAP_E_ARG, "bbmap_add_run_stats: no batch has been mapped yet");
     if (c->statsCounted) return bbfail(BBMAP_E_ARG, "bbmap_add_run_stats: the last batch has been counted already");
+    // calcStatistics runs inside processRead, on the trimmed read (AbstractMapThread.java:518-521 come after it)
+    if (c->untrimmed) return bbfail(BBMAP_E_ARG, "bbmap_add_run_stats: the last batch has been untrimmed already (call it before bbmap_untrim_batch_device)");
     if (!c->batch.reads || c->batch.n_reads != c->stats.reads) return bbfail(BBMAP_E_ARG, "bbmap_add_run_stats: the context does not hold the last batch's reads");
     hipStream_t stream = (hipStream_t)stream_;
     BBHIP(hipSetDevice(c->cfg.device));

@@ -1,6 +1,6 @@
 // Read histograms on the device (include/bbmap_amd.h, bbmap_hist_* / bbpipe_read_hist_*): the launch of read_hist.hip.
 // Out of scope (bbmap_amd.h has the reasons): aqhist=, timehist=, ihist= (bbmap_get_run_stats' histogram), ID_BINS_AUTO /
-// GC_BINS_AUTO / GC_PLOT_X, trimming (TrimRead) and the SamLine branches of pairnum, JNI natives for BBMapHIP.
+// GC_BINS_AUTO / GC_PLOT_X, the SamLine branches of pairnum, JNI natives for BBMapHIP.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -186,11 +186,16 @@ class Mapper:
         return self
 
     @classmethod
-    def from_reads(cls, di, lens, bases, quality=None, kcfg=None, paired=False, device=0, max_sites=32, profile=0, **cfg_kw):
+    def from_reads(cls, di, lens, bases, quality=None, kcfg=None, paired=False, device=0, max_sites=32, profile=0, trim=None, untrim=False,
+                   **cfg_kw):
         """from_records for reads that have no keys yet: lens (one per read) and the bases blob the reads lie in back to back, with
         their numeric phred qualities at the same offsets or None.  Uploads them and runs quickMap's key stage on the device
         (bbmap_amd.keys.make_batch_device), so reads, keyinfo and base_scores exist in device memory only.  kcfg: a bbkeys_config
-        (default: keys.default_config(profile)); profile and cfg_kw as in from_records."""
+        (default: keys.default_config(profile)); profile and cfg_kw as in from_records.
+        trim: a bbtrim_config (bbmap_amd.trim.from_flags / default_config): the trim stage (qtrim= / trimq=) runs on the device in
+        front of the key stage and the mapper maps the trimmed records; self.reads_untrimmed and self.trims keep what untrim() needs.
+        untrim only stores the intent (self.untrim_wanted): step() does not call untrim(), because add_run_stats() has to come before
+        it and that order is the caller's."""
         from . import keys as K
         self = cls.__new__(cls)
         self.L = _lib.load()
@@ -227,6 +232,15 @@ class Mapper:
             q = torch.from_numpy(qblob).to(self.dev)
         self.quality = q                    # add_read_hist()'s default
         self.reads = torch.from_numpy(recs.view(np.uint8).reshape(-1).copy()).to(self.dev)
+        self.reads_untrimmed = self.trims = None
+        self.untrim_wanted = bool(untrim)
+        if trim is not None:
+            from . import trim as T
+            self.reads_untrimmed = self.reads
+            self.reads, self.trims = T.trim_batch_device(self.reads_untrimmed, self.bases[: self.total_bytes], q, trim)
+            if n and int(self.reads.view(torch.int32).view(-1, 6)[:, 4].min().item()) <= 0:
+                raise ValueError("Mapper.from_reads: trimming left a read without bases (possible with minLength <= 0 only); "
+                                 "the mapper takes no zero-length read")
         _, keyinfo, self.base_scores = K.make_batch_device(self.reads, self.bases[: self.total_bytes], q, kcfg or K.default_config(profile))
         self.keyinfo = keyinfo if keyinfo.numel() else torch.zeros(1, dtype=torch.int32, device=self.dev)
         return self
@@ -256,6 +270,7 @@ class Mapper:
         blob = np.ascontiguousarray(bases, np.uint8)
         self.n, self.total_bytes = len(recs), int(blob.size)
         self.quality = None                 # (the qualities from_reads uploaded belong to the reads it was given)
+        self.reads_untrimmed = self.trims = None            # (and so do its trims)
         self.bases = torch.zeros(2 * self.total_bytes, dtype=torch.uint8, device=self.dev)
         self.bases[: self.total_bytes].copy_(torch.from_numpy(blob))
         self.base_scores = torch.from_numpy(np.ascontiguousarray(base_scores, np.int8)).to(self.dev)
@@ -291,6 +306,19 @@ class Mapper:
                                           keyinfo.ctypes.data, keyinfo.size, ns.ctypes.data, offs.ctypes.data, sites.ctypes.data,
                                           sites_cap, C.byref(total)), "bbmap_map_batch")
         return ns, offs, sites[:min(total.value, sites_cap)], total.value
+
+    def untrim(self):
+        """bbmap_untrim_batch_device: TrimRead.untrim over the last step of a context made by from_reads(trim=...): the final records,
+        site lists and match strings get the trimmed ends back as soft clips, and everything called afterwards (final, fetch,
+        sam_records, add_coverage, add_read_hist) works on the full reads.  add_run_stats() must come first (calcStatistics runs on
+        the trimmed read); a second call for one step raises."""
+        if getattr(self, "trims", None) is None:
+            raise ValueError("Mapper.untrim: the context was not made by from_reads(trim=...)")
+        self.L.bbmap_untrim_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.L.bbmap_untrim_batch_device.restype = C.c_int
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(self.L.bbmap_untrim_batch_device(self.h, C.c_void_p(stream), self.reads_untrimmed.data_ptr(), self.trims.data_ptr()),
+                   "bbmap_untrim_batch_device")
 
     def final(self, with_match=True):
         """bbmap_get_final: (records FINAL_DTYPE[n], match blob uint8[]) of the last step, overflow tier included; read r's match

@@ -486,6 +486,44 @@ int bbkeys_make_batch_device(const bbkeys_config *cfg, void *stream, int64_t n_r
                              int8_t *baseScores, void *workspace, int64_t workspace_bytes, int64_t *keyinfo_used);
 
 /* =====================================================================================
+ * Quality trimming: qtrim= / trimq= / untrim=
+ *   align2.TrimRead as the mapping thread applies it: TrimRead.trim before processRead (current/align2/AbstractMapThread.java:484-487)
+ *   and, with untrim=t, TrimRead.untrim behind it (:518-521; bbmap_untrim_batch_device further down).  The trim stage restates
+ *   TrimRead.trim(Read, ...) (current/align2/TrimRead.java:47-63): testOptimal (:264-324, a float32 running sum in read order),
+ *   testRightWindow (:349-365), testLeft / testRight (:327-385), the N-only scans testLeftN / testRightN (:388-413) for a read without
+ *   qualities, and the constructor's clamp to minLength (trim(int,int,int), :164-197: the excess comes off the left side first).
+ *   A read is (bases_off, len) into a blob, so trimming moves no base: reads_out[i] = {bases_off + left, 0, len - left - right, 0}
+ *   and trims[i] = {left, right}, both trims 0 when Java returns null or the clamp leaves nothing to trim.  The key stage
+ *   (bbkeys_make_batch_device) then runs over reads_out.  Two forms with byte for byte the same output: host code (bbtrim_batch) and a
+ *   kernel over a resident batch (bbtrim_batch_device: one read per lane, the error probability table handed to the kernel, no libm
+ *   on the device).  Qualities above 126 are outside the domain, as in Java's table.
+ *   Out of scope: trimBadSequence, trimFast / trimByAmount (BBDuk's callers), qtrim1 / qtrim2 and trimq lists, breakReads.
+ * ===================================================================================== */
+enum { BBTRIM_MODE_OPTIMAL = 0, BBTRIM_MODE_WINDOW = 1, BBTRIM_MODE_INTERVAL = 2 };
+typedef struct bbtrim_config {
+    int32_t mode;              /* TrimRead.optimalMode / windowMode / neither; tested in that order (TrimRead.java:51-61) */
+    int32_t trimLeft, trimRight;
+    int32_t trimq;             /* 0..126 */
+    int32_t minLength;         /* TRIM_MIN_LENGTH */
+    int32_t windowLength;      /* 4 */
+    int32_t minGoodInterval;   /* 2 */
+    float   optimalBias;       /* < 0: off; otherwise replaces PROB_ERROR[trimq] (TrimRead.java:265) */
+} bbtrim_config;               /* 32 bytes */
+typedef struct bbtrim_rec { int32_t left, right; } bbtrim_rec;
+/* BBMap's: optimal mode, both sides off, trimq 6 (Parser.java:930), minLength 60 (AbstractMapper.java:2720), window 4, interval 2,
+ * bias -1 */
+int bbtrim_default_config(bbtrim_config *cfg);
+/* Host form.  Read i occupies bases[reads_in[i].bases_off .. + len), its numeric phred qualities lie at the same offsets in
+ * `quality` (NULL: reads without qualities).  reads_out must not alias reads_in.  BBMAP_E_ARG: a null argument, n_reads < 0,
+ * aliasing, trimq outside 0..126, an unknown mode, windowLength < 1, minGoodInterval < 1, an optimalBias above 1 or NaN. */
+int bbtrim_batch(const bbtrim_config *cfg, int64_t n_reads, const bbidx_read *reads_in, const uint8_t *bases,
+                 const uint8_t *quality, bbidx_read *reads_out, bbtrim_rec *trims);
+/* Device form: every pointer but cfg is a device pointer on the current device.  Enqueues one kernel on `stream`; makes no device
+ * allocation and does not wait.  n_reads == 0: BBMAP_OK, nothing is launched. */
+int bbtrim_batch_device(const bbtrim_config *cfg, void *stream, int64_t n_reads, const bbidx_read *reads_in,
+                        const uint8_t *bases, const uint8_t *quality, bbidx_read *reads_out, bbtrim_rec *trims);
+
+/* =====================================================================================
  * Batch helpers (device-resident) used by the mapper below; also callable on their own.
  * ===================================================================================== */
 /* bases_out[read] = reverse complement of bases_in[read] (AminoAcid.reverseComplementBases) */
@@ -723,6 +761,22 @@ int bbmap_get_overflow_output(bbmap_ctx *ctx, bbmap_overflow_output *out);
  * *match_bytes = bytes the strings take; strings that do not fit match_cap are not written (call again with a larger buffer).
  * match_out may be NULL (records only).  BBMAP_E_ARG when the context runs without the final stage. */
 int bbmap_get_final(bbmap_ctx *ctx, int64_t n_reads, bbmap_final *out, uint8_t *match_out, int64_t match_cap, int64_t *match_bytes);
+/* TrimRead.untrim (current/align2/TrimRead.java:415-508) over the last batch, which was mapped from reads that bbtrim_batch_device
+ * trimmed: reads_untrimmed / trims are that stage's reads_in / trims (device arrays of n_reads entries; reads_untrimmed must stay in
+ * place, it becomes the batch's read array).  For a read with left + right > 0, lt / rt = left / right, swapped on the minus strand
+ * of the record (of the site): the final record gets perfect = 0 and, when mapped, start -= lt, stop += rt; its match string becomes
+ * lt x 'C' + string + rt x 'C'; every site of its list gets start -= lt, stop += rt with its own strand, perfect = semiperfect = 0
+ * and its own string padded the same way.  The overflow tier's records, lists and strings likewise (tier read i = batch read
+ * read_ids[i]).  A read with left + right == 0 is untouched.  One divergence: an unmapped record keeps start = stop = -1.
+ * The strings grow, so they move: a sizing pass, a device-wide scan, an emit pass (one wavefront per read) into a second pool of the
+ * context's, then the pools are swapped -- every string has a new offset afterwards, and strings that shared bytes have copies of
+ * their own.  The reverse complements of the full reads are written again at bases_off + minus_delta.  Everything that reads the
+ * batch afterwards (bbmap_get_output, bbmap_get_final, bbmap_get_scaffold_records, bbmap_get_sam_records, bbmap_add_coverage,
+ * bbmap_add_read_hist) sees the untrimmed reads, as in Java, where those steps come after :521.  calcStatistics runs inside
+ * processRead, before untrim: call bbmap_add_run_stats before this, it refuses a batch that has been untrimmed.
+ * Enqueues on `stream` and waits for it once per context (the new pool's size).  BBMAP_E_ARG: the context runs without the final
+ * stage, no batch has been mapped, or the batch has been untrimmed already. */
+int bbmap_untrim_batch_device(bbmap_ctx *ctx, void *stream, const bbidx_read *reads_untrimmed, const bbtrim_rec *trims);
 /* SamLine's coordinate block (current/stream/SamLine.java:120-187, :267-268) for every final record of the last batch, overflow tier
  * included: which scaffold a read landed on and where.  A record that still spans two scaffolds (Data.isSingleScaffold) is unmapped and
  * its mate unpaired, as SamLine does.  Unmapped after that rule: scaffold = -1 and every coordinate 0. */
@@ -1078,8 +1132,10 @@ int bbmap_reset_coverage(bbmap_ctx *ctx);
  *   qualSumDouble) are not kept, the host derives them from the position x quality table, so BBMAP_RH_QUALITY always keeps that
  *   table.  Reads longer than BBMAP_RH_MAX_POS (the library maps none) are counted up to that position.
  *   Out of scope: aqhist= (a per-read float32 sum in read order through log10: the host holds the qualities it read and can do it
- *   there), timehist=, ihist= (bbmap_get_run_stats' histogram), ID_BINS_AUTO / GC_BINS_AUTO / GC_PLOT_X, trimming (TrimRead) and
- *   the SamLine branches of pairnum, and JNI natives for BBMapHIP.
+ *   there), timehist=, ihist= (bbmap_get_run_stats' histogram), ID_BINS_AUTO / GC_BINS_AUTO / GC_PLOT_X, the SamLine branches
+ *   of pairnum, and JNI natives for BBMapHIP.  With qtrim and untrim=f Java counts qhist / bhist / lhist / gchist on the read BEFORE
+ *   trimming (:478-482) while the context holds the trimmed reads: a host that wants those files calls bbpipe_read_hist_add_device
+ *   for those groups with the untrimmed read array itself.
  * ===================================================================================== */
 enum { BBMAP_RH_MATCH = 1,         /* mhist=: matchSum subSum delSum insSum nSum clipSum otherSum, [7][2][BBMAP_RH_MAXLEN] */
        BBMAP_RH_QUALITY = 2,       /* qhist= / bqhist= / qchist=: qualLength [2][MAXLEN], bqualHist [2][MAXLEN][127], qcountHist [2][127] */
