@@ -14,7 +14,7 @@ EXPORTS = [
     "bbmap_last_error", "bbmap_abi_version",
     "bbmsa_create", "bbmsa_destroy", "bbmsa_align_batch_device", "bbmsa_align_batch",
     "bbmsa_fill_packed", "bbmsa_fill_submit", "bbmsa_fill_collect", "bbmsa_legacy_stats", "bbmsa_last_kernel_ms", "bbmsa_last_kernel_ms3", "bbmsa_last_counts", "bbmsa_align_gapped_batch_device", "bbmsa_align_gapped_batch", "bbmsa_align_batch_device_indirect",
-    "bbmsa_align_gapped_batch_device_indirect", "bbmsa_last_route", "bbmsa_last_unlimited", "bbmsa_geometry",
+    "bbmsa_align_gapped_batch_device_indirect", "bbmsa_last_route", "bbmsa_last_unlimited", "bbmsa_geometry", "bbmsa_debug_sorted_lists",
     "bbband_create", "bbband_destroy", "bbband_align_batch_device", "bbband_align_batch",
     "bbband_align_quadruple_batch", "bbband_align_quadruple_progressive_batch", "bbband_align_double_batch",
     "bbidx_create", "bbidx_destroy", "bbidx_find_batch_device", "bbidx_find_batch", "bbidx_find_batch_device_rc", "bbidx_last_stats", "bbidx_last_launch", "bbidx_set_kernel", "bbidx_set_max_read_len", "bbidx_build", "bbidx_get_params", "bbidx_export_block",
@@ -129,6 +129,8 @@ def load():
     L.bbmsa_last_kernel_ms3.restype = C.c_int
     L.bbmsa_last_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.bbmsa_last_counts.restype = C.c_int
+    L.bbmsa_debug_sorted_lists.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
+    L.bbmsa_debug_sorted_lists.restype = C.c_int
     L.bbmsa_last_route.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.bbmsa_last_route.restype = C.c_int
     L.bbmsa_last_unlimited.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]

@@ -50,6 +50,7 @@ struct bbmap_ctx {
     bool ownsMsa;
     long long narrowMinJobs;        // plain-context launches with at least this many fills run the narrow kernel (BBMAP_NARROW_MIN_JOBS)
     bool sortWide;                  // the second context hands its fills on widest first (BBMAP_SORT_WIDE=0 switches it off)
+    bool sortPlain;                 // so does the first context where it runs the band kernel (BBMAP_SORT_PLAIN=0 switches it off)
     int *d_tierUnits; bbidx_read *d_tierReads; int *d_tierReadIds;
     long long tierReads;            // reads the tier mapped in the last batch
     // The tier's pass runs beside the main pass (its reads are known once begin_kernel has run): its own stream, driven by its

@@ -153,6 +153,13 @@ static int create_impl(bbidx_ctx *index, const bbmap_config *cfg, bbmap_ctx *par
     const int cap = cfg->max_sites;
     c->narrowMinJobs = getenv("BBMAP_NARROW_MIN_JOBS") ? atoll(getenv("BBMAP_NARROW_MIN_JOBS")) : 32768;
     c->sortWide = !(getenv("BBMAP_SORT_WIDE") && atoi(getenv("BBMAP_SORT_WIDE")) == 0);      // (experiments: 0 switches the width order off)
+    c->sortPlain = !(getenv("BBMAP_SORT_PLAIN") && atoi(getenv("BBMAP_SORT_PLAIN")) == 0);
+    if (!pacbio) {
+        // the 64-lane launches (latency route, wide pass) give unlimited fills the prune-free step loop; BBMAP_WIDE_UNLIMITED=0: no
+        const bool wideUnl = !(getenv("BBMAP_WIDE_UNLIMITED") && atoi(getenv("BBMAP_WIDE_UNLIMITED")) == 0);
+        bbmsa_set_wide_unlimited(c->msa, wideUnl);
+        if (c->msaGapped != c->msa) bbmsa_set_wide_unlimited(c->msaGapped, wideUnl);
+    }
     if (!pacbio) {
         // launches of a few hundred fills (the late rounds of scoreSlow and of the final stage) are one wavefront's latency: they take
         // the 64-lane geometry, whose step is the shorter chain (msa_ctx.h; 236 -> 231 ms per step for the second context alone)
@@ -297,9 +304,13 @@ static int run_fills(bbmap_ctx *c, hipStream_t stream, const uint8_t *bases, lon
     // 2 * rows turns however few jobs there are: worth it only for the big first rounds -- of scoreSlow, of rescue and of the final
     // stage (a third to a half of their fills finish in its 32 diagonals).  The second context's wide windows never fit.
     bbmsa_use_narrow(c->msa, nNew >= c->narrowMinJobs);
-    // (not the first context's: its windows span 162..256 columns, and sorted its pass ends 4 ms earlier -- leaving the second
-    // context's latency-bound wide pass to finish on its own: final stage 79.6 -> 85.5 ms)
-    bbmsa_sort_by_width(c->msa, false);
+    // The first context's launches that run the band kernel are sorted too (bbmsa_sort_with_band): two fills share a 32-lane
+    // wavefront and step together as long as the wider one needs.  BBMAP_SORT_PLAIN=0 switches it off (A/B runs).
+    // Measured: 193.9 ms per step with it, 198.5 without; scoreSlow 57.6 / 59.5, the final stage 55.1 / 57.3 ms.
+    // (An older note here had the sorted plain pass lose 6 ms in the final stage; that was before the band kernel took the tight
+    // fills and before the second context's unlimited fills had a build of their own, and no longer holds.)
+    bbmsa_sort_by_width(c->msa, c->sortPlain && nNew >= c->narrowMinJobs);
+    bbmsa_sort_with_band(c->msa, c->sortPlain);
     if (c->msaGapped != c->msa) { bbmsa_use_narrow(c->msaGapped, false); bbmsa_sort_by_width(c->msaGapped, c->sortWide); }
     // the second context's launches first, on their own stream: its blocks take their share of the CUs and the plain context's
     // persistent blocks fill the rest (and the slots the others free)

@@ -135,6 +135,22 @@ __host__ __device__ inline bool fill_is_limited(int flags, int minScore, int row
              ((halfband < 1 || halfband * 3 > columns) && (columns > rows + min(170, rows + 20))));
 }
 
+// The band kernel's candidate rule (msa_fill_band.hip), shared with the width sort in front of it (msa_host.hip), which gives the
+// candidates a list of their own: a limited fill (through the Java gate for BBMSA_FILL_LIMITED, which then runs with
+// minScore - 120) of a shape the band kernel accepts, whose slack maxQuality(rows) - minScore is at most maxSlack points.
+// `columns` is the clamped window's; the context has no band (halfband == 0).  A candidate is always a limited fill.
+__host__ __device__ inline bool band_is_candidate(int flags, int minScore, int rows, int columns, int maxRows, int maxColumns, int bandRows, int maxSlack) {
+    const int mode = flags & BBMSA_MODE_MASK;
+    if (!(rows >= 16 && columns >= rows && rows <= maxRows && rows <= bandRows && columns <= maxColumns && mode != BBMSA_FILL_UNLIMITED_RAW)) return false;
+    int tmin = minScore;
+    if (mode == BBMSA_FILL_LIMITED) {                         // the Java gate, MultiStateAligner11tsJNI.java:137-144 (halfband == 0)
+        if (tmin < 1 || (columns + rows < 90) || (columns > rows + min(170, rows + 20))) return false;
+        tmin -= 120;
+    }
+    // candidates are chosen by slack alone; no tighter bound is ever substituted (tests/test_oracle_final.py)
+    return (70 + 100 * (rows - 1)) - tmin <= maxSlack;
+}
+
 // number of jobs of a launch: a host value, or a counter a previous kernel of the same stream left on the device
 __device__ inline long long job_count(long long njobs, const unsigned int *njobs_dev) {
     if (!njobs_dev) return njobs;
@@ -168,7 +184,8 @@ struct FillParams {
     int bandwidth;
     float bandwidthRatio;
     unsigned int *unl_stats;      // [0] jobs that ran in the unlimited build, [1] unlimited jobs that ran in the general build,
-                                  // [4] / [5] wavefront steps (columns + lanes in use - 1) of the unlimited jobs / of all jobs; NULL: not counted
+                                  // [4] / [5] wavefront steps (columns + lanes in use - 1) of the unlimited jobs / of all jobs,
+                                  // [8] steps the wavefronts ran (each as many as its longest job); NULL: not counted
     // matrix-materialising mode (the legacy per-call JNI shape, msa_legacy.hip; kernels instantiated with MAT only): job j's three
     // score planes go to planes + plane_off[j], each rows x columns ints (state-major; rows 1..rows, columns 1..columns of the matrix), its
     // vertLimit[0..rows] / horizLimit[0..columns] to limits + limits_off[j] (rows + 1 ints, then columns + 1)
@@ -200,6 +217,8 @@ struct NarrowParams {
     unsigned int *dirbuf32;       // per resident wave: (bandRows + 1) x 2 jobs x 64 lanes dwords of records
     int tableLen;                 // entries of the delC / insC tables (see lds_table_ints)
     int bandRows;                 // longest read it takes (its LDS areas and record slots are sized for it)
+    const int *list;              // the jobs to try (the width sort's candidates); NULL = every job of the launch
+    const unsigned int *list_count;   // the list's length, on the device (read when the kernel starts)
 };
 
 struct GenericParams {

@@ -14,7 +14,7 @@ struct bbmsa_ctx {
     int G = 0, R = 0, fastCols = 0, tmpBytes = 0, blocks = 0, ldsBytes = 0, tableLen = 0, wideTableLen = 0;
     long long dirSlotDwords = 0;
     unsigned int *d_dir = nullptr;
-    unsigned int *d_counters = nullptr;   // 16 words; [0]=fast queue, [1]=slow count, [2]=generic queue, ... (bbmsa_align_impl has the list)
+    unsigned int *d_counters = nullptr;   // 32 words; [0]=fast queue, [1]=slow count, [2]=generic queue, ... (bbmsa_align_impl has the list)
     DevBuf slowList;            // ints: the jobs the wavefront kernel hands on; as long as the largest launch so far
     // generic kernel
     int genThreads = 0;
@@ -36,6 +36,9 @@ struct bbmsa_ctx {
     // widest windows first (bbmsa_sort_by_width): two jobs share a wavefront and step together, so a 600-column job beside a
     // 200-column one idles half the wave for 400 steps; in width order neighbours are alike, and the longest jobs do not end up last
     bool sortByWidth = false;
+    bool sortWithBand = false;         // sort also the launches that run the band kernel (bbmsa_sort_with_band): the candidates get a list of their own
+    bool wideUnlimited = false;        // the 64-lane launches run unlimited fills in the prune-free loop (bbmsa_set_wide_unlimited)
+    long long lastJobs = 0;            // jobs of the last launch (bbmsa_debug_sorted_lists)
     bool unlimitedLoop = true;         // a width-sorted launch runs its unlimited fills in the wavefront kernel's build for them (BBMSA_UNLIMITED_LOOP=0: no)
     bool unlimitedStats = false;       // the kernels count for bbmsa_last_unlimited (BBMSA_UNLIMITED_STATS=1 or BBMAP_DP_COUNTS at bbmsa_create)
     unsigned int *d_widthHist = nullptr;
@@ -81,6 +84,17 @@ int bbmsa_wait_first_pass(bbmsa_ctx *c, void *waiter);
 void bbmsa_sort_by_width(bbmsa_ctx *c, bool on);
 // BBMSA_SORT_BY_WIDTH=1 in the environment switches it on for every context bbmsa_create makes (default 0; a caller that sets it,
 // like the mapper, overrides it per context).
+// A context with both the band kernel and bbmsa_sort_by_width on does not sort the launches the band kernel runs in (both write the
+// wavefront kernel's list) -- unless this is on.  Then the sort's key is (class, width): unlimited fills, band candidates (the band
+// kernel's own rule, band_is_candidate), everything else.  The band kernel walks the candidates' list and appends what it hands on
+// behind the sorted general list, which the wavefront kernel's general build reads after it: [general, widest first | hand-overs].
+// Two jobs of a 32-lane wavefront step together for max(columns) + lanes - 1 steps; sorted, partners have one width.
+// Default off; BBMSA_SORT_WITH_BAND=1 in the environment applies it at bbmsa_create.  The mapper asks for it on its first context.
+void bbmsa_sort_with_band(bbmsa_ctx *c, bool on);
+// The launches of the 64-lane geometry (the latency route and the wide pass: one job per wavefront) take the build of the wavefront
+// kernel that holds both step loops and gives an unlimited fill the prune-free one (a limited fill never takes it: fill_is_limited
+// per job).  Default off; BBMSA_WIDE_UNLIMITED=1 applies it at bbmsa_create.  Without effect in a banded context (no such build).
+void bbmsa_set_wide_unlimited(bbmsa_ctx *c, bool on);
 // Launches of at most n jobs skip the first pass and run in the wide pass's geometry (64 lanes x ceil(rows / 64) rows per lane, one job
 // per block): with few jobs a launch costs one wavefront's dependent chain, and three rows per lane make a step ~450 instructions
 // instead of ~740.  Measured on the mapper's late rounds (a few hundred fills each): 236.0 -> 230.9 ms per step for the second

@@ -87,7 +87,8 @@ __global__ __launch_bounds__(256, BBMSA_BAND_OCC) void msa_fill_band_kernel(cons
     const int RB = (p.bandRows + 4 + 3) & ~3, FB = (p.bandRows + B + 4 + 3) & ~3;      // bytes per job: read, reference
     uint8_t *jobLds = reinterpret_cast<uint8_t *>(lds + lds_table_ints(TL)) + (long long)wave * JOBS * (RB + FB);
     unsigned *dir = p.dirbuf32 + ((long long)blockIdx.x * 4 + wave) * (long long)(p.bandRows + 1) * 128;   // [(row * 2 + slot) * 64 + lane]
-    const long long NJ = job_count(p.njobs, p.njobs_dev);
+    // with a list (the width sort's candidates, msa_host.hip) the queue runs over the list's entries; without one over every job
+    const long long NJ = p.list ? (long long)ld_coherent(p.list_count) : job_count(p.njobs, p.njobs_dev);
     unsigned nDone = 0, nLeft = 0;
 
     for (;;) {
@@ -95,26 +96,17 @@ __global__ __launch_bounds__(256, BBMSA_BAND_OCC) void msa_fill_band_kernel(cons
         long long myJ = -1;
         if (lane < JOBS) {
             for (;;) {
-                const long long t_ = (long long)atomicAdd(p.queue, 1u);
-                if (t_ >= NJ) break;
+                const long long e_ = (long long)atomicAdd(p.queue, 1u);
+                if (e_ >= NJ || e_ >= p.njobs) break;
+                const long long t_ = p.list ? (long long)p.list[e_] : e_;
                 const bbmsa_job t = p.jobs[t_];
                 int ta = t.refStartLoc, tb = t.refEndLoc;
-                const int tmode = t.flags & BBMSA_MODE_MASK;
                 if (t.flags & BBMSA_CLAMP_WINDOW) {
                     ta = max(0, ta); tb = min(t.ref_len - 1, tb);
                     if (tb - ta >= p.maxColumns) tb = min(t.ref_len - 1, ta + p.maxColumns - 1);
                 }
-                const int trows = t.read_len, tcols = tb - ta + 1;
-                bool cand = trows >= 16 && tcols >= trows && trows <= p.maxRows && trows <= p.bandRows && tcols <= p.maxColumns &&
-                            tmode != BBMSA_FILL_UNLIMITED_RAW;
-                int tmin = t.minScore;
-                if (cand && tmode == BBMSA_FILL_LIMITED) {            // the Java gate, MultiStateAligner11tsJNI.java:137-144 (halfband == 0)
-                    if (tmin < 1 || (tcols + trows < 90) || (tcols > trows + min(170, trows + 20))) cand = false;
-                    else tmin -= 120;
-                }
-                // candidates are chosen by slack alone; no tighter bound is ever substituted (tests/test_oracle_final.py)
-                if (cand && (70 + 100 * (trows - 1)) - tmin > p.maxSlack) cand = false;
-                if (cand) { myJ = t_; break; }
+                // (msa_common.h: the rule the width sort uses to make the list, so every entry of a list passes it)
+                if (band_is_candidate(t.flags, t.minScore, t.read_len, tb - ta + 1, p.maxRows, p.maxColumns, p.bandRows, p.maxSlack)) { myJ = t_; break; }
                 const unsigned k = atomicAdd(p.fast_count, 1u);
                 p.fast_list[k] = (int)t_;
             }

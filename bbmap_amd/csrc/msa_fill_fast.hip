@@ -70,10 +70,14 @@ __device__ __forceinline__ unsigned load_coherent(const unsigned *p) {
 // code leaves in the Java class's `packed` matrix for score2 / traceback2 to walk (jni/MultiStateAligner11tsJNI.c:124-127, :707-812).
 // A cell that is visited but not "good" is stored as subfloor | time, as the reference stores it (:556-562); cells this schedule
 // computes beyond a row's end are stored as subfloor -- the reference leaves those untouched, and never reads them (its sentinels).
-// UNL: the build for unlimited fills only (fillUnlimited), launched over the unlimited fills of a width-sorted launch in front of the
+// UNL == 1: the build for unlimited fills only (fillUnlimited), launched over the unlimited fills of a width-sorted launch in front of the
 // general build: its step loop has no limits, no prune tests and no good-column extents.  A limited job it met would be handed on.
-template <int R, bool BANDED, bool MAT = false, bool UNL = false>
-__global__ __launch_bounds__(256, BBMSA_MIN_WAVES(R)) void msa_fill_fast_kernel(const FillParams p) {
+// UNL == 2: both step loops in one build, chosen per job by fill_is_limited -- for launches with 64 lanes per job only (the latency
+// route and the wide pass, bbmsa_set_wide_unlimited), where a wavefront holds one job and the choice is wave-uniform.
+template <int R, bool BANDED, bool MAT = false, int UNL = 0>
+// (the build with both loops runs one job per block of one wavefront, eight blocks per CU at the most: it may take the registers of
+// two waves per SIMD, where it holds both loops without a spill)
+__global__ __launch_bounds__(256, (UNL == 2 && BBMSA_MIN_WAVES(R) > 2) ? 2 : BBMSA_MIN_WAVES(R)) void msa_fill_fast_kernel(const FillParams p) {
     extern __shared__ int lds[];
     int *delC = lds;
     const int TL = p.tableLen;
@@ -151,7 +155,7 @@ __global__ __launch_bounds__(256, BBMSA_MIN_WAVES(R)) void msa_fill_fast_kernel(
         const bool limited = fill_is_limited(jb.flags, jb.minScore, rows, columns, halfband);
         const int minScore = (limited && mode != BBMSA_FILL_LIMITED_RAW) ? jb.minScore - 120 : jb.minScore;
         const bool fits = rows <= G * R && columns <= p.fastCols && columns >= rows - 2;   // (narrower windows: see the cell)
-        const bool needGeneric = shapeOK && (!fits || (UNL && limited));
+        const bool needGeneric = shapeOK && (!fits || (UNL == 1 && limited));
         const bool run = shapeOK && !needGeneric;
         // Banded fill (jni/...c:441-442): a row may only extend one column past the last good column of the
         // row above, which this schedule learns one column late.  The kernel assumes a row's good columns have
@@ -242,7 +246,7 @@ __global__ __launch_bounds__(256, BBMSA_MIN_WAVES(R)) void msa_fill_fast_kernel(
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        if (run && gl == 0 && !UNL) {                                    // jni/...c:427-438 (the prune-free loop reads no horizLimit)
+        if (run && gl == 0 && UNL != 1 && (UNL == 0 || limited)) {       // jni/...c:427-438 (the prune-free loop reads no horizLimit)
             int h = minScoreOff;
             bool prevDef = false;
             for (int i = columns - 1; i >= 0; i--) {
@@ -271,10 +275,11 @@ __global__ __launch_bounds__(256, BBMSA_MIN_WAVES(R)) void msa_fill_fast_kernel(
         const int nl = (rows + R - 1) / R;                               // lanes in use
         int steps = run ? columns + nl - 1 : 0;
         if (!MAT && p.unl_stats && gl == 0 && run) {                     // bbmsa_last_unlimited
-            if (!limited) { atomicAdd(p.unl_stats + (UNL ? 0 : 1), 1u); atomicAdd(p.unl_stats + 4, (unsigned)steps); }
+            if (!limited) { atomicAdd(p.unl_stats + (UNL != 0 ? 0 : 1), 1u); atomicAdd(p.unl_stats + 4, (unsigned)steps); }
             atomicAdd(p.unl_stats + 5, (unsigned)steps);
         }
         for (int d = 32; d >= 1; d >>= 1) steps = max(steps, __shfl_xor(steps, d, 64));
+        if (!MAT && p.unl_stats && lane == 0 && steps > 0) atomicAdd(p.unl_stats + 8, (unsigned)steps);      // what the wavefront runs: its longest job's steps
 
         int pM[R], pD[R], pI[R];         // my rows' cells at the previous column
         int minGood[R], maxGood[R];      // first / last good column of each row (-1 / -2 = none)
@@ -306,7 +311,9 @@ __global__ __launch_bounds__(256, BBMSA_MIN_WAVES(R)) void msa_fill_fast_kernel(
         const bool ownerLaneFlag = gl == (max(rows, 1) - 1) / R;
         int bestM = 0, bestD = 0, bestI = 0, bestMc = -1, bestDc = -1, bestIc = -1;
 
-        if constexpr (UNL) {
+        // which step loop: a constant in the builds with one loop; with both, the job's kind (one job per wavefront: uniform)
+        const bool stripped = UNL == 1 || (UNL == 2 && __builtin_amdgcn_readfirstlane((int)notLimited) != 0);
+        if (stripped) {
         // The step loop of fillUnlimited (jni/...c:134-290): the general loop below without limits, "still needed" penalties and
         // good-column extents (iterations = rows x columns).  Rows beyond the read: their deletion and insertion planes sit behind
         // the barrier forces, their match plane computes values nobody reads (each row only feeds the rows below it).
@@ -695,11 +702,19 @@ const void *fast_kernel_mat_for(int R, bool banded) {
     }
     return nullptr;
 }
-#define BBMSA_CASE_UNL(R) case R: return (const void *)msa_fill_fast_kernel<R, false, false, true>;
+#define BBMSA_CASE_UNL(R) case R: return (const void *)msa_fill_fast_kernel<R, false, false, 1>;
 const void *fast_kernel_unl_for(int R) {            // (an unlimited fill has no band: one build serves banded contexts too)
     switch (R) {
         BBMSA_CASE_UNL(1) BBMSA_CASE_UNL(2) BBMSA_CASE_UNL(3) BBMSA_CASE_UNL(4) BBMSA_CASE_UNL(5)
         BBMSA_CASE_UNL(6) BBMSA_CASE_UNL(7) BBMSA_CASE_UNL(8) BBMSA_CASE_UNL(9) BBMSA_CASE_UNL(10)
+    }
+    return nullptr;
+}
+#define BBMSA_CASE_BOTH(R) case R: return (const void *)msa_fill_fast_kernel<R, false, false, 2>;
+const void *fast_kernel_both_for(int R) {           // (launched with 64 lanes per job only; a banded context has none)
+    switch (R) {
+        BBMSA_CASE_BOTH(1) BBMSA_CASE_BOTH(2) BBMSA_CASE_BOTH(3) BBMSA_CASE_BOTH(4) BBMSA_CASE_BOTH(5)
+        BBMSA_CASE_BOTH(6) BBMSA_CASE_BOTH(7) BBMSA_CASE_BOTH(8) BBMSA_CASE_BOTH(9) BBMSA_CASE_BOTH(10)
     }
     return nullptr;
 }

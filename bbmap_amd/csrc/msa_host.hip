@@ -25,46 +25,96 @@ const void *strip_kernel_pacbio_pipelined();
 int strip_pipe_sync_ints(int K);
 const void *fast_kernel_for(int R, bool banded);
 const void *fast_kernel_unl_for(int R);
+const void *fast_kernel_both_for(int R);                       // both step loops, chosen per job (64 lanes per job only); null: no such build
+constexpr int kCounterWords = 32, kCounterBytes = kCounterWords * 4;      // d_counters of every context (bbmsa_align_impl has the list)
 template <class S> __global__ void msa_fill_generic_kernel(const GenericParams p);
 const void *band_kernel();                                     // msa_fill_band.hip
 int band_lds_bytes(int tableLen, int bandRows);
 }  // namespace bbmsa
 
 namespace bbmsa {
-constexpr int WIDTH_BUCKETS = 1024;            // fill kind (major) x columns / 8: 512 widths per kind.  Only 11ts contexts sort, and bbmsa_create
-                                               // refuses one of more than 4,096 columns, so only a window of exactly 4,096 shares its bucket (with 4,088..4,095)
-struct SortKey { int maxColumns, bandwidth; float bandwidthRatio; int byKind; };
-// byKind: the unlimited fills in front of the limited ones, each kind in descending width.  The wavefront kernel has a build of its
-// own for unlimited fills, which is launched over them in front of the general build (bbmsa_align_impl); the scatter gives each
-// kind its own list.
+// The width sort in front of the first pass: a counting sort of the launch's jobs by (class, columns / 8 descending) into one list
+// per class.  Classes: unlimited fills (the wavefront kernel's prune-free build takes them), band candidates (msa_fill_band.hip; only
+// when the launch runs the band kernel over a list, bbmsa_sort_with_band), everything else (the general build).
+constexpr int WIDTH_PER_CLASS = 512;           // columns / 8.  Only 11ts contexts sort, and bbmsa_create refuses one of more than 4,096
+                                               // columns, so only a window of exactly 4,096 shares its bucket (with 4,088..4,095)
+constexpr int WIDTH_CLASSES = 3;
+constexpr int WIDTH_BUCKETS = WIDTH_CLASSES * WIDTH_PER_CLASS;
+enum { CLASS_UNLIMITED = 0, CLASS_CANDIDATE = 1, CLASS_GENERAL = 2 };
+constexpr int SORT_THREADS = 256, SORT_JOBS_PER_THREAD = 4;     // a block of the histogram / scatter kernels takes 1,024 jobs
+struct SortKey { int maxRows, maxColumns, bandwidth; float bandwidthRatio; int byKind, band, bandRows, maxSlack; };
+// byKind: the unlimited fills get their own list (else they are general jobs); band: so do the band kernel's candidates, by the
+// kernel's own rule (band_is_candidate, msa_common.h).
 __device__ inline int job_width_bucket(const bbmsa_job &t, const SortKey k) {
     int a = t.refStartLoc, b = t.refEndLoc;
     if (t.flags & BBMSA_CLAMP_WINDOW) { a = max(0, a); b = min(t.ref_len - 1, b); if (b - a >= k.maxColumns) b = min(t.ref_len - 1, a + k.maxColumns - 1); }
     const int cols = max(0, b - a + 1);
-    const bool limited = fill_is_limited(t.flags, t.minScore, t.read_len, b - a + 1, fill_halfband(t.read_len, b - a + 1, k.bandwidth, k.bandwidthRatio));
-    constexpr int W = WIDTH_BUCKETS / 2;
-    return ((limited || !k.byKind) ? W : 0) + W - 1 - min(W - 1, cols >> 3);  // bucket 0 = the widest unlimited fill, W = the widest limited one
+    int cls = CLASS_GENERAL;
+    if (k.band && band_is_candidate(t.flags, t.minScore, t.read_len, b - a + 1, k.maxRows, k.maxColumns, k.bandRows, k.maxSlack)) cls = CLASS_CANDIDATE;
+    else if (k.byKind && !fill_is_limited(t.flags, t.minScore, t.read_len, b - a + 1, fill_halfband(t.read_len, b - a + 1, k.bandwidth, k.bandwidthRatio))) cls = CLASS_UNLIMITED;
+    constexpr int W = WIDTH_PER_CLASS;
+    return cls * W + W - 1 - min(W - 1, cols >> 3);            // bucket 0 of a class = its widest windows
 }
-__global__ void width_hist_kernel(const bbmsa_job *jobs, long long n, SortKey key, unsigned *hist) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) atomicAdd(&hist[job_width_bucket(jobs[i], key)], 1u);
-}
-// one block of WIDTH_BUCKETS threads: exclusive prefix sums in place, each kind's from 0 (the scatter's cursors); the lengths of the two lists
-__global__ void width_scan_kernel(unsigned *hist, unsigned *listCount, unsigned *unlCount, unsigned n) {
+// Both kernels count in an LDS copy of the histogram first: a launch's windows crowd into a few buckets (half of the plain context's
+// fills have one width), and one global atomic per job on those few words is what the kernels then wait for.  A block adds each bucket
+// it met to the global word once.
+__global__ __launch_bounds__(SORT_THREADS) void width_hist_kernel(const bbmsa_job *jobs, long long n, SortKey key, unsigned *hist) {
     __shared__ unsigned s[WIDTH_BUCKETS];
-    const int t = threadIdx.x;
-    s[t] = hist[t];
+    for (int i = threadIdx.x; i < WIDTH_BUCKETS; i += SORT_THREADS) s[i] = 0;
     __syncthreads();
-    for (int d = 1; d < WIDTH_BUCKETS; d <<= 1) { const unsigned v = t >= d ? s[t - d] : 0u; __syncthreads(); s[t] += v; __syncthreads(); }
-    const unsigned unl = s[WIDTH_BUCKETS / 2 - 1];
-    hist[t] = s[t] - hist[t] - (t >= WIDTH_BUCKETS / 2 ? unl : 0u);
-    if (t == 0) { *listCount = n - unl; *unlCount = unl; }
+    const long long base = (long long)blockIdx.x * (SORT_THREADS * SORT_JOBS_PER_THREAD) + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < SORT_JOBS_PER_THREAD; k++) {
+        const long long i = base + (long long)k * SORT_THREADS;
+        if (i < n) atomicAdd(&s[job_width_bucket(jobs[i], key)], 1u);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < WIDTH_BUCKETS; i += SORT_THREADS) { const unsigned v = s[i]; if (v) atomicAdd(&hist[i], v); }
 }
-__global__ void width_scatter_kernel(const bbmsa_job *jobs, long long n, SortKey key, unsigned *cursor, int *list, int *unlList) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const int bucket = job_width_bucket(jobs[i], key);
-        (bucket < WIDTH_BUCKETS / 2 ? unlList : list)[atomicAdd(&cursor[bucket], 1u)] = (int)i;
+// one block of WIDTH_PER_CLASS threads: exclusive prefix sums in place, each class's from 0 (the scatter's cursors), and the lengths of
+// the three lists.  The general list's length goes to two words: `listCount`, which the band kernel then appends its hand-overs
+// through, and `sortedCount`, which keeps it.
+__global__ void width_scan_kernel(unsigned *hist, unsigned *listCount, unsigned *sortedCount, unsigned *unlCount, unsigned *candCount) {
+    __shared__ unsigned s[WIDTH_PER_CLASS];
+    const int t = threadIdx.x;
+    for (int cls = 0; cls < WIDTH_CLASSES; cls++) {
+        const unsigned own = hist[cls * WIDTH_PER_CLASS + t];
+        s[t] = own;
+        __syncthreads();
+        for (int d = 1; d < WIDTH_PER_CLASS; d <<= 1) { const unsigned v = t >= d ? s[t - d] : 0u; __syncthreads(); s[t] += v; __syncthreads(); }
+        hist[cls * WIDTH_PER_CLASS + t] = s[t] - own;
+        if (t == WIDTH_PER_CLASS - 1) {
+            if (cls == CLASS_UNLIMITED) *unlCount = s[t];
+            else if (cls == CLASS_CANDIDATE) *candCount = s[t];
+            else { *listCount = s[t]; *sortedCount = s[t]; }
+        }
+        __syncthreads();
+    }
+}
+// every list has room for all n jobs; a job's place is its bucket's cursor + the block's share of the bucket + its rank in the block
+__global__ __launch_bounds__(SORT_THREADS) void width_scatter_kernel(const bbmsa_job *jobs, long long n, SortKey key, unsigned *cursor, int *list, int *unlList, int *candList) {
+    __shared__ unsigned s[WIDTH_BUCKETS];
+    for (int i = threadIdx.x; i < WIDTH_BUCKETS; i += SORT_THREADS) s[i] = 0;
+    __syncthreads();
+    const long long base = (long long)blockIdx.x * (SORT_THREADS * SORT_JOBS_PER_THREAD) + threadIdx.x;
+    int bucket[SORT_JOBS_PER_THREAD]; unsigned rank[SORT_JOBS_PER_THREAD];
+#pragma unroll
+    for (int k = 0; k < SORT_JOBS_PER_THREAD; k++) {
+        const long long i = base + (long long)k * SORT_THREADS;
+        bucket[k] = -1; rank[k] = 0;
+        if (i < n) { bucket[k] = job_width_bucket(jobs[i], key); rank[k] = atomicAdd(&s[bucket[k]], 1u); }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < WIDTH_BUCKETS; i += SORT_THREADS) { const unsigned v = s[i]; if (v) s[i] = atomicAdd(&cursor[i], v); }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SORT_JOBS_PER_THREAD; k++) {
+        if (bucket[k] < 0) continue;
+        const long long i = base + (long long)k * SORT_THREADS;
+        const unsigned pos = s[bucket[k]] + rank[k];
+        if ((long long)pos >= n) continue;                      // (cannot happen: a class holds at most n jobs)
+        const int cls = bucket[k] / WIDTH_PER_CLASS;
+        (cls == CLASS_UNLIMITED ? unlList : (cls == CLASS_CANDIDATE ? candList : list))[pos] = (int)i;
     }
 }
 }  // namespace bbmsa
@@ -82,6 +132,8 @@ static int setup_wide_pass(bbmsa_ctx *c) {
     const void *wfn = bbmsa::fast_kernel_for(c->wideR, c->banded);
     if (wfn && c->wideLdsBytes <= 160 * 1024) {
         if (c->wideLdsBytes > 64 * 1024) BBHIP(hipFuncSetAttribute(wfn, hipFuncAttributeMaxDynamicSharedMemorySize, c->wideLdsBytes));
+        const void *bfn = c->banded ? nullptr : bbmsa::fast_kernel_both_for(c->wideR);      // (bbmsa_set_wide_unlimited)
+        if (bfn && c->wideLdsBytes > 64 * 1024) BBHIP(hipFuncSetAttribute(bfn, hipFuncAttributeMaxDynamicSharedMemorySize, c->wideLdsBytes));
         int per = 0;
         BBHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, wfn, 64, c->wideLdsBytes));
         if (per < 1) per = 1;
@@ -119,8 +171,8 @@ extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
     struct Guard { bbmsa_ctx *c; ~Guard() { if (c) bbmsa_destroy(c); } } guard{c};
     if (legacyOnly) {
         // a context for bbmsa_fill_packed only (the per-call JNI shape): one scratch matrix, no batch buffers
-        BBHIP(hipMalloc(&c->d_counters, 64));
-        BBHIP(hipMemset(c->d_counters, 0, 64));
+        BBHIP(hipMalloc(&c->d_counters, bbmsa::kCounterBytes));
+        BBHIP(hipMemset(c->d_counters, 0, bbmsa::kCounterBytes));
         const long long planeInts = (long long)(cfg->maxRows + 1) * (cfg->maxColumns + 2);
         c->genThreads = 1;
         BBHIP(hipMalloc(&c->d_matrix, (size_t)(3 * planeInts * 4)));
@@ -134,8 +186,8 @@ extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
     if (scheme != BBMSA_SCHEME_11TS) {
         // 9PacBio: the strip-tiled wavefront kernel (msa_fill_strip.hip), one alignment per wavefront; banded fills and windows
         // narrower than the read are handed to the one-job-per-thread kernel
-        BBHIP(hipMalloc(&c->d_counters, 64));
-        BBHIP(hipMemset(c->d_counters, 0, 64));
+        BBHIP(hipMalloc(&c->d_counters, bbmsa::kCounterBytes));
+        BBHIP(hipMemset(c->d_counters, 0, bbmsa::kCounterBytes));
         const long long planeInts = (long long)(cfg->maxRows + 1) * (cfg->maxColumns + 2);
         const long long perThread = 3 * planeInts * 4;
         long long budget = (long long)env_int("BBMSA_GENERIC_SCRATCH_MB", 40960) << 20;   // 6019 x 7600 (mapPacBio) needs 35 GB for one wavefront of matrices
@@ -239,8 +291,8 @@ extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
     c->dirSlotDwords = (long long)((maxSteps >> 3) + 1) * c->R * G;
     const long long slots = (long long)c->blocks * 4 * jobsPerWave;
     BBHIP(hipMalloc(&c->d_dir, (size_t)(slots * c->dirSlotDwords * 4)));
-    BBHIP(hipMalloc(&c->d_counters, 64));
-    BBHIP(hipMemset(c->d_counters, 0, 64));
+    BBHIP(hipMalloc(&c->d_counters, bbmsa::kCounterBytes));
+    BBHIP(hipMemset(c->d_counters, 0, bbmsa::kCounterBytes));
 
     // generic kernel scratch: as many threads as a 2 GiB matrix budget allows (at least one wave)
     const long long planeInts = (long long)(cfg->maxRows + 1) * (cfg->maxColumns + 2);
@@ -271,6 +323,8 @@ extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
     }
     // route switches of the environment (msa_ctx.h): defaults off, as the functions they mirror leave a context
     c->sortByWidth = env_int("BBMSA_SORT_BY_WIDTH", 0) != 0;
+    c->sortWithBand = env_int("BBMSA_SORT_WITH_BAND", 0) != 0;
+    c->wideUnlimited = env_int("BBMSA_WIDE_UNLIMITED", 0) != 0;
     c->unlimitedLoop = env_int("BBMSA_UNLIMITED_LOOP", 1) != 0;         // 0: the general build of the wavefront kernel takes every job
     // bbmsa_last_unlimited's counters cost every fill two or three atomics on the same few words: only on request
     c->unlimitedStats = env_int("BBMSA_UNLIMITED_STATS", 0) != 0 || getenv("BBMAP_DP_COUNTS") != nullptr;
@@ -356,7 +410,7 @@ int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t
     BBHIP(c->slowList.grow(listBytes, 0, &stream));
     int *const slowList = c->slowList.as<int>();
     if (c->scheme != BBMSA_SCHEME_11TS) {
-        BBHIP(hipMemsetAsync(c->d_counters, 0, 64, stream));
+        BBHIP(hipMemsetAsync(c->d_counters, 0, bbmsa::kCounterBytes, stream));
         c->narrowUsed = false; c->lastSorted = false; c->lastLatency = false; c->lastIndirect = n_jobs_dev != nullptr;
         BBHIP(hipEventRecord(c->ev[0], stream));
         BBHIP(hipEventRecord(c->ev[3], stream));
@@ -382,38 +436,48 @@ int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t
         return launch_generic<bbmsa::Scheme9PacBio>(c, B, stream, slowList, c->d_counters + 1);
     }
     if (c->wideBlocks > 0) BBHIP(c->slowList2.grow(listBytes, 0, &stream));
-    const bool sortJobs = c->sortByWidth && !n_jobs_dev && n_jobs >= 256 && n_jobs > c->latencyJobs && !(c->narrowBlocks > 0 && !c->narrowOff);
-    if (c->narrowBlocks > 0 || sortJobs) BBHIP(c->fastList.grow(sortJobs ? 2 * listBytes : listBytes, 0, &stream));   // (sorted: the limited fills' list, then the unlimited fills')
+    const bool useNarrow = c->narrowBlocks > 0 && !c->narrowOff;
+    // Both the band kernel and the sort write the wavefront kernel's list.  Together only on request (bbmsa_sort_with_band): the sort
+    // then gives the band kernel a list of its candidates, and the band kernel appends what it hands on behind the sorted list.
+    const bool sortJobs = c->sortByWidth && !n_jobs_dev && n_jobs >= 256 && n_jobs > c->latencyJobs && (!useNarrow || c->sortWithBand);
+    // (sorted: the general list with room for the band kernel's hand-overs, then the unlimited fills' list, then the candidates')
+    if (c->narrowBlocks > 0 || sortJobs) BBHIP(c->fastList.grow(sortJobs ? 3 * listBytes : listBytes, 0, &stream));
     int *const fastList = c->fastList.as<int>();
     // counters: [0] fast queue, [1] slow count, [2] generic queue, [3] narrow queue, [4] fast-list count,
     //           [5] jobs finished by the band kernel (the "narrow" slots), [6] candidates it handed on, [7] wide pass's slow count,
-    //           [8] wide queue, [9] jobs the wavefront kernel's unlimited build ran, [10] unlimited jobs its general build ran,
+    //           [8] wide queue, [9] jobs the wavefront kernel's prune-free loop ran, [10] unlimited jobs its general loop ran,
     //           [11] length of a width-sorted launch's list of unlimited jobs, [12] the unlimited build's queue,
-    //           [13] / [14] wavefront steps of the unlimited jobs / of all jobs (bbmsa_last_unlimited)
-    BBHIP(hipMemsetAsync(c->d_counters, 0, 64, stream));
+    //           [13] / [14] wavefront steps of the unlimited jobs / of all jobs (bbmsa_last_unlimited),
+    //           [15] length of a width-sorted launch's list of band candidates, [16] of its general list as the sort left it
+    //           (before the band kernel's hand-overs), [17] steps the wavefronts ran (a wavefront steps as its longest job)
+    BBHIP(hipMemsetAsync(c->d_counters, 0, bbmsa::kCounterBytes, stream));
     BBHIP(hipEventRecord(c->ev[0], stream));
-    const bool useNarrow = c->narrowBlocks > 0 && !c->narrowOff;
     c->narrowUsed = useNarrow;
+    if (sortJobs) {
+        if (!c->d_widthHist) BBHIP(hipMalloc(&c->d_widthHist, bbmsa::WIDTH_BUCKETS * 4));
+        BBHIP(hipMemsetAsync(c->d_widthHist, 0, bbmsa::WIDTH_BUCKETS * 4, stream));
+        const int perBlock = bbmsa::SORT_THREADS * bbmsa::SORT_JOBS_PER_THREAD;
+        const unsigned sb = (unsigned)((n_jobs + perBlock - 1) / perBlock);
+        const bbmsa::SortKey key = {c->cfg.maxRows, c->cfg.maxColumns, c->cfg.bandwidth, c->cfg.bandwidthRatio, c->unlimitedLoop ? 1 : 0,
+                                    useNarrow ? 1 : 0, c->bandRows, c->narrowSlack};
+        hipLaunchKernelGGL(bbmsa::width_hist_kernel, dim3(sb), dim3(bbmsa::SORT_THREADS), 0, stream, jobs, (long long)n_jobs, key, c->d_widthHist);
+        hipLaunchKernelGGL(bbmsa::width_scan_kernel, dim3(1), dim3(bbmsa::WIDTH_PER_CLASS), 0, stream, c->d_widthHist, c->d_counters + 4, c->d_counters + 16,
+                           c->d_counters + 11, c->d_counters + 15);
+        hipLaunchKernelGGL(bbmsa::width_scatter_kernel, dim3(sb), dim3(bbmsa::SORT_THREADS), 0, stream, jobs, (long long)n_jobs, key, c->d_widthHist,
+                           fastList, fastList + n_jobs, fastList + 2 * n_jobs);
+        BBHIP(hipGetLastError());
+    }
     if (useNarrow) {
         bbmsa::NarrowParams np;
         set_batch(np, c, B);
         np.queue = c->d_counters + 3; np.fast_list = fastList; np.fast_count = c->d_counters + 4;
         np.stats = c->d_counters + 5; np.maxSlack = c->narrowSlack;
         np.dirbuf32 = c->d_bandDir; np.tableLen = c->tableLen; np.bandRows = c->bandRows;
+        np.list = sortJobs ? fastList + 2 * n_jobs : nullptr; np.list_count = sortJobs ? c->d_counters + 15 : nullptr;
         long long nb = (n_jobs + 63) / 64;
         if (nb > c->narrowBlocks) nb = c->narrowBlocks;
         void *nargs[] = {&np};
         BBHIP(hipLaunchKernel(bbmsa::band_kernel(), dim3((unsigned)nb), dim3(256), nargs, (size_t)c->bandLds, stream));
-    }
-    if (sortJobs) {                    // (never together with the narrow kernel: both write the wavefront kernel's list)
-        if (!c->d_widthHist) BBHIP(hipMalloc(&c->d_widthHist, bbmsa::WIDTH_BUCKETS * 4));
-        BBHIP(hipMemsetAsync(c->d_widthHist, 0, bbmsa::WIDTH_BUCKETS * 4, stream));
-        const unsigned sb = (unsigned)((n_jobs + 255) / 256);
-        const bbmsa::SortKey key = {c->cfg.maxColumns, c->cfg.bandwidth, c->cfg.bandwidthRatio, c->unlimitedLoop ? 1 : 0};
-        hipLaunchKernelGGL(bbmsa::width_hist_kernel, dim3(sb), dim3(256), 0, stream, jobs, (long long)n_jobs, key, c->d_widthHist);
-        hipLaunchKernelGGL(bbmsa::width_scan_kernel, dim3(1), dim3(bbmsa::WIDTH_BUCKETS), 0, stream, c->d_widthHist, c->d_counters + 4, c->d_counters + 11, (unsigned)n_jobs);
-        hipLaunchKernelGGL(bbmsa::width_scatter_kernel, dim3(sb), dim3(256), 0, stream, jobs, (long long)n_jobs, key, c->d_widthHist, fastList, fastList + n_jobs);
-        BBHIP(hipGetLastError());
     }
     BBHIP(hipEventRecord(c->ev[3], stream));
 
@@ -429,7 +493,7 @@ int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t
     // pass's geometry (64 lanes x 3 rows, one job per block) has the shorter chain per step (3 rows instead of 5: ~450 instead of
     // ~740 instructions), so such launches go to it directly (bbmsa_set_latency_jobs; the mapper's late rounds hold a few hundred fills).
     const bool latency = c->wideBlocks > 0 && !n_jobs_dev && !useNarrow && n_jobs <= c->latencyJobs;
-    c->lastSorted = sortJobs; c->lastLatency = latency; c->lastIndirect = n_jobs_dev != nullptr;
+    c->lastSorted = sortJobs; c->lastLatency = latency; c->lastIndirect = n_jobs_dev != nullptr; c->lastJobs = n_jobs;
     const int jobsPerBlock = 4 * (64 / c->G);
     long long blocks = (n_jobs + jobsPerBlock - 1) / jobsPerBlock;
     if (blocks > c->blocks) blocks = c->blocks;
@@ -458,7 +522,10 @@ int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t
         wp.priority = widePrio;
         void *wargs[] = {&wp};
         const long long wblocks = latency && n_jobs < c->wideBlocks ? n_jobs : c->wideBlocks;
-        BBHIP(hipLaunchKernel(bbmsa::fast_kernel_for(c->wideR, c->banded), dim3((unsigned)wblocks), dim3(64), wargs, (size_t)c->wideLdsBytes, stream));
+        // one job per wavefront: which step loop runs is wave-uniform, so one build can hold both and give an unlimited fill the
+        // prune-free one (bbmsa_set_wide_unlimited; a banded context has no such build)
+        const void *bothFn = (c->wideUnlimited && !c->banded) ? bbmsa::fast_kernel_both_for(c->wideR) : nullptr;
+        BBHIP(hipLaunchKernel(bothFn ? bothFn : bbmsa::fast_kernel_for(c->wideR, c->banded), dim3((unsigned)wblocks), dim3(64), wargs, (size_t)c->wideLdsBytes, stream));
         genList = wp.slow_list; genCount = c->d_counters + 7;
     }
     BBHIP(hipEventRecord(c->ev[1], stream));
@@ -467,6 +534,8 @@ int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t
 
 void bbmsa_use_narrow(bbmsa_ctx *c, bool on) { if (c) c->narrowOff = !on; }
 void bbmsa_sort_by_width(bbmsa_ctx *c, bool on) { if (c) c->sortByWidth = on; }
+void bbmsa_sort_with_band(bbmsa_ctx *c, bool on) { if (c) c->sortWithBand = on; }
+void bbmsa_set_wide_unlimited(bbmsa_ctx *c, bool on) { if (c) c->wideUnlimited = on; }
 int bbmsa_set_latency_jobs(bbmsa_ctx *c, int64_t n) {
     if (!c || c->scheme != BBMSA_SCHEME_11TS || c->legacyOnly) return BBMAP_OK;
     BBHIP(hipSetDevice(c->device));
@@ -507,10 +576,34 @@ extern "C" int bbmsa_last_counts(bbmsa_ctx *c, int64_t *counts4) {
     if (!c || !c->timed || !counts4) return bbfail(BBMAP_E_ARG, "bbmsa_last_counts: nothing launched yet");
     BBHIP(hipSetDevice(c->device));
     BBHIP(hipEventSynchronize(c->ev[2]));
-    unsigned h[16];
+    unsigned h[bbmsa::kCounterWords];
     BBHIP(hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
-    counts4[0] = h[5]; counts4[1] = h[6]; counts4[2] = c->narrowUsed ? h[4] : 0; counts4[3] = c->wideBlocks > 0 ? h[7] : h[1];
-    if (getenv("BBMAP_DP_COUNTS") && c->wideBlocks > 0) fprintf(stderr, "   (first pass handed %u jobs to the wide pass)\n", h[1]);
+    // the wavefront list: what the band kernel left to the wavefront kernel without trying it, plus what it handed on -- on a sorted
+    // launch the sort's general and unlimited lists, which hold no candidate (finished + handed on + this = the launch's jobs)
+    counts4[0] = h[5]; counts4[1] = h[6]; counts4[2] = c->narrowUsed ? (c->lastSorted ? h[16] + h[11] : h[4]) : 0; counts4[3] = c->wideBlocks > 0 ? h[7] : h[1];
+    if (getenv("BBMAP_DP_COUNTS")) {
+        if (c->wideBlocks > 0) fprintf(stderr, "   (first pass handed %u jobs to the wide pass)\n", h[1]);
+        if (c->lastSorted) fprintf(stderr, "   (sorted: %u general, %u unlimited, %u band candidates)\n", h[16], h[11], h[15]);
+        fprintf(stderr, "   (the wavefronts ran %u steps)\n", h[17]);
+    }
+    return BBMAP_OK;
+}
+
+// Test hook: the three lists the last launch's width sort made, as `n_jobs` ints each in lists3 (general, unlimited, band candidates;
+// entries past a list's length are not written) and their lengths in lens3.  Fails when the last launch was not sorted.
+extern "C" int bbmsa_debug_sorted_lists(bbmsa_ctx *c, int64_t n_jobs, int32_t *lists3, int64_t *lens3) {
+    if (!c || !c->timed || !lists3 || !lens3) return bbfail(BBMAP_E_ARG, "bbmsa_debug_sorted_lists: nothing launched yet");
+    if (!c->lastSorted || n_jobs != c->lastJobs) return bbfail(BBMAP_E_ARG, "bbmsa_debug_sorted_lists: the last launch was not a sorted launch of n_jobs jobs");
+    BBHIP(hipSetDevice(c->device));
+    BBHIP(hipEventSynchronize(c->ev[2]));
+    unsigned h[bbmsa::kCounterWords];
+    BBHIP(hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
+    const unsigned len[3] = {h[16], h[11], h[15]};
+    for (int k = 0; k < 3; k++) {
+        if ((int64_t)len[k] > n_jobs) return bbfail(BBMAP_E_HIP, "bbmsa_debug_sorted_lists: a list is longer than the launch");
+        lens3[k] = len[k];
+        if (len[k]) BBHIP(hipMemcpy(lists3 + (size_t)k * (size_t)n_jobs, c->fastList.as<int>() + (size_t)k * (size_t)n_jobs, (size_t)len[k] * 4, hipMemcpyDeviceToHost));
+    }
     return BBMAP_OK;
 }
 

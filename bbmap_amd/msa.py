@@ -188,6 +188,14 @@ class MSAContext:
         _lib.check(self.L.bbmsa_last_counts(self.h, c), "bbmsa_last_counts")
         return {"narrow": c[0], "narrow_left": c[1], "wave": c[2], "generic": c[3]}
 
+    def debug_sorted_lists(self, n_jobs):
+        """The job lists the last launch's width sort made (bbmsa_debug_sorted_lists): {general, unlimited, candidates}, each an
+        int32 array of job indices in the order the kernels take them.  Raises when the last launch was not sorted."""
+        lists = np.full((3, n_jobs), -1, np.int32)
+        lens = (C.c_int64 * 3)()
+        _lib.check(self.L.bbmsa_debug_sorted_lists(self.h, n_jobs, lists.ctypes.data, lens), "bbmsa_debug_sorted_lists")
+        return {"general": lists[0, :lens[0]].copy(), "unlimited": lists[1, :lens[1]].copy(), "candidates": lists[2, :lens[2]].copy()}
+
     def last_kernel_ms3(self):
         """(narrow-window kernel, wavefront kernel, generic kernel) milliseconds of the last launch sequence."""
         m = (C.c_float * 3)()

@@ -199,8 +199,15 @@ int bbmsa_last_kernel_ms(bbmsa_ctx *ctx, float *ms_fast, float *ms_slow);
 int bbmsa_last_kernel_ms3(bbmsa_ctx *ctx, float *ms3);
 /* Which kernel took how many jobs of the last launch sequence: counts4 = {finished by the band kernel (a job over
  * 8 lanes, a band of 32 diagonals in registers), candidates it handed on because their window left the band, jobs given
- * to the wavefront kernel in total, jobs the wavefront kernel handed to the generic kernel}. */
+ * to the wavefront kernel in total, jobs the wavefront kernel handed to the generic kernel}.  "Given to the wavefront kernel":
+ * the jobs the band kernel did not try plus those it handed on; on a width-sorted launch that runs the band kernel
+ * (BBMSA_SORT_WITH_BAND) the lengths of the sort's general and unlimited lists, so that the first three add up to the launch. */
 int bbmsa_last_counts(bbmsa_ctx *ctx, int64_t *counts4);
+/* Test hook for the width sort in front of a launch (BBMSA_SORT_BY_WIDTH, BBMSA_SORT_WITH_BAND): the job lists the last launch's
+ * sort made -- lists3 holds 3 x n_jobs ints: the general list, the unlimited fills' list, the band kernel's candidates, each in
+ * descending columns / 8; lens3 their lengths (entries past a length are not written).  n_jobs is the last launch's.  Fails when
+ * that launch was not sorted.  Host only; waits for the launch sequence to finish. */
+int bbmsa_debug_sorted_lists(bbmsa_ctx *ctx, int64_t n_jobs, int32_t *lists3, int64_t *lens3);
 /* The route the last launch sequence took (host flags recorded at launch, then the device counters):
  * route8 = {band kernel ran (0/1), first pass in descending window width (0/1), latency route: no first pass, the
  * wide pass took every job (0/1), the context has a wide pass (0/1), job count read on the device (an _indirect entry, 0/1),
@@ -210,7 +217,8 @@ int bbmsa_last_route(bbmsa_ctx *ctx, int64_t *route8);
 /* How the wavefront kernel ran the unlimited fills (fillUnlimited: the raw mode, or MSA.fillLimited's gate) of the last launch
  * sequence, first and wide pass together: counts4 = {fills run by the kernel's build for unlimited fills (no limits, no prune
  * tests: a width-sorted launch sends it the unlimited fills that fit the first pass), unlimited fills run by the general build
- * (every other route, the wide pass, or BBMSA_UNLIMITED_LOOP=0 in the environment of bbmsa_create), wavefront steps (columns +
+ * (every other route, the wide pass, or BBMSA_UNLIMITED_LOOP=0 in the environment of bbmsa_create; with BBMSA_WIDE_UNLIMITED=1 the
+ * latency route and the wide pass run a build that holds both loops, and their unlimited fills count under the first), wavefront steps (columns +
  * lanes in use - 1 per fill) of the unlimited fills, wavefront steps of all fills}.  A fill the first pass hands to the wide pass
  * counts there only.  The kernels count only in a context created with BBMSA_UNLIMITED_STATS=1 (or BBMAP_DP_COUNTS) in the
  * environment, since every fill pays atomics for it; otherwise the call fails.  Host only; waits for the launch sequence to
