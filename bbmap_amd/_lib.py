@@ -32,6 +32,9 @@ EXPORTS = [
     "bbmap_cov_enable", "bbmap_add_coverage", "bbmap_cov_finalize", "bbmap_get_coverage", "bbmap_reset_coverage",
     "bbpipe_read_hist_bytes", "bbpipe_read_hist_view", "bbpipe_read_hist_add_device",
     "bbmap_hist_enable", "bbmap_add_read_hist", "bbmap_get_read_hist_view", "bbmap_get_read_hist", "bbmap_reset_read_hist",
+    "bbpipe_refsplit_state_bytes", "bbpipe_refsplit_add_device", "bbpipe_refsplit_lists_workspace_bytes", "bbpipe_refsplit_lists_device",
+    "bbmap_split_enable", "bbmap_add_split", "bbmap_get_split_records", "bbmap_get_split_lists_device", "bbmap_get_split_lists",
+    "bbmap_get_split_stats", "bbmap_reset_split",
 ]
 # the trim stage's symbols (bbmap_amd.trim); a list of their own: tests/test_abi.py compares EXPORTS with the bbmap_ / bbmsa_ / bbband_ /
 # bbidx_ / bbpipe_ / bbkeys_ names it finds in the header

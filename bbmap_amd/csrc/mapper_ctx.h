@@ -95,6 +95,22 @@ struct bbmap_ctx {
     long long *d_untrimOffsets = nullptr;
     DevBuf untrimTmp;               // the scan's scratch
     bool untrimmed = false;         // the last batch has been untrimmed already
+    // reference-set binning (bbmap_split_enable): null until enabled
+    struct SplitState *split = nullptr;
+    bool splitCounted = false;      // the last batch is in the split state already
+};
+
+// Reference-set binning state of a context (ref_split.hip): the tables are the host's, one entry per scaffold of the index's table as
+// it was at bbmap_split_enable (`gen`).
+struct SplitState {
+    bbmap_split_config cfg = {};
+    int nscaf = 0;
+    long long gen = 0, added = -1, total = 0;       // added: reads of the batch the records belong to (-1 = none yet)
+    hipStream_t stream = nullptr;   // of the last add
+    DevBuf sets, keys, state, recs, ws, setoff, units;
+    SplitState() = default;
+    SplitState(const SplitState &) = delete;
+    ~SplitState() { for (DevBuf *b : {&sets, &keys, &state, &recs, &ws, &setoff, &units}) b->release(); }
 };
 
 // Coverage state of a context: everything is sized by the index's scaffold table as it was at bbmap_cov_enable (`gen`).

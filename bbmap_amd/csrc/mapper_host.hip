@@ -44,6 +44,7 @@ extern "C" void bbmap_destroy(bbmap_ctx *c) {
     for (DevBuf &b : c->buf) b.release();
     c->untrimTmp.release();
     delete c->cov;
+    delete c->split;
     if (c->hostStream) (void)hipStreamDestroy(c->hostStream);
     if (c->tierStream) (void)hipStreamDestroy(c->tierStream);
     if (c->dpStream) (void)hipStreamDestroy(c->dpStream);
@@ -714,7 +715,7 @@ extern "C" int bbmap_map_batch_device(bbmap_ctx *c, void *stream_, int64_t n_rea
     if (!reads || !bases || !baseScores || !keyinfo) return bbfail(BBMAP_E_ARG, "bbmap_map_batch_device: null buffer");
     hipStream_t stream = (hipStream_t)stream_;
     BBHIP(hipSetDevice(c->cfg.device));
-    c->statsCounted = false; c->covCounted = false; c->rhCounted = false; c->untrimmed = false;
+    c->statsCounted = false; c->covCounted = false; c->rhCounted = false; c->splitCounted = false; c->untrimmed = false;
     const bbmap_truth *truth = c->truthNext;
     c->truthNext = nullptr;
     bool skip = false;
@@ -740,7 +741,7 @@ extern "C" int bbmap_final_batch_device(bbmap_ctx *c, void *stream_, int64_t n_r
     BBHIP(hipSetDevice(c->cfg.device));
     c->tierStarted = false; c->tierReads = 0;
     if (c->tier) c->tier->ran = false;
-    c->statsCounted = false; c->covCounted = false; c->rhCounted = false; c->untrimmed = false;
+    c->statsCounted = false; c->covCounted = false; c->rhCounted = false; c->splitCounted = false; c->untrimmed = false;
     memset(&c->stats, 0, sizeof c->stats);
     c->stats.reads = n_reads;
     c->batch = {n_reads, reads, bases, minus_delta, nullptr, nullptr};

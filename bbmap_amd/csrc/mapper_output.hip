@@ -1,5 +1,5 @@
 // What reads a finished batch of the mapper (mapper_host.hip maps it): packed site lists, the host-buffer form of the batch call, the
-// log and final records, scaffold records, SAM records, run statistics, coverage, read histograms.
+// log and final records, scaffold records, SAM records, run statistics, coverage, read histograms, reference-set binning.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -12,6 +12,7 @@
 #include "coverage.h"
 #include "mapper_ctx.h"
 #include "read_hist.h"
+#include "ref_split.h"
 #include "run_stats.h"
 #include "sam_records.h"
 
@@ -584,6 +585,142 @@ extern "C" int bbmap_reset_read_hist(bbmap_ctx *c) {
     BBHIP(hipMemsetAsync(c->d_readHist, 0, 8 * (size_t)bbrh::layout_of(c->rhFlags).words, c->rhStream));      // behind the last accumulation
     BBHIP(hipStreamSynchronize(c->rhStream));
     c->rhCounted = false;           // the state no longer holds the batch the context still has
+    return BBMAP_OK;
+}
+
+// ---- reference-set binning (ref_split.hip): thin wrappers over the raw calls' launches
+extern "C" int bbmap_split_enable(bbmap_ctx *c, const bbmap_split_config *cfg_, const uint64_t *scaf_sets, const int32_t *scaf_key) {
+    if (!c || !cfg_ || !scaf_sets || !scaf_key) return bbfail(BBMAP_E_ARG, "bbmap_split_enable: null argument");
+    if (!c->S.finalStage) return bbfail(BBMAP_E_ARG, "bbmap_split_enable: the context runs without the final stage (bbmap_config.finalStage)");
+    const bbscaf::Table T = c->index->scaf;
+    if (!T.off) return bbfail(BBMAP_E_ARG, "bbmap_split_enable: the index has no scaffold table (bbidx_set_scaffolds)");
+    bbmap_split_config cfg = *cfg_;
+    if (cfg.clearzone == 0) cfg.clearzone = c->S.cz1;                                          // CLEARZONE1()
+    if (cfg.maxSites == 0) cfg.maxSites = c->cfg.reserved[3] == BBIDX_PROFILE_PACBIO ? 100 : 5;     // BBMapPacBio.java:65 / BBMap.java:62
+    cfg.reserved[0] = cfg.reserved[1] = 0;
+    if (const char *why = bbsplit::check_config(cfg)) return bbfail(BBMAP_E_ARG, "bbmap_split_enable: %s", why);
+    if (!cfg.flags) return bbfail(BBMAP_E_ARG, "bbmap_split_enable: nothing selected");
+    if (c->split) {
+        if (memcmp(&c->split->cfg, &cfg, sizeof cfg) != 0) return bbfail(BBMAP_E_ARG, "bbmap_split_enable: the stage is enabled already with another configuration");
+        if (c->split->gen != c->index->scafGen) return bbfail(BBMAP_E_ARG, "bbmap_split_enable: the scaffold table has been replaced since the stage was enabled");
+        return BBMAP_OK;
+    }
+    BBHIP(hipSetDevice(c->cfg.device));
+    std::unique_ptr<SplitState> v(new SplitState);
+    v->cfg = cfg; v->gen = c->index->scafGen;
+    std::vector<int> off((size_t)T.nchroms + 2);
+    BBHIP(hipMemcpy(off.data(), T.off, off.size() * 4, hipMemcpyDeviceToHost));
+    v->nscaf = off[(size_t)T.nchroms + 1];
+    const size_t ns = (size_t)v->nscaf, sb = (size_t)bbpipe_refsplit_state_bytes(cfg.nkeys, cfg.nsets);
+    if (v->sets.grow(ns * 8 + 8) != hipSuccess || v->keys.grow(ns * 4 + 4) != hipSuccess || v->state.grow(sb) != hipSuccess ||
+        v->setoff.grow(8 * (2 * (size_t)cfg.nsets + 1)) != hipSuccess)
+        return bbfail(BBMAP_E_NOMEM, "bbmap_split_enable: device allocation failed");
+    if (cfg.flags & (BBMAP_SPLIT_RECORDS | BBMAP_SPLIT_LISTS))
+        if (v->recs.grow((size_t)(c->cfg.max_reads > 0 ? c->cfg.max_reads : 1) * sizeof(bbmap_splitrec)) != hipSuccess)
+            return bbfail(BBMAP_E_NOMEM, "bbmap_split_enable: device allocation failed");
+    BBHIP(hipMemcpy(v->sets.p, scaf_sets, ns * 8, hipMemcpyHostToDevice));
+    BBHIP(hipMemcpy(v->keys.p, scaf_key, ns * 4, hipMemcpyHostToDevice));
+    BBHIP(hipMemset(v->state.p, 0, sb));
+    BBHIP(hipStreamSynchronize(nullptr));                   // a first add on a non-blocking stream finds the state zeroed
+    c->split = v.release();
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_add_split(bbmap_ctx *c, void *stream_) {
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_add_split: null context");
+    SplitState *v = c->split;
+    if (!v) return bbfail(BBMAP_E_ARG, "bbmap_add_split: the stage is not enabled (bbmap_split_enable)");
+    if (!c->ran) return bbfail(BBMAP_E_ARG, "bbmap_add_split: no batch has been mapped yet");
+    if (c->splitCounted) return bbfail(BBMAP_E_ARG, "bbmap_add_split: the last batch has been added already");
+    if (!c->batch.reads || c->batch.n_reads != c->stats.reads) return bbfail(BBMAP_E_ARG, "bbmap_add_split: the context does not hold the last batch's reads");
+    if (v->gen != c->index->scafGen || !c->index->scaf.off)
+        return bbfail(BBMAP_E_ARG, "bbmap_add_split: the scaffold table has been replaced since the stage was enabled");
+    hipStream_t stream = (hipStream_t)stream_;
+    BBHIP(hipSetDevice(c->cfg.device));
+    const long long n = c->stats.reads;
+    bbsplit::Args a = {};
+    a.reads = c->batch.reads; a.fin = c->d_final; a.sites = c->d_ms; a.nsites = c->d_mcount; a.cap = c->cfg.max_sites;
+    BBTRY(tier_index(c, stream, n, &a.tierIdx));
+    if (a.tierIdx) { const bbmap_ctx *t = c->tier; a.tfin = t->d_final; a.tsites = t->d_ms; a.tnsites = t->d_mcount; a.tcap = t->cfg.max_sites; }
+    a.T = c->index->scaf; a.scafSets = v->sets.as<unsigned long long>(); a.scafKey = v->keys.as<int>();
+    a.n = n; a.paired = c->cfg.paired;
+    a.flags = v->cfg.flags; a.mode = v->cfg.ambiguous2; a.clearzone = v->cfg.clearzone; a.maxSites = v->cfg.maxSites;
+    a.nsets = v->cfg.nsets; a.nkeys = v->cfg.nkeys;
+    a.state = v->state.as<unsigned long long>(); a.recs = v->recs.as<bbmap_splitrec>();
+    BBHIP(bbsplit::launch_assign(a, stream));
+    c->splitCounted = true; v->stream = stream; v->added = n; v->total = -1;
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_get_split_records(bbmap_ctx *c, const bbmap_splitrec **out) {
+    if (!c || !out) return bbfail(BBMAP_E_ARG, "bbmap_get_split_records: null argument");
+    SplitState *v = c->split;
+    if (!v) return bbfail(BBMAP_E_ARG, "bbmap_get_split_records: the stage is not enabled (bbmap_split_enable)");
+    if (!v->recs.p) return bbfail(BBMAP_E_ARG, "bbmap_get_split_records: the stage keeps no records (BBMAP_SPLIT_RECORDS)");
+    if (v->added < 0) return bbfail(BBMAP_E_ARG, "bbmap_get_split_records: no batch has been added yet");
+    *out = v->recs.as<bbmap_splitrec>();
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_get_split_lists_device(bbmap_ctx *c, void *stream_, const int64_t **set_off, const int32_t **units, int64_t *total) {
+    if (!c || !set_off || !units) return bbfail(BBMAP_E_ARG, "bbmap_get_split_lists_device: null argument");
+    SplitState *v = c->split;
+    if (!v) return bbfail(BBMAP_E_ARG, "bbmap_get_split_lists_device: the stage is not enabled (bbmap_split_enable)");
+    if (!(v->cfg.flags & BBMAP_SPLIT_LISTS)) return bbfail(BBMAP_E_ARG, "bbmap_get_split_lists_device: the stage builds no lists (BBMAP_SPLIT_LISTS)");
+    if (v->added < 0) return bbfail(BBMAP_E_ARG, "bbmap_get_split_lists_device: no batch has been added yet");
+    hipStream_t stream = (hipStream_t)stream_;
+    BBHIP(hipSetDevice(c->cfg.device));
+    if (stream != v->stream) BBHIP(hipStreamSynchronize(v->stream));          // behind the add that wrote the records
+    const long long n = v->added;
+    const int paired = c->cfg.paired, nsets = v->cfg.nsets;
+    const long long need = bbsplit::lists_workspace_bytes(n, paired, nsets);
+    if (need < 0) return bbfail(BBMAP_E_ARG, "bbmap_get_split_lists_device: the batch is too large for one scan");
+    BBHIP(v->ws.grow((size_t)need, 0, &stream));
+    long long *so = v->setoff.as<long long>();
+    // sizing pass (counts, scan, set_off), the total comes back once, then the placing pass into an array of that size
+    BBHIP(bbsplit::launch_lists(n, paired, nsets, v->recs.as<bbmap_splitrec>(), v->ws.p, need, so, nullptr, 0, stream));
+    long long tot = 0;
+    BBHIP(hipMemcpyAsync(&tot, so + 2 * nsets, 8, hipMemcpyDeviceToHost, stream));
+    BBHIP(hipStreamSynchronize(stream));
+    BBHIP(v->units.grow((size_t)(tot > 0 ? tot : 1) * 4, (size_t)tot));
+    if (tot > 0) BBHIP(bbsplit::launch_lists(n, paired, nsets, v->recs.as<bbmap_splitrec>(), v->ws.p, need, so, v->units.as<int>(), tot, stream));
+    v->total = tot;
+    *set_off = v->setoff.as<int64_t>(); *units = v->units.as<int32_t>();
+    if (total) *total = tot;
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_get_split_lists(bbmap_ctx *c, int64_t *set_off_out, int32_t *units_out, int64_t units_cap, int64_t *total_out) {
+    if (!c || !set_off_out) return bbfail(BBMAP_E_ARG, "bbmap_get_split_lists: null argument");
+    if (units_cap < 0 || (units_cap > 0 && !units_out)) return bbfail(BBMAP_E_ARG, "bbmap_get_split_lists: bad buffer");
+    const int64_t *so = nullptr; const int32_t *un = nullptr; int64_t tot = 0;
+    BBTRY(bbmap_get_split_lists_device(c, nullptr, &so, &un, &tot));
+    BBHIP(hipMemcpy(set_off_out, so, 8 * (2 * (size_t)c->split->cfg.nsets + 1), hipMemcpyDeviceToHost));      // (waits for the null stream)
+    if (tot > 0 && tot <= units_cap) BBHIP(hipMemcpy(units_out, un, (size_t)tot * 4, hipMemcpyDeviceToHost));
+    if (total_out) *total_out = tot;
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_get_split_stats(bbmap_ctx *c, int64_t *out, int64_t cap_words) {
+    if (!c || !out) return bbfail(BBMAP_E_ARG, "bbmap_get_split_stats: null argument");
+    SplitState *v = c->split;
+    if (!v) return bbfail(BBMAP_E_ARG, "bbmap_get_split_stats: the stage is not enabled (bbmap_split_enable)");
+    const int64_t bytes = bbpipe_refsplit_state_bytes(v->cfg.nkeys, v->cfg.nsets);
+    if (cap_words * 8 < bytes) return bbfail(BBMAP_E_ARG, "bbmap_get_split_stats: the buffer is too small (4 + 4 nkeys + 4 nsets words)");
+    BBHIP(hipSetDevice(c->cfg.device));
+    BBHIP(hipStreamSynchronize(v->stream));                 // the state is written on that stream only
+    BBHIP(hipMemcpy(out, v->state.p, (size_t)bytes, hipMemcpyDeviceToHost));
+    return BBMAP_OK;
+}
+
+extern "C" int bbmap_reset_split(bbmap_ctx *c) {
+    if (!c) return bbfail(BBMAP_E_ARG, "bbmap_reset_split: null context");
+    SplitState *v = c->split;
+    if (!v) return BBMAP_OK;
+    BBHIP(hipSetDevice(c->cfg.device));
+    BBHIP(hipMemsetAsync(v->state.p, 0, (size_t)bbpipe_refsplit_state_bytes(v->cfg.nkeys, v->cfg.nsets), v->stream));      // behind the last add
+    BBHIP(hipStreamSynchronize(v->stream));
+    c->splitCounted = false;        // the state no longer holds the batch the context still has
     return BBMAP_OK;
 }
 

@@ -572,3 +572,56 @@ class Mapper:
         self.L.bbmap_reset_read_hist.argtypes = [C.c_void_p]
         self.L.bbmap_reset_read_hist.restype = C.c_int
         _lib.check(self.L.bbmap_reset_read_hist(self.h), "bbmap_reset_read_hist")
+
+    def enable_split(self, tables, flags=None, ambiguous2=0, clearzone=0, max_sites=0):
+        """bbmap_split_enable: reference-set binning over the index's scaffold table.  tables: bbmap_amd.refsplit.tables(...) of the
+        reference's scaffold names; clearzone / max_sites 0 = the context's CLEARZONE1 and the profile's MAX_SITESCORES_TO_PRINT."""
+        from . import refsplit as S
+        S._bind()
+        cfg = S.config(S.SPLIT_ALL if flags is None else flags, ambiguous2, clearzone, max_sites, tables.nsets, tables.nkeys)
+        sets, keys = np.ascontiguousarray(tables.scaf_sets, np.uint64), np.ascontiguousarray(tables.scaf_key, np.int32)
+        _lib.check(self.L.bbmap_split_enable(self.h, C.byref(cfg), sets.ctypes.data, keys.ctypes.data), "bbmap_split_enable")
+        self._split_tables = tables
+
+    def add_split(self):
+        """bbmap_add_split: adds the last step, overflow tier included.  A second call for one step raises."""
+        from . import refsplit as S
+        S._bind()
+        _lib.check(self.L.bbmap_add_split(self.h, C.c_void_p(torch.cuda.current_stream().cuda_stream)), "bbmap_add_split")
+
+    def split_records(self):
+        """Host copy of the last added step's per-read records (refsplit.SPLITREC_DTYPE)."""
+        from . import refsplit as S
+        S._bind()
+        p = C.c_void_p()
+        _lib.check(self.L.bbmap_get_split_records(self.h, C.byref(p)), "bbmap_get_split_records")
+        torch.cuda.current_stream().synchronize()
+        return _copy(p.value, self.n * 32, self.dev).view(S.SPLITREC_DTYPE)
+
+    def split_lists(self):
+        """bbmap_get_split_lists: (set_off int64[2 nsets + 1], units int32[total]) of the last added step, on the host; rows 0 .. nsets - 1
+        are the sets' streams, the rest their ambiguous streams (refsplit.lists_of splits them)."""
+        from . import refsplit as S
+        S._bind()
+        torch.cuda.current_stream().synchronize()
+        set_off = np.zeros(2 * self._split_tables.nsets + 1, np.int64)
+        total = C.c_int64()
+        _lib.check(self.L.bbmap_get_split_lists(self.h, set_off.ctypes.data, None, 0, C.byref(total)), "bbmap_get_split_lists")
+        units = np.zeros(total.value, np.int32)
+        if total.value:
+            _lib.check(self.L.bbmap_get_split_lists(self.h, set_off.ctypes.data, units.ctypes.data, units.size, C.byref(total)), "bbmap_get_split_lists")
+        return set_off, units
+
+    def split_stats(self):
+        """bbmap_get_split_stats: everything added so far as a refsplit.SplitStats."""
+        from . import refsplit as S
+        S._bind()
+        t = self._split_tables
+        words = np.zeros(S.STATE_HEAD + 4 * (t.nkeys + t.nsets), np.int64)
+        _lib.check(self.L.bbmap_get_split_stats(self.h, words.ctypes.data, words.size), "bbmap_get_split_stats")
+        return S.SplitStats.from_words(words, t.nkeys, t.nsets, t.key_names, t.set_names)
+
+    def reset_split(self):
+        from . import refsplit as S
+        S._bind()
+        _lib.check(self.L.bbmap_reset_split(self.h), "bbmap_reset_split")

@@ -1208,6 +1208,106 @@ int bbmap_get_read_hist(bbmap_ctx *ctx, int64_t *out, int64_t cap_words, bbmap_r
  * one stream, or the caller orders them. */
 int bbmap_reset_read_hist(bbmap_ctx *ctx);
 
+/* =====================================================================================
+ * Reference-set binning: scafstats= / refstats= and the stream assignment of bbsplit.sh
+ *   align2.BBSplitter.printReads as AbstractMapThread.writeList calls it (current/align2/AbstractMapThread.java:608-610) on lists
+ *   that capSiteList has cut to MAX_SITESCORES_TO_PRINT sites (:496, :510-511, :1309-1315; 5 in BBMap.java:62, 100 in
+ *   BBMapPacBio.java:65): printReadsAndProcessAmbiguous (current/align2/BBSplitter.java:641-757), addToScafCounts (:782-820),
+ *   getSets (:824-864), getScaffolds (:867-933), toListNames (:1033-1048).  The scaffold of a read or a site is
+ *   Data.scaffoldIndex(chrom, (start + stop) / 2) (current/stream/Read.java:3304-3316, current/stream/SiteScore.java:367-377,
+ *   current/dna/Data.java:1091-1108); no single-scaffold rule applies and a read is mapped when bbmap_final.mapped says so.
+ *   Names stay with the host (bbmap_amd/refsplit.py): it turns the scaffold names `sets$name` into one 64-bit mask of reference sets
+ *   per scaffold (scaf_sets; several bits for a comma-separated prefix) and one key index per scaffold (scaf_key; scaffolds whose
+ *   names share the part behind the first `$` share a key, :882-887).  Sets of names become ORs of masks, containsAll / equals
+ *   become mask arithmetic.  At most 64 reference sets (BBMAP_SPLIT_MAX_SETS): more are refused with BBMAP_E_ARG.
+ *   The device's site lists are not truncated: the stage looks at the first min(nsites, maxSites) entries of a list.
+ *   A mapped, ambiguous read whose list is empty cannot occur in the reference (the cap is at least 1); here it yields no key and
+ *   no set.  A scaffold or chromosome number outside the tables yields none either.
+ *   Out of scope: AMBIGUOUS2_RANDOM (the reference throws, :694-695; refused here), more than 64 sets, BBSplit's reference merging
+ *   and its file streams, bamscript=.  The text of the two files is the host's (scafstats_lines / refstats_lines restate
+ *   printCounts, :1157-1189).
+ * ===================================================================================== */
+enum { BBMAP_SPLIT_SCAF_STATS = 1, /* the per-key counters (scafstats=) */
+       BBMAP_SPLIT_SET_STATS = 2,  /* the per-set counters (refstats=) */
+       BBMAP_SPLIT_RECORDS = 4,    /* one bbmap_splitrec per read */
+       BBMAP_SPLIT_LISTS = 8,      /* the stream lists (they are built from the records) */
+       BBMAP_SPLIT_ALL = 15 };
+enum { BBMAP_AMBIG2_UNSET = 0, BBMAP_AMBIG2_FIRST = 1, BBMAP_AMBIG2_SPLIT = 2, BBMAP_AMBIG2_TOSS = 3, BBMAP_AMBIG2_RANDOM = 4,
+       BBMAP_AMBIG2_ALL = 5 };     /* BBSplitter.java:1203-1208 */
+enum { BBMAP_SPLIT_MAX_SETS = 64 };
+/* the assign kernel's tiles: a workgroup (256 lanes, one read per lane) combines equal keys in an open-addressed LDS table of
+ * BBMAP_SPLIT_LDS_SLOTS slots (key -> four 64-bit partial sums; slot of a key = ((uint32)key * 2654435761u) >> 22, linear probing,
+ * at most BBMAP_SPLIT_MAX_PROBES slots are tried, then the add goes to the state directly) and adds every slot that moved to the state
+ * once per chunk of BBMAP_SPLIT_CHUNK_READS reads */
+enum { BBMAP_SPLIT_LDS_SLOTS = 1024, BBMAP_SPLIT_MAX_PROBES = 8, BBMAP_SPLIT_CHUNK_READS = 4096, BBMAP_SPLIT_MAX_BLOCKS = 1024 };
+enum { BBMAP_SPLIT_LIST_BLOCK = 256 };     /* units per workgroup of the two list passes */
+typedef struct bbmap_split_config {
+    int32_t flags;                 /* BBMAP_SPLIT_* */
+    int32_t ambiguous2;            /* BBMAP_AMBIG2_* */
+    int32_t clearzone;             /* CLEARZONE1() of the mapping thread (BBMapThread.java:78,114,124: 200; BBMapThreadPacBio.java:75,111,121:
+                                    * 220); bbmap_split_enable: 0 = the context's own */
+    int32_t maxSites;              /* MAX_SITESCORES_TO_PRINT, >= 1; bbmap_split_enable: 0 = the profile's (5 / 100) */
+    int32_t nsets;                 /* 0 .. 64 (0: no prefixes, no sets) */
+    int32_t nkeys;                 /* >= 0 */
+    int32_t reserved[2];
+} bbmap_split_config;              /* 32 bytes */
+enum { BBMAP_SPLITREC_AMBIG_SETS = 1,      /* the read (pair) is ambiguous between reference sets (:661-663) */
+       BBMAP_SPLITREC_AMBIG_READ = 2,      /* the read counts in scafstats' ambiguous columns (mapped and Read.ambiguous()) */
+       BBMAP_SPLITREC_MAPPED = 4 };
+typedef struct bbmap_splitrec {    /* the mates of a pair carry the same three masks */
+    uint64_t primary_mask;         /* sets whose stream the read (pair) goes to (splitTable, :701-710) */
+    uint64_t ambig_mask;           /* sets whose AMBIGUOUS stream it goes to (splitTableA, :712-721; only AMBIG2_SPLIT fills it) */
+    int32_t flags;                 /* BBMAP_SPLITREC_* */
+    int32_t key;                   /* key of the scaffold of the read's own record, -1 = not mapped (or outside the tables) */
+    uint64_t stats_mask;           /* sets whose refstats counters the read (pair) moved (:723-754), whether or not they are kept */
+} bbmap_splitrec;                  /* 32 bytes */
+/* The counter state: int64 words -- [0] totalReads (readsUsed1 + readsUsed2, AbstractMapper.java:1858-1862: every add puts its n_reads
+ * there), [1..3] zero, then per key and then per set four words: unambiguous reads, unambiguous bases, ambiguous reads, ambiguous
+ * bases (SetCount.mappedReads / mappedBases / ambiguousReads / ambiguousBases, :1149-1153). */
+enum { BBMAP_SPLIT_STATE_HEAD = 4 };
+/* Bytes of the state (< 0: bad argument). */
+int64_t bbpipe_refsplit_state_bytes(int32_t nkeys, int32_t nsets);
+/* The raw form over device arrays the caller owns: reads (len is used), one final record per read, site lists of cap_stride
+ * records per read with nsites[r] entries in use (a negative count is an empty list; BBMAP_NSITES_OVERFLOW / _MATE_OVERFLOW: the read is
+ * not mapped whatever its record says), the scaffold table as bbidx_set_scaffolds lays it out (see bbpipe_coverage_add_device),
+ * scaf_sets / scaf_key by global scaffold number (key indices outside 0 .. nkeys - 1 and set bits from nsets up are ignored).
+ * paired: reads 2p and 2p + 1 are mates.  ADDS to `state` (zero it first; may be NULL without the two STATS flags); writes
+ * records_out[n_reads] (may be NULL without BBMAP_SPLIT_RECORDS / _LISTS).  BBMAP_E_ARG: unknown flag bits, AMBIG2_RANDOM or an unknown
+ * mode, nsets > 64, maxSites < 1.  Enqueues on `stream`. */
+int bbpipe_refsplit_add_device(void *stream, int64_t n_reads, int32_t paired, const bbmap_split_config *cfg, const bbidx_read *reads,
+                               const bbmap_final *finals, const bbmap_msite *sites, const int32_t *nsites, int32_t cap_stride,
+                               int32_t nchroms, const int32_t *scaf_off, const int32_t *scaf_loc, int32_t pad, const uint64_t *scaf_sets,
+                               const int32_t *scaf_key, void *state, bbmap_splitrec *records_out);
+/* The stream lists of a batch from its records: a CSR table of 2 x nsets rows, rows 0 .. nsets - 1 the sets' streams (primary_mask),
+ * rows nsets .. 2 nsets - 1 their ambiguous streams (ambig_mask).  set_off[2 nsets + 1] (int64), units[set_off[row] .. set_off[row + 1])
+ * = the units of that row in read-list order (strictly ascending); a unit is named by the index of its read, a pair by that of its
+ * first mate (r1, :708 / :719).  A stable partition without atomics: per-workgroup counts, a device-wide scan, a placing pass.
+ * Entries beyond units_cap are not written (compare set_off[2 nsets] with units_cap).  Enqueues on `stream`. */
+int64_t bbpipe_refsplit_lists_workspace_bytes(int64_t n_reads, int32_t paired, int32_t nsets);
+int bbpipe_refsplit_lists_device(void *stream, int64_t n_reads, int32_t paired, int32_t nsets, const bbmap_splitrec *records, void *workspace,
+                                 int64_t workspace_bytes, int64_t *set_off, int32_t *units, int64_t units_cap);
+/* Allocates the zeroed state for the index's scaffold table as it is now.  scaf_sets / scaf_key: HOST arrays, one entry per scaffold
+ * (global number).  cfg->clearzone == 0 / cfg->maxSites == 0 select the context's own.  A second call with the same configuration and
+ * tables' generation changes nothing.  BBMAP_E_ARG: the context runs without the final stage, the index has no scaffold table, a bad
+ * configuration (as above), or the stage is enabled already with another configuration. */
+int bbmap_split_enable(bbmap_ctx *ctx, const bbmap_split_config *cfg, const uint64_t *scaf_sets, const int32_t *scaf_key);
+/* Adds the last batch, overflow tier included (a read the tier mapped takes the tier's record and list), with the batch's current read
+ * lengths; enqueues on `stream`.  BBMAP_E_ARG: not enabled, no batch has been mapped, this batch has been added already, or the
+ * scaffold table has been replaced. */
+int bbmap_add_split(bbmap_ctx *ctx, void *stream);
+/* Device pointer to the records of the last batch added (n_reads of them; valid until the next add).  BBMAP_E_ARG without
+ * BBMAP_SPLIT_RECORDS or before the first add. */
+int bbmap_get_split_records(bbmap_ctx *ctx, const bbmap_splitrec **out);
+/* The stream lists of the last batch added, built on `stream` (the call waits for it once: the total sizes the unit array): device
+ * views, valid until the next add or call.  BBMAP_E_ARG without BBMAP_SPLIT_LISTS or before the first add. */
+int bbmap_get_split_lists_device(bbmap_ctx *ctx, void *stream, const int64_t **set_off, const int32_t **units, int64_t *total);
+/* Host form (null stream): set_off_out[2 nsets + 1] always, the units only into a buffer that holds them; *total_out = units. */
+int bbmap_get_split_lists(bbmap_ctx *ctx, int64_t *set_off_out, int32_t *units_out, int64_t units_cap, int64_t *total_out);
+/* Host copy of the state (cap_words >= 4 + 4 nkeys + 4 nsets, else BBMAP_E_ARG); waits for the stream of the last add. */
+int bbmap_get_split_stats(bbmap_ctx *ctx, int64_t *out, int64_t cap_words);
+/* Zeroes the state behind the last add and waits.  The batch the context still holds counts as not added again. */
+int bbmap_reset_split(bbmap_ctx *ctx);
+
 /* The last batch's site lists without their empty slots, for a host that copies them back: counts (n_reads + 1 ints), offsets
  * (n_reads + 1 int64: exclusive prefix sums, offsets[n_reads] = total) and packed (packed_cap records) are device buffers of the
  * caller's; read r's counts[r] sites are packed[offsets[r] ...] (0 for a read without a list, a flagged one, or one the overflow
