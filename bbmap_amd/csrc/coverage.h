@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "batch_view.h"
 #include "bbmap_amd.h"
 #include "scaffold.h"
 
@@ -20,11 +21,8 @@ static_assert(sizeof(bbmap_covrec) == 8 * REC_WORDS && sizeof(bbmap_covstrand) =
 static_assert(sizeof(bbmap_covtotals) == 32, "bbmap_covtotals is 4 words");
 
 struct AddArgs {
-    const bbidx_read *reads; const uint8_t *bases;
-    const bbmap_final *fin; const uint8_t *pool;
-    // the overflow tier's records and pool, read -> tier record (nullptr = no tier reads) and the main lists' counts that flag a tier read
-    const bbmap_final *tfin; const uint8_t *tpool; const int *tierIdx; const int *nsites;
-    long long n; int paired, flags;
+    BatchView V;
+    int flags;
     bbscaf::Table T; int nscaf;
     const long long *covoff;
     int *diff[2];

@@ -34,18 +34,6 @@ using wavep::uni;
 
 // ------------------------------------------------------------------------------------------------------------------ accumulate
 
-struct Rec { const bbmap_final *f; const uint8_t *m; int ml; };
-// a read the overflow tier mapped takes the tier's record and pool (run_stats.hip::record_of)
-__device__ inline Rec record_of(const AddArgs &A, long long r) {
-    Rec R;
-    R.f = A.fin + r;
-    const uint8_t *pl = A.pool;
-    if (A.tierIdx && A.nsites[r] == BBMAP_NSITES_IN_TIER && A.tierIdx[r] >= 0) { R.f = A.tfin + A.tierIdx[r]; pl = A.tpool; }
-    R.ml = R.f->match_len > 0 ? R.f->match_len : 0;
-    R.m = R.ml ? pl + R.f->match_off : nullptr;
-    return R;
-}
-
 // addCoverageIgnoringDeletions' loop (:682-695) over the long-format string, 64 symbols per step: `for(rpos=start, mpos=0;
 // mpos<match.length && rpos<=stop; mpos++)`, m / S / N cover rpos and advance it, D advances it, I / X / Y / C do nothing.
 // Symbols that cover consecutive positions form a run; a run is broken by a D, by rpos > stop or by the string's end.  A run adds +1
@@ -88,9 +76,9 @@ __global__ __launch_bounds__(TB) void coverage_add_kernel(const AddArgs A) {
     __syncthreads();
     long long nProcessed = 0, nMapped = 0, nBases = 0;         // wave-uniform; added to the totals once per wavefront
     const long long nwaves = (long long)gridDim.x * WAVES_PER_BLOCK;
-    for (long long r = (long long)blockIdx.x * WAVES_PER_BLOCK + wid; r < A.n; r += nwaves) {
+    for (long long r = (long long)blockIdx.x * WAVES_PER_BLOCK + wid; r < A.V.n; r += nwaves) {
         nProcessed++;                                           // processRead :785
-        const Rec R = record_of(A, r);
+        const ReadRec R = record_of<TierRule::ByList>(A.V, r);
         const bbmap_final &f = *R.f;
         if (!f.mapped) continue;
         const int chrom = uni(f.chrom), start = uni(f.start), stop = uni(f.stop), strand = uni(f.strand);
@@ -103,12 +91,12 @@ __global__ __launch_bounds__(TB) void coverage_add_kernel(const AddArgs A) {
         const int L = A.T.len[gs];
         const int start0 = start - A.T.loc[gs], stop0 = start0 - start + stop;          // scaffoldRelativeLoc, :48-49
         const int a = max(start0, 0), b = min(stop0, L - 1);                            // addCoverage :605-606
-        const bbidx_read rd = A.reads[r];
+        const bbidx_read rd = A.V.reads[r];
         const int len = rd.len;
         nMapped++; nBases += len;                                                       // :612-613
         // basecount (:619-624): charToNum's slots 0-3 are A/a, C/c, G/g, T/t/U/u
         int cA = 0, cC = 0, cG = 0, cT = 0;
-        const uint8_t *bases = A.bases + rd.bases_off;
+        const uint8_t *bases = A.V.bases + rd.bases_off;
         for (int base = 0; base < len; base += 64) {
             const int ch = (base + lane < len ? bases[base + lane] : 0) & ~0x20;
             cA += popc(__ballot(ch == 'A')); cC += popc(__ballot(ch == 'C'));
@@ -128,7 +116,7 @@ __global__ __launch_bounds__(TB) void coverage_add_kernel(const AddArgs A) {
         mine = lane == A_basehits ? basehits : mine;
         mine = lane == A_readhits ? 1 : mine;
         mine = lane == A_readhitsMinus ? (strand == 1) : mine;
-        mine = lane == A_fraghits ? (A.paired ? 1 : 2) : mine;
+        mine = lane == A_fraghits ? (A.V.paired ? 1 : 2) : mine;
         mine = lane == A_readBases ? cA : lane == A_readBases + 1 ? cC : lane == A_readBases + 2 ? cG : lane == A_readBases + 3 ? cT : mine;
         if (lane < N_ACC && mine) {
             if (useLds) atomicAdd(&acc[gs * N_ACC + lane], (u64)mine);
@@ -147,8 +135,8 @@ __global__ __launch_bounds__(TB) void coverage_add_kernel(const AddArgs A) {
 }
 
 hipError_t launch_add(const AddArgs &a, hipStream_t stream) {
-    if (a.n <= 0) return hipSuccess;
-    const long long want = (a.n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    if (a.V.n <= 0) return hipSuccess;
+    const long long want = (a.V.n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     const unsigned blocks = (unsigned)(want < MAX_BLOCKS ? want : MAX_BLOCKS);
     hipLaunchKernelGGL(coverage_add_kernel, dim3(blocks), dim3(TB), 0, stream, a);
     return hipGetLastError();
@@ -558,8 +546,8 @@ extern "C" int bbpipe_coverage_add_device(void *stream, int64_t n_reads, int32_t
         ((flags & BBMAP_COV_STRANDED) && !diff1))
         return bbfail(BBMAP_E_ARG, "bbpipe_coverage_add_device: null buffer");
     bbcov::AddArgs a = {};
-    a.reads = reads; a.bases = bases; a.fin = finals; a.pool = pool;
-    a.n = n_reads; a.paired = paired ? 1 : 0; a.flags = flags;
+    a.V.reads = reads; a.V.bases = bases; a.V.fin = finals; a.V.pool = pool;      // (no tier)
+    a.V.n = n_reads; a.V.paired = paired ? 1 : 0; a.flags = flags;
     a.T.off = scaf_off; a.T.loc = scaf_loc; a.T.len = scaf_len; a.T.pad = pad; a.T.nchroms = nchroms;
     a.nscaf = nscaf; a.covoff = (const long long *)covoff;
     a.diff[0] = diff0; a.diff[1] = diff1;

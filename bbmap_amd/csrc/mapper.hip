@@ -1048,38 +1048,23 @@ __device__ inline void put_scafrec(bbmap_scafrec *out, const ScafMate &q, int pa
     *out = w;
 }
 
-// a read the overflow tier mapped takes the tier's record (as bbmap_get_final does)
-__device__ inline const bbmap_final *scaf_source(const bbmap_final *fin, const uint8_t *pool, const bbmap_final *tfin, const uint8_t *tpool,
-                                                 const int *tierIdx, long long r, const uint8_t *&m) {
-    const bbmap_final *f = fin + r;
-    const uint8_t *pl = pool;
-    if (tierIdx && f->nsites == BBMAP_NSITES_IN_TIER && tierIdx[r] >= 0) { f = tfin + tierIdx[r]; pl = tpool; }
-    m = f->match_len > 0 ? pl + f->match_off : nullptr;
-    return f;
-}
-
-__global__ __launch_bounds__(256) void scaffold_coords_kernel(const bbscaf::Table T, const bbmap_final *fin, const uint8_t *pool,
-                                                              const bbmap_final *tfin, const uint8_t *tpool, const int *tierIdx,
-                                                              long long units, int paired, bbmap_scafrec *out) {
+__global__ __launch_bounds__(256) void scaffold_coords_kernel(const bbscaf::Table T, const BatchView V, bbmap_scafrec *out) {
     const long long u = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (u >= units) return;
+    if (u >= (V.paired ? V.n / 2 : V.n)) return;
     const bool lead = (threadIdx.x & 63) == 0;
-    if (!paired) {
-        const uint8_t *m;
-        const bbmap_final *f = scaf_source(fin, pool, tfin, tpool, tierIdx, u, m);
-        const ScafMate q = scaf_mate(T, *f, m);
-        if (lead) put_scafrec(out + u, q, f->paired != 0, 0);
+    if (!V.paired) {
+        const ReadRec R = record_of<TierRule::ByRecord>(V, u);
+        const ScafMate q = scaf_mate(T, *R.f, R.m);
+        if (lead) put_scafrec(out + u, q, R.f->paired != 0, 0);
         return;
     }
-    const uint8_t *m1, *m2;
-    const bbmap_final *f1 = scaf_source(fin, pool, tfin, tpool, tierIdx, 2 * u, m1);
-    const bbmap_final *f2 = scaf_source(fin, pool, tfin, tpool, tierIdx, 2 * u + 1, m2);
-    const ScafMate q1 = scaf_mate(T, *f1, m1), q2 = scaf_mate(T, *f2, m2);
+    const ReadRec R1 = record_of<TierRule::ByRecord>(V, 2 * u), R2 = record_of<TierRule::ByRecord>(V, 2 * u + 1);
+    const ScafMate q1 = scaf_mate(T, *R1.f, R1.m), q2 = scaf_mate(T, *R2.f, R2.m);
     const bool both = q1.single && q2.single;               // a mate that spans two scaffolds unpairs the other (:137-138, :157-158)
     const int same = q1.mapped && q2.mapped && q1.gscaf == q2.gscaf;       // sameScaf (:160): idx1 == idx2 on the same chromosome
     if (lead) {
-        put_scafrec(out + 2 * u, q1, both && f1->paired != 0, same);
-        put_scafrec(out + 2 * u + 1, q2, both && f2->paired != 0, same);
+        put_scafrec(out + 2 * u, q1, both && R1.f->paired != 0, same);
+        put_scafrec(out + 2 * u + 1, q2, both && R2.f->paired != 0, same);
     }
 }
 __global__ __launch_bounds__(256) void tier_index_kernel(const int *ids, long long n, long long nreads, int *tierIdx) {

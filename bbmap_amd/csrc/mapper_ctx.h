@@ -17,6 +17,12 @@
 // scratch of bbmap_pack_sites_device, and bbmap_get_sam_records' scan scratch and text blob
 enum { HIO_READS, HIO_BASES, HIO_SCORES, HIO_KEYINFO, HIO_COUNTS, HIO_OFFSETS, HIO_PACKED, BUF_PACK_TMP, BUF_SAM_TMP, BUF_SAM_TEXT, BUF_COUNT };
 
+// The stages that accumulate finished batches into a state of their own.  Each takes a batch once (`counted`, cleared when the next
+// batch is mapped or the state is reset), and only the work on `stream` -- that of the stage's last add, or of coverage's last
+// finalize -- writes its state: getters wait for that stream, resets queue behind it.
+enum { ACC_STATS, ACC_COV, ACC_HIST, ACC_SPLIT, ACC_COUNT };
+struct Accum { bool counted = false; hipStream_t stream = nullptr; };
+
 struct bbmap_ctx {
     bbmap_config cfg;
     bbidx_ctx *index;
@@ -75,19 +81,14 @@ struct bbmap_ctx {
     long long samTextBytes = 0;
     // run statistics (bbmap_add_run_stats): the running counters and the insert-size histogram, allocated on first use
     unsigned long long *d_runStats = nullptr, *d_insertHist = nullptr;
-    bool statsCounted = false;      // the last batch is in the counters already
     int adaptive = 0;               // BBMAP_ADAPT_*
     long long numMatedSeen = 0;     // numMated after the last accumulation the insert-length rule looked at
     const bbmap_truth *truthNext = nullptr;     // bbmap_set_truth: for the next batch's own accumulation
-    hipStream_t statsStream = nullptr;          // the stream of the last accumulation: the only work that writes the counters
     // coverage (bbmap_cov_enable): null until enabled
     struct CovState *cov = nullptr;
-    bool covCounted = false;        // the last batch is in the coverage state already
     // read histograms (bbmap_hist_enable): null until enabled
     unsigned long long *d_readHist = nullptr;
     int rhFlags = 0;
-    bool rhCounted = false;         // the last batch is in the histograms already
-    hipStream_t rhStream = nullptr; // the stream of the last accumulation: the only work that writes the state
     // bbmap_untrim_batch_device (untrim.hip): the second match-string pool (swapped with d_pool by the call), per-read byte counts and
     // their prefix sums, allocated on first use
     uint8_t *d_pool2 = nullptr; long long pool2Units = 0;
@@ -97,7 +98,9 @@ struct bbmap_ctx {
     bool untrimmed = false;         // the last batch has been untrimmed already
     // reference-set binning (bbmap_split_enable): null until enabled
     struct SplitState *split = nullptr;
-    bool splitCounted = false;      // the last batch is in the split state already
+    Accum accum[ACC_COUNT];         // run statistics, coverage, read histograms, reference-set binning
+    // a new batch: no stage has taken it yet
+    void new_batch() { for (Accum &a : accum) a.counted = false; untrimmed = false; }
 };
 
 // Reference-set binning state of a context (ref_split.hip): the tables are the host's, one entry per scaffold of the index's table as
@@ -106,7 +109,6 @@ struct SplitState {
     bbmap_split_config cfg = {};
     int nscaf = 0;
     long long gen = 0, added = -1, total = 0;       // added: reads of the batch the records belong to (-1 = none yet)
-    hipStream_t stream = nullptr;   // of the last add
     DevBuf sets, keys, state, recs, ws, setoff, units;
     SplitState() = default;
     SplitState(const SplitState &) = delete;
@@ -117,7 +119,6 @@ struct SplitState {
 struct CovState {
     int flags = 0, nscaf = 0, binsize = -1;
     long long slots = 0, nbins = 0, gen = 0;
-    hipStream_t stream = nullptr;   // of the last accumulation or finalize
     DevBuf covoff, len, diff[2], depth[2], recs, hist[2], totals, ws, refgc, binoff, bins[2];
     std::vector<int> hostLen;
     CovState() = default;

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "batch_view.h"
 #include "bbmap_amd.h"
 #include "scaffold.h"
 
@@ -135,9 +136,6 @@ struct FinalRead {
     int reservedI;
 };
 
-// (a scan's accumulator type follows its INPUT type: int counts go in as long long so that offsets beyond 2^31 stay exact)
-struct ToLL { __host__ __device__ long long operator()(int x) const { return (long long)x; } };
-
 // ---- the kernels the host launches (defined in mapper.hip and mapper_final.h)
 __global__ void begin_kernel(const Dev D);
 __global__ void score_kernel(const Dev D);
@@ -156,8 +154,7 @@ __global__ void gather_reads_kernel(const bbidx_read *reads, const int *ids, int
 __global__ void mark_tier_kernel(int *mcount, const int *tierCount, const int *readIds, int n, unsigned *resolved);
 __global__ void pack_counts_kernel(const int *mcount, long long n, int *counts);
 __global__ void pack_sites_kernel(const Site *ms, const int *mcount, const long long *offsets, long long n, int cap, long long packedCap, Site *packed);
-__global__ void scaffold_coords_kernel(const bbscaf::Table T, const bbmap_final *fin, const uint8_t *pool, const bbmap_final *tfin,
-                                       const uint8_t *tpool, const int *tierIdx, long long units, int paired, bbmap_scafrec *out);
+__global__ void scaffold_coords_kernel(const bbscaf::Table T, const BatchView V, bbmap_scafrec *out);
 __global__ void tier_index_kernel(const int *ids, long long n, long long nreads, int *tierIdx);
 
 }  // namespace bbmapper

@@ -634,7 +634,7 @@ static int rescue_skip_rule(bbmap_ctx *c, bool *skip) {
     *skip = false;
     if (!c->d_runStats) return BBMAP_OK;
     bbmap_runstats rs;
-    BBHIP(hipStreamSynchronize(c->statsStream));            // not the device: only that stream's work writes the counters
+    BBHIP(hipStreamSynchronize(c->accum[ACC_STATS].stream));        // not the device: only that stream's work writes the counters
     BBHIP(hipMemcpy(&rs, c->d_runStats, sizeof rs, hipMemcpyDeviceToHost));
     *skip = rs.mappedRetained2 > 1000 && rs.numMated * 20LL < rs.mappedRetained2;
     return BBMAP_OK;
@@ -715,7 +715,7 @@ extern "C" int bbmap_map_batch_device(bbmap_ctx *c, void *stream_, int64_t n_rea
     if (!reads || !bases || !baseScores || !keyinfo) return bbfail(BBMAP_E_ARG, "bbmap_map_batch_device: null buffer");
     hipStream_t stream = (hipStream_t)stream_;
     BBHIP(hipSetDevice(c->cfg.device));
-    c->statsCounted = false; c->covCounted = false; c->rhCounted = false; c->splitCounted = false; c->untrimmed = false;
+    c->new_batch();
     const bbmap_truth *truth = c->truthNext;
     c->truthNext = nullptr;
     bool skip = false;
@@ -741,7 +741,7 @@ extern "C" int bbmap_final_batch_device(bbmap_ctx *c, void *stream_, int64_t n_r
     BBHIP(hipSetDevice(c->cfg.device));
     c->tierStarted = false; c->tierReads = 0;
     if (c->tier) c->tier->ran = false;
-    c->statsCounted = false; c->covCounted = false; c->rhCounted = false; c->splitCounted = false; c->untrimmed = false;
+    c->new_batch();
     memset(&c->stats, 0, sizeof c->stats);
     c->stats.reads = n_reads;
     c->batch = {n_reads, reads, bases, minus_delta, nullptr, nullptr};

@@ -3,11 +3,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <vector>
-
-#include <hipcub/hipcub.hpp>
-
+#include <initializer_list>
 #include <memory>
+#include <vector>
 
 #include "coverage.h"
 #include "mapper_ctx.h"
@@ -15,6 +13,7 @@
 #include "ref_split.h"
 #include "run_stats.h"
 #include "sam_records.h"
+#include "scan_offsets.h"
 
 using namespace bbmapper;
 
@@ -27,15 +26,8 @@ extern "C" int bbmap_pack_sites_device(bbmap_ctx *c, void *stream_, int64_t n_re
     hipStream_t stream = (hipStream_t)stream_;
     BBHIP(hipSetDevice(c->cfg.device));
     const long long n = n_reads;
-    size_t need = 0;
-    // (the scan's accumulator type follows its INPUT type: the counts go in as long long so that offsets beyond 2^31 records stay exact)
-    auto wide = hipcub::TransformInputIterator<long long, ToLL, const int *>((const int *)counts, ToLL());
-    BBHIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, wide, (long long *)offsets, (int)(n + 1), stream));
-    BBHIP(c->buf[BUF_PACK_TMP].grow(need, 0, &stream));          // (exact size; the stream may still be scanning in the old one)
-    // counts has n + 1 entries for the scan (the last one a zero), so that offsets[n] is the total
     BBTRY(launch<256>(pack_counts_kernel, n, stream, c->d_mcount, n, counts));
-    BBHIP(hipMemsetAsync(counts + n, 0, 4, stream));
-    BBHIP(hipcub::DeviceScan::ExclusiveSum(c->buf[BUF_PACK_TMP].p, need, wide, (long long *)offsets, (int)(n + 1), stream));
+    BBTRY(scan_offsets(counts, n, (long long *)offsets, c->buf[BUF_PACK_TMP], stream, nullptr));
     const long long threads = n * c->cfg.max_sites * 8;
     BBTRY(launch<256>(pack_sites_kernel, threads, stream, c->d_ms, c->d_mcount, (const long long *)offsets, n, c->cfg.max_sites, (long long)packed_cap, packed));
     return BBMAP_OK;
@@ -194,37 +186,44 @@ extern "C" int bbmap_get_final(bbmap_ctx *c, int64_t n_reads, bbmap_final *out, 
     return BBMAP_OK;
 }
 
-// read -> overflow-tier record of the last batch (-1 = not a tier read); *out = nullptr when the tier mapped no read
-static int tier_index(bbmap_ctx *c, hipStream_t stream, long long n, const int **out) {
-    *out = nullptr;
-    if (!(c->tier && c->tierReads > 0 && c->tier->ran && n > 0)) return BBMAP_OK;
+// The last batch as the stages' kernels see it (batch_view.h), on `stream`: the main context's arrays, and where the tier mapped reads
+// its arrays and the map read -> tier record (-1 = not a tier read), which is filled here.
+static int batch_view(bbmap_ctx *c, hipStream_t stream, BatchView *V) {
+    *V = BatchView{};
+    V->reads = c->batch.reads; V->bases = c->batch.bases; V->n = c->stats.reads; V->paired = c->cfg.paired;
+    V->fin = c->d_final; V->pool = c->d_pool; V->sites = c->d_ms; V->nsites = c->d_mcount; V->cap = c->cfg.max_sites;
+    const bbmap_ctx *t = c->tier;
+    if (!(t && c->tierReads > 0 && t->ran && V->n > 0)) return BBMAP_OK;
     if (!c->d_scafTier) BBTRY(dalloc(c, &c->d_scafTier, (size_t)c->cfg.max_reads));
-    BBHIP(hipMemsetAsync(c->d_scafTier, 0xff, (size_t)n * 4, stream));
-    BBTRY(launch<256>(tier_index_kernel, c->tierReads, stream, c->d_tierReadIds, c->tierReads, n, c->d_scafTier));
-    *out = c->d_scafTier;
+    BBHIP(hipMemsetAsync(c->d_scafTier, 0xff, (size_t)V->n * 4, stream));
+    BBTRY(launch<256>(tier_index_kernel, c->tierReads, stream, c->d_tierReadIds, c->tierReads, V->n, c->d_scafTier));
+    V->tfin = t->d_final; V->tpool = t->d_pool; V->tsites = t->d_ms; V->tnsites = t->d_mcount; V->tcap = t->cfg.max_sites;
+    V->tierIdx = c->d_scafTier;
     return BBMAP_OK;
 }
 
-extern "C" int bbmap_get_scaffold_records(bbmap_ctx *c, void *stream_, const bbmap_scafrec **out) {
-    if (!c || !out) return bbfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: null argument");
+// bbmap_get_scaffold_records; *V is the view it made, for a caller that goes on with the same batch on the same stream
+static int scaffold_records(bbmap_ctx *c, hipStream_t stream, BatchView *V, const bbmap_scafrec **out) {
     if (!c->S.finalStage) return bbfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: the context runs without the final stage (bbmap_config.finalStage)");
     if (!c->ran) return bbfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: no batch has been mapped yet");
     const bbscaf::Table T = c->index->scaf;
     if (!T.off) return bbfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: the index has no scaffold table (bbidx_set_scaffolds)");
     BBHIP(hipSetDevice(c->cfg.device));
-    hipStream_t stream = (hipStream_t)stream_;
-    const long long n = c->stats.reads;
     if (!c->d_scafRec) {
         BBTRY(dalloc(c, &c->d_scafRec, (size_t)c->cfg.max_reads));
     }
-    const int *tierIdx = nullptr; const bbmap_final *tfin = nullptr; const uint8_t *tpool = nullptr;
-    BBTRY(tier_index(c, stream, n, &tierIdx));
-    if (tierIdx) { tfin = c->tier->d_final; tpool = c->tier->d_pool; }
-    const long long units = c->cfg.paired ? n / 2 : n;
+    BBTRY(batch_view(c, stream, V));
+    const long long units = V->paired ? V->n / 2 : V->n;
     if (units > 0)          // one wavefront per unit
-        BBTRY(launch<256>(scaffold_coords_kernel, 64 * units, stream, T, c->d_final, c->d_pool, tfin, tpool, tierIdx, units, c->cfg.paired, c->d_scafRec));
+        BBTRY(launch<256>(scaffold_coords_kernel, 64 * units, stream, T, *V, c->d_scafRec));
     *out = c->d_scafRec;
     return BBMAP_OK;
+}
+
+extern "C" int bbmap_get_scaffold_records(bbmap_ctx *c, void *stream_, const bbmap_scafrec **out) {
+    if (!c || !out) return bbfail(BBMAP_E_ARG, "bbmap_get_scaffold_records: null argument");
+    BatchView V;
+    return scaffold_records(c, (hipStream_t)stream_, &V, out);
 }
 
 // SamLine's remaining fields for the last batch (sam_records.hip): the coordinate kernel, the sizing pass, a device-wide exclusive scan
@@ -233,12 +232,12 @@ extern "C" int bbmap_get_sam_records(bbmap_ctx *c, void *stream_, int32_t flags,
                                      int64_t *text_bytes) {
     if (!c || !recs || !text) return bbfail(BBMAP_E_ARG, "bbmap_get_sam_records: null argument");
     if (flags & ~(BBMAP_SAM_CIGAR13 | BBMAP_SAM_MD)) return bbfail(BBMAP_E_ARG, "bbmap_get_sam_records: unknown flag bits");
-    const bbmap_scafrec *scaf = nullptr;
-    BBTRY(bbmap_get_scaffold_records(c, stream_, &scaf));    // its error cases are this call's: no final stage, no batch, no scaffold table
+    hipStream_t stream = (hipStream_t)stream_;
+    bbsam::Args a;
+    BBTRY(scaffold_records(c, stream, &a.V, &a.scaf));      // its error cases are this call's: no final stage, no batch, no scaffold table
     if (!c->batch.reads || !c->batch.bases || c->batch.n_reads != c->stats.reads)
         return bbfail(BBMAP_E_ARG, "bbmap_get_sam_records: the context does not hold the last batch's reads");
-    hipStream_t stream = (hipStream_t)stream_;
-    const long long n = c->stats.reads;
+    const long long n = a.V.n;
     const int maxLen = c->cfg.max_read_len;
     if (!c->d_samRec) {
         BBTRY(dalloc(c, &c->d_samRec, (size_t)c->cfg.max_reads));
@@ -249,24 +248,12 @@ extern "C" int bbmap_get_sam_records(bbmap_ctx *c, void *stream_, int32_t flags,
         bbsam::fill_mapq_max(table.data(), maxLen);
         BBHIP(hipMemcpy(c->d_mapqMax, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
     }
-    bbsam::Args a;
-    a.fin = c->d_final; a.pool = c->d_pool; a.tfin = nullptr; a.tpool = nullptr; a.tierIdx = nullptr;
-    // (bbmap_get_scaffold_records above went through tier_index under this same condition: d_scafTier is allocated and filled on `stream`)
-    if (c->tier && c->tierReads > 0 && c->tier->ran && n > 0) { a.tierIdx = c->d_scafTier; a.tfin = c->tier->d_final; a.tpool = c->tier->d_pool; }
-    a.scaf = scaf; a.reads = c->batch.reads; a.bases = c->batch.bases;
     a.chromArr = c->d_chromArr; a.chromArrLen = c->d_chromArrLen;
     a.mapqMax = c->d_mapqMax; a.mapqMaxLen = maxLen;
-    a.n = n; a.paired = c->cfg.paired; a.flags = flags;
-    size_t need = 0;
-    auto wide = hipcub::TransformInputIterator<long long, ToLL, const int *>((const int *)c->d_samCounts, ToLL());
-    BBHIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, wide, c->d_samOffsets, (int)(n + 1), stream));
-    BBHIP(c->buf[BUF_SAM_TMP].grow(need, 0, &stream));
+    a.flags = flags;
     BBHIP(bbsam::launch_size(a, c->d_samRec, c->d_samCounts, stream));
-    BBHIP(hipMemsetAsync(c->d_samCounts + n, 0, 4, stream));                 // n + 1 entries, so that offsets[n] is the total
-    BBHIP(hipcub::DeviceScan::ExclusiveSum(c->buf[BUF_SAM_TMP].p, need, wide, c->d_samOffsets, (int)(n + 1), stream));
     long long total = 0;
-    BBHIP(hipMemcpyAsync(&total, c->d_samOffsets + n, 8, hipMemcpyDeviceToHost, stream));
-    BBHIP(hipStreamSynchronize(stream));
+    BBTRY(scan_offsets(c->d_samCounts, n, c->d_samOffsets, c->buf[BUF_SAM_TMP], stream, &total));
     BBHIP(c->buf[BUF_SAM_TEXT].grow((size_t)total, (size_t)total / 4 + 256));       // (the stream has just been waited for)
     uint8_t *blob = (uint8_t *)c->buf[BUF_SAM_TEXT].p;
     BBHIP(bbsam::launch_emit(a, c->d_samRec, c->d_samOffsets, blob, stream));
@@ -290,6 +277,60 @@ extern "C" int bbmap_get_sam(bbmap_ctx *c, int64_t n_reads, int32_t flags, bbmap
     return BBMAP_OK;
 }
 
+// ---- the accumulating stages (Accum, mapper_ctx.h): what their add, get, reset and enable calls share
+enum { NEEDS_FINAL = 1, NEEDS_TRIMMED = 2, NEEDS_BASES = 4, SAYS_ADDED = 8 };
+
+static bool table_replaced(const bbmap_ctx *c, long long gen) { return gen != c->index->scafGen || !c->index->scaf.off; }
+
+// Whether `fn` may add the last batch to stage `st`: the refusals of every add call, in the order they have always been tested.
+// off: what to say when the stage is not enabled (null: it is).  needs: what the stage reads (NEEDS_*).  gen: the scaffold table's
+// generation when the stage was enabled (null: the stage reads no table); `since` names the stage in that refusal.
+static int may_add(bbmap_ctx *c, int st, const char *fn, const char *off, int needs, const long long *gen = nullptr, const char *since = nullptr) {
+    if (off) return bbfail(BBMAP_E_ARG, "%s: %s", fn, off);
+    if ((needs & NEEDS_FINAL) && !c->S.finalStage) return bbfail(BBMAP_E_ARG, "%s: the context runs without the final stage (bbmap_config.finalStage)", fn);
+    if (!c->ran) return bbfail(BBMAP_E_ARG, "%s: no batch has been mapped yet", fn);
+    if (c->accum[st].counted) return bbfail(BBMAP_E_ARG, "%s: the last batch has been %s already", fn, needs & SAYS_ADDED ? "added" : "counted");
+    if ((needs & NEEDS_TRIMMED) && c->untrimmed)
+        return bbfail(BBMAP_E_ARG, "%s: the last batch has been untrimmed already (call it before bbmap_untrim_batch_device)", fn);
+    if (!c->batch.reads || ((needs & NEEDS_BASES) && !c->batch.bases) || c->batch.n_reads != c->stats.reads)
+        return bbfail(BBMAP_E_ARG, "%s: the context does not hold the last batch's reads", fn);
+    if (gen && table_replaced(c, *gen)) return bbfail(BBMAP_E_ARG, "%s: the scaffold table has been replaced since %s enabled", fn, since);
+    return BBMAP_OK;
+}
+
+// `bytes` of a stage's state to the host, behind the work that last wrote it
+static int copy_out(bbmap_ctx *c, int st, void *dst, const void *src, size_t bytes) {
+    BBHIP(hipStreamSynchronize(c->accum[st].stream));       // the state is written on that stream only
+    BBHIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return BBMAP_OK;
+}
+
+// Zeroes a stage's state behind its last add and waits.  forget: the state no longer holds the batch the context still has, so that
+// batch may be added again.
+struct Span { void *p; size_t bytes; };
+static int reset_state(bbmap_ctx *c, int st, std::initializer_list<Span> spans, bool forget = true) {
+    Accum &a = c->accum[st];
+    BBHIP(hipSetDevice(c->cfg.device));
+    for (const Span &s : spans)
+        if (s.bytes) BBHIP(hipMemsetAsync(s.p, 0, s.bytes, a.stream));
+    BBHIP(hipStreamSynchronize(a.stream));
+    if (forget) a.counted = false;
+    return BBMAP_OK;
+}
+
+// The index's scaffold table as a stage that is sized by it keeps it: the number of scaffolds, the table's generation, and (hostLen
+// not null) the scaffolds' lengths on the host.
+static int scaf_snapshot(bbmap_ctx *c, int *nscaf, long long *gen, std::vector<int> *hostLen) {
+    const bbscaf::Table T = c->index->scaf;
+    std::vector<int> off((size_t)T.nchroms + 2);
+    BBHIP(hipMemcpy(off.data(), T.off, off.size() * 4, hipMemcpyDeviceToHost));
+    *nscaf = off[(size_t)T.nchroms + 1]; *gen = c->index->scafGen;
+    if (!hostLen) return BBMAP_OK;
+    hostLen->resize((size_t)*nscaf);
+    BBHIP(hipMemcpy(hostLen->data(), T.len, (size_t)*nscaf * 4, hipMemcpyDeviceToHost));
+    return BBMAP_OK;
+}
+
 // ---- run statistics (run_stats.hip) and the adaptive state they drive
 static int run_stats_buffers(bbmap_ctx *c) {
     if (c->d_runStats) return BBMAP_OK;
@@ -304,26 +345,18 @@ static int run_stats_buffers(bbmap_ctx *c) {
 
 extern "C" int bbmap_add_run_stats(bbmap_ctx *c, void *stream_, const bbmap_truth *truth) {
     if (!c) return bbfail(BBMAP_E_ARG, "bbmap_add_run_stats: null context");
-    if (!c->S.finalStage) return bbfail(BBMAP_E_ARG, "bbmap_add_run_stats: the context runs without the final stage (bbmap_config.finalStage)");
-    if (!c->ran) return bbfail(BBMAP_E_ARG, "bbmap_add_run_stats: no batch has been mapped yet");
-    if (c->statsCounted) return bbfail(BBMAP_E_ARG, "bbmap_add_run_stats: the last batch has been counted already");
-    // calcStatistics runs inside processRead, on the trimmed read (AbstractMapThread.java:518-521 come after it)
-    if (c->untrimmed) return bbfail(BBMAP_E_ARG, "bbmap_add_run_stats: the last batch has been untrimmed already (call it before bbmap_untrim_batch_device)");
-    if (!c->batch.reads || c->batch.n_reads != c->stats.reads) return bbfail(BBMAP_E_ARG, "bbmap_add_run_stats: the context does not hold the last batch's reads");
+    // (NEEDS_TRIMMED: calcStatistics runs inside processRead, on the trimmed read; AbstractMapThread.java:518-521 come after it)
+    BBTRY(may_add(c, ACC_STATS, "bbmap_add_run_stats", nullptr, NEEDS_FINAL | NEEDS_TRIMMED));
     hipStream_t stream = (hipStream_t)stream_;
     BBHIP(hipSetDevice(c->cfg.device));
     BBTRY(run_stats_buffers(c));
-    const long long n = c->stats.reads;
     bbrunstats::Args a = {};
-    a.reads = c->batch.reads;
-    a.fin = c->d_final; a.pool = c->d_pool; a.sites = c->d_ms; a.nsites = c->d_mcount; a.cap = c->cfg.max_sites;
-    BBTRY(tier_index(c, stream, n, &a.tierIdx));
-    if (a.tierIdx) { const bbmap_ctx *t = c->tier; a.tfin = t->d_final; a.tpool = t->d_pool; a.tsites = t->d_ms; a.tnsites = t->d_mcount; a.tcap = t->cfg.max_sites; }
-    a.truth = truth; a.n = n; a.paired = c->cfg.paired;
+    BBTRY(batch_view(c, stream, &a.V));
+    a.truth = truth;
     a.ptsMatch = c->S.ptsMatch; a.ptsMatch2 = c->S.ptsMatch2;
     a.thresh = 0; a.maxPairDist = c->cfg.maxPairDist;
     BBHIP(bbrunstats::launch(a, c->d_runStats, c->d_insertHist, stream));
-    c->statsCounted = true; c->statsStream = stream;
+    c->accum[ACC_STATS] = {true, stream};
     return BBMAP_OK;
 }
 
@@ -335,9 +368,8 @@ extern "C" int bbmap_get_run_stats(bbmap_ctx *c, bbmap_runstats *out, int64_t *i
         if (ihist_out) memset(ihist_out, 0, 8 * (size_t)BBMAP_INSERT_HIST_BINS);
         return BBMAP_OK;
     }
-    BBHIP(hipStreamSynchronize(c->statsStream));            // the counters are written on that stream only
-    BBHIP(hipMemcpy(out, c->d_runStats, sizeof *out, hipMemcpyDeviceToHost));
-    if (ihist_out) BBHIP(hipMemcpy(ihist_out, c->d_insertHist, 8 * (size_t)BBMAP_INSERT_HIST_BINS, hipMemcpyDeviceToHost));
+    BBTRY(copy_out(c, ACC_STATS, out, c->d_runStats, sizeof *out));
+    if (ihist_out) BBTRY(copy_out(c, ACC_STATS, ihist_out, c->d_insertHist, 8 * (size_t)BBMAP_INSERT_HIST_BINS));
     return BBMAP_OK;
 }
 
@@ -345,11 +377,8 @@ extern "C" int bbmap_reset_run_stats(bbmap_ctx *c) {
     if (!c) return bbfail(BBMAP_E_ARG, "bbmap_reset_run_stats: null context");
     c->numMatedSeen = 0;
     if (!c->d_runStats) return BBMAP_OK;
-    BBHIP(hipSetDevice(c->cfg.device));
-    BBHIP(hipMemsetAsync(c->d_runStats, 0, sizeof(bbmap_runstats), c->statsStream));      // behind the last accumulation
-    BBHIP(hipMemsetAsync(c->d_insertHist, 0, 8 * (size_t)BBMAP_INSERT_HIST_BINS, c->statsStream));
-    BBHIP(hipStreamSynchronize(c->statsStream));
-    return BBMAP_OK;
+    // (the one reset that does not forget the batch: a second add of it stays refused)
+    return reset_state(c, ACC_STATS, {{c->d_runStats, sizeof(bbmap_runstats)}, {c->d_insertHist, 8 * (size_t)BBMAP_INSERT_HIST_BINS}}, false);
 }
 
 extern "C" int bbmap_set_adaptive(bbmap_ctx *c, int32_t flags) {
@@ -377,18 +406,14 @@ extern "C" int bbmap_cov_enable(bbmap_ctx *c, int32_t flags) {
     if (flags & ~COV_FLAGS) return bbfail(BBMAP_E_ARG, "bbmap_cov_enable: unknown flag bits");
     if (c->cov) {
         if (c->cov->flags != flags) return bbfail(BBMAP_E_ARG, "bbmap_cov_enable: coverage is enabled already with other flags");
-        if (c->cov->gen != c->index->scafGen) return bbfail(BBMAP_E_ARG, "bbmap_cov_enable: the scaffold table has been replaced since coverage was enabled");
+        if (table_replaced(c, c->cov->gen)) return bbfail(BBMAP_E_ARG, "bbmap_cov_enable: the scaffold table has been replaced since coverage was enabled");
         return BBMAP_OK;
     }
     BBHIP(hipSetDevice(c->cfg.device));
     std::unique_ptr<CovState> v(new CovState);
-    v->flags = flags; v->gen = c->index->scafGen;
-    std::vector<int> off((size_t)T.nchroms + 2);
-    BBHIP(hipMemcpy(off.data(), T.off, off.size() * 4, hipMemcpyDeviceToHost));
-    v->nscaf = off[(size_t)T.nchroms + 1];
+    v->flags = flags;
+    BBTRY(scaf_snapshot(c, &v->nscaf, &v->gen, &v->hostLen));
     const size_t ns = (size_t)v->nscaf;
-    v->hostLen.resize(ns);
-    BBHIP(hipMemcpy(v->hostLen.data(), T.len, ns * 4, hipMemcpyDeviceToHost));
     std::vector<int64_t> covoff(ns + 1);
     BBTRY(bbpipe_coverage_layout(v->nscaf, v->hostLen.data(), 0, covoff.data(), nullptr));
     v->slots = covoff[ns];
@@ -415,27 +440,19 @@ extern "C" int bbmap_cov_enable(bbmap_ctx *c, int32_t flags) {
 
 extern "C" int bbmap_add_coverage(bbmap_ctx *c, void *stream_) {
     if (!c) return bbfail(BBMAP_E_ARG, "bbmap_add_coverage: null context");
-    if (!c->cov) return bbfail(BBMAP_E_ARG, "bbmap_add_coverage: coverage is not enabled (bbmap_cov_enable)");
-    if (!c->ran) return bbfail(BBMAP_E_ARG, "bbmap_add_coverage: no batch has been mapped yet");
-    if (c->covCounted) return bbfail(BBMAP_E_ARG, "bbmap_add_coverage: the last batch has been counted already");
-    if (!c->batch.reads || !c->batch.bases || c->batch.n_reads != c->stats.reads)
-        return bbfail(BBMAP_E_ARG, "bbmap_add_coverage: the context does not hold the last batch's reads");
     CovState *v = c->cov;
-    if (v->gen != c->index->scafGen || !c->index->scaf.off)
-        return bbfail(BBMAP_E_ARG, "bbmap_add_coverage: the scaffold table has been replaced since coverage was enabled");
+    BBTRY(may_add(c, ACC_COV, "bbmap_add_coverage", v ? nullptr : "coverage is not enabled (bbmap_cov_enable)", NEEDS_BASES, v ? &v->gen : nullptr,
+                  "coverage was"));
     hipStream_t stream = (hipStream_t)stream_;
     BBHIP(hipSetDevice(c->cfg.device));
-    const long long n = c->stats.reads;
     bbcov::AddArgs a = {};
-    a.reads = c->batch.reads; a.bases = c->batch.bases; a.fin = c->d_final; a.pool = c->d_pool;
-    BBTRY(tier_index(c, stream, n, &a.tierIdx));
-    if (a.tierIdx) { a.tfin = c->tier->d_final; a.tpool = c->tier->d_pool; a.nsites = c->d_mcount; }
-    a.n = n; a.paired = c->cfg.paired; a.flags = v->flags;
+    BBTRY(batch_view(c, stream, &a.V));
+    a.flags = v->flags;
     a.T = c->index->scaf; a.nscaf = v->nscaf; a.covoff = v->covoff.as<long long>();
     a.diff[0] = v->diff[0].as<int>(); a.diff[1] = v->diff[1].as<int>();
     a.recs = v->recs.as<unsigned long long>(); a.totals = v->totals.as<unsigned long long>();
     BBHIP(bbcov::launch_add(a, stream));
-    c->covCounted = true; v->stream = stream;
+    c->accum[ACC_COV] = {true, stream};
     return BBMAP_OK;
 }
 
@@ -444,13 +461,13 @@ extern "C" int bbmap_cov_finalize(bbmap_ctx *c, void *stream_, int32_t binsize, 
     if (!c->cov) return bbfail(BBMAP_E_ARG, "bbmap_cov_finalize: coverage is not enabled (bbmap_cov_enable)");
     if (binsize < 0) return bbfail(BBMAP_E_ARG, "bbmap_cov_finalize: binsize must be >= 0");
     CovState *v = c->cov;
-    if (v->gen != c->index->scafGen || !c->index->scaf.off)
-        return bbfail(BBMAP_E_ARG, "bbmap_cov_finalize: the scaffold table has been replaced since coverage was enabled");
+    if (table_replaced(c, v->gen)) return bbfail(BBMAP_E_ARG, "bbmap_cov_finalize: the scaffold table has been replaced since coverage was enabled");
     hipStream_t stream = (hipStream_t)stream_;
     BBHIP(hipSetDevice(c->cfg.device));
     const int strands = v->flags & BBMAP_COV_STRANDED ? 2 : 1;
     const size_t ns = (size_t)v->nscaf;
-    if (stream != v->stream) BBHIP(hipStreamSynchronize(v->stream));       // behind everything added so far
+    Accum &acc = c->accum[ACC_COV];
+    if (stream != acc.stream) BBHIP(hipStreamSynchronize(acc.stream));     // behind everything added so far
     if (binsize != v->binsize) {
         std::vector<int64_t> binoff(ns + 1, 0);
         BBTRY(bbpipe_coverage_layout(v->nscaf, v->hostLen.data(), binsize, nullptr, binoff.data()));
@@ -469,7 +486,7 @@ extern "C" int bbmap_cov_finalize(bbmap_ctx *c, void *stream_, int32_t binsize, 
     a.binsize = binsize; a.binoff = v->binoff.as<long long>(); a.nbins = v->nbins;
     a.totals = v->totals.as<unsigned long long>(); a.ws = v->ws.p;
     BBHIP(bbcov::launch_finalize(a, stream));
-    v->stream = stream;
+    acc.stream = stream;
     memset(out, 0, sizeof *out);
     out->flags = v->flags; out->nscaf = v->nscaf; out->binsize = binsize; out->depth_bytes = v->flags & BBMAP_COV_32BIT ? 4 : 2;
     out->slots = v->slots; out->hist_bins = bbcov::hist_bins(v->flags); out->nbins = v->nbins;
@@ -507,14 +524,9 @@ extern "C" int bbmap_reset_coverage(bbmap_ctx *c) {
     if (!c) return bbfail(BBMAP_E_ARG, "bbmap_reset_coverage: null context");
     CovState *v = c->cov;
     if (!v) return BBMAP_OK;
-    BBHIP(hipSetDevice(c->cfg.device));
-    const int strands = v->flags & BBMAP_COV_STRANDED ? 2 : 1;
-    for (int t = 0; t < strands; t++) BBHIP(hipMemsetAsync(v->diff[t].p, 0, (size_t)v->slots * 4, v->stream));      // behind the last accumulation
-    BBHIP(hipMemsetAsync(v->recs.p, 0, (size_t)v->nscaf * sizeof(bbmap_covrec), v->stream));
-    BBHIP(hipMemsetAsync(v->totals.p, 0, sizeof(bbmap_covtotals), v->stream));
-    BBHIP(hipStreamSynchronize(v->stream));
-    c->covCounted = false;          // the state no longer holds the batch the context still has
-    return BBMAP_OK;
+    const size_t diff = (size_t)v->slots * 4;                  // (an unstranded state has no second array: an empty span)
+    return reset_state(c, ACC_COV, {{v->diff[0].p, diff}, {v->diff[1].p, v->flags & BBMAP_COV_STRANDED ? diff : 0},
+                                    {v->recs.p, (size_t)v->nscaf * sizeof(bbmap_covrec)}, {v->totals.p, sizeof(bbmap_covtotals)}});
 }
 
 // ---- read histograms (read_hist.hip): thin wrappers over the raw calls' launch
@@ -539,22 +551,15 @@ extern "C" int bbmap_hist_enable(bbmap_ctx *c, int32_t flags) {
 
 extern "C" int bbmap_add_read_hist(bbmap_ctx *c, void *stream_, const uint8_t *quality) {
     if (!c) return bbfail(BBMAP_E_ARG, "bbmap_add_read_hist: null context");
-    if (!c->d_readHist) return bbfail(BBMAP_E_ARG, "bbmap_add_read_hist: the histograms are not enabled (bbmap_hist_enable)");
-    if (!c->ran) return bbfail(BBMAP_E_ARG, "bbmap_add_read_hist: no batch has been mapped yet");
-    if (c->rhCounted) return bbfail(BBMAP_E_ARG, "bbmap_add_read_hist: the last batch has been counted already");
-    if (!c->batch.reads || !c->batch.bases || c->batch.n_reads != c->stats.reads)
-        return bbfail(BBMAP_E_ARG, "bbmap_add_read_hist: the context does not hold the last batch's reads");
+    BBTRY(may_add(c, ACC_HIST, "bbmap_add_read_hist", c->d_readHist ? nullptr : "the histograms are not enabled (bbmap_hist_enable)", NEEDS_BASES));
     hipStream_t stream = (hipStream_t)stream_;
     BBHIP(hipSetDevice(c->cfg.device));
-    const long long n = c->stats.reads;
     bbrh::Args a = {};
-    a.reads = c->batch.reads; a.bases = c->batch.bases; a.qual = quality; a.fin = c->d_final; a.pool = c->d_pool;
-    BBTRY(tier_index(c, stream, n, &a.tierIdx));
-    if (a.tierIdx) { a.tfin = c->tier->d_final; a.tpool = c->tier->d_pool; a.nsites = c->d_mcount; }
-    a.n = n; a.paired = c->cfg.paired; a.flags = c->rhFlags;
+    BBTRY(batch_view(c, stream, &a.V));
+    a.qual = quality; a.flags = c->rhFlags;
     a.state = c->d_readHist;
     BBHIP(bbrh::launch_add(a, stream));
-    c->rhCounted = true; c->rhStream = stream;
+    c->accum[ACC_HIST] = {true, stream};
     return BBMAP_OK;
 }
 
@@ -573,19 +578,13 @@ extern "C" int bbmap_get_read_hist(bbmap_ctx *c, int64_t *out, int64_t cap_words
     if (view_out) *view_out = w;
     if (cap_words < w.words) return BBMAP_OK;
     BBHIP(hipSetDevice(c->cfg.device));
-    BBHIP(hipStreamSynchronize(c->rhStream));               // the state is written on that stream only
-    BBHIP(hipMemcpy(out, c->d_readHist, 8 * (size_t)w.words, hipMemcpyDeviceToHost));
-    return BBMAP_OK;
+    return copy_out(c, ACC_HIST, out, c->d_readHist, 8 * (size_t)w.words);
 }
 
 extern "C" int bbmap_reset_read_hist(bbmap_ctx *c) {
     if (!c) return bbfail(BBMAP_E_ARG, "bbmap_reset_read_hist: null context");
     if (!c->d_readHist) return BBMAP_OK;
-    BBHIP(hipSetDevice(c->cfg.device));
-    BBHIP(hipMemsetAsync(c->d_readHist, 0, 8 * (size_t)bbrh::layout_of(c->rhFlags).words, c->rhStream));      // behind the last accumulation
-    BBHIP(hipStreamSynchronize(c->rhStream));
-    c->rhCounted = false;           // the state no longer holds the batch the context still has
-    return BBMAP_OK;
+    return reset_state(c, ACC_HIST, {{c->d_readHist, 8 * (size_t)bbrh::layout_of(c->rhFlags).words}});
 }
 
 // ---- reference-set binning (ref_split.hip): thin wrappers over the raw calls' launches
@@ -602,15 +601,13 @@ extern "C" int bbmap_split_enable(bbmap_ctx *c, const bbmap_split_config *cfg_, 
     if (!cfg.flags) return bbfail(BBMAP_E_ARG, "bbmap_split_enable: nothing selected");
     if (c->split) {
         if (memcmp(&c->split->cfg, &cfg, sizeof cfg) != 0) return bbfail(BBMAP_E_ARG, "bbmap_split_enable: the stage is enabled already with another configuration");
-        if (c->split->gen != c->index->scafGen) return bbfail(BBMAP_E_ARG, "bbmap_split_enable: the scaffold table has been replaced since the stage was enabled");
+        if (table_replaced(c, c->split->gen)) return bbfail(BBMAP_E_ARG, "bbmap_split_enable: the scaffold table has been replaced since the stage was enabled");
         return BBMAP_OK;
     }
     BBHIP(hipSetDevice(c->cfg.device));
     std::unique_ptr<SplitState> v(new SplitState);
-    v->cfg = cfg; v->gen = c->index->scafGen;
-    std::vector<int> off((size_t)T.nchroms + 2);
-    BBHIP(hipMemcpy(off.data(), T.off, off.size() * 4, hipMemcpyDeviceToHost));
-    v->nscaf = off[(size_t)T.nchroms + 1];
+    v->cfg = cfg;
+    BBTRY(scaf_snapshot(c, &v->nscaf, &v->gen, nullptr));
     const size_t ns = (size_t)v->nscaf, sb = (size_t)bbpipe_refsplit_state_bytes(cfg.nkeys, cfg.nsets);
     if (v->sets.grow(ns * 8 + 8) != hipSuccess || v->keys.grow(ns * 4 + 4) != hipSuccess || v->state.grow(sb) != hipSuccess ||
         v->setoff.grow(8 * (2 * (size_t)cfg.nsets + 1)) != hipSuccess)
@@ -629,26 +626,19 @@ extern "C" int bbmap_split_enable(bbmap_ctx *c, const bbmap_split_config *cfg_, 
 extern "C" int bbmap_add_split(bbmap_ctx *c, void *stream_) {
     if (!c) return bbfail(BBMAP_E_ARG, "bbmap_add_split: null context");
     SplitState *v = c->split;
-    if (!v) return bbfail(BBMAP_E_ARG, "bbmap_add_split: the stage is not enabled (bbmap_split_enable)");
-    if (!c->ran) return bbfail(BBMAP_E_ARG, "bbmap_add_split: no batch has been mapped yet");
-    if (c->splitCounted) return bbfail(BBMAP_E_ARG, "bbmap_add_split: the last batch has been added already");
-    if (!c->batch.reads || c->batch.n_reads != c->stats.reads) return bbfail(BBMAP_E_ARG, "bbmap_add_split: the context does not hold the last batch's reads");
-    if (v->gen != c->index->scafGen || !c->index->scaf.off)
-        return bbfail(BBMAP_E_ARG, "bbmap_add_split: the scaffold table has been replaced since the stage was enabled");
+    BBTRY(may_add(c, ACC_SPLIT, "bbmap_add_split", v ? nullptr : "the stage is not enabled (bbmap_split_enable)", SAYS_ADDED, v ? &v->gen : nullptr,
+                  "the stage was"));
     hipStream_t stream = (hipStream_t)stream_;
     BBHIP(hipSetDevice(c->cfg.device));
-    const long long n = c->stats.reads;
     bbsplit::Args a = {};
-    a.reads = c->batch.reads; a.fin = c->d_final; a.sites = c->d_ms; a.nsites = c->d_mcount; a.cap = c->cfg.max_sites;
-    BBTRY(tier_index(c, stream, n, &a.tierIdx));
-    if (a.tierIdx) { const bbmap_ctx *t = c->tier; a.tfin = t->d_final; a.tsites = t->d_ms; a.tnsites = t->d_mcount; a.tcap = t->cfg.max_sites; }
+    BBTRY(batch_view(c, stream, &a.V));
     a.T = c->index->scaf; a.scafSets = v->sets.as<unsigned long long>(); a.scafKey = v->keys.as<int>();
-    a.n = n; a.paired = c->cfg.paired;
     a.flags = v->cfg.flags; a.mode = v->cfg.ambiguous2; a.clearzone = v->cfg.clearzone; a.maxSites = v->cfg.maxSites;
     a.nsets = v->cfg.nsets; a.nkeys = v->cfg.nkeys;
     a.state = v->state.as<unsigned long long>(); a.recs = v->recs.as<bbmap_splitrec>();
     BBHIP(bbsplit::launch_assign(a, stream));
-    c->splitCounted = true; v->stream = stream; v->added = n; v->total = -1;
+    c->accum[ACC_SPLIT] = {true, stream};
+    v->added = a.V.n; v->total = -1;
     return BBMAP_OK;
 }
 
@@ -670,7 +660,7 @@ extern "C" int bbmap_get_split_lists_device(bbmap_ctx *c, void *stream_, const i
     if (v->added < 0) return bbfail(BBMAP_E_ARG, "bbmap_get_split_lists_device: no batch has been added yet");
     hipStream_t stream = (hipStream_t)stream_;
     BBHIP(hipSetDevice(c->cfg.device));
-    if (stream != v->stream) BBHIP(hipStreamSynchronize(v->stream));          // behind the add that wrote the records
+    if (stream != c->accum[ACC_SPLIT].stream) BBHIP(hipStreamSynchronize(c->accum[ACC_SPLIT].stream));      // behind the add that wrote the records
     const long long n = v->added;
     const int paired = c->cfg.paired, nsets = v->cfg.nsets;
     const long long need = bbsplit::lists_workspace_bytes(n, paired, nsets);
@@ -708,20 +698,14 @@ extern "C" int bbmap_get_split_stats(bbmap_ctx *c, int64_t *out, int64_t cap_wor
     const int64_t bytes = bbpipe_refsplit_state_bytes(v->cfg.nkeys, v->cfg.nsets);
     if (cap_words * 8 < bytes) return bbfail(BBMAP_E_ARG, "bbmap_get_split_stats: the buffer is too small (4 + 4 nkeys + 4 nsets words)");
     BBHIP(hipSetDevice(c->cfg.device));
-    BBHIP(hipStreamSynchronize(v->stream));                 // the state is written on that stream only
-    BBHIP(hipMemcpy(out, v->state.p, (size_t)bytes, hipMemcpyDeviceToHost));
-    return BBMAP_OK;
+    return copy_out(c, ACC_SPLIT, out, v->state.p, (size_t)bytes);
 }
 
 extern "C" int bbmap_reset_split(bbmap_ctx *c) {
     if (!c) return bbfail(BBMAP_E_ARG, "bbmap_reset_split: null context");
     SplitState *v = c->split;
     if (!v) return BBMAP_OK;
-    BBHIP(hipSetDevice(c->cfg.device));
-    BBHIP(hipMemsetAsync(v->state.p, 0, (size_t)bbpipe_refsplit_state_bytes(v->cfg.nkeys, v->cfg.nsets), v->stream));      // behind the last add
-    BBHIP(hipStreamSynchronize(v->stream));
-    c->splitCounted = false;        // the state no longer holds the batch the context still has
-    return BBMAP_OK;
+    return reset_state(c, ACC_SPLIT, {{v->state.p, (size_t)bbpipe_refsplit_state_bytes(v->cfg.nkeys, v->cfg.nsets)}});
 }
 
 extern "C" int bbidx_get_chrom_table(bbidx_ctx *ix, int32_t *nchroms, const uint8_t **chromArr, int32_t *chromArrLen, int32_t cap) {

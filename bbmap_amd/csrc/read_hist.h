@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "batch_view.h"
 #include "bbmap_amd.h"
 
 namespace bbrh {
@@ -39,11 +40,9 @@ struct Layout { long long off[N_ARRAYS]; long long words; };           // off < 
 Layout layout_of(int flags);
 
 struct Args {
-    const bbidx_read *reads; const uint8_t *bases, *qual;              // qual == nullptr: no qualities
-    const bbmap_final *fin; const uint8_t *pool;
-    // the overflow tier's records and pool, read -> tier record (nullptr = no tier reads) and the main lists' counts that flag a tier read
-    const bbmap_final *tfin; const uint8_t *tpool; const int *tierIdx; const int *nsites;
-    long long n; int paired, flags;
+    BatchView V;
+    const uint8_t *qual;                                               // by bases_off, as V.bases; nullptr: no qualities
+    int flags;
     unsigned long long *state;
 };
 hipError_t launch_add(const Args &a, hipStream_t stream);

@@ -75,18 +75,6 @@ static Table table_of(int flags) {
     return T;
 }
 
-struct Rec { const bbmap_final *f; const uint8_t *m; int ml; };
-// a read the overflow tier mapped takes the tier's record and pool (coverage.hip::record_of)
-__device__ inline Rec record_of(const Args &A, long long r) {
-    Rec R;
-    R.f = A.fin + r;
-    const uint8_t *pl = A.pool;
-    if (A.tierIdx && A.nsites[r] == BBMAP_NSITES_IN_TIER && A.tierIdx[r] >= 0) { R.f = A.tfin + A.tierIdx[r]; pl = A.tpool; }
-    R.ml = R.f->match_len > 0 ? R.f->match_len : 0;
-    R.m = R.ml ? pl + R.f->match_off : nullptr;
-    return R;
-}
-
 // AminoAcid.baseToNumber
 __device__ inline int base_to_number(int b) {
     const int c = b & ~0x20;
@@ -256,8 +244,8 @@ __global__ __launch_bounds__(TB) void read_hist_add_kernel(const Args A, const T
     const int wid = uni((int)(threadIdx.x >> 6));
     for (int k = threadIdx.x; k < L_TOTAL; k += TB) cnt[k] = 0;
     __syncthreads();
-    const long long units = A.paired ? A.n / 2 : A.n;
-    const int mates = A.paired ? 2 : 1;
+    const long long units = A.V.paired ? A.V.n / 2 : A.V.n;
+    const int mates = A.V.paired ? 2 : 1;
     const int needString = BBMAP_RH_MATCH | BBMAP_RH_ACCURACY | BBMAP_RH_ERROR | BBMAP_RH_IDENTITY | BBMAP_RH_INDEL;
     for (long long chunk = blockIdx.x; chunk * CHUNK < units; chunk += gridDim.x) {
         const long long end = min(units, (chunk + 1) * CHUNK);
@@ -266,14 +254,14 @@ __global__ __launch_bounds__(TB) void read_hist_add_kernel(const Args A, const T
             int lenOf[2] = {0, 0};
             for (int mate = 0; mate < mates; mate++) {
                 const long long r = u * mates + mate;
-                const bbidx_read rd = A.reads[r];
+                const bbidx_read rd = A.V.reads[r];
                 const int len = uni(min(max(rd.len, 0), (int)MAXPOS));
-                const uint8_t *bases = A.bases + rd.bases_off, *qual = A.qual ? A.qual + rd.bases_off : nullptr;
+                const uint8_t *bases = A.V.bases + rd.bases_off, *qual = A.qual ? A.qual + rd.bases_off : nullptr;
                 const float gc = read_pass(X, bases, qual, len, mate);
                 lenOf[mate] = len;
                 gcOf[mate] = len > 0 ? gc : -1.f;                                         // :418-419
                 if (!(A.flags & needString) || len < 1) continue;
-                const Rec R = record_of(A, r);
+                const ReadRec R = record_of<TierRule::ByList>(A.V, r);
                 const int ml = uni(R.ml);
                 if (!uni(R.f->mapped) || ml < 1) continue;
                 if (A.flags & (needString & ~BBMAP_RH_INDEL)) match_pass(X, R.m, ml, uni(R.f->strand) == 0, bases, qual, len, mate);
@@ -315,7 +303,7 @@ __global__ __launch_bounds__(TB) void read_hist_add_kernel(const Args A, const T
 }
 
 hipError_t launch_add(const Args &a, hipStream_t stream) {
-    const long long units = a.paired ? a.n / 2 : a.n;
+    const long long units = a.V.paired ? a.V.n / 2 : a.V.n;
     if (units <= 0) return hipSuccess;
     const long long want = (units + CHUNK - 1) / CHUNK;
     const unsigned blocks = (unsigned)(want < MAX_BLOCKS ? want : MAX_BLOCKS);
@@ -355,8 +343,9 @@ extern "C" int bbpipe_read_hist_add_device(void *stream, int64_t n_reads, int32_
     if (n_reads == 0 || flags == 0) return BBMAP_OK;
     if (!reads || !bases || !finals || !pool || !state) return bbfail(BBMAP_E_ARG, "bbpipe_read_hist_add_device: null buffer");
     bbrh::Args a = {};
-    a.reads = reads; a.bases = bases; a.qual = quality; a.fin = finals; a.pool = pool;
-    a.n = n_reads; a.paired = paired ? 1 : 0; a.flags = flags;
+    a.V.reads = reads; a.V.bases = bases; a.V.fin = finals; a.V.pool = pool;      // (no tier)
+    a.qual = quality;
+    a.V.n = n_reads; a.V.paired = paired ? 1 : 0; a.flags = flags;
     a.state = (unsigned long long *)state;
     BBHIP(bbrh::launch_add(a, (hipStream_t)stream));
     return BBMAP_OK;

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "batch_view.h"
 #include "bbmap_amd.h"
 #include "scaffold.h"
 
@@ -19,14 +20,9 @@ static_assert(CHUNK % TB == 0 && TB % 2 == 0, "mates sit in neighbouring lanes o
 static_assert(sizeof(bbmap_splitrec) == 32 && sizeof(bbmap_split_config) == 32, "ABI sizes");
 
 struct Args {
-    const bbidx_read *reads;
-    const bbmap_final *fin; const bbmap_msite *sites; const int *nsites; int cap;
-    // the overflow tier's records and lists, and read -> tier record (nullptr = no tier reads)
-    const bbmap_final *tfin; const bbmap_msite *tsites; const int *tnsites; int tcap;
-    const int *tierIdx;
+    BatchView V;                    // (bases and match strings are not read)
     bbscaf::Table T;
     const unsigned long long *scafSets; const int *scafKey;
-    long long n; int paired;
     int flags, mode, clearzone, maxSites, nsets, nkeys;
     unsigned long long *state;      // HEAD words, 4 per key, 4 per set
     bbmap_splitrec *recs;           // nullptr = not wanted

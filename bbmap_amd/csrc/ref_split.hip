@@ -74,23 +74,6 @@ __device__ inline int scaffold_of(const bbscaf::Table &T, int chrom, int start, 
     return b + (ns < 2 ? 0 : bbscaf::last_at_or_below(T.loc + b, ns, key));
 }
 
-struct Rec { const bbmap_final *f; const bbmap_msite *s; int n; bool flagged; };
-// a read the overflow tier mapped takes the tier's record and list (run_stats.hip::record_of); the list is cut at maxSites (capSiteList)
-__device__ inline Rec record_of(const Args &A, long long r) {
-    Rec R;
-    R.f = A.fin + r;
-    R.s = A.sites + r * A.cap;
-    int n = A.nsites[r], cap = A.cap;
-    R.flagged = (n == BBMAP_NSITES_OVERFLOW) | (n == BBMAP_NSITES_MATE_OVERFLOW);
-    if (A.tierIdx && n == BBMAP_NSITES_IN_TIER && A.tierIdx[r] >= 0) {
-        const long long t = A.tierIdx[r];
-        R.f = A.tfin + t; R.s = A.tsites + t * A.tcap; n = A.tnsites[t]; cap = A.tcap;
-    }
-    n = n < 0 ? 0 : n > cap ? cap : n;
-    R.n = min(n, A.maxSites);
-    return R;
-}
-
 __global__ __launch_bounds__(TB) void refsplit_assign_kernel(const Args A) {
     __shared__ Lds L;
     const bool doScaf = (A.flags & BBMAP_SPLIT_SCAF_STATS) && A.state && A.nkeys > 0;
@@ -101,9 +84,9 @@ __global__ __launch_bounds__(TB) void refsplit_assign_kernel(const Args A) {
     for (int k = threadIdx.x; k < SLOTS * 4; k += TB) L.sum[k] = 0;
     for (int k = threadIdx.x; k < MAX_SETS * 4; k += TB) L.set[k] = 0;
     __syncthreads();
-    if (A.state && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(A.state, (u64)A.n);         // totalReads
-    for (long long chunk = blockIdx.x; chunk * CHUNK < A.n; chunk += gridDim.x) {
-        const long long end = min(A.n, (chunk + 1) * CHUNK);
+    if (A.state && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(A.state, (u64)A.V.n);         // totalReads
+    for (long long chunk = blockIdx.x; chunk * CHUNK < A.V.n; chunk += gridDim.x) {
+        const long long end = min(A.V.n, (chunk + 1) * CHUNK);
         for (long long base = chunk * CHUNK; base < end; base += TB) {
             const long long r = base + threadIdx.x;
             const bool valid = r < end;
@@ -111,9 +94,11 @@ __global__ __launch_bounds__(TB) void refsplit_assign_kernel(const Args A) {
             int mapScore = 0, len = 0, ownKey = -1;
             bool mapped = false, ambRead = false;
             if (valid) {
-                const Rec R = record_of(A, r);
-                len = A.reads[r].len;
-                mapped = R.f->mapped != 0 && !R.flagged;
+                const ReadRec R = record_of<TierRule::ByList, true>(A.V, r);
+                const int nlist = min(R.n, A.maxSites);                                          // capSiteList
+                const bool flagged = (R.flag == BBMAP_NSITES_OVERFLOW) | (R.flag == BBMAP_NSITES_MATE_OVERFLOW);
+                len = A.V.reads[r].len;
+                mapped = R.f->mapped != 0 && !flagged;
                 mapScore = R.f->mapScore;
                 ambRead = mapped && R.f->ambiguous != 0;
                 if (mapped) {
@@ -122,12 +107,12 @@ __global__ __launch_bounds__(TB) void refsplit_assign_kernel(const Args A) {
                     ownKey = (unsigned)k < (unsigned)A.nkeys ? k : -1;
                     if (doScaf && !ambRead && ownKey >= 0) add_key(L, keyState, ownKey, 0, len);         // :872-893
                 }
-                if (mapped && R.n > 0) {
+                if (mapped && nlist > 0) {
                     int kept[KEEP], nk = 0;
 #pragma unroll
                     for (int k = 0; k < KEEP; k++) kept[k] = -1;
                     const int s0 = R.s[0].score;
-                    for (int j = 0; j < R.n; j++) {
+                    for (int j = 0; j < nlist; j++) {
                         const bbmap_msite *ss = R.s + j;
                         if (j > 0 && (int)((unsigned)ss->score + (unsigned)A.clearzone) < s0) break;     // :844 / :900
                         const int gs = scaffold_of(A.T, ss->chrom, ss->start, ss->stop);
@@ -154,16 +139,16 @@ __global__ __launch_bounds__(TB) void refsplit_assign_kernel(const Args A) {
                 }
             }
             // the mate's values (lanes r and r ^ 1: CHUNK and TB are even, so a valid lane's mate is valid and in this wavefront)
-            const int mate = A.paired ? (int)(threadIdx.x & 1) : 0;
+            const int mate = A.V.paired ? (int)(threadIdx.x & 1) : 0;
             u64 po = __shfl_xor(p, 1, 64), oo = __shfl_xor(o, 1, 64);
             int mso = __shfl_xor(mapScore, 1, 64), leno = __shfl_xor(len, 1, 64);
-            if (!A.paired) { po = 0; oo = 0; mso = 0; leno = 0; }
+            if (!A.V.paired) { po = 0; oo = 0; mso = 0; leno = 0; }
             const u64 p1 = mate ? po : p, s1 = mate ? oo : o, p2 = mate ? p : po, s2 = mate ? o : oo;
             const int ms1 = mate ? mso : mapScore, ms2 = mate ? mapScore : mso;
             // (an unmapped read has empty sets, so getSets' "neither mate is mapped" needs no test of its own)
             const bool amb = (p1 && p2 && p1 != p2) || (p1 && (s1 & ~p1)) || (p2 && (s2 & ~p2));          // :661-663
             u64 prim, ambm = 0;
-            if (A.mode == BBMAP_AMBIG2_FIRST || A.mode == BBMAP_AMBIG2_UNSET) prim = (!A.paired || ms1 >= ms2) ? p1 : p2;        // :672-677
+            if (A.mode == BBMAP_AMBIG2_FIRST || A.mode == BBMAP_AMBIG2_UNSET) prim = (!A.V.paired || ms1 >= ms2) ? p1 : p2;        // :672-677
             else prim = p1 | p2;                                                                    // :678-681
             if (amb) {                                                                              // :684-699
                 if (A.mode == BBMAP_AMBIG2_SPLIT) { ambm = prim | s1 | s2; prim = 0; }
@@ -172,7 +157,7 @@ __global__ __launch_bounds__(TB) void refsplit_assign_kernel(const Args A) {
             }
             const u64 stat = p1 | p2 | (amb ? s1 | s2 : 0ull);                                      // :725-732
             if (doSet && valid && mate == 0 && stat) {
-                const u64 incrR = A.paired ? 2 : 1, incrB = (u64)((long long)len + (long long)leno);  // :734-735
+                const u64 incrR = A.V.paired ? 2 : 1, incrB = (u64)((long long)len + (long long)leno);  // :734-735
                 for (u64 m = stat; m; m &= m - 1) {
                     const int s = __builtin_ctzll(m);
                     atomicAdd(&L.set[s * 4 + (amb ? 2 : 0)], incrR);
@@ -213,8 +198,8 @@ __global__ __launch_bounds__(TB) void refsplit_assign_kernel(const Args A) {
 }
 
 hipError_t launch_assign(const Args &a, hipStream_t stream) {
-    if (a.n <= 0) return hipSuccess;
-    const long long want = (a.n + CHUNK - 1) / CHUNK;
+    if (a.V.n <= 0) return hipSuccess;
+    const long long want = (a.V.n + CHUNK - 1) / CHUNK;
     const unsigned blocks = (unsigned)(want < MAX_BLOCKS ? want : MAX_BLOCKS);
     hipLaunchKernelGGL(refsplit_assign_kernel, dim3(blocks), dim3(TB), 0, stream, a);
     return hipGetLastError();
@@ -331,10 +316,10 @@ extern "C" int bbpipe_refsplit_add_device(void *stream, int64_t n_reads, int32_t
     if ((cfg->flags & (BBMAP_SPLIT_SCAF_STATS | BBMAP_SPLIT_SET_STATS)) && !state) return bbfail(BBMAP_E_ARG, "bbpipe_refsplit_add_device: null state");
     if ((cfg->flags & (BBMAP_SPLIT_RECORDS | BBMAP_SPLIT_LISTS)) && !records_out) return bbfail(BBMAP_E_ARG, "bbpipe_refsplit_add_device: null records");
     bbsplit::Args a = {};
-    a.reads = reads; a.fin = finals; a.sites = sites; a.nsites = nsites; a.cap = cap_stride;
+    a.V.reads = reads; a.V.fin = finals; a.V.sites = sites; a.V.nsites = nsites; a.V.cap = cap_stride;      // (no tier)
     a.T.off = scaf_off; a.T.loc = scaf_loc; a.T.len = nullptr; a.T.pad = pad; a.T.nchroms = nchroms;
     a.scafSets = (const unsigned long long *)scaf_sets; a.scafKey = scaf_key;
-    a.n = n_reads; a.paired = paired ? 1 : 0;
+    a.V.n = n_reads; a.V.paired = paired ? 1 : 0;
     a.flags = cfg->flags; a.mode = cfg->ambiguous2; a.clearzone = cfg->clearzone; a.maxSites = cfg->maxSites; a.nsets = cfg->nsets; a.nkeys = cfg->nkeys;
     a.state = (unsigned long long *)state;
     a.recs = cfg->flags & (BBMAP_SPLIT_RECORDS | BBMAP_SPLIT_LISTS) ? records_out : nullptr;

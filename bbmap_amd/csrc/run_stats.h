@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "batch_view.h"
 #include "bbmap_amd.h"
 
 namespace bbrunstats {
@@ -13,13 +14,8 @@ static_assert(sizeof(bbmap_runstats) == 8 * N_COUNTERS, "bbmap_runstats is 96 co
 static_assert(PER_MATE + PAIR_LEVEL <= 64, "one lane per counter a read can move");
 
 struct Args {
-    const bbidx_read *reads;
-    const bbmap_final *fin; const uint8_t *pool; const bbmap_msite *sites; const int *nsites; int cap;
-    // the overflow tier's records, pool and lists, and read -> tier record (nullptr = no tier reads)
-    const bbmap_final *tfin; const uint8_t *tpool; const bbmap_msite *tsites; const int *tnsites; int tcap;
-    const int *tierIdx;
+    BatchView V;                                            // (bases are not read)
     const bbmap_truth *truth;                               // nullptr = no read has a truth record
-    long long n; int paired;
     int ptsMatch, ptsMatch2;                                // MSA.maxQuality(len) = ptsMatch + (len - 1) * ptsMatch2
     int thresh, maxPairDist;
 };

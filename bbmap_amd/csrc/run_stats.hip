@@ -47,29 +47,6 @@ enum { P_bothUnmapped = PER_MATE, P_bothUnmappedBases, P_numMated, P_numMatedBas
        P_outerLengthSum, P_insertSizeSum, P_END };
 static_assert(P_END - PER_MATE == PAIR_LEVEL, "pair-level counters");
 
-struct Rec {                        // one read as calcStatistics sees it, wave-uniform
-    const bbmap_final *f; const uint8_t *m; int ml;
-    const bbmap_msite *s; int n;    // r.sites
-    int len;
-};
-// a read the overflow tier mapped takes the tier's record, pool and list (as bbmap_get_final does)
-__device__ inline Rec record_of(const Args &A, long long r) {
-    Rec R;
-    R.f = A.fin + r;
-    const uint8_t *pl = A.pool;
-    R.s = A.sites + r * A.cap;
-    int n = A.nsites[r], cap = A.cap;
-    if (A.tierIdx && n == BBMAP_NSITES_IN_TIER && A.tierIdx[r] >= 0) {
-        const long long t = A.tierIdx[r];
-        R.f = A.tfin + t; pl = A.tpool; R.s = A.tsites + t * A.tcap; n = A.tnsites[t]; cap = A.tcap;
-    }
-    R.n = n < 0 ? 0 : n > cap ? cap : n;
-    R.ml = R.f->match_len > 0 ? R.f->match_len : 0;
-    R.m = R.ml ? pl + R.f->match_off : nullptr;
-    R.len = A.reads[r].len;
-    return R;
-}
-
 // Read.countErrors {M, S, D, I, N}: `X`, `Y` and `I` all count as insertions, `C` counts with `N`
 struct Errors { int m, s, d, i, n; };
 __device__ inline Errors count_errors(const uint8_t *m, int ml, int lane) {
@@ -164,11 +141,11 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void run_stats_kernel(const A
     for (int k = lane; k < N_COUNTERS; k += 64) acc[wid][k] = 0;           // a wave touches its own row only, until the block's flush
     __syncthreads();
     const long long nwaves = (long long)gridDim.x * WAVES_PER_BLOCK;
-    for (long long r = (long long)blockIdx.x * WAVES_PER_BLOCK + wid; r < A.n; r += nwaves) {
-        const int mate = A.paired ? (int)(r & 1) : 0;
-        const Rec R = record_of(A, r);
+    for (long long r = (long long)blockIdx.x * WAVES_PER_BLOCK + wid; r < A.V.n; r += nwaves) {
+        const int mate = A.V.paired ? (int)(r & 1) : 0;
+        const ReadRec R = record_of<TierRule::ByList, true>(A.V, r);         // one read as calcStatistics sees it, wave-uniform
         const bbmap_final &f = *R.f;
-        const int len = R.len, elements = R.n;
+        const int len = A.V.reads[r].len, elements = R.n;                    // elements: r.sites
         const bool mapped = f.mapped != 0, paired = f.paired != 0, rescued = f.rescued != 0, plus = f.strand == 0;
         long long mine = 0;
         SET(C_readsUsed, 1); SET(C_basesUsed, len);
@@ -204,13 +181,13 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void run_stats_kernel(const A
         } else SET(C_noHit, 1);
         // the pair-level part of calcStatistics1: mate 1's wavefront, or every read of a single-ended run (r2 == null)
         if (mate == 0) {
-            const bool hasMate = A.paired != 0;
+            const bool hasMate = A.V.paired != 0;
             bool mateMapped = false;
             Mate m2 = {0, 0, 0, 0, 0};
             if (hasMate) {
-                const Rec Q = record_of(A, r + 1);
+                const ReadRec Q = record_of<TierRule::ByList>(A.V, r + 1);
                 mateMapped = Q.f->mapped != 0;
-                m2.strand = Q.f->strand; m2.start = Q.f->start; m2.stop = Q.f->stop; m2.chrom = Q.f->chrom; m2.len = Q.len;
+                m2.strand = Q.f->strand; m2.start = Q.f->start; m2.stop = Q.f->stop; m2.chrom = Q.f->chrom; m2.len = A.V.reads[r + 1].len;
             }
             const int len2 = hasMate ? len : 0;                             // `len2=(r2==null ? 0 : r.length())` (:1481): mate 1's length
             if (!mapped && !mateMapped) {                                   // :1489-1496
@@ -246,8 +223,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void run_stats_kernel(const A
 #undef SET
 
 hipError_t launch(const Args &a, unsigned long long *counters, unsigned long long *ihist, hipStream_t stream) {
-    if (a.n <= 0) return hipSuccess;
-    const long long want = (a.n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    if (a.V.n <= 0) return hipSuccess;
+    const long long want = (a.V.n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     const unsigned blocks = (unsigned)(want < MAX_BLOCKS ? want : MAX_BLOCKS);
     hipLaunchKernelGGL(run_stats_kernel, dim3(blocks), dim3(64 * WAVES_PER_BLOCK), 0, stream, a, counters, ihist);
     return hipGetLastError();
@@ -264,8 +241,8 @@ extern "C" int bbpipe_run_stats_device(void *stream, int64_t n_reads, int32_t pa
     if (n_reads == 0) return BBMAP_OK;
     if (!reads || !finals || !pool || !sites || !nsites || !counters) return bbfail(BBMAP_E_ARG, "bbpipe_run_stats_device: null buffer");
     bbrunstats::Args a = {};
-    a.reads = reads; a.fin = finals; a.pool = pool; a.sites = sites; a.nsites = nsites; a.cap = cap;
-    a.truth = truth; a.n = n_reads; a.paired = paired ? 1 : 0;
+    a.V.reads = reads; a.V.fin = finals; a.V.pool = pool; a.V.sites = sites; a.V.nsites = nsites; a.V.cap = cap;      // (no tier)
+    a.truth = truth; a.V.n = n_reads; a.V.paired = paired ? 1 : 0;
     a.ptsMatch = scheme == BBMSA_SCHEME_9PACBIO ? 90 : 70; a.ptsMatch2 = 100;     // POINTS_MATCH / POINTS_MATCH2 of the two aligner classes
     a.thresh = thresh; a.maxPairDist = 32000;                                      // MAX_PAIR_DIST (AbstractMapThread.java:2975)
     BBHIP(bbrunstats::launch(a, (unsigned long long *)counters, (unsigned long long *)ihist, (hipStream_t)stream));

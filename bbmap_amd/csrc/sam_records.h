@@ -2,19 +2,17 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "batch_view.h"
 #include "bbmap_amd.h"
 
 namespace bbsam {
 
 struct Args {
-    const bbmap_final *fin; const uint8_t *pool;            // the batch's final records and their string pool
-    const bbmap_final *tfin; const uint8_t *tpool;          // the overflow tier's, and read -> tier record (nullptr = no tier reads)
-    const int *tierIdx;
+    BatchView V;                                            // (the site lists are not read)
     const bbmap_scafrec *scaf;                              // bbmap_get_scaffold_records' output for the same batch
-    const bbidx_read *reads; const uint8_t *bases;          // the batch's reads, plus strands
     const uint8_t *const *chromArr; const int *chromArrLen;
     const float *mapqMax; int mapqMaxLen;                   // 1.5f * (float)log2(length) + 36 by read length, [0, mapqMaxLen]
-    long long n; int paired; int flags;                     // BBMAP_SAM_*
+    int flags;                                              // BBMAP_SAM_*
 };
 
 // mapqMax[len] as SamLine.toMapq computes it (current/stream/SamLine.java:1718, Tools.log2 current/align2/Tools.java:2304-2317)

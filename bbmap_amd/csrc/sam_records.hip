@@ -44,15 +44,6 @@ __device__ inline int wave_excl_sum(int v, int lane, int &total) {
 // ChromosomeArray.get (current/dna/ChromosomeArray.java:232-234) with minIndex 0 and maxIndex = length - 1, as these arrays have them
 __device__ inline int chrom_get(const uint8_t *chr, int chrLen, int loc) { return loc < 0 || loc >= chrLen - 1 ? 'N' : chr[loc]; }
 
-// a read the overflow tier mapped takes the tier's record (as bbmap_get_final does)
-__device__ inline const bbmap_final *source(const Args &A, long long r, const uint8_t *&m) {
-    const bbmap_final *f = A.fin + r;
-    const uint8_t *pl = A.pool;
-    if (A.tierIdx && f->nsites == BBMAP_NSITES_IN_TIER && A.tierIdx[r] >= 0) { f = A.tfin + A.tierIdx[r]; pl = A.tpool; }
-    m = f->match_len > 0 ? pl + f->match_off : nullptr;
-    return f;
-}
-
 // SamLine.countTrailingClip (:959-972)
 __device__ inline int trailing_clip(const uint8_t *m, int ml, int lane) {
     int tclip = 0;
@@ -290,18 +281,19 @@ struct Line {                       // what both passes need of one read, wave-u
 };
 __device__ inline Line line_of(const Args &A, long long r) {
     Line L;
-    L.f = source(A, r, L.m);
+    const ReadRec R = record_of<TierRule::ByRecord>(A.V, r);
+    L.f = R.f; L.m = R.m;
     L.s = A.scaf[r];
     L.mapped = (L.s.flags & BBMAP_SCAF_MAPPED) != 0;
     L.ml = L.mapped && L.f->match_len > 0 ? L.f->match_len : 0;        // a record the scaffold rule unmapped has lost its string (:138)
     if (!L.ml) L.m = nullptr;
-    L.len = A.reads[r].len; L.call = A.bases + A.reads[r].bases_off;
+    L.len = A.V.reads[r].len; L.call = A.V.bases + A.V.reads[r].bases_off;
     return L;
 }
 
 __global__ __launch_bounds__(256) void sam_size_kernel(const Args A, bbmap_samrec *recs, int *counts) {
     const long long r = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (r >= A.n) return;
+    if (r >= A.V.n) return;
     const int lane = threadIdx.x & 63;
     const Line L = line_of(A, r);
     const bbmap_final &f = *L.f;
@@ -316,14 +308,15 @@ __global__ __launch_bounds__(256) void sam_size_kernel(const Args A, bbmap_samre
     int flag = 0;                                           // makeFlag (:2134-2151)
     bool mateMapped = false;
     int mateScore = 0, mateLen = 1;
-    if (A.paired) {
+    if (A.V.paired) {
         const long long q = r ^ 1;
-        const uint8_t *m2;
-        const bbmap_final *f2 = source(A, q, m2);
+        const ReadRec Q = record_of<TierRule::ByRecord>(A.V, q);
+        const bbmap_final *f2 = Q.f;
+        const uint8_t *m2 = Q.m;
         const bbmap_scafrec s2 = A.scaf[q];
         mateMapped = (s2.flags & BBMAP_SCAF_MAPPED) != 0;
         const bool mateMatch = mateMapped && f2->match_len > 0;
-        mateScore = f2->mapScore; mateLen = A.reads[q].len;
+        mateScore = f2->mapScore; mateLen = A.V.reads[q].len;
         const int name2 = mateMapped ? s2.scaffold : -1;
         const int pos0m = mateMapped ? s2.pos : 0;
         // pos1_mate is NOT limited to the scaffold: `if(pos1_mate>scaflen){pos1=scaflen;}` (:207) limits pos1, by this line's scaflen
@@ -377,7 +370,7 @@ __global__ __launch_bounds__(256) void sam_size_kernel(const Args A, bbmap_samre
         if (f.ambiguous) w.tags |= BBMAP_SAM_TAG_XT;
         if (perfect) w.nm = 0;
         else if (hasMatch) w.nm = nm_count(L.m, L.ml, leftclip, len - rightclip);
-        const int other = !A.paired ? w.mapq : (mateMapped ? max(1, mateScore / max(mateLen, 1)) : 0);
+        const int other = !A.V.paired ? w.mapq : (mateMapped ? max(1, mateScore / max(mateLen, 1)) : 0);
         w.am = min(w.mapq, other);
         if ((A.flags & BBMAP_SAM_MD) && hasMatch)
             mdLen = md_walk<false>(L.m, L.ml, A.chromArr[f.chrom], A.chromArrLen[f.chrom], f.start, L.call, len, f.start - L.s.start,
@@ -389,7 +382,7 @@ __global__ __launch_bounds__(256) void sam_size_kernel(const Args A, bbmap_samre
 
 __global__ __launch_bounds__(256) void sam_emit_kernel(const Args A, bbmap_samrec *recs, const long long *offsets, uint8_t *text) {
     const long long r = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (r >= A.n) return;
+    if (r >= A.V.n) return;
     const int lane = threadIdx.x & 63;
     const int kind = (int)recs[r].cigar_off, cigarLen = recs[r].cigar_len, mdLen = recs[r].md_len;
     const long long off = offsets[r];
@@ -419,11 +412,11 @@ void fill_mapq_max(float *table, int maxLen) {
 }
 
 hipError_t launch_size(const Args &a, bbmap_samrec *recs, int *counts, hipStream_t stream) {
-    if (a.n > 0) hipLaunchKernelGGL(sam_size_kernel, dim3((unsigned)((a.n + 3) / 4)), dim3(256), 0, stream, a, recs, counts);
+    if (a.V.n > 0) hipLaunchKernelGGL(sam_size_kernel, dim3((unsigned)((a.V.n + 3) / 4)), dim3(256), 0, stream, a, recs, counts);
     return hipGetLastError();
 }
 hipError_t launch_emit(const Args &a, bbmap_samrec *recs, const long long *offsets, uint8_t *text, hipStream_t stream) {
-    if (a.n > 0) hipLaunchKernelGGL(sam_emit_kernel, dim3((unsigned)((a.n + 3) / 4)), dim3(256), 0, stream, a, recs, offsets, text);
+    if (a.V.n > 0) hipLaunchKernelGGL(sam_emit_kernel, dim3((unsigned)((a.V.n + 3) / 4)), dim3(256), 0, stream, a, recs, offsets, text);
     return hipGetLastError();
 }
 

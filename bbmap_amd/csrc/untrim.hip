@@ -9,11 +9,10 @@
 // lanes share a string's bytes, lane 0 writes the record.  Every string gets a copy of its own in the new pool.
 #include <hip/hip_runtime.h>
 
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 
 #include "mapper_ctx.h"
+#include "scan_offsets.h"
 
 using namespace bbmapper;
 
@@ -109,16 +108,9 @@ static int untrim_ctx(bbmap_ctx *c, hipStream_t stream, long long n, const int *
     Args a;
     a.fin = c->d_final; a.sites = c->d_ms; a.nsites = c->d_mcount; a.cap = c->cfg.max_sites;
     a.pool = c->d_pool; a.poolBytes = c->poolUsed; a.ids = ids; a.trims = trims; a.n = n;
-    size_t need = 0;
-    auto wide = hipcub::TransformInputIterator<long long, ToLL, const int *>((const int *)c->d_untrimCounts, ToLL());
-    BBHIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, wide, c->d_untrimOffsets, (int)(n + 1), stream));
-    BBHIP(c->untrimTmp.grow(need, 0, &stream));
     BBTRY(launch<256>(size_kernel, 64 * n, stream, a, c->d_untrimCounts));
-    BBHIP(hipMemsetAsync(c->d_untrimCounts + n, 0, 4, stream));              // n + 1 entries, so that offsets[n] is the total
-    BBHIP(hipcub::DeviceScan::ExclusiveSum(c->untrimTmp.p, need, wide, c->d_untrimOffsets, (int)(n + 1), stream));
     long long total = 0;
-    BBHIP(hipMemcpyAsync(&total, c->d_untrimOffsets + n, 8, hipMemcpyDeviceToHost, stream));
-    BBHIP(hipStreamSynchronize(stream));
+    BBTRY(scan_offsets(c->d_untrimCounts, n, c->d_untrimOffsets, c->untrimTmp, stream, &total));
     if (total / 4 > 0x7ffffff0LL) return bbfail(BBMAP_E_NOMEM, "bbmap_untrim_batch_device: the match strings exceed 8 GB; map smaller batches");
     if (!c->d_pool2 || c->pool2Units * 4 < total) {         // (the stream has just been waited for: nothing reads the old one)
         const long long units = std::max(c->poolUnits, total / 4 + 16384);
