@@ -135,7 +135,7 @@ __host__ __device__ inline bool fill_is_limited(int flags, int minScore, int row
              ((halfband < 1 || halfband * 3 > columns) && (columns > rows + min(170, rows + 20))));
 }
 
-// The band kernel's candidate rule (msa_fill_band.hip), shared with the width sort in front of it (msa_host.hip), which gives the
+// The band kernel's candidate rule (msa_fill_band.hip), shared with the width sort in front of it (msa_sort.hip), which gives the
 // candidates a list of their own: a limited fill (through the Java gate for BBMSA_FILL_LIMITED, which then runs with
 // minScore - 120) of a shape the band kernel accepts, whose slack maxQuality(rows) - minScore is at most maxSlack points.
 // `columns` is the clamped window's; the context has no band (halfband == 0).  A candidate is always a limited fill.
@@ -157,6 +157,47 @@ __device__ inline long long job_count(long long njobs, const unsigned int *njobs
     const long long n = (long long)__hip_atomic_load(njobs_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return n < njobs ? n : njobs;
 }
+
+// The words of a context's d_counters, zeroed in front of every launch.  The host hands them out by these names; the band kernel and
+// the wavefront kernel write theirs relative to a base pointer (NarrowParams::stats, FillParams::unl_stats), whose offsets have names
+// of their own below.  The legacy service's private block (msa_legacy.hip) has the first three.
+constexpr int kCounterWords = 32, kCounterBytes = kCounterWords * 4;
+enum CounterSlot {
+    CNT_FAST_QUEUE = 0,         // first pass's work queue (9PacBio: the strip kernel's)
+    CNT_SLOW_COUNT = 1,         // jobs the first pass handed on (9PacBio: the strip kernel to the generic kernel)
+    CNT_GENERIC_QUEUE = 2,
+    CNT_BAND_QUEUE = 3,
+    CNT_LIST_COUNT = 4,         // length of the first pass's list: the band kernel appends to it, the width sort starts it
+    CNT_BAND_DONE = 5,          // jobs the band kernel finished
+    CNT_BAND_HANDED = 6,        // candidates that left the band
+    CNT_WIDE_SLOW_COUNT = 7,    // jobs the wide pass handed on
+    CNT_WIDE_QUEUE = 8,
+    CNT_UNL_RAN_UNL = 9,        // unlimited fills the prune-free loop ran
+    CNT_UNL_RAN_GENERAL = 10,   // unlimited fills the general loop ran
+    CNT_UNL_LIST_COUNT = 11,    // length of a width-sorted launch's list of unlimited fills
+    CNT_UNL_QUEUE = 12,         // the unlimited build's work queue
+    CNT_UNL_STEPS = 13,         // wavefront steps (columns + lanes in use - 1) of the unlimited fills
+    CNT_ALL_STEPS = 14,         // ... of all fills
+    CNT_CAND_COUNT = 15,        // length of a width-sorted launch's list of band candidates
+    CNT_SORTED_COUNT = 16,      // length of its general list as the sort left it (before the band kernel's hand-overs)
+    CNT_WAVE_STEPS = 17,        // steps the wavefronts ran (a wavefront steps as its longest job)
+};
+constexpr int CNT_BAND_STATS = 5, CNT_UNL_STATS = 9;               // what NarrowParams::stats / FillParams::unl_stats point at
+enum BandStat { BAND_STAT_DONE = 0, BAND_STAT_HANDED = 1 };
+enum UnlStat { UNL_STAT_RAN_UNL = 0, UNL_STAT_RAN_GENERAL = 1, UNL_STAT_STEPS = 4, UNL_STAT_ALL_STEPS = 5, UNL_STAT_WAVE_STEPS = 8 };
+static_assert(CNT_BAND_DONE == CNT_BAND_STATS + BAND_STAT_DONE && CNT_BAND_HANDED == CNT_BAND_STATS + BAND_STAT_HANDED, "band kernel's counters");
+static_assert(CNT_UNL_RAN_UNL == CNT_UNL_STATS + UNL_STAT_RAN_UNL && CNT_UNL_RAN_GENERAL == CNT_UNL_STATS + UNL_STAT_RAN_GENERAL &&
+              CNT_UNL_STEPS == CNT_UNL_STATS + UNL_STAT_STEPS && CNT_ALL_STEPS == CNT_UNL_STATS + UNL_STAT_ALL_STEPS &&
+              CNT_WAVE_STEPS == CNT_UNL_STATS + UNL_STAT_WAVE_STEPS, "wavefront kernel's counters");
+constexpr bool counter_slots_distinct() {         // every name a word of its own, inside the block
+    constexpr int all[] = {CNT_FAST_QUEUE, CNT_SLOW_COUNT, CNT_GENERIC_QUEUE, CNT_BAND_QUEUE, CNT_LIST_COUNT, CNT_BAND_DONE, CNT_BAND_HANDED,
+                           CNT_WIDE_SLOW_COUNT, CNT_WIDE_QUEUE, CNT_UNL_RAN_UNL, CNT_UNL_RAN_GENERAL, CNT_UNL_LIST_COUNT, CNT_UNL_QUEUE,
+                           CNT_UNL_STEPS, CNT_ALL_STEPS, CNT_CAND_COUNT, CNT_SORTED_COUNT, CNT_WAVE_STEPS};
+    unsigned seen = 0;
+    for (int s : all) { if (s < 0 || s >= kCounterWords || ((seen >> s) & 1u)) return false; seen |= 1u << s; }
+    return true;
+}
+static_assert(counter_slots_distinct(), "two counter names share a word, or one lies outside d_counters");
 
 struct FillParams {
     const bbmsa_job *jobs;
@@ -183,9 +224,7 @@ struct FillParams {
     int maxRows, maxColumns;      // context limits (MSA(maxRows_, maxColumns_))
     int bandwidth;
     float bandwidthRatio;
-    unsigned int *unl_stats;      // [0] jobs that ran in the unlimited build, [1] unlimited jobs that ran in the general build,
-                                  // [4] / [5] wavefront steps (columns + lanes in use - 1) of the unlimited jobs / of all jobs,
-                                  // [8] steps the wavefronts ran (each as many as its longest job); NULL: not counted
+    unsigned int *unl_stats;      // bbmsa_last_unlimited's counters, indexed by UnlStat; NULL: not counted
     // matrix-materialising mode (the legacy per-call JNI shape, msa_legacy.hip; kernels instantiated with MAT only): job j's three
     // score planes go to planes + plane_off[j], each rows x columns ints (state-major; rows 1..rows, columns 1..columns of the matrix), its
     // vertLimit[0..rows] / horizLimit[0..columns] to limits + limits_off[j] (rows + 1 ints, then columns + 1)
@@ -208,7 +247,7 @@ struct NarrowParams {
     unsigned int *queue;          // work-queue head (zeroed before launch)
     int *fast_list;               // jobs left to the wavefront kernel
     unsigned int *fast_count;
-    unsigned int *stats;          // [0] jobs finished here, [1] candidates that left the band (handed on)
+    unsigned int *stats;          // indexed by BandStat: jobs finished here, candidates that left the band (handed on)
     int match_stride;
     int maxRows, maxColumns;
     int bandwidth;

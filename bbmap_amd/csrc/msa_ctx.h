@@ -1,20 +1,22 @@
-// Host-side context of the MultiStateAligner11ts entry points (msa_host.hip, msa_gapped.hip).
+// Host-side context of the MultiStateAligner11ts entry points (msa_host.hip, msa_sort.hip, msa_gapped.hip, msa_legacy.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "bbmap_amd.h"
 #include "host_common.h"
+#include "msa_route.h"
 
 struct bbmsa_ctx {
     bbmsa_config cfg = {};
     int device = 0;
     int numCUs = 0;
-    int scheme = 0;             // BBMSA_SCHEME_*
+    RouteSwitches sw;           // scheme, band, and every switch the route of a launch depends on (msa_route.h)
+    Route last;                 // the last launch's route, for the read-back entries (bbmsa_last_route, bbmsa_last_counts, ...)
     // fast kernel geometry
     int G = 0, R = 0, fastCols = 0, tmpBytes = 0, blocks = 0, ldsBytes = 0, tableLen = 0, wideTableLen = 0;
     long long dirSlotDwords = 0;
     unsigned int *d_dir = nullptr;
-    unsigned int *d_counters = nullptr;   // 32 words; [0]=fast queue, [1]=slow count, [2]=generic queue, ... (bbmsa_align_impl has the list)
+    unsigned int *d_counters = nullptr;   // bbmsa::kCounterWords words, named by bbmsa::CounterSlot (msa_common.h)
     DevBuf slowList;            // ints: the jobs the wavefront kernel hands on; as long as the largest launch so far
     // generic kernel
     int genThreads = 0;
@@ -29,20 +31,8 @@ struct bbmsa_ctx {
     // band kernel (msa_fill_band.hip): a job over 8 lanes, 32 diagonals, in front of the first pass.  Its switches and counters keep the
     // name of its predecessor, the one-job-per-lane narrow-window kernel.
     int narrowBlocks = 0, narrowSlack = 0;     // 0 blocks = disabled
-    bool narrowOff = false;            // switched off by the caller for launches whose jobs it cannot take (bbmsa_use_narrow)
-    bool narrowUsed = false;           // whether the last launch ran it
-    bool lastSorted = false, lastLatency = false, lastIndirect = false;   // the last launch's route (bbmsa_last_route): width-sorted first pass,
-                                                                          // latency route, job count read on the device
-    // widest windows first (bbmsa_sort_by_width): two jobs share a wavefront and step together, so a 600-column job beside a
-    // 200-column one idles half the wave for 400 steps; in width order neighbours are alike, and the longest jobs do not end up last
-    bool sortByWidth = false;
-    bool sortWithBand = false;         // sort also the launches that run the band kernel (bbmsa_sort_with_band): the candidates get a list of their own
-    bool wideUnlimited = false;        // the 64-lane launches run unlimited fills in the prune-free loop (bbmsa_set_wide_unlimited)
-    long long lastJobs = 0;            // jobs of the last launch (bbmsa_debug_sorted_lists)
-    bool unlimitedLoop = true;         // a width-sorted launch runs its unlimited fills in the wavefront kernel's build for them (BBMSA_UNLIMITED_LOOP=0: no)
     bool unlimitedStats = false;       // the kernels count for bbmsa_last_unlimited (BBMSA_UNLIMITED_STATS=1 or BBMAP_DP_COUNTS at bbmsa_create)
-    unsigned int *d_widthHist = nullptr;
-    long long latencyJobs = 0;         // launches with at most this many jobs go straight to the 64-lane geometry (bbmsa_set_latency_jobs)
+    unsigned int *d_widthHist = nullptr;       // the width sort's buckets (msa_sort.hip), allocated by the first sorted launch
     int bandRows = 0, bandLds = 0;     // longest read the band kernel takes, its LDS bytes per block
     unsigned int *d_bandDir = nullptr; // its records: per resident wave (bandRows + 1) x 2 jobs x 64 lanes dwords
     DevBuf fastList;            // ints: the wavefront kernel's job list when the band kernel or the width sort writes one
@@ -50,7 +40,6 @@ struct bbmsa_ctx {
     DevBuf gref, gaux, gjobs;
     hipEvent_t ev[4] = {};  // start, after wavefront kernel, after generic kernel, after band kernel
     bool timed = false;
-    bool banded = false;
     bool legacyOnly = false;    // created with BBMSA_LEGACY_ONLY: bbmsa_fill_submit / _collect / _packed only
     struct bbmsa_legacy *legacy = nullptr;   // the per-call service of such a context (msa_legacy.hip)
     // strip-tiled wavefront kernel of the 9PacBio scheme (msa_fill_strip.hip)
@@ -59,9 +48,26 @@ struct bbmsa_ctx {
     int *d_stripBoundary = nullptr;
     uint8_t *d_stripTmp = nullptr;
     // pipelined form of the strip kernel for launches with few jobs: pipeK wavefronts per job, pipeSlots jobs at a time
-    int pipeK = 0, pipeSlots = 0, pipeJobsMax = 0;
+    int pipeK = 0, pipeSlots = 0;
     int *d_pipeBoundary = nullptr, *d_pipeSync = nullptr;
 };
+
+// the caller's arguments of one launch
+struct JobBatch {
+    int64_t n_jobs; const uint32_t *n_jobs_dev; const bbmsa_job *jobs; const uint8_t *reads, *refs; bbmsa_result *results; uint8_t *match;
+    int32_t match_stride;
+};
+// what every kernel's parameter struct takes from the batch and the context
+template <class P> void set_batch(P &p, const bbmsa_ctx *c, const JobBatch &B) {
+    p.jobs = B.jobs; p.reads = B.reads; p.refs = B.refs; p.results = B.results; p.match = B.match;
+    p.njobs = B.n_jobs; p.njobs_dev = B.n_jobs_dev; p.match_stride = B.match_stride;
+    p.maxRows = c->cfg.maxRows; p.maxColumns = c->cfg.maxColumns; p.bandwidth = c->cfg.bandwidth; p.bandwidthRatio = c->cfg.bandwidthRatio;
+}
+
+// msa_sort.hip: the width sort in front of a sorted launch's first pass.  Writes the three thirds of c->fastList (each n_jobs ints:
+// general, unlimited, band candidates) and the lists' lengths (CNT_LIST_COUNT and CNT_SORTED_COUNT, CNT_UNL_LIST_COUNT,
+// CNT_CAND_COUNT).  band: the launch runs the band kernel, so its candidates get the third list.
+int bbmsa_width_sort(bbmsa_ctx *c, hipStream_t stream, const bbmsa_job *jobs, int64_t n_jobs, bool band);
 
 // msa_host.hip.  n_jobs_dev == NULL: n_jobs jobs.  Otherwise n_jobs is the capacity of the buffers and the kernels read the real
 // count from *n_jobs_dev when they run.

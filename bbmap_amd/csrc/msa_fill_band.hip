@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256, BBMSA_BAND_OCC) void msa_fill_band_kernel(cons
     const int RB = (p.bandRows + 4 + 3) & ~3, FB = (p.bandRows + B + 4 + 3) & ~3;      // bytes per job: read, reference
     uint8_t *jobLds = reinterpret_cast<uint8_t *>(lds + lds_table_ints(TL)) + (long long)wave * JOBS * (RB + FB);
     unsigned *dir = p.dirbuf32 + ((long long)blockIdx.x * 4 + wave) * (long long)(p.bandRows + 1) * 128;   // [(row * 2 + slot) * 64 + lane]
-    // with a list (the width sort's candidates, msa_host.hip) the queue runs over the list's entries; without one over every job
+    // with a list (the width sort's candidates, msa_sort.hip) the queue runs over the list's entries; without one over every job
     const long long NJ = p.list ? (long long)ld_coherent(p.list_count) : job_count(p.njobs, p.njobs_dev);
     unsigned nDone = 0, nLeft = 0;
 
@@ -450,7 +450,7 @@ __global__ __launch_bounds__(256, BBMSA_BAND_OCC) void msa_fill_band_kernel(cons
     }
     if (p.stats) {
         for (int d = 32; d >= 1; d >>= 1) { nDone += __shfl_xor(nDone, d, 64); nLeft += __shfl_xor(nLeft, d, 64); }
-        if (lane == 0) { if (nDone) atomicAdd(&p.stats[0], nDone); if (nLeft) atomicAdd(&p.stats[1], nLeft); }
+        if (lane == 0) { if (nDone) atomicAdd(&p.stats[BAND_STAT_DONE], nDone); if (nLeft) atomicAdd(&p.stats[BAND_STAT_HANDED], nLeft); }
     }
 }
 

@@ -275,11 +275,11 @@ __global__ __launch_bounds__(256, (UNL == 2 && BBMSA_MIN_WAVES(R) > 2) ? 2 : BBM
         const int nl = (rows + R - 1) / R;                               // lanes in use
         int steps = run ? columns + nl - 1 : 0;
         if (!MAT && p.unl_stats && gl == 0 && run) {                     // bbmsa_last_unlimited
-            if (!limited) { atomicAdd(p.unl_stats + (UNL != 0 ? 0 : 1), 1u); atomicAdd(p.unl_stats + 4, (unsigned)steps); }
-            atomicAdd(p.unl_stats + 5, (unsigned)steps);
+            if (!limited) { atomicAdd(p.unl_stats + (UNL != 0 ? UNL_STAT_RAN_UNL : UNL_STAT_RAN_GENERAL), 1u); atomicAdd(p.unl_stats + UNL_STAT_STEPS, (unsigned)steps); }
+            atomicAdd(p.unl_stats + UNL_STAT_ALL_STEPS, (unsigned)steps);
         }
         for (int d = 32; d >= 1; d >>= 1) steps = max(steps, __shfl_xor(steps, d, 64));
-        if (!MAT && p.unl_stats && lane == 0 && steps > 0) atomicAdd(p.unl_stats + 8, (unsigned)steps);      // what the wavefront runs: its longest job's steps
+        if (!MAT && p.unl_stats && lane == 0 && steps > 0) atomicAdd(p.unl_stats + UNL_STAT_WAVE_STEPS, (unsigned)steps);      // what the wavefront runs: its longest job's steps
 
         int pM[R], pD[R], pI[R];         // my rows' cells at the previous column
         int minGood[R], maxGood[R];      // first / last good column of each row (-1 / -2 = none)

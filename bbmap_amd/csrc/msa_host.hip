@@ -26,98 +26,12 @@ int strip_pipe_sync_ints(int K);
 const void *fast_kernel_for(int R, bool banded);
 const void *fast_kernel_unl_for(int R);
 const void *fast_kernel_both_for(int R);                       // both step loops, chosen per job (64 lanes per job only); null: no such build
-constexpr int kCounterWords = 32, kCounterBytes = kCounterWords * 4;      // d_counters of every context (bbmsa_align_impl has the list)
 template <class S> __global__ void msa_fill_generic_kernel(const GenericParams p);
 const void *band_kernel();                                     // msa_fill_band.hip
 int band_lds_bytes(int tableLen, int bandRows);
 }  // namespace bbmsa
 
-namespace bbmsa {
-// The width sort in front of the first pass: a counting sort of the launch's jobs by (class, columns / 8 descending) into one list
-// per class.  Classes: unlimited fills (the wavefront kernel's prune-free build takes them), band candidates (msa_fill_band.hip; only
-// when the launch runs the band kernel over a list, bbmsa_sort_with_band), everything else (the general build).
-constexpr int WIDTH_PER_CLASS = 512;           // columns / 8.  Only 11ts contexts sort, and bbmsa_create refuses one of more than 4,096
-                                               // columns, so only a window of exactly 4,096 shares its bucket (with 4,088..4,095)
-constexpr int WIDTH_CLASSES = 3;
-constexpr int WIDTH_BUCKETS = WIDTH_CLASSES * WIDTH_PER_CLASS;
-enum { CLASS_UNLIMITED = 0, CLASS_CANDIDATE = 1, CLASS_GENERAL = 2 };
-constexpr int SORT_THREADS = 256, SORT_JOBS_PER_THREAD = 4;     // a block of the histogram / scatter kernels takes 1,024 jobs
-struct SortKey { int maxRows, maxColumns, bandwidth; float bandwidthRatio; int byKind, band, bandRows, maxSlack; };
-// byKind: the unlimited fills get their own list (else they are general jobs); band: so do the band kernel's candidates, by the
-// kernel's own rule (band_is_candidate, msa_common.h).
-__device__ inline int job_width_bucket(const bbmsa_job &t, const SortKey k) {
-    int a = t.refStartLoc, b = t.refEndLoc;
-    if (t.flags & BBMSA_CLAMP_WINDOW) { a = max(0, a); b = min(t.ref_len - 1, b); if (b - a >= k.maxColumns) b = min(t.ref_len - 1, a + k.maxColumns - 1); }
-    const int cols = max(0, b - a + 1);
-    int cls = CLASS_GENERAL;
-    if (k.band && band_is_candidate(t.flags, t.minScore, t.read_len, b - a + 1, k.maxRows, k.maxColumns, k.bandRows, k.maxSlack)) cls = CLASS_CANDIDATE;
-    else if (k.byKind && !fill_is_limited(t.flags, t.minScore, t.read_len, b - a + 1, fill_halfband(t.read_len, b - a + 1, k.bandwidth, k.bandwidthRatio))) cls = CLASS_UNLIMITED;
-    constexpr int W = WIDTH_PER_CLASS;
-    return cls * W + W - 1 - min(W - 1, cols >> 3);            // bucket 0 of a class = its widest windows
-}
-// Both kernels count in an LDS copy of the histogram first: a launch's windows crowd into a few buckets (half of the plain context's
-// fills have one width), and one global atomic per job on those few words is what the kernels then wait for.  A block adds each bucket
-// it met to the global word once.
-__global__ __launch_bounds__(SORT_THREADS) void width_hist_kernel(const bbmsa_job *jobs, long long n, SortKey key, unsigned *hist) {
-    __shared__ unsigned s[WIDTH_BUCKETS];
-    for (int i = threadIdx.x; i < WIDTH_BUCKETS; i += SORT_THREADS) s[i] = 0;
-    __syncthreads();
-    const long long base = (long long)blockIdx.x * (SORT_THREADS * SORT_JOBS_PER_THREAD) + threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < SORT_JOBS_PER_THREAD; k++) {
-        const long long i = base + (long long)k * SORT_THREADS;
-        if (i < n) atomicAdd(&s[job_width_bucket(jobs[i], key)], 1u);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < WIDTH_BUCKETS; i += SORT_THREADS) { const unsigned v = s[i]; if (v) atomicAdd(&hist[i], v); }
-}
-// one block of WIDTH_PER_CLASS threads: exclusive prefix sums in place, each class's from 0 (the scatter's cursors), and the lengths of
-// the three lists.  The general list's length goes to two words: `listCount`, which the band kernel then appends its hand-overs
-// through, and `sortedCount`, which keeps it.
-__global__ void width_scan_kernel(unsigned *hist, unsigned *listCount, unsigned *sortedCount, unsigned *unlCount, unsigned *candCount) {
-    __shared__ unsigned s[WIDTH_PER_CLASS];
-    const int t = threadIdx.x;
-    for (int cls = 0; cls < WIDTH_CLASSES; cls++) {
-        const unsigned own = hist[cls * WIDTH_PER_CLASS + t];
-        s[t] = own;
-        __syncthreads();
-        for (int d = 1; d < WIDTH_PER_CLASS; d <<= 1) { const unsigned v = t >= d ? s[t - d] : 0u; __syncthreads(); s[t] += v; __syncthreads(); }
-        hist[cls * WIDTH_PER_CLASS + t] = s[t] - own;
-        if (t == WIDTH_PER_CLASS - 1) {
-            if (cls == CLASS_UNLIMITED) *unlCount = s[t];
-            else if (cls == CLASS_CANDIDATE) *candCount = s[t];
-            else { *listCount = s[t]; *sortedCount = s[t]; }
-        }
-        __syncthreads();
-    }
-}
-// every list has room for all n jobs; a job's place is its bucket's cursor + the block's share of the bucket + its rank in the block
-__global__ __launch_bounds__(SORT_THREADS) void width_scatter_kernel(const bbmsa_job *jobs, long long n, SortKey key, unsigned *cursor, int *list, int *unlList, int *candList) {
-    __shared__ unsigned s[WIDTH_BUCKETS];
-    for (int i = threadIdx.x; i < WIDTH_BUCKETS; i += SORT_THREADS) s[i] = 0;
-    __syncthreads();
-    const long long base = (long long)blockIdx.x * (SORT_THREADS * SORT_JOBS_PER_THREAD) + threadIdx.x;
-    int bucket[SORT_JOBS_PER_THREAD]; unsigned rank[SORT_JOBS_PER_THREAD];
-#pragma unroll
-    for (int k = 0; k < SORT_JOBS_PER_THREAD; k++) {
-        const long long i = base + (long long)k * SORT_THREADS;
-        bucket[k] = -1; rank[k] = 0;
-        if (i < n) { bucket[k] = job_width_bucket(jobs[i], key); rank[k] = atomicAdd(&s[bucket[k]], 1u); }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < WIDTH_BUCKETS; i += SORT_THREADS) { const unsigned v = s[i]; if (v) s[i] = atomicAdd(&cursor[i], v); }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < SORT_JOBS_PER_THREAD; k++) {
-        if (bucket[k] < 0) continue;
-        const long long i = base + (long long)k * SORT_THREADS;
-        const unsigned pos = s[bucket[k]] + rank[k];
-        if ((long long)pos >= n) continue;                      // (cannot happen: a class holds at most n jobs)
-        const int cls = bucket[k] / WIDTH_PER_CLASS;
-        (cls == CLASS_UNLIMITED ? unlList : (cls == CLASS_CANDIDATE ? candList : list))[pos] = (int)i;
-    }
-}
-}  // namespace bbmsa
+static int clamp_occupancy(int per, int most) { return per < 1 ? 1 : (per > most ? most : per); }
 
 // The wavefront kernel's second geometry: 64 lanes per job, one job per 64-thread block, an LDS column buffer as wide as maxColumns.
 // It takes the windows wider than the first pass's buffer (the wide pass) and, at the caller's request, whole launches that hold
@@ -129,121 +43,94 @@ static int setup_wide_pass(bbmsa_ctx *c) {
     c->wideTmpBytes = ((64 * c->wideR + c->wideCols + 8) + 3) & ~3;
     const int perJob = bbmsa::lds_job_ints(c->wideCols, c->wideTmpBytes);
     c->wideLdsBytes = (bbmsa::lds_table_ints(c->wideTableLen) + perJob) * 4;
-    const void *wfn = bbmsa::fast_kernel_for(c->wideR, c->banded);
+    const void *wfn = bbmsa::fast_kernel_for(c->wideR, c->sw.banded);
     if (wfn && c->wideLdsBytes <= 160 * 1024) {
         if (c->wideLdsBytes > 64 * 1024) BBHIP(hipFuncSetAttribute(wfn, hipFuncAttributeMaxDynamicSharedMemorySize, c->wideLdsBytes));
-        const void *bfn = c->banded ? nullptr : bbmsa::fast_kernel_both_for(c->wideR);      // (bbmsa_set_wide_unlimited)
+        const void *bfn = c->sw.banded ? nullptr : bbmsa::fast_kernel_both_for(c->wideR);      // (bbmsa_set_wide_unlimited)
         if (bfn && c->wideLdsBytes > 64 * 1024) BBHIP(hipFuncSetAttribute(bfn, hipFuncAttributeMaxDynamicSharedMemorySize, c->wideLdsBytes));
         int per = 0;
         BBHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, wfn, 64, c->wideLdsBytes));
-        if (per < 1) per = 1;
-        if (per > 8) per = 8;
+        per = clamp_occupancy(per, 8);
         const long long slotDwords = (long long)(((c->wideCols + 64 - 1) >> 3) + 1) * c->wideR * 64;
         BBHIP(hipMalloc(&c->d_wideDir, (size_t)((long long)c->numCUs * per * slotDwords * 4)));
         c->wideDirSlotDwords = slotDwords;
         c->wideBlocks = c->numCUs * per;
+        c->sw.widePresent = true;
     }
     return BBMAP_OK;
 }
 
-extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
-    if (!cfg || !out) return bbfail(BBMAP_E_ARG, "bbmsa_create: null argument");
-    *out = nullptr;
-    const int scheme = cfg->reserved[2] & 0xFF;
-    const bool legacyOnly = (cfg->reserved[2] & BBMSA_LEGACY_ONLY) != 0;
-    if (scheme != BBMSA_SCHEME_11TS && scheme != BBMSA_SCHEME_9PACBIO) return bbfail(BBMAP_E_ARG, "bbmsa_create: unknown scoring scheme");
-    if (scheme == BBMSA_SCHEME_11TS && (cfg->maxRows < 1 || cfg->maxRows > 640 || cfg->maxColumns < 1 || cfg->maxColumns > 4096))
-        return bbfail(BBMAP_E_ARG, "bbmsa_create: maxRows must be 1..640 and maxColumns 1..4096");
-    if (scheme == BBMSA_SCHEME_9PACBIO && (cfg->maxRows < 1 || cfg->maxRows > 6100 || cfg->maxColumns < 1 || cfg->maxColumns > 8192))
-        return bbfail(BBMAP_E_ARG, "bbmsa_create: the PacBio scheme takes maxRows 1..6100 and maxColumns 1..8192");
-    hipDeviceProp_t prop;
-    BBTRY(bb_use_gfx950("bbmsa_create", cfg->device, &prop));
+// The generic kernel's scratch, one slot per thread (three score planes and the two limit arrays).  Threads: as many as the matrix
+// budget allows (BBMSA_GENERIC_SCRATCH_MB, `defaultMB` without it), whole wavefronts, at most `mostThreads`.
+static int generic_threads(const bbmsa_config &cfg, int defaultMB, long long mostThreads, int *out) {
+    const long long perThread = 3LL * (cfg.maxRows + 1) * (cfg.maxColumns + 2) * 4;
+    long long threads = ((long long)env_int("BBMSA_GENERIC_SCRATCH_MB", defaultMB) << 20) / perThread;
+    if (threads > mostThreads) threads = mostThreads;
+    threads = (threads / 64) * 64;
+    if (threads < 64) return bbfail(BBMAP_E_NOMEM, "bbmsa_create: BBMSA_GENERIC_SCRATCH_MB cannot hold one wavefront of scratch matrices for this maxRows x maxColumns");
+    *out = (int)threads;
+    return BBMAP_OK;
+}
+static int alloc_generic_scratch(bbmsa_ctx *c, int threads) {
+    c->genThreads = threads;
+    BBHIP(hipMalloc(&c->d_matrix, (size_t)threads * 3 * (size_t)(c->cfg.maxRows + 1) * (size_t)(c->cfg.maxColumns + 2) * 4));
+    BBHIP(hipMalloc(&c->d_limits, (size_t)threads * (size_t)(c->cfg.maxRows + c->cfg.maxColumns + 4) * 4));
+    return BBMAP_OK;
+}
 
-    bbmsa_ctx *c = new (std::nothrow) bbmsa_ctx();
-    if (!c) return bbfail(BBMAP_E_NOMEM, "bbmsa_create: out of host memory");
-    c->cfg = *cfg;
-    c->device = cfg->device;
-    c->numCUs = prop.multiProcessorCount;
+// a context for bbmsa_fill_packed only (the per-call JNI shape): one scratch matrix, no batch buffers
+static int create_legacy_only(bbmsa_ctx *c) {
+    BBTRY(alloc_generic_scratch(c, 1));
+    return bbmsa_legacy_create(c);
+}
 
-    c->scheme = scheme;
-    c->legacyOnly = legacyOnly;
-    // every failure below leaves through bbmsa_destroy(c): nothing allocated so far is leaked
-    struct Guard { bbmsa_ctx *c; ~Guard() { if (c) bbmsa_destroy(c); } } guard{c};
-    if (legacyOnly) {
-        // a context for bbmsa_fill_packed only (the per-call JNI shape): one scratch matrix, no batch buffers
-        BBHIP(hipMalloc(&c->d_counters, bbmsa::kCounterBytes));
-        BBHIP(hipMemset(c->d_counters, 0, bbmsa::kCounterBytes));
-        const long long planeInts = (long long)(cfg->maxRows + 1) * (cfg->maxColumns + 2);
-        c->genThreads = 1;
-        BBHIP(hipMalloc(&c->d_matrix, (size_t)(3 * planeInts * 4)));
-        BBHIP(hipMalloc(&c->d_limits, (size_t)((cfg->maxRows + cfg->maxColumns + 4) * 4)));
-        for (int i = 0; i < 4; i++) BBHIP(hipEventCreate(&c->ev[i]));
-        BBTRY(bbmsa_legacy_create(c));
-        guard.c = nullptr;
-        *out = c;
-        return BBMAP_OK;
-    }
-    if (scheme != BBMSA_SCHEME_11TS) {
-        // 9PacBio: the strip-tiled wavefront kernel (msa_fill_strip.hip), one alignment per wavefront; banded fills and windows
-        // narrower than the read are handed to the one-job-per-thread kernel
-        BBHIP(hipMalloc(&c->d_counters, bbmsa::kCounterBytes));
-        BBHIP(hipMemset(c->d_counters, 0, bbmsa::kCounterBytes));
-        const long long planeInts = (long long)(cfg->maxRows + 1) * (cfg->maxColumns + 2);
-        const long long perThread = 3 * planeInts * 4;
-        long long budget = (long long)env_int("BBMSA_GENERIC_SCRATCH_MB", 40960) << 20;   // 6019 x 7600 (mapPacBio) needs 35 GB for one wavefront of matrices
-        long long threads = budget / perThread;
-        if (threads > 4096) threads = 4096;
-        threads = (threads / 64) * 64;
-        if (threads < 64) return bbfail(BBMAP_E_NOMEM, "bbmsa_create: BBMSA_GENERIC_SCRATCH_MB cannot hold one wavefront of scratch matrices for this maxRows x maxColumns");
-        c->genThreads = (int)threads;
-        BBHIP(hipMalloc(&c->d_matrix, (size_t)(threads * perThread)));
-        BBHIP(hipMalloc(&c->d_limits, (size_t)(threads * (cfg->maxRows + cfg->maxColumns + 4) * 4)));
-        {
-            const int R = bbmsa::strip_rows_per_lane();
-            c->stripLds = (cfg->maxColumns + 2) * 4 + ((cfg->maxColumns + 2 + 7) & ~7);     // horizLimit ints + reference bytes
-            const void *kfn = bbmsa::strip_kernel_pacbio();
-            if (c->stripLds > 64 * 1024) BBHIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, c->stripLds));
-            // Resident wavefronts per CU, from the LDS a wavefront takes (160 KB per CU; the kernel holds ~128 VGPRs, up to 4 waves per
-            // SIMD, so LDS is what limits it).  Not asked of hipOccupancyMaxActiveBlocksPerMultiprocessor: that query was seen to fail with
-            // hipErrorUnknown depending on what the process had done before (after the CPU oracle had run in it), for reasons the
-            // runtime's log does not give; nothing here depends on the exact figure (the pipelined form no longer assumes co-residency).
-            int per = (160 * 1024) / (c->stripLds + 512);
-            if (per < 1) per = 1;
-            if (per > 8) per = 8;
-            c->stripBlocks = c->numCUs * per;
-            const int strips = (cfg->maxRows + 64 * R - 1) / (64 * R);
-            c->stripDwords = (long long)(((cfg->maxColumns + 64) >> 3) + 1) * R * 64;
-            c->stripSlotDwords = c->stripDwords * strips;
-            // traceback records: 4 bits per cell of every resident job (23 MB per 6,000 x 7,600 job)
-            long long dirBudget = (long long)env_int("BBMSA_STRIP_DIR_MB", 32768) << 20;
-            while (c->stripBlocks > c->numCUs && (long long)c->stripBlocks * c->stripSlotDwords * 4 > dirBudget) c->stripBlocks -= c->numCUs;
-            while (c->stripBlocks > 1 && (long long)c->stripBlocks * c->stripSlotDwords * 4 > dirBudget) c->stripBlocks /= 2;
-            {   // the pipelined form for launches with few jobs: the strips of one job in `strips` wavefronts
-                const void *kp = bbmsa::strip_kernel_pacbio_pipelined();
-                if (c->stripLds > 64 * 1024) BBHIP(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, c->stripLds));
-                int perP = (160 * 1024) / (c->stripLds + 512);
-                if (perP < 1) perP = 1;
-                if (perP > 8) perP = 8;
-                c->pipeK = strips;
-                c->pipeSlots = (c->numCUs * perP) / strips;                  // every wavefront of every slot is resident: the hand-shakes need it
-                if (c->pipeSlots > c->stripBlocks) c->pipeSlots = c->stripBlocks;
-                if (c->pipeSlots > 256) c->pipeSlots = 256;
-                c->pipeJobsMax = env_int("BBMSA_STRIP_PIPE_JOBS", 512);      // launches with at most this many jobs take the pipelined form
-                if (strips < 2 || c->pipeSlots < 1) c->pipeJobsMax = 0;
-                if (c->pipeJobsMax > 0) {
-                    BBHIP(hipMalloc(&c->d_pipeBoundary, (size_t)((long long)c->pipeSlots * strips * 3 * (cfg->maxColumns + 2) * 4)));
-                    BBHIP(hipMalloc(&c->d_pipeSync, (size_t)((long long)c->pipeSlots * bbmsa::strip_pipe_sync_ints(strips) * 4)));
-                }
-            }
-            BBHIP(hipMalloc(&c->d_dir, (size_t)((long long)c->stripBlocks * c->stripSlotDwords * 4)));
-            BBHIP(hipMalloc(&c->d_stripBoundary, (size_t)((long long)c->stripBlocks * 6 * (cfg->maxColumns + 2) * 4)));
-            BBHIP(hipMalloc(&c->d_stripTmp, (size_t)((long long)c->stripBlocks * (cfg->maxRows + cfg->maxColumns + 8))));
+// 9PacBio: the strip-tiled wavefront kernel (msa_fill_strip.hip), one alignment per wavefront; banded fills and windows narrower
+// than the read are handed to the one-job-per-thread kernel
+static int create_pacbio(bbmsa_ctx *c) {
+    const bbmsa_config *cfg = &c->cfg;
+    int threads = 0;
+    BBTRY(generic_threads(*cfg, 40960, 4096, &threads));          // 6019 x 7600 (mapPacBio) needs 35 GB for one wavefront of matrices
+    BBTRY(alloc_generic_scratch(c, threads));
+    const int R = bbmsa::strip_rows_per_lane();
+    c->stripLds = (cfg->maxColumns + 2) * 4 + ((cfg->maxColumns + 2 + 7) & ~7);     // horizLimit ints + reference bytes
+    const void *kfn = bbmsa::strip_kernel_pacbio();
+    if (c->stripLds > 64 * 1024) BBHIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, c->stripLds));
+    // Resident wavefronts per CU, from the LDS a wavefront takes (160 KB per CU; the kernel holds ~128 VGPRs, up to 4 waves per
+    // SIMD, so LDS is what limits it).  Not asked of hipOccupancyMaxActiveBlocksPerMultiprocessor: that query was seen to fail with
+    // hipErrorUnknown depending on what the process had done before (after the CPU oracle had run in it), for reasons the
+    // runtime's log does not give; nothing here depends on the exact figure (the pipelined form no longer assumes co-residency).
+    const int per = clamp_occupancy((160 * 1024) / (c->stripLds + 512), 8);
+    c->stripBlocks = c->numCUs * per;
+    const int strips = (cfg->maxRows + 64 * R - 1) / (64 * R);
+    c->stripDwords = (long long)(((cfg->maxColumns + 64) >> 3) + 1) * R * 64;
+    c->stripSlotDwords = c->stripDwords * strips;
+    // traceback records: 4 bits per cell of every resident job (23 MB per 6,000 x 7,600 job)
+    long long dirBudget = (long long)env_int("BBMSA_STRIP_DIR_MB", 32768) << 20;
+    while (c->stripBlocks > c->numCUs && (long long)c->stripBlocks * c->stripSlotDwords * 4 > dirBudget) c->stripBlocks -= c->numCUs;
+    while (c->stripBlocks > 1 && (long long)c->stripBlocks * c->stripSlotDwords * 4 > dirBudget) c->stripBlocks /= 2;
+    {   // the pipelined form for launches with few jobs: the strips of one job in `strips` wavefronts
+        const void *kp = bbmsa::strip_kernel_pacbio_pipelined();
+        if (c->stripLds > 64 * 1024) BBHIP(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, c->stripLds));
+        c->pipeK = strips;
+        c->pipeSlots = (c->numCUs * per) / strips;                  // every wavefront of every slot is resident: the hand-shakes need it
+        if (c->pipeSlots > c->stripBlocks) c->pipeSlots = c->stripBlocks;
+        if (c->pipeSlots > 256) c->pipeSlots = 256;
+        c->sw.pipeJobsMax = env_int("BBMSA_STRIP_PIPE_JOBS", 512);  // launches with at most this many jobs take the pipelined form
+        if (strips < 2 || c->pipeSlots < 1) c->sw.pipeJobsMax = 0;
+        if (c->sw.pipeJobsMax > 0) {
+            BBHIP(hipMalloc(&c->d_pipeBoundary, (size_t)((long long)c->pipeSlots * strips * 3 * (cfg->maxColumns + 2) * 4)));
+            BBHIP(hipMalloc(&c->d_pipeSync, (size_t)((long long)c->pipeSlots * bbmsa::strip_pipe_sync_ints(strips) * 4)));
         }
-        for (int i = 0; i < 4; i++) BBHIP(hipEventCreate(&c->ev[i]));
-        guard.c = nullptr;
-        *out = c;
-        return BBMAP_OK;
     }
+    BBHIP(hipMalloc(&c->d_dir, (size_t)((long long)c->stripBlocks * c->stripSlotDwords * 4)));
+    BBHIP(hipMalloc(&c->d_stripBoundary, (size_t)((long long)c->stripBlocks * 6 * (cfg->maxColumns + 2) * 4)));
+    BBHIP(hipMalloc(&c->d_stripTmp, (size_t)((long long)c->stripBlocks * (cfg->maxRows + cfg->maxColumns + 8))));
+    return BBMAP_OK;
+}
+
+// 11ts: the wavefront kernel's first pass, the wide pass behind it where windows can exceed its buffer, the band kernel in front
+static int create_11ts(bbmsa_ctx *c) {
+    const bbmsa_config *cfg = &c->cfg;
     // lanes per job / rows per lane: smallest lane group whose <=10 rows per lane cover maxRows
     int G = cfg->reserved[0];
     if (G != 16 && G != 32 && G != 64) {
@@ -273,8 +160,8 @@ extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
     c->ldsBytes = (bbmsa::lds_table_ints(c->tableLen) + 4 * jobsPerWave * perJobInts) * 4;
     if (c->ldsBytes > 160 * 1024) return bbfail(BBMAP_E_ARG, "bbmsa_create: fast-path LDS budget exceeded; lower reserved[1] (fastCols)");
 
-    c->banded = !(cfg->bandwidth < 1 && cfg->bandwidthRatio <= 0.0f);
-    const void *kfn = bbmsa::fast_kernel_for(c->R, c->banded);
+    c->sw.banded = !(cfg->bandwidth < 1 && cfg->bandwidthRatio <= 0.0f);
+    const void *kfn = bbmsa::fast_kernel_for(c->R, c->sw.banded);
     if (!kfn) return bbfail(BBMAP_E_ARG, "bbmsa_create: no kernel for this rows-per-lane");
     if (c->ldsBytes > 64 * 1024) {
         BBHIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, c->ldsBytes));
@@ -291,44 +178,61 @@ extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
     c->dirSlotDwords = (long long)((maxSteps >> 3) + 1) * c->R * G;
     const long long slots = (long long)c->blocks * 4 * jobsPerWave;
     BBHIP(hipMalloc(&c->d_dir, (size_t)(slots * c->dirSlotDwords * 4)));
-    BBHIP(hipMalloc(&c->d_counters, bbmsa::kCounterBytes));
-    BBHIP(hipMemset(c->d_counters, 0, bbmsa::kCounterBytes));
 
-    // generic kernel scratch: as many threads as a 2 GiB matrix budget allows (at least one wave)
-    const long long planeInts = (long long)(cfg->maxRows + 1) * (cfg->maxColumns + 2);
-    const long long perThread = 3 * planeInts * 4;
-    long long budget = (long long)env_int("BBMSA_GENERIC_SCRATCH_MB", 2048) << 20;
-    long long threads = budget / perThread;
-    if (threads > 16384) threads = 16384;
-    threads = (threads / 64) * 64;
-    if (threads < 64) return bbfail(BBMAP_E_NOMEM, "bbmsa_create: BBMSA_GENERIC_SCRATCH_MB cannot hold one wavefront of scratch matrices for this maxRows x maxColumns");
-    c->genThreads = (int)threads;
-    BBHIP(hipMalloc(&c->d_matrix, (size_t)(threads * perThread)));
-    BBHIP(hipMalloc(&c->d_limits, (size_t)(threads * (cfg->maxRows + cfg->maxColumns + 4) * 4)));
+    int threads = 0;
+    BBTRY(generic_threads(*cfg, 2048, 16384, &threads));
+    BBTRY(alloc_generic_scratch(c, threads));
     // wide pass geometry (only when some windows can exceed the first pass's column buffer)
     if (cfg->maxColumns > fastCols) BBTRY(setup_wide_pass(c));
     // band kernel (msa_fill_band.hip) in front of the first pass: only without a band (a band changes the window rule);
     // BBMSA_NARROW=0 disables it (the switches keep the name of its predecessor, the one-job-per-lane narrow-window kernel)
     c->narrowSlack = env_int("BBMSA_NARROW_SLACK", 2000);
-    if (!c->banded && env_int("BBMSA_NARROW", 1) != 0) {
+    if (!c->sw.banded && env_int("BBMSA_NARROW", 1) != 0) {
         int perCU = 0;
         c->bandRows = cfg->maxRows < 256 ? cfg->maxRows : 256;
         c->bandLds = bbmsa::band_lds_bytes(c->tableLen, c->bandRows);
         if (c->bandLds > 64 * 1024) BBHIP(hipFuncSetAttribute(bbmsa::band_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, c->bandLds));
         BBHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, bbmsa::band_kernel(), 256, c->bandLds));
-        if (perCU < 1) perCU = 1;
-        if (perCU > 4) perCU = 4;
-        c->narrowBlocks = c->numCUs * perCU;
+        c->narrowBlocks = c->numCUs * clamp_occupancy(perCU, 4);
+        c->sw.bandPresent = true;
         BBHIP(hipMalloc(&c->d_bandDir, (size_t)c->narrowBlocks * 4 * (size_t)(c->bandRows + 1) * 128 * 4));
     }
     // route switches of the environment (msa_ctx.h): defaults off, as the functions they mirror leave a context
-    c->sortByWidth = env_int("BBMSA_SORT_BY_WIDTH", 0) != 0;
-    c->sortWithBand = env_int("BBMSA_SORT_WITH_BAND", 0) != 0;
-    c->wideUnlimited = env_int("BBMSA_WIDE_UNLIMITED", 0) != 0;
-    c->unlimitedLoop = env_int("BBMSA_UNLIMITED_LOOP", 1) != 0;         // 0: the general build of the wavefront kernel takes every job
+    c->sw.sortByWidth = env_int("BBMSA_SORT_BY_WIDTH", 0) != 0;
+    c->sw.sortWithBand = env_int("BBMSA_SORT_WITH_BAND", 0) != 0;
+    c->sw.wideUnlimited = env_int("BBMSA_WIDE_UNLIMITED", 0) != 0;
+    c->sw.unlimitedLoop = env_int("BBMSA_UNLIMITED_LOOP", 1) != 0;      // 0: the general build of the wavefront kernel takes every job
     // bbmsa_last_unlimited's counters cost every fill two or three atomics on the same few words: only on request
     c->unlimitedStats = env_int("BBMSA_UNLIMITED_STATS", 0) != 0 || getenv("BBMAP_DP_COUNTS") != nullptr;
     { const int lat = env_int("BBMSA_LATENCY_JOBS", 0); if (lat > 0) BBTRY(bbmsa_set_latency_jobs(c, lat)); }
+    return BBMAP_OK;
+}
+
+extern "C" int bbmsa_create(const bbmsa_config *cfg, bbmsa_ctx **out) {
+    if (!cfg || !out) return bbfail(BBMAP_E_ARG, "bbmsa_create: null argument");
+    *out = nullptr;
+    const int scheme = cfg->reserved[2] & 0xFF;
+    const bool legacyOnly = (cfg->reserved[2] & BBMSA_LEGACY_ONLY) != 0;
+    if (scheme != BBMSA_SCHEME_11TS && scheme != BBMSA_SCHEME_9PACBIO) return bbfail(BBMAP_E_ARG, "bbmsa_create: unknown scoring scheme");
+    if (scheme == BBMSA_SCHEME_11TS && (cfg->maxRows < 1 || cfg->maxRows > 640 || cfg->maxColumns < 1 || cfg->maxColumns > 4096))
+        return bbfail(BBMAP_E_ARG, "bbmsa_create: maxRows must be 1..640 and maxColumns 1..4096");
+    if (scheme == BBMSA_SCHEME_9PACBIO && (cfg->maxRows < 1 || cfg->maxRows > 6100 || cfg->maxColumns < 1 || cfg->maxColumns > 8192))
+        return bbfail(BBMAP_E_ARG, "bbmsa_create: the PacBio scheme takes maxRows 1..6100 and maxColumns 1..8192");
+    hipDeviceProp_t prop;
+    BBTRY(bb_use_gfx950("bbmsa_create", cfg->device, &prop));
+
+    bbmsa_ctx *c = new (std::nothrow) bbmsa_ctx();
+    if (!c) return bbfail(BBMAP_E_NOMEM, "bbmsa_create: out of host memory");
+    c->cfg = *cfg;
+    c->device = cfg->device;
+    c->numCUs = prop.multiProcessorCount;
+    c->sw.scheme = scheme;
+    c->legacyOnly = legacyOnly;
+    // every failure below leaves through bbmsa_destroy(c): nothing allocated so far is leaked
+    struct Guard { bbmsa_ctx *c; ~Guard() { if (c) bbmsa_destroy(c); } } guard{c};
+    BBTRY(legacyOnly ? create_legacy_only(c) : scheme != BBMSA_SCHEME_11TS ? create_pacbio(c) : create_11ts(c));
+    BBHIP(hipMalloc(&c->d_counters, bbmsa::kCounterBytes));
+    BBHIP(hipMemset(c->d_counters, 0, bbmsa::kCounterBytes));
     for (int i = 0; i < 4; i++) BBHIP(hipEventCreate(&c->ev[i]));
     guard.c = nullptr;
     *out = c;
@@ -368,28 +272,96 @@ extern "C" int bbmsa_align_batch_device_indirect(bbmsa_ctx *c, void *stream_, co
     return bbmsa_align_impl(c, stream_, max_jobs, n_jobs_dev, jobs, reads, refs, results, match, match_stride);
 }
 
+// The steps of one launch sequence, in the order bbmsa_align_impl runs them.  Each takes the launch's Route (msa_route.h).
 namespace {
-// the caller's arguments of one launch
-struct Batch {
-    int64_t n_jobs; const uint32_t *n_jobs_dev; const bbmsa_job *jobs; const uint8_t *reads, *refs; bbmsa_result *results; uint8_t *match;
-    int32_t match_stride;
-};
-// what every kernel's parameter struct takes from the batch and the context
-template <class P> void set_batch(P &p, const bbmsa_ctx *c, const Batch &B) {
-    p.jobs = B.jobs; p.reads = B.reads; p.refs = B.refs; p.results = B.results; p.match = B.match;
-    p.njobs = B.n_jobs; p.njobs_dev = B.n_jobs_dev; p.match_stride = B.match_stride;
-    p.maxRows = c->cfg.maxRows; p.maxColumns = c->cfg.maxColumns; p.bandwidth = c->cfg.bandwidth; p.bandwidthRatio = c->cfg.bandwidthRatio;
-}
+using namespace bbmsa;
+
 // the last kernel of every launch: the one-job-per-thread kernel over the jobs the passes before it handed on
-template <class S> int launch_generic(bbmsa_ctx *c, const Batch &B, hipStream_t stream, const int *list, const unsigned int *count) {
+template <class S> int launch_generic(bbmsa_ctx *c, const JobBatch &B, hipStream_t stream, const int *list, const unsigned int *count) {
     bbmsa::GenericParams gp;
     set_batch(gp, c, B);
     gp.list = list; gp.list_count = count;
-    gp.matrix = c->d_matrix; gp.limits = c->d_limits; gp.queue = c->d_counters + 2;
+    gp.matrix = c->d_matrix; gp.limits = c->d_limits; gp.queue = c->d_counters + CNT_GENERIC_QUEUE;
     hipLaunchKernelGGL(bbmsa::msa_fill_generic_kernel<S>, dim3(c->genThreads / 64), dim3(64), 0, stream, gp);
     BBHIP(hipGetLastError());
     BBHIP(hipEventRecord(c->ev[2], stream));
     c->timed = true;
+    return BBMAP_OK;
+}
+
+// 9PacBio's first kernel: a job per wavefront, or (Route::pipelined) a job's strips over pipeK wavefronts
+int launch_strip(bbmsa_ctx *c, const JobBatch &B, const Route &r, hipStream_t stream) {
+    bbmsa::StripParams sp;
+    set_batch(sp, c, B);
+    sp.queue = c->d_counters + CNT_FAST_QUEUE; sp.dirbuf = c->d_dir; sp.dir_slot_dwords = c->stripSlotDwords; sp.dir_strip_dwords = c->stripDwords;
+    sp.boundary = c->d_stripBoundary; sp.tmpbuf = c->d_stripTmp; sp.slow_list = c->slowList.as<int>(); sp.slow_count = c->d_counters + CNT_SLOW_COUNT;
+    sp.pipeK = 0; sp.pipeSlots = 0; sp.pipeBoundary = nullptr; sp.pipeSync = nullptr;
+    sp.pipeSpinLimit = env_int("BBMSA_PIPE_SPIN_LIMIT", 1 << 21);          // polls before a wave of the pipelined form gives up (~3 s; tests force timeouts)
+    if (sp.pipeSpinLimit < 1) sp.pipeSpinLimit = 1;
+    void *sargs[] = {&sp};
+    if (r.pipelined) {
+        const long long slots = r.jobs < c->pipeSlots ? r.jobs : c->pipeSlots;
+        sp.pipeK = c->pipeK; sp.pipeSlots = (int)slots; sp.pipeBoundary = c->d_pipeBoundary; sp.pipeSync = c->d_pipeSync;
+        BBHIP(hipMemsetAsync(c->d_pipeSync, 0, (size_t)(slots * bbmsa::strip_pipe_sync_ints(c->pipeK) * 4), stream));
+        BBHIP(hipLaunchKernel(bbmsa::strip_kernel_pacbio_pipelined(), dim3((unsigned)(slots * c->pipeK)), dim3(64), sargs, (size_t)c->stripLds, stream));
+        return BBMAP_OK;
+    }
+    const long long sblocks = r.jobs < c->stripBlocks ? r.jobs : c->stripBlocks;
+    BBHIP(hipLaunchKernel(bbmsa::strip_kernel_pacbio(), dim3((unsigned)sblocks), dim3(64), sargs, (size_t)c->stripLds, stream));
+    return BBMAP_OK;
+}
+
+// the band kernel in front of the first pass: over every job, or over the sort's list of candidates (the third of fastList)
+int launch_band(bbmsa_ctx *c, const JobBatch &B, const Route &r, hipStream_t stream) {
+    int *const fastList = c->fastList.as<int>();
+    bbmsa::NarrowParams np;
+    set_batch(np, c, B);
+    np.queue = c->d_counters + CNT_BAND_QUEUE; np.fast_list = fastList; np.fast_count = c->d_counters + CNT_LIST_COUNT;
+    np.stats = c->d_counters + CNT_BAND_STATS; np.maxSlack = c->narrowSlack;
+    np.dirbuf32 = c->d_bandDir; np.tableLen = c->tableLen; np.bandRows = c->bandRows;
+    np.list = r.sorted ? fastList + 2 * r.jobs : nullptr; np.list_count = r.sorted ? c->d_counters + CNT_CAND_COUNT : nullptr;
+    long long nb = (r.jobs + 63) / 64;
+    if (nb > c->narrowBlocks) nb = c->narrowBlocks;
+    void *nargs[] = {&np};
+    BBHIP(hipLaunchKernel(bbmsa::band_kernel(), dim3((unsigned)nb), dim3(256), nargs, (size_t)c->bandLds, stream));
+    return BBMAP_OK;
+}
+
+// what the first pass takes; the unlimited build's launch and the 64-lane launch start from a copy
+bbmsa::FillParams first_pass_params(const bbmsa_ctx *c, const JobBatch &B, const Route &r) {
+    bbmsa::FillParams fp = {};
+    set_batch(fp, c, B);
+    fp.queue = c->d_counters + CNT_FAST_QUEUE; fp.dirbuf = c->d_dir; fp.dir_slot_dwords = c->dirSlotDwords;
+    fp.list = (r.band || r.sorted) ? c->fastList.as<int>() : nullptr; fp.list_count = c->d_counters + CNT_LIST_COUNT; fp.priority = 0;
+    fp.slow_list = c->slowList.as<int>(); fp.slow_count = c->d_counters + CNT_SLOW_COUNT;
+    fp.lanesPerJob = c->G; fp.fastCols = c->fastCols; fp.tmpBytes = c->tmpBytes; fp.tableLen = c->tableLen;
+    fp.unl_stats = c->unlimitedStats ? c->d_counters + CNT_UNL_STATS : nullptr;
+    return fp;
+}
+
+// the build without limits and prune tests, over the sort's list of unlimited fills (the second third of fastList)
+int launch_unlimited(bbmsa_ctx *c, const bbmsa::FillParams &fp, const Route &r, long long blocks, hipStream_t stream) {
+    bbmsa::FillParams up = fp;
+    up.queue = c->d_counters + CNT_UNL_QUEUE; up.list = c->fastList.as<int>() + r.jobs; up.list_count = c->d_counters + CNT_UNL_LIST_COUNT;
+    void *uargs[] = {&up};
+    BBHIP(hipLaunchKernel(bbmsa::fast_kernel_unl_for(c->R), dim3((unsigned)blocks), dim3(256), uargs, (size_t)c->ldsBytes, stream));
+    return BBMAP_OK;
+}
+
+// The 64-lane geometry: the wide pass over the first pass's hand-overs or, on the latency route, over every job of the launch.  What
+// it cannot take either (banded rows with holes) goes on to the generic kernel through the second list.
+int launch_wide(bbmsa_ctx *c, const bbmsa::FillParams &fp, const Route &r, hipStream_t stream) {
+    bbmsa::FillParams wp = fp;
+    wp.queue = c->d_counters + CNT_WIDE_QUEUE; wp.dirbuf = c->d_wideDir; wp.dir_slot_dwords = c->wideDirSlotDwords;
+    wp.list = r.latency ? nullptr : fp.slow_list; wp.list_count = r.latency ? nullptr : fp.slow_count;
+    wp.slow_list = c->slowList2.as<int>(); wp.slow_count = c->d_counters + CNT_WIDE_SLOW_COUNT;
+    wp.lanesPerJob = 64; wp.fastCols = c->wideCols; wp.tmpBytes = c->wideTmpBytes; wp.tableLen = c->wideTableLen;
+    static const int widePrio = env_int("BBMSA_WIDE_PRIORITY", 2);
+    wp.priority = widePrio;
+    void *wargs[] = {&wp};
+    const long long wblocks = r.latency && r.jobs < c->wideBlocks ? r.jobs : c->wideBlocks;
+    const void *bothFn = r.wideBoth ? bbmsa::fast_kernel_both_for(c->wideR) : nullptr;      // null: no such build, the general one runs
+    BBHIP(hipLaunchKernel(bothFn ? bothFn : bbmsa::fast_kernel_for(c->wideR, c->sw.banded), dim3((unsigned)wblocks), dim3(64), wargs, (size_t)c->wideLdsBytes, stream));
     return BBMAP_OK;
 }
 }  // namespace
@@ -405,143 +377,49 @@ int bbmsa_align_impl(bbmsa_ctx *c, void *stream_, int64_t n_jobs, const uint32_t
     hipStream_t stream = (hipStream_t)stream_;
     BBHIP(hipSetDevice(c->device));
     if (c->legacyOnly) return bbfail(BBMAP_E_ARG, "bbmsa_align_batch_device: this context was created for bbmsa_fill_packed only (BBMSA_LEGACY_ONLY)");
-    const Batch B = {n_jobs, n_jobs_dev, jobs, reads, refs, results, match, match_stride};
+    const JobBatch B = {n_jobs, n_jobs_dev, jobs, reads, refs, results, match, match_stride};
+    const Route r = plan_route(c->sw, n_jobs, n_jobs_dev != nullptr);
     const size_t listBytes = (size_t)n_jobs * 4;
     BBHIP(c->slowList.grow(listBytes, 0, &stream));
-    int *const slowList = c->slowList.as<int>();
-    if (c->scheme != BBMSA_SCHEME_11TS) {
-        BBHIP(hipMemsetAsync(c->d_counters, 0, bbmsa::kCounterBytes, stream));
-        c->narrowUsed = false; c->lastSorted = false; c->lastLatency = false; c->lastIndirect = n_jobs_dev != nullptr;
-        BBHIP(hipEventRecord(c->ev[0], stream));
-        BBHIP(hipEventRecord(c->ev[3], stream));
-        bbmsa::StripParams sp;
-        set_batch(sp, c, B);
-        sp.queue = c->d_counters; sp.dirbuf = c->d_dir; sp.dir_slot_dwords = c->stripSlotDwords; sp.dir_strip_dwords = c->stripDwords;
-        sp.boundary = c->d_stripBoundary; sp.tmpbuf = c->d_stripTmp; sp.slow_list = slowList; sp.slow_count = c->d_counters + 1;
-        long long sblocks = n_jobs < c->stripBlocks ? n_jobs : c->stripBlocks;
-        sp.pipeK = 0; sp.pipeSlots = 0; sp.pipeBoundary = nullptr; sp.pipeSync = nullptr;
-        sp.pipeSpinLimit = env_int("BBMSA_PIPE_SPIN_LIMIT", 1 << 21);          // polls before a wave of the pipelined form gives up (~3 s; tests force timeouts)
-        if (sp.pipeSpinLimit < 1) sp.pipeSpinLimit = 1;
-        void *sargs[] = {&sp};
-        if (!n_jobs_dev && c->pipeJobsMax > 0 && n_jobs <= c->pipeJobsMax) {
-            // few jobs (the late scoreSlow rounds of mapPacBio): a lone 6,000 x 6,100 fill is one wavefront's dependent chain, 370 ms;
-            // with its strips pipelined over `pipeK` wavefronts it is ~50
-            const long long slots = n_jobs < c->pipeSlots ? n_jobs : c->pipeSlots;
-            sp.pipeK = c->pipeK; sp.pipeSlots = (int)slots; sp.pipeBoundary = c->d_pipeBoundary; sp.pipeSync = c->d_pipeSync;
-            BBHIP(hipMemsetAsync(c->d_pipeSync, 0, (size_t)(slots * bbmsa::strip_pipe_sync_ints(c->pipeK) * 4), stream));
-            BBHIP(hipLaunchKernel(bbmsa::strip_kernel_pacbio_pipelined(), dim3((unsigned)(slots * c->pipeK)), dim3(64), sargs, (size_t)c->stripLds, stream));
-        } else
-        BBHIP(hipLaunchKernel(bbmsa::strip_kernel_pacbio(), dim3((unsigned)sblocks), dim3(64), sargs, (size_t)c->stripLds, stream));
-        BBHIP(hipEventRecord(c->ev[1], stream));
-        return launch_generic<bbmsa::Scheme9PacBio>(c, B, stream, slowList, c->d_counters + 1);
-    }
-    if (c->wideBlocks > 0) BBHIP(c->slowList2.grow(listBytes, 0, &stream));
-    const bool useNarrow = c->narrowBlocks > 0 && !c->narrowOff;
-    // Both the band kernel and the sort write the wavefront kernel's list.  Together only on request (bbmsa_sort_with_band): the sort
-    // then gives the band kernel a list of its candidates, and the band kernel appends what it hands on behind the sorted list.
-    const bool sortJobs = c->sortByWidth && !n_jobs_dev && n_jobs >= 256 && n_jobs > c->latencyJobs && (!useNarrow || c->sortWithBand);
+    if (r.wide) BBHIP(c->slowList2.grow(listBytes, 0, &stream));
     // (sorted: the general list with room for the band kernel's hand-overs, then the unlimited fills' list, then the candidates')
-    if (c->narrowBlocks > 0 || sortJobs) BBHIP(c->fastList.grow(sortJobs ? 3 * listBytes : listBytes, 0, &stream));
-    int *const fastList = c->fastList.as<int>();
-    // counters: [0] fast queue, [1] slow count, [2] generic queue, [3] narrow queue, [4] fast-list count,
-    //           [5] jobs finished by the band kernel (the "narrow" slots), [6] candidates it handed on, [7] wide pass's slow count,
-    //           [8] wide queue, [9] jobs the wavefront kernel's prune-free loop ran, [10] unlimited jobs its general loop ran,
-    //           [11] length of a width-sorted launch's list of unlimited jobs, [12] the unlimited build's queue,
-    //           [13] / [14] wavefront steps of the unlimited jobs / of all jobs (bbmsa_last_unlimited),
-    //           [15] length of a width-sorted launch's list of band candidates, [16] of its general list as the sort left it
-    //           (before the band kernel's hand-overs), [17] steps the wavefronts ran (a wavefront steps as its longest job)
+    if (c->sw.bandPresent || r.sorted) BBHIP(c->fastList.grow(r.sorted ? 3 * listBytes : listBytes, 0, &stream));
     BBHIP(hipMemsetAsync(c->d_counters, 0, bbmsa::kCounterBytes, stream));
+    c->last = r;
     BBHIP(hipEventRecord(c->ev[0], stream));
-    c->narrowUsed = useNarrow;
-    if (sortJobs) {
-        if (!c->d_widthHist) BBHIP(hipMalloc(&c->d_widthHist, bbmsa::WIDTH_BUCKETS * 4));
-        BBHIP(hipMemsetAsync(c->d_widthHist, 0, bbmsa::WIDTH_BUCKETS * 4, stream));
-        const int perBlock = bbmsa::SORT_THREADS * bbmsa::SORT_JOBS_PER_THREAD;
-        const unsigned sb = (unsigned)((n_jobs + perBlock - 1) / perBlock);
-        const bbmsa::SortKey key = {c->cfg.maxRows, c->cfg.maxColumns, c->cfg.bandwidth, c->cfg.bandwidthRatio, c->unlimitedLoop ? 1 : 0,
-                                    useNarrow ? 1 : 0, c->bandRows, c->narrowSlack};
-        hipLaunchKernelGGL(bbmsa::width_hist_kernel, dim3(sb), dim3(bbmsa::SORT_THREADS), 0, stream, jobs, (long long)n_jobs, key, c->d_widthHist);
-        hipLaunchKernelGGL(bbmsa::width_scan_kernel, dim3(1), dim3(bbmsa::WIDTH_PER_CLASS), 0, stream, c->d_widthHist, c->d_counters + 4, c->d_counters + 16,
-                           c->d_counters + 11, c->d_counters + 15);
-        hipLaunchKernelGGL(bbmsa::width_scatter_kernel, dim3(sb), dim3(bbmsa::SORT_THREADS), 0, stream, jobs, (long long)n_jobs, key, c->d_widthHist,
-                           fastList, fastList + n_jobs, fastList + 2 * n_jobs);
-        BBHIP(hipGetLastError());
+    if (c->sw.scheme != BBMSA_SCHEME_11TS) {
+        BBHIP(hipEventRecord(c->ev[3], stream));
+        BBTRY(launch_strip(c, B, r, stream));
+        BBHIP(hipEventRecord(c->ev[1], stream));
+        return launch_generic<bbmsa::Scheme9PacBio>(c, B, stream, c->slowList.as<int>(), c->d_counters + CNT_SLOW_COUNT);
     }
-    if (useNarrow) {
-        bbmsa::NarrowParams np;
-        set_batch(np, c, B);
-        np.queue = c->d_counters + 3; np.fast_list = fastList; np.fast_count = c->d_counters + 4;
-        np.stats = c->d_counters + 5; np.maxSlack = c->narrowSlack;
-        np.dirbuf32 = c->d_bandDir; np.tableLen = c->tableLen; np.bandRows = c->bandRows;
-        np.list = sortJobs ? fastList + 2 * n_jobs : nullptr; np.list_count = sortJobs ? c->d_counters + 15 : nullptr;
-        long long nb = (n_jobs + 63) / 64;
-        if (nb > c->narrowBlocks) nb = c->narrowBlocks;
-        void *nargs[] = {&np};
-        BBHIP(hipLaunchKernel(bbmsa::band_kernel(), dim3((unsigned)nb), dim3(256), nargs, (size_t)c->bandLds, stream));
-    }
+    if (r.sorted) BBTRY(bbmsa_width_sort(c, stream, jobs, n_jobs, r.band));
+    if (r.band) BBTRY(launch_band(c, B, r, stream));
     BBHIP(hipEventRecord(c->ev[3], stream));
-
-    bbmsa::FillParams fp = {};
-    set_batch(fp, c, B);
-    fp.queue = c->d_counters; fp.dirbuf = c->d_dir; fp.dir_slot_dwords = c->dirSlotDwords;
-    fp.list = (useNarrow || sortJobs) ? fastList : nullptr; fp.list_count = c->d_counters + 4; fp.priority = 0;
-    fp.slow_list = slowList; fp.slow_count = c->d_counters + 1;
-    fp.lanesPerJob = c->G; fp.fastCols = c->fastCols; fp.tmpBytes = c->tmpBytes; fp.tableLen = c->tableLen;
-    fp.unl_stats = c->unlimitedStats ? c->d_counters + 9 : nullptr;
-
-    // A launch with few jobs is a wavefront's latency, not throughput: (columns + lanes - 1) steps of one dependent chain.  The wide
-    // pass's geometry (64 lanes x 3 rows, one job per block) has the shorter chain per step (3 rows instead of 5: ~450 instead of
-    // ~740 instructions), so such launches go to it directly (bbmsa_set_latency_jobs; the mapper's late rounds hold a few hundred fills).
-    const bool latency = c->wideBlocks > 0 && !n_jobs_dev && !useNarrow && n_jobs <= c->latencyJobs;
-    c->lastSorted = sortJobs; c->lastLatency = latency; c->lastIndirect = n_jobs_dev != nullptr; c->lastJobs = n_jobs;
+    bbmsa::FillParams fp = first_pass_params(c, B, r);
     const int jobsPerBlock = 4 * (64 / c->G);
     long long blocks = (n_jobs + jobsPerBlock - 1) / jobsPerBlock;
     if (blocks > c->blocks) blocks = c->blocks;
-    if (sortJobs && c->unlimitedLoop) {
-        // the sort made a list of the unlimited fills: the build without limits and prune tests takes them, the general build the rest
-        bbmsa::FillParams up = fp;
-        up.queue = c->d_counters + 12; up.list = fastList + n_jobs; up.list_count = c->d_counters + 11;
-        void *uargs[] = {&up};
-        BBHIP(hipLaunchKernel(bbmsa::fast_kernel_unl_for(c->R), dim3((unsigned)blocks), dim3(256), uargs, (size_t)c->ldsBytes, stream));
-    }
+    if (r.unlList) BBTRY(launch_unlimited(c, fp, r, blocks, stream));
     void *args[] = {&fp};
-    if (!latency)
-        BBHIP(hipLaunchKernel(bbmsa::fast_kernel_for(c->R, c->banded), dim3((unsigned)blocks), dim3(256), args, (size_t)c->ldsBytes, stream));
-    const int *genList = slowList;
-    const unsigned int *genCount = c->d_counters + 1;
-    if (c->wideBlocks > 0) {
-        // wide pass over the first pass's hand-overs; what it cannot take either (banded rows with holes) goes on to the
-        // generic kernel through the second list ([7] = its count, [8] = wide queue)
-        bbmsa::FillParams wp = fp;
-        wp.queue = c->d_counters + 8; wp.dirbuf = c->d_wideDir; wp.dir_slot_dwords = c->wideDirSlotDwords;
-        wp.list = slowList; wp.list_count = c->d_counters + 1;
-        if (latency) { wp.list = nullptr; wp.list_count = nullptr; }          // every job of the launch
-        wp.slow_list = c->slowList2.as<int>(); wp.slow_count = c->d_counters + 7;
-        wp.lanesPerJob = 64; wp.fastCols = c->wideCols; wp.tmpBytes = c->wideTmpBytes; wp.tableLen = c->wideTableLen;
-        static const int widePrio = env_int("BBMSA_WIDE_PRIORITY", 2);
-        wp.priority = widePrio;
-        void *wargs[] = {&wp};
-        const long long wblocks = latency && n_jobs < c->wideBlocks ? n_jobs : c->wideBlocks;
-        // one job per wavefront: which step loop runs is wave-uniform, so one build can hold both and give an unlimited fill the
-        // prune-free one (bbmsa_set_wide_unlimited; a banded context has no such build)
-        const void *bothFn = (c->wideUnlimited && !c->banded) ? bbmsa::fast_kernel_both_for(c->wideR) : nullptr;
-        BBHIP(hipLaunchKernel(bothFn ? bothFn : bbmsa::fast_kernel_for(c->wideR, c->banded), dim3((unsigned)wblocks), dim3(64), wargs, (size_t)c->wideLdsBytes, stream));
-        genList = wp.slow_list; genCount = c->d_counters + 7;
-    }
+    if (!r.latency)
+        BBHIP(hipLaunchKernel(bbmsa::fast_kernel_for(c->R, c->sw.banded), dim3((unsigned)blocks), dim3(256), args, (size_t)c->ldsBytes, stream));
+    if (r.wide) BBTRY(launch_wide(c, fp, r, stream));
     BBHIP(hipEventRecord(c->ev[1], stream));
-    return launch_generic<bbmsa::Scheme11ts>(c, B, stream, genList, genCount);
+    return launch_generic<bbmsa::Scheme11ts>(c, B, stream, r.wide ? c->slowList2.as<int>() : fp.slow_list,
+                                             c->d_counters + (r.wide ? CNT_WIDE_SLOW_COUNT : CNT_SLOW_COUNT));
 }
 
-void bbmsa_use_narrow(bbmsa_ctx *c, bool on) { if (c) c->narrowOff = !on; }
-void bbmsa_sort_by_width(bbmsa_ctx *c, bool on) { if (c) c->sortByWidth = on; }
-void bbmsa_sort_with_band(bbmsa_ctx *c, bool on) { if (c) c->sortWithBand = on; }
-void bbmsa_set_wide_unlimited(bbmsa_ctx *c, bool on) { if (c) c->wideUnlimited = on; }
+void bbmsa_use_narrow(bbmsa_ctx *c, bool on) { if (c) c->sw.bandOff = !on; }
+void bbmsa_sort_by_width(bbmsa_ctx *c, bool on) { if (c) c->sw.sortByWidth = on; }
+void bbmsa_sort_with_band(bbmsa_ctx *c, bool on) { if (c) c->sw.sortWithBand = on; }
+void bbmsa_set_wide_unlimited(bbmsa_ctx *c, bool on) { if (c) c->sw.wideUnlimited = on; }
 int bbmsa_set_latency_jobs(bbmsa_ctx *c, int64_t n) {
-    if (!c || c->scheme != BBMSA_SCHEME_11TS || c->legacyOnly) return BBMAP_OK;
+    if (!c || c->sw.scheme != BBMSA_SCHEME_11TS || c->legacyOnly) return BBMAP_OK;
     BBHIP(hipSetDevice(c->device));
     if (n > 0) BBTRY(setup_wide_pass(c));
     if (n > 0 && !c->slowList2.p) BBHIP(c->slowList2.grow(c->slowList.cap));   // (its hand-over list, late: as long as the first)
-    c->latencyJobs = c->wideBlocks > 0 ? n : 0;
+    c->sw.latencyJobs = c->sw.widePresent ? n : 0;
     return BBMAP_OK;
 }
 int bbmsa_wait_first_pass(bbmsa_ctx *c, void *waiter) {
@@ -572,19 +450,28 @@ extern "C" int bbmsa_last_kernel_ms3(bbmsa_ctx *c, float *ms3) {
     return BBMAP_OK;
 }
 
-extern "C" int bbmsa_last_counts(bbmsa_ctx *c, int64_t *counts4) {
-    if (!c || !c->timed || !counts4) return bbfail(BBMAP_E_ARG, "bbmsa_last_counts: nothing launched yet");
+// the last launch's counters on the host, once its sequence has finished: what every read-back entry below starts with
+static int read_counters(bbmsa_ctx *c, unsigned (&h)[bbmsa::kCounterWords]) {
     BBHIP(hipSetDevice(c->device));
     BBHIP(hipEventSynchronize(c->ev[2]));
-    unsigned h[bbmsa::kCounterWords];
     BBHIP(hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
+    return BBMAP_OK;
+}
+
+extern "C" int bbmsa_last_counts(bbmsa_ctx *c, int64_t *counts4) {
+    if (!c || !c->timed || !counts4) return bbfail(BBMAP_E_ARG, "bbmsa_last_counts: nothing launched yet");
+    unsigned h[bbmsa::kCounterWords];
+    BBTRY(read_counters(c, h));
+    const Route &r = c->last;
     // the wavefront list: what the band kernel left to the wavefront kernel without trying it, plus what it handed on -- on a sorted
     // launch the sort's general and unlimited lists, which hold no candidate (finished + handed on + this = the launch's jobs)
-    counts4[0] = h[5]; counts4[1] = h[6]; counts4[2] = c->narrowUsed ? (c->lastSorted ? h[16] + h[11] : h[4]) : 0; counts4[3] = c->wideBlocks > 0 ? h[7] : h[1];
+    counts4[0] = h[CNT_BAND_DONE]; counts4[1] = h[CNT_BAND_HANDED];
+    counts4[2] = r.band ? (r.sorted ? h[CNT_SORTED_COUNT] + h[CNT_UNL_LIST_COUNT] : h[CNT_LIST_COUNT]) : 0;
+    counts4[3] = r.wide ? h[CNT_WIDE_SLOW_COUNT] : h[CNT_SLOW_COUNT];
     if (getenv("BBMAP_DP_COUNTS")) {
-        if (c->wideBlocks > 0) fprintf(stderr, "   (first pass handed %u jobs to the wide pass)\n", h[1]);
-        if (c->lastSorted) fprintf(stderr, "   (sorted: %u general, %u unlimited, %u band candidates)\n", h[16], h[11], h[15]);
-        fprintf(stderr, "   (the wavefronts ran %u steps)\n", h[17]);
+        if (r.wide) fprintf(stderr, "   (first pass handed %u jobs to the wide pass)\n", h[CNT_SLOW_COUNT]);
+        if (r.sorted) fprintf(stderr, "   (sorted: %u general, %u unlimited, %u band candidates)\n", h[CNT_SORTED_COUNT], h[CNT_UNL_LIST_COUNT], h[CNT_CAND_COUNT]);
+        fprintf(stderr, "   (the wavefronts ran %u steps)\n", h[CNT_WAVE_STEPS]);
     }
     return BBMAP_OK;
 }
@@ -593,12 +480,10 @@ extern "C" int bbmsa_last_counts(bbmsa_ctx *c, int64_t *counts4) {
 // entries past a list's length are not written) and their lengths in lens3.  Fails when the last launch was not sorted.
 extern "C" int bbmsa_debug_sorted_lists(bbmsa_ctx *c, int64_t n_jobs, int32_t *lists3, int64_t *lens3) {
     if (!c || !c->timed || !lists3 || !lens3) return bbfail(BBMAP_E_ARG, "bbmsa_debug_sorted_lists: nothing launched yet");
-    if (!c->lastSorted || n_jobs != c->lastJobs) return bbfail(BBMAP_E_ARG, "bbmsa_debug_sorted_lists: the last launch was not a sorted launch of n_jobs jobs");
-    BBHIP(hipSetDevice(c->device));
-    BBHIP(hipEventSynchronize(c->ev[2]));
+    if (!c->last.sorted || n_jobs != c->last.jobs) return bbfail(BBMAP_E_ARG, "bbmsa_debug_sorted_lists: the last launch was not a sorted launch of n_jobs jobs");
     unsigned h[bbmsa::kCounterWords];
-    BBHIP(hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
-    const unsigned len[3] = {h[16], h[11], h[15]};
+    BBTRY(read_counters(c, h));
+    const unsigned len[3] = {h[CNT_SORTED_COUNT], h[CNT_UNL_LIST_COUNT], h[CNT_CAND_COUNT]};
     for (int k = 0; k < 3; k++) {
         if ((int64_t)len[k] > n_jobs) return bbfail(BBMAP_E_HIP, "bbmsa_debug_sorted_lists: a list is longer than the launch");
         lens3[k] = len[k];
@@ -609,30 +494,27 @@ extern "C" int bbmsa_debug_sorted_lists(bbmsa_ctx *c, int64_t n_jobs, int32_t *l
 
 extern "C" int bbmsa_last_unlimited(bbmsa_ctx *c, int64_t *counts4) {
     if (!c || !c->timed || !counts4) return bbfail(BBMAP_E_ARG, "bbmsa_last_unlimited: nothing launched yet");
-    if (c->scheme == BBMSA_SCHEME_11TS && !c->legacyOnly && !c->unlimitedStats) return bbfail(BBMAP_E_ARG, "bbmsa_last_unlimited: the context does not count (create it with BBMSA_UNLIMITED_STATS=1 in the environment)");
-    BBHIP(hipSetDevice(c->device));
-    BBHIP(hipEventSynchronize(c->ev[2]));
-    unsigned h[16];
-    BBHIP(hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
-    const bool wave = c->scheme == BBMSA_SCHEME_11TS && !c->legacyOnly;
-    counts4[0] = wave ? h[9] : 0; counts4[1] = wave ? h[10] : 0; counts4[2] = wave ? h[13] : 0; counts4[3] = wave ? h[14] : 0;
+    const bool wave = c->sw.scheme == BBMSA_SCHEME_11TS && !c->legacyOnly;
+    if (wave && !c->unlimitedStats) return bbfail(BBMAP_E_ARG, "bbmsa_last_unlimited: the context does not count (create it with BBMSA_UNLIMITED_STATS=1 in the environment)");
+    unsigned h[bbmsa::kCounterWords];
+    BBTRY(read_counters(c, h));
+    counts4[0] = wave ? h[CNT_UNL_RAN_UNL] : 0; counts4[1] = wave ? h[CNT_UNL_RAN_GENERAL] : 0;
+    counts4[2] = wave ? h[CNT_UNL_STEPS] : 0; counts4[3] = wave ? h[CNT_ALL_STEPS] : 0;
     return BBMAP_OK;
 }
 
 int bbmsa_last_route_flags(const bbmsa_ctx *c) {
     if (!c || !c->timed) return 0;
-    return (c->narrowUsed ? BBMSA_ROUTE_NARROW : 0) | (c->lastSorted ? BBMSA_ROUTE_SORTED : 0) | (c->lastLatency ? BBMSA_ROUTE_LATENCY : 0);
+    return (c->last.band ? BBMSA_ROUTE_NARROW : 0) | (c->last.sorted ? BBMSA_ROUTE_SORTED : 0) | (c->last.latency ? BBMSA_ROUTE_LATENCY : 0);
 }
 
 extern "C" int bbmsa_last_route(bbmsa_ctx *c, int64_t *route8) {
     if (!c || !c->timed || !route8) return bbfail(BBMAP_E_ARG, "bbmsa_last_route: nothing launched yet");
-    BBHIP(hipSetDevice(c->device));
-    BBHIP(hipEventSynchronize(c->ev[2]));
-    unsigned h[16];
-    BBHIP(hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
-    const bool wide = c->scheme == BBMSA_SCHEME_11TS && c->wideBlocks > 0;
-    route8[0] = c->narrowUsed; route8[1] = c->lastSorted; route8[2] = c->lastLatency; route8[3] = wide; route8[4] = c->lastIndirect;
-    route8[5] = h[1]; route8[6] = wide ? h[7] : 0; route8[7] = c->narrowUsed ? h[5] : 0;
+    unsigned h[bbmsa::kCounterWords];
+    BBTRY(read_counters(c, h));
+    const Route &r = c->last;
+    route8[0] = r.band; route8[1] = r.sorted; route8[2] = r.latency; route8[3] = r.wide; route8[4] = r.indirect;
+    route8[5] = h[CNT_SLOW_COUNT]; route8[6] = r.wide ? h[CNT_WIDE_SLOW_COUNT] : 0; route8[7] = r.band ? h[CNT_BAND_DONE] : 0;
     return BBMAP_OK;
 }
 
@@ -643,7 +525,7 @@ extern "C" int bbmsa_geometry(bbmsa_ctx *c, int32_t *geo4) {
         int last = 0, mask = 0;
         bbmsa_legacy_rows_per_lane(c, &last, &mask);
         geo4[0] = 64; geo4[1] = last; geo4[2] = c->cfg.maxColumns; geo4[3] = mask;
-    } else if (c->scheme == BBMSA_SCHEME_11TS) {
+    } else if (c->sw.scheme == BBMSA_SCHEME_11TS) {
         geo4[0] = c->G; geo4[1] = c->R; geo4[2] = c->fastCols; geo4[3] = c->wideBlocks > 0 ? c->wideR : 0;
     }
     return BBMAP_OK;

@@ -36,6 +36,9 @@ template <class S> __global__ void msa_fill_generic_kernel(const GenericParams p
 namespace {
 
 enum { OPEN = 0, RUNNING = 1, DONE = 2 };
+using namespace bbmsa;
+constexpr int kLegacyCounterBytes = 64;       // a batch's private counters: CNT_FAST_QUEUE, CNT_SLOW_COUNT, CNT_GENERIC_QUEUE of a 16-word block
+static_assert(CNT_FAST_QUEUE < 16 && CNT_SLOW_COUNT < 16 && CNT_GENERIC_QUEUE < 16, "the legacy block holds these three");
 
 struct Batch {
     // pinned input arena and its device mirror: [jobs | plane_off | limits_off | sequence bytes]
@@ -44,7 +47,7 @@ struct Batch {
     int *d_planes, *h_planes;
     int *d_limits, *h_limits;
     bbmsa_result *d_results, *h_results;
-    unsigned int *d_counters, *h_counters;       // [0] queue, [1] hand-over count, [2] generic queue
+    unsigned int *d_counters, *h_counters;       // kLegacyCounterBytes each
     int *d_slow, *h_slow;
     int njobs;
     long long usedBytes, usedInts, usedLimits;
@@ -92,8 +95,8 @@ int alloc_batch(bbmsa_legacy *S, Batch &b) {
     BBHIP(hipHostMalloc((void **)&b.h_limits, (size_t)S->capLimits * 4, hipHostMallocDefault));
     BBHIP(hipMalloc((void **)&b.d_results, (size_t)S->capJobs * sizeof(bbmsa_result)));
     BBHIP(hipHostMalloc((void **)&b.h_results, (size_t)S->capJobs * sizeof(bbmsa_result), hipHostMallocDefault));
-    BBHIP(hipMalloc((void **)&b.d_counters, 64));
-    BBHIP(hipHostMalloc((void **)&b.h_counters, 64, hipHostMallocDefault));
+    BBHIP(hipMalloc((void **)&b.d_counters, kLegacyCounterBytes));
+    BBHIP(hipHostMalloc((void **)&b.h_counters, kLegacyCounterBytes, hipHostMallocDefault));
     BBHIP(hipMalloc((void **)&b.d_slow, (size_t)S->capJobs * 4));
     BBHIP(hipHostMalloc((void **)&b.h_slow, (size_t)S->capJobs * 4, hipHostMallocDefault));
     b.state = OPEN;
@@ -126,7 +129,7 @@ int run_batch(bbmsa_ctx *c, Batch &b) {
     const auto t0 = std::chrono::steady_clock::now();
     auto since = [](std::chrono::steady_clock::time_point a) { return (long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - a).count(); };
     BBHIP(hipMemcpyAsync(b.d_in, b.h_in, (size_t)(S->offBytes + b.usedBytes), hipMemcpyHostToDevice, st));
-    BBHIP(hipMemsetAsync(b.d_counters, 0, 64, st));
+    BBHIP(hipMemsetAsync(b.d_counters, 0, kLegacyCounterBytes, st));
     const bbmsa_job *d_jobs = (const bbmsa_job *)b.d_in;
     const long long *d_planeOff = (const long long *)(b.d_in + S->offPlaneOff);
     const long long *d_limitsOff = (const long long *)(b.d_in + S->offLimitsOff);
@@ -141,16 +144,11 @@ int run_batch(bbmsa_ctx *c, Batch &b) {
     };
     int nslow = n;
     if (S->wave) {
-        bbmsa::FillParams fp;
-        memset(&fp, 0, sizeof fp);
-        fp.jobs = d_jobs; fp.reads = d_bytes; fp.refs = d_bytes; fp.results = b.d_results; fp.match = nullptr;
-        fp.njobs = n; fp.njobs_dev = nullptr;
-        fp.queue = b.d_counters; fp.dirbuf = S->d_dir; fp.dir_slot_dwords = S->dirSlotDwords;
-        fp.list = nullptr; fp.list_count = nullptr; fp.priority = 0;
-        fp.slow_list = b.d_slow; fp.slow_count = b.d_counters + 1;
-        fp.match_stride = 0; fp.lanesPerJob = 64; fp.fastCols = S->cols; fp.tmpBytes = S->tmpBytes; fp.tableLen = S->tableLen;
-        fp.maxRows = c->cfg.maxRows; fp.maxColumns = c->cfg.maxColumns;
-        fp.bandwidth = c->cfg.bandwidth; fp.bandwidthRatio = c->cfg.bandwidthRatio;
+        bbmsa::FillParams fp = {};                    // (no list, no priority, no statistics)
+        set_batch(fp, c, JobBatch{n, nullptr, d_jobs, d_bytes, d_bytes, b.d_results, nullptr, 0});
+        fp.queue = b.d_counters + CNT_FAST_QUEUE; fp.dirbuf = S->d_dir; fp.dir_slot_dwords = S->dirSlotDwords;
+        fp.slow_list = b.d_slow; fp.slow_count = b.d_counters + CNT_SLOW_COUNT;
+        fp.lanesPerJob = 64; fp.fastCols = S->cols; fp.tmpBytes = S->tmpBytes; fp.tableLen = S->tableLen;
         fp.planes = b.d_planes; fp.plane_off = d_planeOff; fp.limits = b.d_limits; fp.limits_off = d_limitsOff;
         void *args[] = {&fp};
         const int blocks = n < S->blocks ? n : S->blocks;
@@ -160,12 +158,12 @@ int run_batch(bbmsa_ctx *c, Batch &b) {
         for (int i = 0; i < n; i++) if (b.jobs()[i].read_len > maxLen) maxLen = b.jobs()[i].read_len;
         const int R = (maxLen + 63) / 64;
         S->lastR = R; S->rMask |= 1 << R;
-        BBHIP(hipLaunchKernel(bbmsa::fast_kernel_mat_for(R, c->banded), dim3((unsigned)blocks), dim3(64), args, (size_t)S->ldsBytes, st));
-        BBHIP(hipMemcpyAsync(b.h_counters, b.d_counters, 64, hipMemcpyDeviceToHost, st));
+        BBHIP(hipLaunchKernel(bbmsa::fast_kernel_mat_for(R, c->sw.banded), dim3((unsigned)blocks), dim3(64), args, (size_t)S->ldsBytes, st));
+        BBHIP(hipMemcpyAsync(b.h_counters, b.d_counters, kLegacyCounterBytes, hipMemcpyDeviceToHost, st));
         BBHIP(hipMemcpyAsync(b.h_slow, b.d_slow, (size_t)n * 4, hipMemcpyDeviceToHost, st));
         { const int rc = download(); if (rc != BBMAP_OK) return rc; }
         BBHIP(hipStreamSynchronize(st));
-        nslow = (int)b.h_counters[1];
+        nslow = (int)b.h_counters[CNT_SLOW_COUNT];
         S->nsWave += since(t0);
         if (nslow == 0) return BBMAP_OK;             // the usual case: one launch, one synchronisation
     } else {
@@ -178,8 +176,8 @@ int run_batch(bbmsa_ctx *c, Batch &b) {
         const int j = b.h_slow[k];
         const bbmsa_job &jb = b.jobs()[j];
         const int rows = jb.read_len, columns = jb.refEndLoc - jb.refStartLoc + 1;
-        BBHIP(hipMemsetAsync(b.d_counters + 2, 0, 4, st));
-        if (c->scheme == BBMSA_SCHEME_11TS) {   // the scratch matrix keeps cells of earlier fills (as the reference's `packed` does); cells this fill does not visit
+        BBHIP(hipMemsetAsync(b.d_counters + CNT_GENERIC_QUEUE, 0, 4, st));
+        if (c->sw.scheme == BBMSA_SCHEME_11TS) {   // the scratch matrix keeps cells of earlier fills (as the reference's `packed` does); cells this fill does not visit
             // are handed out as subfloor, like the wavefront kernel's, so that a fill's planes do not depend on what ran before it
             const long long maxGain = (long long)(rows - 1) * bbmsa::P_MATCH2 + bbmsa::P_MATCH;
             const bool lim = (jb.flags & BBMSA_MODE_MASK) == BBMSA_FILL_LIMITED_RAW;
@@ -188,13 +186,10 @@ int run_batch(bbmsa_ctx *c, Batch &b) {
                 BBHIP(hipMemsetD32Async((hipDeviceptr_t)(c->d_matrix + (long long)s * fullPlane), (int)subfloor,
                                         (size_t)(rows + 1) * (size_t)(columns + 2), st));
         }
-        bbmsa::GenericParams gp;
-        gp.jobs = d_jobs + j; gp.reads = d_bytes; gp.refs = d_bytes; gp.results = b.d_results + j; gp.match = nullptr;
-        gp.list = nullptr; gp.list_count = nullptr; gp.njobs = 1; gp.njobs_dev = nullptr;
-        gp.matrix = c->d_matrix; gp.limits = c->d_limits; gp.queue = b.d_counters + 2;
-        gp.match_stride = 0; gp.maxRows = c->cfg.maxRows; gp.maxColumns = c->cfg.maxColumns;
-        gp.bandwidth = c->cfg.bandwidth; gp.bandwidthRatio = c->cfg.bandwidthRatio;
-        if (c->scheme == BBMSA_SCHEME_9PACBIO)
+        bbmsa::GenericParams gp = {};                 // job j alone, without a list
+        set_batch(gp, c, JobBatch{1, nullptr, d_jobs + j, d_bytes, d_bytes, b.d_results + j, nullptr, 0});
+        gp.matrix = c->d_matrix; gp.limits = c->d_limits; gp.queue = b.d_counters + CNT_GENERIC_QUEUE;
+        if (c->sw.scheme == BBMSA_SCHEME_9PACBIO)
             hipLaunchKernelGGL(bbmsa::msa_fill_generic_kernel<bbmsa::Scheme9PacBio>, dim3(1), dim3(1), 0, st, gp);
         else
             hipLaunchKernelGGL(bbmsa::msa_fill_generic_kernel<bbmsa::Scheme11ts>, dim3(1), dim3(1), 0, st, gp);
@@ -270,7 +265,7 @@ int bbmsa_legacy_create(bbmsa_ctx *c) {
     S->B[0].gen = S->nextGen;
     // geometry of the matrix-materialising wavefront launch
     S->wave = false;
-    if (c->scheme == BBMSA_SCHEME_11TS) {
+    if (c->sw.scheme == BBMSA_SCHEME_11TS) {
         S->R = (maxRows + 63) / 64;
         S->cols = maxCols;
         S->tmpBytes = ((64 * S->R + S->cols + 8) + 3) & ~3;
@@ -280,12 +275,12 @@ int bbmsa_legacy_create(bbmsa_ctx *c) {
         S->tableLen = (S->tableLen + 3) & ~3;
         const int perJob = bbmsa::lds_job_ints(S->cols, S->tmpBytes);
         S->ldsBytes = (bbmsa::lds_table_ints(S->tableLen) + perJob) * 4;
-        c->banded = !(c->cfg.bandwidth < 1 && c->cfg.bandwidthRatio <= 0.0f);
-        const void *kfn = bbmsa::fast_kernel_mat_for(S->R, c->banded);
+        c->sw.banded = !(c->cfg.bandwidth < 1 && c->cfg.bandwidthRatio <= 0.0f);
+        const void *kfn = bbmsa::fast_kernel_mat_for(S->R, c->sw.banded);
         if (kfn && S->ldsBytes <= 160 * 1024) {
             if (S->ldsBytes > 64 * 1024)
                 for (int r = 1; r <= S->R; r++)
-                    BBHIP(hipFuncSetAttribute(bbmsa::fast_kernel_mat_for(r, c->banded), hipFuncAttributeMaxDynamicSharedMemorySize, S->ldsBytes));
+                    BBHIP(hipFuncSetAttribute(bbmsa::fast_kernel_mat_for(r, c->sw.banded), hipFuncAttributeMaxDynamicSharedMemorySize, S->ldsBytes));
             int per = 0;
             BBHIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kfn, 64, S->ldsBytes));
             if (per < 1) per = 1;
