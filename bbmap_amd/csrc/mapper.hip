@@ -22,6 +22,14 @@
 
 namespace bbmapper {
 
+// The argument block of a Dev kernel (mapper_dev.h, DEV_KERNEL): the by-value parameter, or the bytes the launch wrote for it at the
+// start of the kernel-argument segment (Dev is every such kernel's only parameter).  That segment is read-only global memory, so the
+// reference may go to any helper.
+template <bool KARG> __device__ __forceinline__ const Dev &dev_of(const Dev &byValue) {
+    if (KARG) return *(const Dev *)__builtin_amdgcn_kernarg_segment_ptr();
+    return byValue;
+}
+
 __device__ inline int imin(int a, int b) { return a < b ? a : b; }
 __device__ inline int imax(int a, int b) { return a > b ? a : b; }
 __device__ inline int iabsdif(int a, int b) { return a > b ? a - b : b - a; }
@@ -105,7 +113,42 @@ struct Words {
         lo = hi;
         return x;
     }
+    // What the next eight calls of next() return, with their eight loads issued together: one trip to L2 / HBM per 32 bytes of a
+    // stream instead of eight in a row.  Needs n > 0.  A word next() would not load (none of its bytes is below n) is not loaded here
+    // either: the load goes to the last word that holds such a byte, which init() or next() reads as well, and its value is dropped.
+    __device__ void next8(unsigned (&x)[8]) {
+        const int last = (n + sh - 1) >> 2;
+        unsigned hi[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) hi[j] = w[k + j + 1 < last ? k + j + 1 : last];
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            if (k + j + 1 > last) hi[j] = 0u;
+            x[j] = sh ? __builtin_amdgcn_alignbyte(hi[j], lo, (unsigned)sh) : lo;
+            lo = hi[j];
+        }
+        k += 8;
+    }
 };
+// The byte loops below take two streams four bytes at a time (Words::next) or, with Settings.chunkLoads, eight words at a time
+// (Words::next8), and run the same step over every word: step(c4, r4, i) sees bytes i .. i + 3 of both and returns false to stop.
+template <class F> __device__ __forceinline__ void words_loop(const Settings &S, int n, Words &A, Words &B, F step) {
+    if (S.chunkLoads) {
+        for (int i0 = 0; i0 < n; i0 += 32) {
+            unsigned c8[8], r8[8];
+            A.next8(c8); B.next8(r8);
+            // (one copy of the step: the chunk moves down a word per turn instead of being indexed)
+#pragma nounroll
+            for (int i = i0; i < i0 + 32 && i < n; i += 4) {
+                if (!step(c8[0], r8[0], i)) return;
+#pragma unroll
+                for (int j = 0; j < 7; j++) { c8[j] = c8[j + 1]; r8[j] = r8[j + 1]; }
+            }
+        }
+    } else {
+        for (int i = 0; i < n; i += 4) { const unsigned c4 = A.next(), r4 = B.next(); if (!step(c4, r4, i)) return; }
+    }
+}
 // MSA.scoreNoIndels(read, ref, refStart) (MultiStateAligner11tsJNI.java:1034-1089; MultiStateAligner9PacBio.java:1876-1937 is the
 // same statement with its own points)
 __device__ int score_no_indels(const Settings &S, const uint8_t *read, int len, const uint8_t *ref, int reflen, int refStart) {
@@ -117,8 +160,7 @@ __device__ int score_no_indels(const Settings &S, const uint8_t *read, int len, 
     if (n <= 0) return 0;
     Words A, B;
     A.init(read + readStart, n); B.init(ref + refStart + readStart, n);
-    for (int i = 0; i < n; i += 4) {
-        const unsigned c4 = A.next(), r4 = B.next();
+    words_loop(S, n, A, B, [&](unsigned c4, unsigned r4, int i) __attribute__((always_inline)) {
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             if (i + q < n) {
@@ -129,11 +171,12 @@ __device__ int score_no_indels(const Settings &S, const uint8_t *read, int len, 
                 else { if (mode == 1) t++; else t = 0; score += (t + 1 > 5 ? S.ptsSub3 : (t + 1 > 1 ? S.ptsSub2 : S.ptsSub)); mode = 1; }
             }
         }
-    }
+        return true;
+    });
     return score;
 }
 // SiteScore.setPerfect(bases) (current/stream/SiteScore.java:239-292)
-__device__ void set_perfect(Site &ss, const uint8_t *bases, int len, const uint8_t *ref, int reflen) {
+__device__ void set_perfect(const Settings &S, Site &ss, const uint8_t *bases, int len, const uint8_t *ref, int reflen) {
     ss.perfect = 0; ss.semiperfect = 0;
     if (len != ss.stop - ss.start + 1) return;
     bool perfect = true, semi = true;
@@ -146,9 +189,9 @@ __device__ void set_perfect(Site &ss, const uint8_t *bases, int len, const uint8
     if (n > 0) {
         Words A, B;
         A.init(bases + readloc, n); B.init(ref + refloc, n);
-        for (int i = 0; i < n; i += 4) {
-            const unsigned c4 = A.next(), r4 = B.next();
-            if (c4 == r4 && !(((c4 ^ 0x4E4E4E4Eu) - 0x01010101u) & ~(c4 ^ 0x4E4E4E4Eu) & 0x80808080u) && i + 4 <= n) continue;   // four equal bases, none of them 'N'
+        bool gaveUp = false;
+        words_loop(S, n, A, B, [&](unsigned c4, unsigned r4, int i) __attribute__((always_inline)) {
+            if (c4 == r4 && !(((c4 ^ 0x4E4E4E4Eu) - 0x01010101u) & ~(c4 ^ 0x4E4E4E4Eu) & 0x80808080u) && i + 4 <= n) return true;   // four equal bases, none of them 'N'
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 if (i + q < n) {
@@ -156,11 +199,13 @@ __device__ void set_perfect(Site &ss, const uint8_t *bases, int len, const uint8
                     if (c != r || c == 'N') {
                         perfect = false;
                         if (c == 'N') semi = false;
-                        if (r != 'N' || (N = N + 1) > nlimit) return;
+                        if (r != 'N' || (N = N + 1) > nlimit) { gaveUp = true; return false; }
                     }
                 }
             }
-        }
+            return true;
+        });
+        if (gaveUp) return;
     }
     semi = semi && N <= nlimit;
     perfect = perfect && semi && N == 0;
@@ -424,6 +469,50 @@ __device__ inline void wave_add(unsigned *ctr, int v) {
     if ((int)(threadIdx.x & 63) == __builtin_ctzll(m)) atomicAdd(ctr, tot);
 }
 
+// Class lists (Dev.classList).  Appends a lane's reads ra and rb (the mates of its pair; rb < 0: one read) to the long-path (class 0)
+// or the short-path list (class 1), a read of class < 0 to neither.  One reservation per wavefront for both lists and both reads --
+// the two counters are neighbours and take one 64-bit add -- and behind it the lanes' reads in lane order, ra before rb (as
+// slow_round_kernel builds activeOut).  The class only decides which reads share a wavefront: a read on the "wrong" list is
+// processed like any other.
+__device__ inline void class_append(const Dev &D, long long ra, int ca, long long rb, int cb) {
+    const int lane = threadIdx.x & 63;
+    if (D.classSwap) { if (ca >= 0) ca ^= 1; if (cb >= 0) cb ^= 1; }
+    if (rb < 0) cb = -1;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const unsigned long long a0 = __ballot(ca == 0), b0 = __ballot(cb == 0), a1 = __ballot(ca == 1), b1 = __ballot(cb == 1);
+    const unsigned long long any = a0 | b0 | a1 | b1;
+    if (!any) return;
+    const int lead = __builtin_ctzll(any);
+    const unsigned long long n0 = __builtin_popcountll(a0) + __builtin_popcountll(b0), n1 = __builtin_popcountll(a1) + __builtin_popcountll(b1);
+    unsigned long long base = 0;
+    static_assert(CNT_CLASS_SHORT == CNT_CLASS_LONG + 1 && CNT_CLASS_LONG % 2 == 0, "the two class counters are one aligned 64-bit word");
+    if (lane == lead) base = atomicAdd(reinterpret_cast<unsigned long long *>(&D.counters[CNT_CLASS_LONG]), n0 | (n1 << 32));
+    base = __shfl(base, lead);
+    const long long at0 = (long long)(unsigned)base + __builtin_popcountll(a0 & below) + __builtin_popcountll(b0 & below);
+    const long long at1 = D.nreads + (long long)(unsigned)(base >> 32) + __builtin_popcountll(a1 & below) + __builtin_popcountll(b1 & below);
+    if (ca == 0) D.classList[at0] = (int)ra; else if (ca == 1) D.classList[at1] = (int)ra;
+    if (cb == 0) D.classList[at0 + (ca == 0)] = (int)rb; else if (cb == 1) D.classList[at1 + (ca == 1)] = (int)rb;
+}
+// thread t's read in a first round that follows the class lists: the long list, then the short one; -1 beyond both
+__device__ inline long long class_read(const Dev &D, long long t) {
+    const long long nl = D.counters[CNT_CLASS_LONG], ns = D.counters[CNT_CLASS_SHORT];
+    if (t < nl) return D.classList[t];
+    if (t < nl + ns) return D.classList[D.nreads + (t - nl)];
+    return -1;
+}
+// the state score_kernel gives a read without a site list; with class lists such a read is on neither, and begin_kernel writes it
+__device__ inline SlowState slow_finished() {
+    SlowState st; st.idx = 0; st.phase = 3; st.minMsaLimit = 0; st.pending = -1; st.oldJob = -1; st.expectedLen = 0; st.minscore = 0; st.seq = 0;
+    return st;
+}
+// begin_kernel's class of a read with n sites: short path when every site is perfect (score_kernel then has no reference to read,
+// scoreSlow no fill to ask for)
+__device__ inline int begin_class(const Dev &D, long long r, const Site *s, int n) {
+    if (n <= 0) { D.slow[r] = slow_finished(); return -1; }
+    for (int i = 0; i < n; i++) if (!s[i].perfect) return 0;
+    return 1;
+}
+
 // pairSiteScoresInitial (BBMapThread.java:736-940); REQUIRE_CORRECT_STRANDS_PAIRS = true, SAME_STRAND_PAIRS = false
 __device__ void pair_initial(const Settings &S, Site *s1, int &n1, Site *s2, int &n2, int len1, int len2) {
     if (n1 < 1 || n2 < 1) return;
@@ -483,6 +572,7 @@ __global__ __launch_bounds__(128) void begin_kernel(const Dev D) {
         if (n1 < 0 || n2 < 0) {                            // one mate's probe overflowed: the pair is reported, not mapped
             atomicAdd(&D.counters[CNT_OVERFLOWED], (unsigned)((n1 < 0) + (n2 < 0)));
             D.mcount[r1] = n1 < 0 ? -1 : -2; D.mcount[r2] = n2 < 0 ? -1 : -2;
+            if (D.classList) { D.slow[r1] = slow_finished(); D.slow[r2] = slow_finished(); }
             return;                                        // (the overflow tier maps the pair again and counts its removals there)
         }
         if (D.scaf.off) wave_add(&D.counters[CNT_CROSS_SCAFFOLD], drop1 + drop2);
@@ -499,12 +589,13 @@ __global__ __launch_bounds__(128) void begin_kernel(const Dev D) {
         D.mcount[r1] = n1; D.mcount[r2] = n2;
         if (n1 == 0) atomicAdd(&D.counters[CNT_NO_SITE], 1u);
         if (n2 == 0) atomicAdd(&D.counters[CNT_NO_SITE], 1u);
+        if (D.classList) class_append(D, r1, begin_class(D, r1, s1, n1), r2, begin_class(D, r2, s2, n2));
     } else {
         if (u >= D.nreads) return;
         Site *s = D.ms + u * D.cap;
         int drop = 0;
         int n = load_sites(D, u, s, drop);
-        if (n < 0) { atomicAdd(&D.counters[CNT_OVERFLOWED], 1u); D.mcount[u] = -1; return; }
+        if (n < 0) { atomicAdd(&D.counters[CNT_OVERFLOWED], 1u); D.mcount[u] = -1; if (D.classList) D.slow[u] = slow_finished(); return; }
         if (D.scaf.off) wave_add(&D.counters[CNT_CROSS_SCAFFOLD], drop);
         if (D.S.trimList && n > 1) {
             sort_sites<false>(s, n);
@@ -512,16 +603,23 @@ __global__ __launch_bounds__(128) void begin_kernel(const Dev D) {
         }
         D.mcount[u] = n;
         if (n == 0) atomicAdd(&D.counters[CNT_NO_SITE], 1u);
+        if (D.classList) class_append(D, u, begin_class(D, u, s, n), -1, -1);
     }
 }
 
 // ---------------------------------------------------------------------------------------------- stage 2: scoreNoIndels + sort + tip deletions
 // AbstractMapThread.scoreNoIndels (:762-856), Collections.sort, findTipDeletions (:1075-1105), and scoreSlow's opening
 // (BBMapThread.java:255-260).  One thread per read.
-__global__ __launch_bounds__(128) void score_kernel(const Dev D) {
-    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+// (six waves per SIMD, as before the byte loops had chunks: the bound keeps the chunk from costing one)
+#ifndef SCORE_MIN_WAVES
+#define SCORE_MIN_WAVES 6
+#endif
+template <bool KARG> __global__ __launch_bounds__(128, SCORE_MIN_WAVES) void score_kernel(const Dev Darg) {
+    const Dev &D = dev_of<KARG>(Darg);
+    long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= D.nreads) return;
-    SlowState st; st.idx = 0; st.phase = 3; st.minMsaLimit = 0; st.pending = -1; st.oldJob = -1; st.expectedLen = 0; st.minscore = 0; st.seq = 0;
+    if (D.classList && (r = class_read(D, r)) < 0) return;
+    SlowState st = slow_finished();
     const int n = D.mcount[r];
     if (n <= 0) { D.slow[r] = st; return; }
     const bbidx_read rr = D.reads[r];
@@ -538,14 +636,14 @@ __global__ __launch_bounds__(128) void score_kernel(const Dev D) {
             int sw = score_no_indels(D.S, bases, len, ref, reflen, ss.start);
             if (sw < oldScore && oldScore >= maxImp && ss.stop - ss.start + 1 != len) {            // :806-813
                 const int sw2 = score_no_indels(D.S, bases, len, ref, reflen, ss.stop - len + 1);
-                if (sw2 >= maxImp) { sw = sw2; set_start(ss, ss.stop - len + 1); set_perfect(ss, bases, len, ref, reflen); }
+                if (sw2 >= maxImp) { sw = sw2; set_start(ss, ss.stop - len + 1); set_perfect(D.S, ss, bases, len, ref, reflen); }
             }
             set_slow_score(ss, sw); ss.score = sw;
             if (sw >= maxImp) {
                 near++;
                 set_stop(ss, ss.start + len - 1); ss.ngaps = 0;
                 if (sw >= maxSw) ss.perfect = ss.semiperfect = 1;
-                else set_perfect(ss, bases, len, ref, reflen);
+                else set_perfect(D.S, ss, bases, len, ref, reflen);
             } else if (oldScore >= maxImp) force = true;
         }
     }
@@ -561,7 +659,7 @@ __global__ __launch_bounds__(128) void score_kernel(const Dev D) {
                     ss.match_job = -1;
                     set_slow_score(ss, score_no_indels(D.S, bases, len, ref, reflen, ss.start));
                     if (ss.slowScore == maxSw) { set_stop(ss, ss.start + len - 1); ss.perfect = ss.semiperfect = 1; }
-                    else { ss.perfect = 0; set_perfect(ss, bases, len, ref, reflen); }
+                    else { ss.perfect = 0; set_perfect(D.S, ss, bases, len, ref, reflen); }
                     s[j] = ss;
                 }
             }
@@ -590,13 +688,24 @@ __device__ inline bbmsa_job make_job(const Dev &D, const bbidx_read &rr, const S
 // NO_ROOM when that log is full: the caller then leaves its state untouched and asks again in the next round, before which the host
 // has grown the log (the reference's lists have no capacity; nothing may be lost or the batch refused because a log was sized too small)
 constexpr int NO_ROOM = -2;
+// A log slot for every lane that is here: one atomicAdd for all of them (the lanes of a wavefront that emit in the same turn of their
+// loops), slots in lane order.  With the class lists a wavefront of the first round is all fills, and one add per fill on one word
+// is what the round then waits for; the counter ends at the same value either way.
+__device__ inline unsigned wave_slot(unsigned *ctr) {
+    const unsigned long long m = __ballot(true);
+    const int lane = threadIdx.x & 63, lead = __builtin_ctzll(m);
+    unsigned base = 0;
+    if (lane == lead) base = atomicAdd(ctr, (unsigned)__builtin_popcountll(m));
+    base = __shfl(base, lead);
+    return base + (unsigned)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+}
 __device__ int emit_fill(const Dev &D, long long r, const bbidx_read &rr, const Site &ss, int site, int pad, int minscore, int kind, int seq) {
     bbmap_jobinfo info; info.read = (int)r; info.seq = seq; info.kind = kind; info.site = site;
     const bbmsa_job j = make_job(D, rr, ss, pad, minscore);
     // the wide list (second DP context: BBMap's 3000 columns) takes the sites with a gap array and the windows wider than the
     // first context's column limit; a job without gaps is an ordinary job there
     if (ss.ngaps || (imin(j.ref_len - 1, j.refEndLoc) - imax(0, j.refStartLoc) + 1) > D.plainColumns) {
-        const unsigned k = atomicAdd(&D.counters[CNT_GAPPED_FILLS], 1u);
+        const unsigned k = D.classList ? wave_slot(&D.counters[CNT_GAPPED_FILLS]) : atomicAdd(&D.counters[CNT_GAPPED_FILLS], 1u);
         if ((long long)k >= D.gjobCap) return NO_ROOM;
         D.gjobs[k] = j; D.ginfo[k] = info;
         bbmsa_gaps g; g.ngaps = ss.ngaps;
@@ -604,7 +713,7 @@ __device__ int emit_fill(const Dev &D, long long r, const bbidx_read &rr, const 
         D.ggaps[k] = g;
         return (int)k | GAPPED_BIT;
     }
-    const unsigned k = atomicAdd(&D.counters[CNT_FILLS], 1u);
+    const unsigned k = D.classList ? wave_slot(&D.counters[CNT_FILLS]) : atomicAdd(&D.counters[CNT_FILLS], 1u);
     if ((long long)k >= D.jobCap) return NO_ROOM;
     D.jobs[k] = j; D.jinfo[k] = info;
     return (int)k;
@@ -623,7 +732,7 @@ __device__ void finish_site(const Dev &D, SlowState &st, Site &ss, int job, cons
     st.minMsaLimit = imax(st.minMsaLimit, ss.slowScore - D.S.clearzone3);
     ss.perfect = (ss.slowScore == maxSw);
     if (ss.perfect) ss.semiperfect = 1;
-    else if (!ss.semiperfect) set_perfect(ss, bases, len, D.chromArr[ss.chrom], D.chromArrLen[ss.chrom]);
+    else if (!ss.semiperfect) set_perfect(D.S, ss, bases, len, D.chromArr[ss.chrom], D.chromArrLen[ss.chrom]);
 }
 
 // scoreSlow's per-site opening (BBMapThread.java:278-303): a site whose span differs from the read length loses its ungapped
@@ -643,7 +752,7 @@ __device__ inline int prepare_site(const Settings &S, Site &ss, int len, int &ex
 __device__ inline bbmap_jobinfo &job_info(const Dev &D, int job) { return (job & GAPPED_BIT) ? D.ginfo[job & ~GAPPED_BIT] : D.jinfo[job]; }
 
 // One round: every active read consumes the result of its fill in flight and moves on to its next fill (or finishes).
-// activeIn == nullptr: every read of the batch (round 1).
+// activeIn == nullptr: every read of the batch (round 1), in the class lists' order when there are lists.
 //
 // Fills ahead of time.  Strictly one fill per read and round would make a read with m candidate sites take m rounds, and a
 // round costs the latency of a whole DP launch sequence however few jobs it holds.  A site's fill depends on the sites before
@@ -653,13 +762,17 @@ __device__ inline bbmap_jobinfo &job_info(const Dev &D, int job) { return (job &
 // minScore used).  When the loop reaches such a site it recomputes the minScore the reference would use: equal -> the finished
 // fill IS the reference's fill and is adopted (numbered in the read's sequence at that moment); different -> it is dropped
 // (its log entry keeps seq = -1) and the site is filled again.  Results are those of the sequential loop in every case.
-__global__ __launch_bounds__(128) void slow_round_kernel(const Dev D) {
+// (five waves per SIMD, as before the byte loops had chunks)
+#ifndef SLOW_ROUND_MIN_WAVES
+#define SLOW_ROUND_MIN_WAVES 5
+#endif
+__global__ __launch_bounds__(128, SLOW_ROUND_MIN_WAVES) void slow_round_kernel(const Dev D) {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long count = D.activeIn ? D.nActiveIn : D.nreads;
     bool stillActive = false;
     long long r = -1;
-    if (t < count) {
-        r = D.activeIn ? D.activeIn[t] : t;
+    if (t < count) r = D.activeIn ? D.activeIn[t] : (D.classList ? class_read(D, t) : t);
+    if (r >= 0) {
         SlowState st = D.slow[r];
         if (st.phase != 3) {
             const bbidx_read rr = D.reads[r];
@@ -827,7 +940,8 @@ __global__ __launch_bounds__(128) void rescue_plan_kernel(const Dev D) {
 
 // rescue()'s body after quickRescue + slowRescue up to its fill (AbstractMapThread.java:1222-1226, :1246-1265).  One thread per
 // pair, its searches in anchor order (a read's fills are numbered in the order the reference issues them).
-__global__ __launch_bounds__(128) void rescue_prep_kernel(const Dev D) {
+template <bool KARG> __global__ __launch_bounds__(128, 5) void rescue_prep_kernel(const Dev Darg) {
+    const Dev &D = dev_of<KARG>(Darg);
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (2 * p + 1 >= D.nreads) return;
     const PairResc pr = D.pres[p];
@@ -901,7 +1015,7 @@ __global__ __launch_bounds__(128) void rescue_finish_kernel(const Dev D) {
         ss.reserved[0] = ss.reserved[1] = 0;
         ss.pairedScore = ss.score + 1;
         ss.perfect = (ss.slowScore == maxScore);
-        if (ss.perfect) ss.semiperfect = 1; else set_perfect(ss, bases, L, ref, reflen);
+        if (ss.perfect) ss.semiperfect = 1; else set_perfect(D.S, ss, bases, L, ref, reflen);
         if (ss.score > pr.retainLimit && ss.start >= 0 && ss.stop <= reflen - 1) {
             Site &ssa = sa[ri.anchorSite];
             if (ss.score > pr.retainLimit2) {
@@ -916,6 +1030,11 @@ __global__ __launch_bounds__(128) void rescue_finish_kernel(const Dev D) {
 }
 
 #include "mapper_final.h"
+
+// both builds of the kernels that come in two (the host picks one per context, DEV_KERNEL)
+#define DEV_KERNEL_BUILDS(name) template __global__ void name<false>(const Dev); template __global__ void name<true>(const Dev);
+DEV_KERNEL_BUILDS(score_kernel) DEV_KERNEL_BUILDS(rescue_prep_kernel) DEV_KERNEL_BUILDS(final_round_kernel)
+#undef DEV_KERNEL_BUILDS
 
 // ---------------------------------------------------------------------------------------------- reads the probe leaves alone
 // The probe writes the reverse complement of the reads it probes.  A read shorter than k or without a key is not probed (quickMap's

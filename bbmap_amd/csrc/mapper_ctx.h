@@ -36,6 +36,7 @@ struct bbmap_ctx {
     bbmap_msite *d_ms; int *d_mcount, *d_near;
     bbmapper::SlowState *d_slow;
     int *d_active[2];
+    int *d_classList;               // Dev.classList: the long-path and the short-path read list (2 x max_reads), null without classOrder
     unsigned *d_counters;
     bbmsa_job *d_jobs; bbmap_jobinfo *d_jinfo; bbmsa_result *d_results; uint8_t *d_match;
     bbmsa_job *d_gjobs; bbmsa_gaps *d_ggaps; bbmap_jobinfo *d_ginfo; bbmsa_result *d_gresults; uint8_t *d_gmatch;
@@ -57,6 +58,9 @@ struct bbmap_ctx {
     long long narrowMinJobs;        // plain-context launches with at least this many fills run the narrow kernel (BBMAP_NARROW_MIN_JOBS)
     bool sortWide;                  // the second context hands its fills on widest first (BBMAP_SORT_WIDE=0 switches it off)
     bool sortPlain;                 // so does the first context where it runs the band kernel (BBMAP_SORT_PLAIN=0 switches it off)
+    bool classSwap;                 // BBMAP_CLASS_ORDER=2: the two lists swapped (tests: a read on the wrong list only costs time)
+    bool classOrder;                // first rounds take their reads by class (BBMAP_CLASS_ORDER=0 switches it off)
+    bool kernargDev;                // score / rescue_prep / final_round kernels read Dev in the kernel-argument segment (BBMAP_KERNARG_DEV=0: by value)
     int *d_tierUnits; bbidx_read *d_tierReads; int *d_tierReadIds;
     long long tierReads;            // reads the tier mapped in the last batch
     // The tier's pass runs beside the main pass (its reads are known once begin_kernel has run): its own stream, driven by its

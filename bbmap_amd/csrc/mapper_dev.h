@@ -36,6 +36,7 @@ struct Settings {
     // the mapping thread's tail (final_begin_kernel / final_end_kernel): 0 = BBMapThread's, 1 = BBMapThreadPacBio's; its clearzones
     // CLEARZONEP / CLEARZONE1 / 1b / 1c = (int)(CLEARZONE_RATIO* x POINTS_MATCH2), CLEARZONE_LIMIT1e (BBMapThread only)
     int finalPolicy, czP, cz1, cz1b, cz1c, czLimit1e;
+    int chunkLoads;             // BBMAP_CHUNK_LOADS: the byte loops load eight words per stream ahead of their use (Words::next8)
 };
 
 struct SlowState {      // scoreSlow's loop state of one read
@@ -70,6 +71,8 @@ enum {
     CNT_RESCUE_FILLS = 7,       // rescue fills
     CNT_FILLS_DROPPED = 8,      // fills ahead of time that were dropped
     CNT_CROSS_SCAFFOLD = 9,     // sites quickMap's tail removed for spanning two scaffolds
+    CNT_CLASS_LONG = 10,        // reads on the long-path class list (begin_kernel's, then final_begin_kernel's)
+    CNT_CLASS_SHORT = 11,       // reads on the short-path class list, the word behind it
     CNT_TIER_FOUND = 16,        // units collect_overflow_kernel found for the overflow tier
     CNT_TIER_RESOLVED = 17,     // overflowed reads the tier gave a list (mark_tier_kernel)
     CNT_POOL_UNITS = 20,        // pool units handed out (beyond the capacity once a request failed)
@@ -99,6 +102,12 @@ struct Dev {
     int *nearArr;
     SlowState *slow;
     const int *activeIn; int *activeOut; int nActiveIn;
+    // Class lists (BBMAP_CLASS_ORDER, nullptr = off): the reads with work ahead of them ("long path": a site that is not perfect) in
+    // [0, nreads), the others ("short path") in [nreads, 2 * nreads), CNT_CLASS_LONG / CNT_CLASS_SHORT entries.  begin_kernel writes
+    // them for score_kernel and scoreSlow's first round, final_begin_kernel for genMatchString's first round: those launches take
+    // their reads long list first, so that a wavefront holds one kind of read and does not last as long as its one slow lane.
+    int *classList;
+    int classSwap;              // BBMAP_CLASS_ORDER=2 (tests): every read goes to the OTHER list -- results must not depend on the class
     unsigned *counters;         // CNT_*
     bbmsa_job *jobs; bbmap_jobinfo *jinfo; const bbmsa_result *results; long long jobCap;
     bbmsa_job *gjobs; bbmsa_gaps *ggaps; bbmap_jobinfo *ginfo; const bbmsa_result *gresults; long long gjobCap;
@@ -137,15 +146,22 @@ struct FinalRead {
 };
 
 // ---- the kernels the host launches (defined in mapper.hip and mapper_final.h)
+// score_kernel, rescue_prep_kernel and final_round_kernel come in two builds.  KARG = false reads the by-value argument as written;
+// where its address is needed (a helper that takes `const Dev &` or `const Settings &` and is not inlined) the compiler then copies
+// all of it to private memory, in every lane of every launch -- these three do.  KARG = true reads the same bytes where the launch
+// put them, in the kernel-argument segment, through a reference: no copy.  DEV_KERNEL picks the build (bbmap_ctx.kernargDev,
+// BBMAP_KERNARG_DEV).  The other Dev kernels keep their argument in SGPRs as they are and have one build (slow_round_kernel's first
+// round took 2.0 ms with the reference against 0.8 by value: DESIGN 8, "the per-read kernels").
+#define DEV_KERNEL(c, name) ((c)->kernargDev ? name<true> : name<false>)
 __global__ void begin_kernel(const Dev D);
-__global__ void score_kernel(const Dev D);
+template <bool KARG> __global__ void score_kernel(const Dev D);
 __global__ void slow_round_kernel(const Dev D);
 __global__ void finish_kernel(const Dev D);
 __global__ void rescue_plan_kernel(const Dev D);
-__global__ void rescue_prep_kernel(const Dev D);
+template <bool KARG> __global__ void rescue_prep_kernel(const Dev D);
 __global__ void rescue_finish_kernel(const Dev D);
 __global__ void final_begin_kernel(const Dev D);
-__global__ void final_round_kernel(const Dev D);
+template <bool KARG> __global__ void final_round_kernel(const Dev D);
 __global__ void final_end_kernel(const Dev D);
 __global__ void final_local_kernel(const Dev D);
 __global__ void revcomp_unprobed_kernel(const bbidx_read *reads, long long n, int k, const uint8_t *in, uint8_t *out);

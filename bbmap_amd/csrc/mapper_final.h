@@ -237,7 +237,7 @@ __device__ bool clip_tip_indels(const Dev &D, Site &ss, const uint8_t *bases, in
         const int oldScore = ss.slowScore;
         set_slow_score(ss, msa_score_match(D.S, match, n));
         ss.score = ss.score + (ss.slowScore - oldScore);
-        set_perfect(ss, bases, L, D.chromArr[ss.chrom], D.chromArrLen[ss.chrom]);
+        set_perfect(D.S, ss, bases, L, D.chromArr[ss.chrom], D.chromArrLen[ss.chrom]);
     }
     return left | right;
 }
@@ -296,7 +296,7 @@ __device__ bool fix_xy(const Dev &D, Site &ss, const uint8_t *bases, int L) {
     const int oldScore = ss.slowScore;
     set_slow_score(ss, msa_score_match(D.S, match, n));
     ss.score = ss.score + (ss.slowScore - oldScore);
-    set_perfect(ss, bases, L, D.chromArr[ss.chrom], D.chromArrLen[ss.chrom]);
+    set_perfect(D.S, ss, bases, L, D.chromArr[ss.chrom], D.chromArrLen[ss.chrom]);
     return success;
 }
 __device__ void fix_limits_xy(const Dev &D, Site &ss) {                         // SiteScore.fixLimitsXY (:916-931)
@@ -315,8 +315,7 @@ __device__ int score_no_indels_match(const Settings &S, const uint8_t *read, int
     unsigned acc = 0;
     Words A, B;                                                      // (aligned word loads of the read and the reference, as scoreNoIndels)
     A.init(read, len); B.init(ref + refStart, len);
-    for (int i0 = 0; i0 < len; i0 += 4) {
-        const unsigned c4 = A.next(), r4 = B.next();
+    words_loop(S, len, A, B, [&](unsigned c4, unsigned r4, int i0) __attribute__((always_inline)) {
         acc = 0;
 #pragma unroll
         for (int q = 0; q < 4; q++) {
@@ -332,7 +331,8 @@ __device__ int score_no_indels_match(const Settings &S, const uint8_t *read, int
             }
         }
         if (i0 + 4 <= len) mw[i0 >> 2] = acc;
-    }
+        return true;
+    });
     for (int i = len & ~3; i < len; i++) match[i] = (uint8_t)(acc >> (8 * (i & 3)));
     return score;
 }
@@ -544,9 +544,14 @@ __device__ inline void gen_begin(FinalRead &f, int n) {      // genMatchString's
     if (n > 0) { f.pc = PC_SITE_LOOP; f.i = 0; f.best = INT_MIN; f.scoreChanged = 0; f.sorting = 0; }
 }
 
+// final_begin_kernel's class of a read (class_append): genMatchString starts at the top site, and a perfect one only gets its 'm's;
+// a read without sites has finished (PC_DONE) and is on neither list
+__device__ inline int final_class(const Site *s, int n) { return n <= 0 ? -1 : (s[0].perfect ? 1 : 0); }
+
 // ---------------------------------------------------------------------------------------------- kernel 1: policy before genMatchString
 // single-ended: BBMapThread.java:504-557; paired: :1116-1206.  One thread per read / pair.
-__global__ __launch_bounds__(128) void final_begin_kernel(const Dev D) {
+// (six waves per SIMD, as before the class lists: unbounded, their append costs four VGPRs and with them a wave)
+__global__ __launch_bounds__(128, 6) void final_begin_kernel(const Dev D) {
     const long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const Settings &S = D.S;
     if (S.paired) {
@@ -574,6 +579,7 @@ __global__ __launch_bounds__(128) void final_begin_kernel(const Dev D) {
         gen_begin(f1, n1); gen_begin(f2, n2);
         D.mcount[r1] = n1; D.mcount[r2] = n2;
         D.fin[r1] = f1; D.fin[r2] = f2;
+        if (D.classList) class_append(D, r1, final_class(s1, n1), r2, final_class(s2, n2));
     } else {
         if (u >= D.nreads) return;
         FinalRead f; fin_init(f, D.slow[u].seq);
@@ -605,6 +611,7 @@ __global__ __launch_bounds__(128) void final_begin_kernel(const Dev D) {
         gen_begin(f, n);
         D.mcount[u] = n;
         D.fin[u] = f;
+        if (D.classList) class_append(D, u, final_class(s, n), -1, -1);
     }
 }
 
@@ -726,7 +733,17 @@ __device__ bool final_advance(const Dev &D, long long r, FinalRead &f, PreAlloc 
                 if (gsyms == 0) {                                               // (log slots and pool strings both start on 4-byte boundaries)
                     const unsigned *sw = reinterpret_cast<const unsigned *>(src);
                     unsigned *dw = reinterpret_cast<unsigned *>(m);
-                    for (int q = 0; q < (clen >> 2); q++) dw[q] = sw[q];
+                    int q = 0;
+                    if (S.chunkLoads) {                                         // eight loads on their way before the first store
+                        for (; q + 8 <= (clen >> 2); q += 8) {
+                            unsigned t8[8];
+#pragma unroll
+                            for (int j = 0; j < 8; j++) t8[j] = sw[q + j];
+#pragma unroll
+                            for (int j = 0; j < 8; j++) dw[q + j] = t8[j];
+                        }
+                    }
+                    for (; q < (clen >> 2); q++) dw[q] = sw[q];
                     for (int q = clen & ~3; q < clen; q++) m[q] = src[q];
                 } else {
                     int o = 0;
@@ -756,7 +773,7 @@ __device__ bool final_advance(const Dev &D, long long r, FinalRead &f, PreAlloc 
                 }
                 if (f.fixXY && match_contains_xy(m, mlen)) fix_xy(D, ss, bases, L);
             }
-            set_perfect(ss, bases, L, D.chromArr[ss.chrom], D.chromArrLen[ss.chrom]);
+            set_perfect(D.S, ss, bases, L, D.chromArr[ss.chrom], D.chromArrLen[ss.chrom]);
             s[cur] = ss; f.pc = PC_GEN_AFTER_REALIGN;
             break;
         }
@@ -777,7 +794,7 @@ __device__ bool final_advance(const Dev &D, long long r, FinalRead &f, PreAlloc 
                 }
             }
             if (maxSw == ss.slowScore) ss.perfect = ss.semiperfect = 1;         // SiteScore.setPerfectFlag
-            else set_perfect(ss, bases, L, D.chromArr[ss.chrom], D.chromArrLen[ss.chrom]);
+            else set_perfect(D.S, ss, bases, L, D.chromArr[ss.chrom], D.chromArrLen[ss.chrom]);
             s[cur] = ss; f.pc = PC_GEN_CLIP;
             break;
         }
@@ -861,18 +878,22 @@ __device__ int first_request(const Dev &D, long long r, const FinalRead &f) {
 
 // (Left to itself the compiler gives this state machine 248 VGPRs -- site records are 32 registers each -- and ONE wavefront per SIMD,
 // for a kernel that waits on scattered loads.  Asked for 4 blocks per CU it keeps 128 and spills 112 bytes more per lane: the final
-// stage 74.9 -> 72.6 ms; at 6 / 8 blocks (80 / 64 VGPRs) the spills cost more than the waves bring: 77.2 / 77.4.)
+// stage 74.9 -> 72.6 ms; at 6 / 8 blocks (80 / 64 VGPRs) the spills cost more than the waves bring: 77.2 / 77.4.  Run again with
+// Dev out of its scratch (KARG, 1,232 -> 656 bytes per lane): the kernel's eleven launches of a step take 5.70 / 6.13 / 8.20 ms at
+// 4 / 6 / 8, profiles/glue_variants.md.)
 #ifndef FINAL_ROUND_MIN_BLOCKS
 #define FINAL_ROUND_MIN_BLOCKS 4
 #endif
-__global__ __launch_bounds__(128, FINAL_ROUND_MIN_BLOCKS) void final_round_kernel(const Dev D) {
+template <bool KARG> __global__ __launch_bounds__(128, FINAL_ROUND_MIN_BLOCKS) void final_round_kernel(const Dev Darg) {
+    const Dev &D = dev_of<KARG>(Darg);
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long count = D.activeIn ? D.nActiveIn : D.nreads;
     const int lane = threadIdx.x & 63;
     bool stillActive = false;
     long long r = -1;
     FinalRead f; f.pc = PC_DONE;
-    if (t < count) { r = D.activeIn ? D.activeIn[t] : t; f = D.fin[r]; }
+    if (t < count) r = D.activeIn ? D.activeIn[t] : (D.classList ? class_read(D, t) : t);
+    if (r >= 0) f = D.fin[r];
     // one pool request per wavefront for the reads' first strings: inclusive prefix sum of the lanes' units, one atomicAdd
     PreAlloc pre; pre.ref = 0; pre.units = 0;
     {

@@ -155,6 +155,12 @@ static int create_impl(bbidx_ctx *index, const bbmap_config *cfg, bbmap_ctx *par
     c->narrowMinJobs = getenv("BBMAP_NARROW_MIN_JOBS") ? atoll(getenv("BBMAP_NARROW_MIN_JOBS")) : 32768;
     c->sortWide = !(getenv("BBMAP_SORT_WIDE") && atoi(getenv("BBMAP_SORT_WIDE")) == 0);      // (experiments: 0 switches the width order off)
     c->sortPlain = !(getenv("BBMAP_SORT_PLAIN") && atoi(getenv("BBMAP_SORT_PLAIN")) == 0);
+    // the per-read kernels (0 switches a part off for A/B runs): first rounds in class order, Dev read in
+    // place, chunked loads in the byte loops
+    c->classOrder = !(getenv("BBMAP_CLASS_ORDER") && atoi(getenv("BBMAP_CLASS_ORDER")) == 0);
+    c->classSwap = getenv("BBMAP_CLASS_ORDER") && atoi(getenv("BBMAP_CLASS_ORDER")) == 2;       // (tests: every read on the other list)
+    c->kernargDev = !(getenv("BBMAP_KERNARG_DEV") && atoi(getenv("BBMAP_KERNARG_DEV")) == 0);
+    S.chunkLoads = !(getenv("BBMAP_CHUNK_LOADS") && atoi(getenv("BBMAP_CHUNK_LOADS")) == 0);
     if (!pacbio) {
         // the 64-lane launches (latency route, wide pass) give unlimited fills the prune-free step loop; BBMAP_WIDE_UNLIMITED=0: no
         const bool wideUnl = !(getenv("BBMAP_WIDE_UNLIMITED") && atoi(getenv("BBMAP_WIDE_UNLIMITED")) == 0);
@@ -184,6 +190,8 @@ static int create_impl(bbidx_ctx *index, const bbmap_config *cfg, bbmap_ctx *par
     DA(c->d_ms, n * cap); DA(c->d_mcount, n); DA(c->d_near, n);
     DA(c->d_slow, n);
     DA(c->d_active[0], n); DA(c->d_active[1], n);
+    c->d_classList = nullptr;
+    if (c->classOrder) DA(c->d_classList, 2 * n);
     DA(c->d_counters, CNT_WORDS);
     DA(c->d_jobs, c->jobCap); DA(c->d_jinfo, c->jobCap); DA(c->d_results, c->jobCap); DA(c->d_match, c->jobCap * c->matchStride);
     DA(c->d_gjobs, c->gjobCap); DA(c->d_ggaps, c->gjobCap); DA(c->d_ginfo, c->gjobCap); DA(c->d_gresults, c->gjobCap); DA(c->d_gmatch, c->gjobCap * c->gmatchStride);
@@ -414,11 +422,12 @@ static int run_final_stage(bbmap_ctx *c, hipStream_t stream, Dev &D, int64_t n_r
     const unsigned *h = c->h_counters;
     D.fin = c->d_fin; D.finalOut = c->d_final; D.pool = c->d_pool; D.poolUnits = c->poolUnits;
     D.match = c->d_match; D.gmatch = c->d_gmatch; D.matchStride = c->matchStride; D.gmatchStride = c->gmatchStride;
+    if (D.classList) BBHIP(hipMemsetAsync(c->d_counters + CNT_CLASS_LONG, 0, 8, stream));       // and CNT_CLASS_SHORT behind it
     BBTRY(launch<128>(final_begin_kernel, units, stream, D));
     Rounds R; R.finalStage = true; R.jobBase = jobBase; R.gBase = gBase; R.nActive = n_reads;
     for (int round = 0; R.nActive > 0; round++) {
         if (round > 64 * c->cfg.max_sites + 64) return bbfail(BBMAP_E_HIP, "bbmap_map_batch_device: the final stage does not come to an end (internal error)");
-        BBTRY(round_begin(c, stream, D, R, final_round_kernel));
+        BBTRY(round_begin(c, stream, D, R, DEV_KERNEL(c, final_round_kernel)));
         BBTRY(round_end(c, stream, D, R, bases));
         if (h[CNT_POOL_FAILED] > 0) {           // the match-string pool was full for some reads: they repeat their step next round
             const long long used = h[CNT_POOL_AT_FAILURE];                      // units handed out before the first request that failed
@@ -447,6 +456,7 @@ static void fill_dev(bbmap_ctx *c, Dev &D, int64_t n_reads, const bbidx_read *re
     D.chromArr = c->d_chromArr; D.chromArrLen = c->d_chromArrLen; D.refsBase = c->refsBase;
     D.psites = c->d_psites; D.pnsites = c->d_pnsites; D.maxSites = c->cfg.max_sites;
     D.ms = c->d_ms; D.mcount = c->d_mcount; D.cap = c->cfg.max_sites; D.nearArr = c->d_near; D.slow = c->d_slow;
+    D.classList = c->d_classList; D.classSwap = c->classSwap ? 1 : 0;
     D.counters = c->d_counters; D.plainColumns = c->plainColumns; D.fillAhead = c->cfg.reserved[0] ? 0 : 1;
     D.jobs = c->d_jobs; D.jinfo = c->d_jinfo; D.results = c->d_results; D.jobCap = c->jobCap;
     D.gjobs = c->d_gjobs; D.ggaps = c->d_ggaps; D.ginfo = c->d_ginfo; D.gresults = c->d_gresults; D.gjobCap = c->gjobCap;
@@ -503,7 +513,7 @@ static int map_records(bbmap_ctx *c, hipStream_t stream, int64_t n_reads, const 
         BBTRY(launch<128>(collect_overflow_kernel, units, stream, c->d_mcount, units, c->cfg.paired, c->d_tierUnits, c->d_counters + CNT_TIER_FOUND));
     }
     BBHIP(hipEventRecord(c->ev[EV_BEGIN_END], stream));
-    BBTRY(launch<128>(score_kernel, n_reads, stream, D));
+    BBTRY(launch<128>(DEV_KERNEL(c, score_kernel), n_reads, stream, D));
     BBHIP(hipEventRecord(c->ev[EV_SCORE_END], stream));
     // ---- scoreSlow in rounds
     Rounds R; R.finalStage = false; R.jobBase = R.gBase = 0; R.nActive = n_reads;
@@ -546,7 +556,7 @@ static int map_records(bbmap_ctx *c, hipStream_t stream, int64_t n_reads, const 
             BBHIP(hipEventRecord(q1, stream));
             // every search issues at most one fill, into either log: room for all of them before the kernel that writes them
             if (jobBase + nsearch > c->jobCap || gBase + nsearch > c->gjobCap) BBTRY(grow_logs(c, stream, D, jobBase + nsearch, gBase + nsearch, jobBase, gBase));
-            BBTRY(launch<128>(rescue_prep_kernel, pairs, stream, D));
+            BBTRY(launch<128>(DEV_KERNEL(c, rescue_prep_kernel), pairs, stream, D));
             BBTRY(read_counters(c, stream));
             { float ms = 0; if (hipEventElapsedTime(&ms, q0, q1) == hipSuccess) c->stats.ms_quick_rescue += ms; }
             const long long total = c->h_counters[CNT_FILLS], gtotal = c->h_counters[CNT_GAPPED_FILLS];
