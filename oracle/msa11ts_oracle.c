@@ -433,7 +433,16 @@ void orc_fill_limited_raw(orc_msa *m, const uint8_t *read, int read_len,
             /* :660-668 row end + right sentinel in the row above */
             if (col >= colStop) {
                 if (col > colStop && (maxGoodCol < col || halfband > 0)) break;
+                /* col + 1 > maxColumns happens only with columns == maxColumns.  The 11ts JNI C keeps flat planes and performs the
+                 * write (jni/MultiStateAligner11tsJNI.c:660-667): it lands on column 0 of `row`, the constructor's seed column, which
+                 * row + 1 reads as its diagonal, in this fill and in every later one of the object.  That is the reference's
+                 * behaviour and is restated.  MultiStateAligner9PacBio is Java alone: packed[..][row-1] has no element
+                 * maxColumns + 1 (the write would throw), so its restatement must not spoil a neighbouring cell instead. */
+#ifdef ORC_PACBIO
+                if (row > 1 && col < m->maxColumns) {
+#else
                 if (row > 1) {
+#endif
                     M[up + col + 1] = subfloor; I[up + col + 1] = subfloor; D[up + col + 1] = subfloor;
                 }
             }
