@@ -24,7 +24,8 @@ EXPORTS = [
     "bbidx_build_profile", "bbkeys_default_config", "bbkeys_make", "bbkeys_make_batch", "bbmap_default_config_profile",
     "bbmap_get_final", "bbmap_set_average_pair_dist", "bbmap_final_batch_device", "bbmap_untrim_batch_device",
     "bbidx_set_scaffolds", "bbmap_get_scaffold_records",
-    "bbmap_get_sam_records", "bbmap_get_sam",
+    "bbmap_get_sam_records", "bbmap_get_sam", "bbmap_sam_default_config", "bbmap_get_sam_records_cfg", "bbmap_get_sam_cfg",
+    "bbpipe_sam_records_workspace_bytes", "bbpipe_sam_records_device",
     "bbkeys_device_workspace_bytes", "bbkeys_make_batch_device",
     "bbpipe_run_stats_device", "bbmap_add_run_stats", "bbmap_get_run_stats", "bbmap_reset_run_stats", "bbmap_set_adaptive", "bbmap_set_truth",
     "bbmap_get_adaptive_state",

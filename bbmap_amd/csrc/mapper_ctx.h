@@ -79,6 +79,7 @@ struct bbmap_ctx {
     int *d_scafTier = nullptr;
     // bbmap_get_sam_records: records, per-read byte counts and their prefix sums, the MAPQ table (allocated on first use)
     bbmap_samrec *d_samRec = nullptr;
+    bbmap_samtags *d_samTags = nullptr;     // (bbmap_get_sam_records_cfg with tags wanted: on its first use)
     int *d_samCounts = nullptr;
     long long *d_samOffsets = nullptr;
     float *d_mapqMax = nullptr;

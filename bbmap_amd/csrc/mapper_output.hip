@@ -2,6 +2,7 @@
 // log and final records, scaffold records, SAM records, run statistics, coverage, read histograms, reference-set binning.
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstring>
 #include <initializer_list>
 #include <memory>
@@ -226,14 +227,34 @@ extern "C" int bbmap_get_scaffold_records(bbmap_ctx *c, void *stream_, const bbm
     return scaffold_records(c, (hipStream_t)stream_, &V, out);
 }
 
-// SamLine's remaining fields for the last batch (sam_records.hip): the coordinate kernel, the sizing pass, a device-wide exclusive scan
-// of the per-read byte counts, the emit pass.  The blob's size comes back once between the scan and the emit pass (it sizes the blob).
-extern "C" int bbmap_get_sam_records(bbmap_ctx *c, void *stream_, int32_t flags, const bbmap_samrec **recs, const uint8_t **text,
-                                     int64_t *text_bytes) {
-    if (!c || !recs || !text) return bbfail(BBMAP_E_ARG, "bbmap_get_sam_records: null argument");
-    if (flags & ~(BBMAP_SAM_CIGAR13 | BBMAP_SAM_MD)) return bbfail(BBMAP_E_ARG, "bbmap_get_sam_records: unknown flag bits");
-    hipStream_t stream = (hipStream_t)stream_;
-    bbsam::Args a;
+// ---- SAM records (sam_records.hip)
+static const int SAM_ALL_FLAGS = BBMAP_SAM_CIGAR13 | BBMAP_SAM_MD;
+static const int SAM_ALL_TAGS = BBMAP_SAM_MAKE_NM | BBMAP_SAM_MAKE_AM | BBMAP_SAM_MAKE_SM | BBMAP_SAM_MAKE_XM | BBMAP_SAM_MAKE_XS |
+                                BBMAP_SAM_XS_SECONDSTRAND | BBMAP_SAM_MAKE_NH | BBMAP_SAM_MAKE_STOP | BBMAP_SAM_MAKE_LENGTH |
+                                BBMAP_SAM_MAKE_IDENTITY | BBMAP_SAM_MAKE_SCORE | BBMAP_SAM_MAKE_INSERT | BBMAP_SAM_MAKE_BOUNDS | BBMAP_SAM_NO_TAGS;
+static const int SAM_MAX_READ_LEN = 6016;                   // bbmap_config.max_read_len's limit
+
+extern "C" int bbmap_sam_default_config(bbmap_sam_config *cfg) {
+    if (!cfg) return bbfail(BBMAP_E_ARG, "bbmap_sam_default_config: null argument");
+    memset(cfg, 0, sizeof *cfg);
+    cfg->intronLimit = INT32_MAX;                           // SamLine.INTRON_LIMIT = Integer.MAX_VALUE (SamLine.java:2424)
+    cfg->tags = BBMAP_SAM_MAKE_NM | BBMAP_SAM_MAKE_AM;
+    return BBMAP_OK;
+}
+
+static int check_sam_config(const char *fn, const bbmap_sam_config *cfg) {
+    if (!cfg) return bbfail(BBMAP_E_ARG, "%s: null argument", fn);
+    if (cfg->flags & ~SAM_ALL_FLAGS) return bbfail(BBMAP_E_ARG, "%s: unknown flag bits", fn);
+    if (cfg->tags & ~SAM_ALL_TAGS) return bbfail(BBMAP_E_ARG, "%s: unknown tag bits", fn);
+    if (cfg->intronLimit < 0) return bbfail(BBMAP_E_ARG, "%s: negative intron limit", fn);
+    return BBMAP_OK;
+}
+
+// SamLine's remaining fields for the last batch: the coordinate kernel, the sizing pass, a device-wide exclusive scan of the per-read
+// byte counts, the emit pass.  The blob's size comes back once between the scan and the emit pass (it sizes the blob).
+static int sam_records(bbmap_ctx *c, hipStream_t stream, const bbmap_sam_config &cfg, bool wantTags, const bbmap_samrec **recs,
+                       const bbmap_samtags **tags, const uint8_t **text, int64_t *text_bytes) {
+    bbsam::Args a = {};
     BBTRY(scaffold_records(c, stream, &a.V, &a.scaf));      // its error cases are this call's: no final stage, no batch, no scaffold table
     if (!c->batch.reads || !c->batch.bases || c->batch.n_reads != c->stats.reads)
         return bbfail(BBMAP_E_ARG, "bbmap_get_sam_records: the context does not hold the last batch's reads");
@@ -248,22 +269,58 @@ extern "C" int bbmap_get_sam_records(bbmap_ctx *c, void *stream_, int32_t flags,
         bbsam::fill_mapq_max(table.data(), maxLen);
         BBHIP(hipMemcpy(c->d_mapqMax, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
     }
+    if (wantTags && !c->d_samTags) BBTRY(dalloc(c, &c->d_samTags, (size_t)c->cfg.max_reads));
     a.chromArr = c->d_chromArr; a.chromArrLen = c->d_chromArrLen;
     a.mapqMax = c->d_mapqMax; a.mapqMaxLen = maxLen;
-    a.flags = flags;
-    BBHIP(bbsam::launch_size(a, c->d_samRec, c->d_samCounts, stream));
+    a.flags = cfg.flags; a.intronLimit = cfg.intronLimit; a.tags = cfg.tags;
+    BBHIP(bbsam::launch_size(a, c->d_samRec, wantTags ? c->d_samTags : nullptr, c->d_samCounts, stream));
     long long total = 0;
     BBTRY(scan_offsets(c->d_samCounts, n, c->d_samOffsets, c->buf[BUF_SAM_TMP], stream, &total));
     BBHIP(c->buf[BUF_SAM_TEXT].grow((size_t)total, (size_t)total / 4 + 256));       // (the stream has just been waited for)
     uint8_t *blob = (uint8_t *)c->buf[BUF_SAM_TEXT].p;
+    a.textCap = total;
     BBHIP(bbsam::launch_emit(a, c->d_samRec, c->d_samOffsets, blob, stream));
     c->samTextBytes = total;
     *recs = c->d_samRec; *text = blob;
+    if (tags) *tags = wantTags ? c->d_samTags : nullptr;
     if (text_bytes) *text_bytes = total;
     return BBMAP_OK;
 }
 
-// Host form: the records and the blob as they are on the device (packed in read order already), two copies.
+// (the default configuration of the call below)
+extern "C" int bbmap_get_sam_records(bbmap_ctx *c, void *stream_, int32_t flags, const bbmap_samrec **recs, const uint8_t **text,
+                                     int64_t *text_bytes) {
+    if (!c || !recs || !text) return bbfail(BBMAP_E_ARG, "bbmap_get_sam_records: null argument");
+    if (flags & ~SAM_ALL_FLAGS) return bbfail(BBMAP_E_ARG, "bbmap_get_sam_records: unknown flag bits");
+    bbmap_sam_config cfg;
+    bbmap_sam_default_config(&cfg);
+    cfg.flags = flags;
+    return sam_records(c, (hipStream_t)stream_, cfg, false, recs, nullptr, text, text_bytes);
+}
+
+extern "C" int bbmap_get_sam_records_cfg(bbmap_ctx *c, void *stream_, const bbmap_sam_config *cfg, const bbmap_samrec **recs,
+                                         const bbmap_samtags **tags, const uint8_t **text, int64_t *text_bytes) {
+    if (!c || !recs || !text) return bbfail(BBMAP_E_ARG, "bbmap_get_sam_records_cfg: null argument");
+    BBTRY(check_sam_config("bbmap_get_sam_records_cfg", cfg));
+    return sam_records(c, (hipStream_t)stream_, *cfg, tags != nullptr, recs, tags, text, text_bytes);
+}
+
+// Host forms: the records and the blob as they are on the device (packed in read order already), two or three copies.
+extern "C" int bbmap_get_sam_cfg(bbmap_ctx *c, int64_t n_reads, const bbmap_sam_config *cfg, bbmap_samrec *out, bbmap_samtags *tags_out,
+                                 uint8_t *text_out, int64_t text_cap, int64_t *text_bytes) {
+    if (!c || !out) return bbfail(BBMAP_E_ARG, "bbmap_get_sam_cfg: null argument");
+    BBTRY(check_sam_config("bbmap_get_sam_cfg", cfg));
+    if (!c->ran || n_reads != c->stats.reads) return bbfail(BBMAP_E_ARG, "bbmap_get_sam_cfg: n_reads is not the last batch's");
+    if (text_cap < 0 || (text_cap > 0 && !text_out)) return bbfail(BBMAP_E_ARG, "bbmap_get_sam_cfg: bad text buffer");
+    const bbmap_samrec *recs = nullptr; const bbmap_samtags *tags = nullptr; const uint8_t *text = nullptr; int64_t total = 0;
+    BBTRY(sam_records(c, nullptr, *cfg, tags_out != nullptr, &recs, &tags, &text, &total));
+    if (n_reads > 0) BBHIP(hipMemcpy(out, recs, (size_t)n_reads * sizeof(bbmap_samrec), hipMemcpyDeviceToHost));    // (waits for the null stream)
+    if (n_reads > 0 && tags_out) BBHIP(hipMemcpy(tags_out, tags, (size_t)n_reads * sizeof(bbmap_samtags), hipMemcpyDeviceToHost));
+    if (text_out && total > 0 && total <= text_cap) BBHIP(hipMemcpy(text_out, text, (size_t)total, hipMemcpyDeviceToHost));
+    if (text_bytes) *text_bytes = total;
+    return BBMAP_OK;
+}
+
 extern "C" int bbmap_get_sam(bbmap_ctx *c, int64_t n_reads, int32_t flags, bbmap_samrec *out, uint8_t *text_out, int64_t text_cap,
                              int64_t *text_bytes) {
     if (!c || !out) return bbfail(BBMAP_E_ARG, "bbmap_get_sam: null argument");
@@ -274,6 +331,72 @@ extern "C" int bbmap_get_sam(bbmap_ctx *c, int64_t n_reads, int32_t flags, bbmap
     if (n_reads > 0) BBHIP(hipMemcpy(out, recs, (size_t)n_reads * sizeof(bbmap_samrec), hipMemcpyDeviceToHost));    // (waits for the null stream)
     if (text_out && total > 0 && total <= text_cap) BBHIP(hipMemcpy(text_out, text, (size_t)total, hipMemcpyDeviceToHost));
     if (text_bytes) *text_bytes = total;
+    return BBMAP_OK;
+}
+
+// The raw form over arrays the caller owns (include/bbmap_amd.h).  Workspace: the MAPQ table, the per-read byte counts, their prefix
+// sums, the scan's scratch, each at a multiple of 256 bytes.
+static size_t sam_align(size_t b) { return (b + 255) & ~(size_t)255; }
+static const std::vector<float> &sam_mapq_table() {          // (a static: the asynchronous upload reads it after the call has returned)
+    static const std::vector<float> table = [] {
+        std::vector<float> t((size_t)SAM_MAX_READ_LEN + 1);
+        bbsam::fill_mapq_max(t.data(), SAM_MAX_READ_LEN);
+        return t;
+    }();
+    return table;
+}
+static long long sam_workspace_bytes(long long n, int maxLen, size_t *scanBytes) {
+    if (scan_scratch_bytes(n, scanBytes) != hipSuccess) return -1;
+    return (long long)(sam_align(((size_t)maxLen + 1) * 4) + sam_align(((size_t)n + 1) * 4) + sam_align(((size_t)n + 1) * 8) + sam_align(*scanBytes) + 256);
+}
+
+extern "C" int64_t bbpipe_sam_records_workspace_bytes(int64_t n_reads, int32_t max_read_len) {
+    if (n_reads < 0 || n_reads >= (1ll << 31) - 1 || max_read_len < 1 || max_read_len > SAM_MAX_READ_LEN)
+        return bbfail(BBMAP_E_ARG, "bbpipe_sam_records_workspace_bytes: bad argument");
+    size_t scanBytes = 0;
+    const long long b = sam_workspace_bytes(n_reads, max_read_len, &scanBytes);
+    if (b < 0) return bbfail(BBMAP_E_HIP, "bbpipe_sam_records_workspace_bytes: the scan could not be sized");
+    return b;
+}
+
+extern "C" int bbpipe_sam_records_device(void *stream_, int64_t n_reads, int32_t paired, const bbmap_sam_config *cfg, int32_t max_read_len,
+                                         const bbidx_read *reads, const uint8_t *bases, const bbmap_final *finals, const uint8_t *pool,
+                                         const bbmap_scafrec *scaf, const bbmap_msite *sites, const int32_t *nsites, int32_t cap,
+                                         const uint8_t *const *chrom_arr, const int32_t *chrom_arr_len, bbmap_samrec *recs, bbmap_samtags *tags,
+                                         uint8_t *text, int64_t text_cap, int64_t *text_bytes_dev, void *workspace, int64_t workspace_bytes) {
+    if (n_reads < 0 || n_reads >= (1ll << 31) - 1 || (paired && (n_reads & 1)) || max_read_len < 1 || max_read_len > SAM_MAX_READ_LEN ||
+        text_cap < 0 || cap < 0 || cap > BBMAP_MAX_SITES_LIMIT)
+        return bbfail(BBMAP_E_ARG, "bbpipe_sam_records_device: bad argument");
+    BBTRY(check_sam_config("bbpipe_sam_records_device", cfg));
+    if (!text_bytes_dev || (text_cap > 0 && !text)) return bbfail(BBMAP_E_ARG, "bbpipe_sam_records_device: null buffer");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_reads == 0) { BBHIP(hipMemsetAsync(text_bytes_dev, 0, 8, stream)); return BBMAP_OK; }
+    if (!reads || !bases || !finals || !pool || !scaf || !recs) return bbfail(BBMAP_E_ARG, "bbpipe_sam_records_device: null buffer");
+    const bool tagged = !(cfg->tags & BBMAP_SAM_NO_TAGS);
+    if (tagged && tags && (cfg->tags & BBMAP_SAM_MAKE_XM) && (!sites || !nsites || cap < 1))
+        return bbfail(BBMAP_E_ARG, "bbpipe_sam_records_device: BBMAP_SAM_MAKE_XM needs the site lists");
+    if (tagged && (cfg->flags & BBMAP_SAM_MD) && (!chrom_arr || !chrom_arr_len))
+        return bbfail(BBMAP_E_ARG, "bbpipe_sam_records_device: BBMAP_SAM_MD needs the chromosome arrays");
+    size_t scanBytes = 0;
+    const long long need = sam_workspace_bytes(n_reads, max_read_len, &scanBytes);
+    if (need < 0) return bbfail(BBMAP_E_HIP, "bbpipe_sam_records_device: the scan could not be sized");
+    if (!workspace || workspace_bytes < need)
+        return bbfail(BBMAP_E_ARG, "bbpipe_sam_records_device: the workspace is too small (bbpipe_sam_records_workspace_bytes)");
+    uint8_t *ws = (uint8_t *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    float *mapqMax = (float *)ws; ws += sam_align(((size_t)max_read_len + 1) * 4);
+    int *counts = (int *)ws; ws += sam_align(((size_t)n_reads + 1) * 4);
+    long long *offsets = (long long *)ws; ws += sam_align(((size_t)n_reads + 1) * 8);
+    BBHIP(hipMemcpyAsync(mapqMax, sam_mapq_table().data(), ((size_t)max_read_len + 1) * 4, hipMemcpyHostToDevice, stream));
+    bbsam::Args a = {};
+    a.V.reads = reads; a.V.bases = bases; a.V.n = n_reads; a.V.paired = paired ? 1 : 0;
+    a.V.fin = finals; a.V.pool = pool; a.V.sites = sites; a.V.nsites = nsites; a.V.cap = cap;      // (no tier)
+    a.scaf = scaf; a.chromArr = chrom_arr; a.chromArrLen = chrom_arr_len;
+    a.mapqMax = mapqMax; a.mapqMaxLen = max_read_len;
+    a.flags = cfg->flags; a.intronLimit = cfg->intronLimit; a.tags = cfg->tags; a.textCap = text_cap;
+    BBHIP(bbsam::launch_size(a, recs, tags, counts, stream));
+    BBHIP(scan_offsets_scratch(counts, n_reads, offsets, ws, scanBytes, stream));
+    BBHIP(bbsam::launch_emit(a, recs, offsets, text, stream));
+    BBHIP(hipMemcpyAsync(text_bytes_dev, offsets + n_reads, 8, hipMemcpyDeviceToDevice, stream));
     return BBMAP_OK;
 }
 

@@ -29,7 +29,20 @@ SAMREC_DTYPE = np.dtype([("flag", "<i4"), ("mapq", "<i4"), ("rname", "<i4"), ("r
                          ("md_len", "<i4"), ("md_off", "<i8")])
 SAM_CIGAR13, SAM_MD = 1, 2
 SAM_TAG_XT = 1
+# bbmap_samtags: the further optional tags of a SAM line as values (bbmap_get_sam_records_cfg); `present` = SAM_MAKE_* bits
+SAMTAGS_DTYPE = np.dtype([(n, "<i4") for n in ("present", "xs", "nh", "sm", "xm", "ys", "yl_query", "yl_ref", "yi_good", "yi_bad",
+                                               "yi_perfect", "yr", "x8", "xb", "introns", "splices")])
+# bbmap_sam_config.tags: which optional tags are made (BBMAP_SAM_MAKE_*; one Python copy of the bits, in bbmap_amd.sam)
+from .sam import (MAKE_AM as SAM_MAKE_AM, MAKE_BOUNDS as SAM_MAKE_BOUNDS, MAKE_IDENTITY as SAM_MAKE_IDENTITY,  # noqa: E402
+                  MAKE_INSERT as SAM_MAKE_INSERT, MAKE_LENGTH as SAM_MAKE_LENGTH, MAKE_NH as SAM_MAKE_NH, MAKE_NM as SAM_MAKE_NM,
+                  MAKE_SCORE as SAM_MAKE_SCORE, MAKE_SM as SAM_MAKE_SM, MAKE_STOP as SAM_MAKE_STOP, MAKE_XM as SAM_MAKE_XM,
+                  MAKE_XS as SAM_MAKE_XS, NO_TAGS as SAM_NO_TAGS, XS_SECONDSTRAND as SAM_XS_SECONDSTRAND)
+SAM_DEFAULT_TAGS = SAM_MAKE_NM | SAM_MAKE_AM
+SAM_ALL_TAGS = (SAM_DEFAULT_TAGS | SAM_MAKE_SM | SAM_MAKE_XM | SAM_MAKE_XS | SAM_MAKE_NH | SAM_MAKE_STOP | SAM_MAKE_LENGTH |
+                SAM_MAKE_IDENTITY | SAM_MAKE_SCORE | SAM_MAKE_INSERT | SAM_MAKE_BOUNDS)
+SAM_NO_INTRON_LIMIT = 2 ** 31 - 1
 assert MSITE_DTYPE.itemsize == 128 and FINAL_DTYPE.itemsize == 64 and SCAFREC_DTYPE.itemsize == 32 and SAMREC_DTYPE.itemsize == 64
+assert SAMTAGS_DTYPE.itemsize == 64
 GAPPED_BIT = 1 << 30
 
 
@@ -39,6 +52,16 @@ class bbmap_config(C.Structure):
                     "slowAlignPadding", "slowRescuePadding", "extraPadding", "tipSearchDist", "maxPairDist", "averagePairDist",
                     "maxRescueDist", "maxRescueMismatches", "maxTrimSitesToRetain", "trimList", "doRescue", "alignColumns",
                     "clearzone3", "msaMaxColumns", "fastCols", "jobsPerRead", "finalStage")] + [("reserved", C.c_int32 * 4)]
+
+
+class bbmap_sam_config(C.Structure):
+    _fields_ = [("flags", C.c_int32), ("intronLimit", C.c_int32), ("tags", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+def sam_config(flags=0, intron_limit=None, tags=None):
+    """bbmap_sam_default_config with the given fields replaced (None = the default: no limit, NM and AM)."""
+    return bbmap_sam_config(int(flags), SAM_NO_INTRON_LIMIT if intron_limit is None else int(intron_limit),
+                            SAM_DEFAULT_TAGS if tags is None else int(tags))
 
 
 class bbmap_output(C.Structure):
@@ -94,6 +117,19 @@ def _bind(L):
     L.bbmap_get_sam_records.restype = C.c_int
     L.bbmap_get_sam.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.bbmap_get_sam.restype = C.c_int
+    L.bbmap_sam_default_config.argtypes = [C.POINTER(bbmap_sam_config)]
+    L.bbmap_sam_default_config.restype = C.c_int
+    L.bbmap_get_sam_records_cfg.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(bbmap_sam_config), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.bbmap_get_sam_records_cfg.restype = C.c_int
+    L.bbmap_get_sam_cfg.argtypes = [C.c_void_p, C.c_int64, C.POINTER(bbmap_sam_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.POINTER(C.c_int64)]
+    L.bbmap_get_sam_cfg.restype = C.c_int
+    L.bbpipe_sam_records_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+    L.bbpipe_sam_records_workspace_bytes.restype = C.c_int64
+    L.bbpipe_sam_records_device.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(bbmap_sam_config), C.c_int32] + [C.c_void_p] * 7 + \
+        [C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
+    L.bbpipe_sam_records_device.restype = C.c_int
     L.bbmap_add_run_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.bbmap_get_run_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.bbmap_reset_run_stats.argtypes = [C.c_void_p]
@@ -106,6 +142,36 @@ def _bind(L):
     for f in ("bbmap_default_config", "bbmap_create", "bbmap_map_batch_device", "bbmap_get_output", "bbmap_last_stats",
               "bbmap_get_overflow_output"):
         getattr(L, f).restype = C.c_int
+
+
+def sam_workspace_bytes(n_reads, max_read_len):
+    """bbpipe_sam_records_workspace_bytes"""
+    L = _lib.load()
+    _bind(L)
+    b = L.bbpipe_sam_records_workspace_bytes(int(n_reads), int(max_read_len))
+    if b < 0:
+        _lib.check(int(b), "bbpipe_sam_records_workspace_bytes")
+    return int(b)
+
+
+def sam_records_device(reads, bases, finals, pool, scaf, recs, text, text_bytes, workspace, paired=False, flags=0, intron_limit=None,
+                       tags=None, tagrecs=None, sites=None, nsites=None, cap=0, chrom_arr=None, chrom_arr_len=None, max_read_len=600):
+    """bbpipe_sam_records_device over torch device tensors the caller owns: uint8 views of READ_DTYPE / FINAL_DTYPE / SCAFREC_DTYPE
+    records, the bases and the match-string pool (uint8); outputs recs (uint8, n x 64 bytes), tagrecs (uint8, n x 64 bytes, or None: the
+    tag records are not made), text (uint8: its length is the blob's capacity), text_bytes (int64[1]: the bytes the blob needs);
+    workspace: uint8, sam_workspace_bytes(n, max_read_len) long.  sites (uint8 view of MSITE_DTYPE[n, cap]) / nsites (int32) for XM;
+    chrom_arr (int64: device addresses by chromosome number) / chrom_arr_len (int32) for MD.  Enqueues on the current stream and does
+    not wait."""
+    L = _lib.load()
+    _bind(L)
+    n = reads.numel() // READ_DTYPE.itemsize
+    cfg = sam_config(flags, intron_limit, tags)
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    stream = torch.cuda.current_stream().cuda_stream
+    _lib.check(L.bbpipe_sam_records_device(C.c_void_p(stream), n, int(bool(paired)), C.byref(cfg), int(max_read_len), ptr(reads), ptr(bases),
+                                           ptr(finals), ptr(pool), ptr(scaf), ptr(sites), ptr(nsites), int(cap), ptr(chrom_arr),
+                                           ptr(chrom_arr_len), ptr(recs), ptr(tagrecs), ptr(text), int(text.numel()), ptr(text_bytes),
+                                           ptr(workspace), int(workspace.numel())), "bbpipe_sam_records_device")
 
 
 def _copy(ptr, nbytes, dev=None):
@@ -355,22 +421,39 @@ class Mapper:
         recs = _copy(p.value, self.n * SCAFREC_DTYPE.itemsize, self.dev).view(SCAFREC_DTYPE)
         return recs, getattr(self.di, "scaffold_names", None)
 
-    def sam_records(self, flags=0):
+    def sam_records(self, flags=0, intron_limit=None, tags=None):
         """bbmap_get_sam_records: SamLine's fields for the last step's final records, overflow tier included, built on the device.
         flags: SAM_CIGAR13 | SAM_MD.  Returns (SAMREC_DTYPE[n], text uint8[]): read r's CIGAR is text[cigar_off : + cigar_len], its MD
-        value text[md_off : + md_len] (bbmap_amd.sam formats lines from them)."""
+        value text[md_off : + md_len] (bbmap_amd.sam formats lines from them).
+        With intron_limit (SamLine.INTRON_LIMIT, `intronlen=`) or tags (SAM_MAKE_* bits) given: bbmap_get_sam_records_cfg, and the return
+        value is (SAMREC_DTYPE[n], SAMTAGS_DTYPE[n], text)."""
         p, t, nb = C.c_void_p(), C.c_void_p(), C.c_int64(0)
         stream = torch.cuda.current_stream().cuda_stream
+        if intron_limit is not None or tags is not None:
+            g, cfg = C.c_void_p(), sam_config(flags, intron_limit, tags)
+            _lib.check(self.L.bbmap_get_sam_records_cfg(self.h, C.c_void_p(stream), C.byref(cfg), C.byref(p), C.byref(g), C.byref(t), C.byref(nb)),
+                       "bbmap_get_sam_records_cfg")
+            torch.cuda.current_stream().synchronize()
+            return (_copy(p.value, self.n * SAMREC_DTYPE.itemsize, self.dev).view(SAMREC_DTYPE),
+                    _copy(g.value, self.n * SAMTAGS_DTYPE.itemsize, self.dev).view(SAMTAGS_DTYPE), _copy(t.value, nb.value, self.dev))
         _lib.check(self.L.bbmap_get_sam_records(self.h, C.c_void_p(stream), int(flags), C.byref(p), C.byref(t), C.byref(nb)),
                    "bbmap_get_sam_records")
         torch.cuda.current_stream().synchronize()
         recs = _copy(p.value, self.n * SAMREC_DTYPE.itemsize, self.dev).view(SAMREC_DTYPE)
         return recs, _copy(t.value, nb.value, self.dev)
 
-    def sam_records_host(self, flags=0):
-        """bbmap_get_sam: the same through the host-buffer form (records first, then the blob once its size is known)."""
+    def sam_records_host(self, flags=0, intron_limit=None, tags=None):
+        """bbmap_get_sam: the same through the host-buffer form (records first, then the blob once its size is known); with
+        intron_limit or tags given bbmap_get_sam_cfg, returning (recs, tags, text)."""
         recs = np.zeros(self.n, SAMREC_DTYPE)
         nb = C.c_int64(0)
+        if intron_limit is not None or tags is not None:
+            cfg, tg = sam_config(flags, intron_limit, tags), np.zeros(self.n, SAMTAGS_DTYPE)
+            _lib.check(self.L.bbmap_get_sam_cfg(self.h, self.n, C.byref(cfg), recs.ctypes.data, tg.ctypes.data, None, 0, C.byref(nb)), "bbmap_get_sam_cfg")
+            text = np.zeros(max(1, nb.value), np.uint8)
+            _lib.check(self.L.bbmap_get_sam_cfg(self.h, self.n, C.byref(cfg), recs.ctypes.data, tg.ctypes.data, text.ctypes.data, text.size,
+                                                C.byref(nb)), "bbmap_get_sam_cfg")
+            return recs, tg, text[:nb.value]
         _lib.check(self.L.bbmap_get_sam(self.h, self.n, int(flags), recs.ctypes.data, None, 0, C.byref(nb)), "bbmap_get_sam")
         text = np.zeros(max(1, nb.value), np.uint8)
         _lib.check(self.L.bbmap_get_sam(self.h, self.n, int(flags), recs.ctypes.data, text.ctypes.data, text.size, C.byref(nb)), "bbmap_get_sam")

@@ -19,6 +19,8 @@
 extern "C" {
 #endif
 
+/* (Still 6 with the configurable SAM stage: bbmap_sam_config, bbmap_samtags, bbmap_get_sam_records_cfg, bbmap_get_sam_cfg and
+ * bbpipe_sam_records_device are additions; no earlier symbol, record or default changed, so no caller breaks.) */
 #define BBMAP_AMD_ABI_VERSION 6
 
 enum {
@@ -581,7 +583,8 @@ int bbpipe_quick_rescue_device(void *stream, int64_t n_jobs, const bbresc_job *j
  *   local alignment).
  *   Scaffolds: with a table set (bbidx_set_scaffolds) quickMap's tail drops sites that span two scaffolds, and
  *   bbmap_get_scaffold_records gives SamLine's scaffold coordinates, and bbmap_get_sam_records the rest of SamLine's constructor
- *   (FLAG, POS / PNEXT / TLEN, MAPQ, CIGAR, NM, AM, MD); names, SEQ / QUAL text and file I/O stay with the host.
+ *   (FLAG, POS / PNEXT / TLEN, MAPQ, CIGAR with the `N` operator under an intron limit, NM, AM, MD and the values of the further
+ *   optional tags); names, SEQ / QUAL text and file I/O stay with the host.
  *   Added product: every successful fill also returns its traceback string (as the quickmatch=t branch obtains it,
  *   BBMapThread.java:345, without fixXY / clipTipIndels); site state follows the default (quickmatch=f) flow.
  * ===================================================================================== */
@@ -809,8 +812,9 @@ int bbmap_get_scaffold_records(bbmap_ctx *ctx, void *stream, const bbmap_scafrec
  * (current/stream/SamLine.java:82-413) behind the coordinate block above -- makeFlag (:2134-2151), the POS / PNEXT / TLEN table and its
  * sign rule (:220-253, :349-354), RNAME / RNEXT (:164, :315), toMapq (:1703-1722), the CIGAR (toCigar14 :679-750, toCigar13 :600-663 and
  * the `len=` / `lenM` shortcut :269-301), the default tags XT:A:R / NM / AM (makeOptionalTags :1481-1549) and MD (makeMdTag :1361-1445).
- * Fixed at the reference's defaults, not configurable: SOFT_CLIP = true, PENALIZE_AMBIG = true, INTRON_LIMIT = Integer.MAX_VALUE (no
- * `N` operator, no dropped deletion), MAKE_NM_TAG and MAKE_AM_TAG on, every other tag off; primary alignments only.
+ * bbmap_get_sam_records / bbmap_get_sam run at the reference's defaults: INTRON_LIMIT = Integer.MAX_VALUE (no `N` operator, no dropped
+ * deletion), MAKE_NM_TAG and MAKE_AM_TAG on, every other tag off.  bbmap_get_sam_records_cfg / bbmap_get_sam_cfg take a bbmap_sam_config
+ * (below): the intron limit and the tag switches.  Fixed in both: SOFT_CLIP = true, PENALIZE_AMBIG = true; primary alignments only.
  * Strings live in one text blob, packed in read order without gaps: per read its CIGAR, then its MD value (without "MD:Z:"). */
 enum { BBMAP_SAM_CIGAR13 = 1,          /* SamLine.VERSION <= 1.3: M instead of = and X (default: 1.4) */
        BBMAP_SAM_MD = 2 };             /* MAKE_MD_TAG (off by default, as in the reference) */
@@ -841,6 +845,78 @@ int bbmap_get_sam_records(bbmap_ctx *ctx, void *stream, int32_t flags, const bbm
  * takes; when it does not fit text_cap nothing of it is written (call again with a larger buffer).  Two copies, no re-packing. */
 int bbmap_get_sam(bbmap_ctx *ctx, int64_t n_reads, int32_t flags, bbmap_samrec *out, uint8_t *text_out, int64_t text_cap,
                   int64_t *text_bytes);
+/* The configurable form: `intronlen=`, `xstag=` and the `...tag=t` switches (Parser.java:686-744; the statics at SamLine.java:2400-2422).
+ *   intronLimit  SamLine.INTRON_LIMIT (Parser.java:715-717 sets it without a clamp; < 0 is BBMAP_E_ARG here).  One run of `D` meets three
+ *                thresholds, all the reference's: count > limit prints `N` instead of `D` (toCigar14 :725 / :738, toCigar13 :641 / :654; the
+ *                count is the CIGAR's, without columns inside a soft-clipped stretch), is left out of NM (:1529, :1535) and of MD
+ *                (makeMdTag :1380 -- which then never resets `dels`, so every later deletion of that line is left out of MD as well);
+ *                count < limit makes the run count against the identity (Read.identityFlat, Read.java:1557); count >= max(limit, 1)
+ *                makes it a splice (Read.countErrors, Read.java:2200-2217).
+ *   tags         BBMAP_SAM_MAKE_* bits: which optional tags makeOptionalTags (:1481-1684) adds.  NM and AM land in bbmap_samrec as
+ *                before; the others in bbmap_samtags.  MD stays in `flags`.  BBMAP_SAM_NO_TAGS: no tag at all, XT and MD included (:1482).
+ * Not carried over: SOFT_CLIP = false, PENALIZE_AMBIG = false, secondary lines, the Tophat tags, the custom X1-X7 tags, X0, X9 and RG. */
+enum { BBMAP_SAM_MAKE_NM = 1,            /* MAKE_NM_TAG (default on) */
+       BBMAP_SAM_MAKE_AM = 2,            /* MAKE_AM_TAG (default on) */
+       BBMAP_SAM_MAKE_SM = 4,            /* MAKE_SM_TAG: SM:i:<mapq> (:1548) */
+       BBMAP_SAM_MAKE_XM = 8,            /* MAKE_XM_TAG (:1565-1581) */
+       BBMAP_SAM_MAKE_XS = 16,           /* MAKE_XS_TAG: XS:A:+/- on a mapped line whose CIGAR holds an N (makeXSTag :1346-1359) */
+       BBMAP_SAM_XS_SECONDSTRAND = 32,   /* XS_SECONDSTRAND (`xstag=ss`): inverts XS */
+       BBMAP_SAM_MAKE_NH = 64,           /* MAKE_NH_TAG: NH:i:1 (:1599-1605; no secondary output) */
+       BBMAP_SAM_MAKE_STOP = 128,        /* MAKE_STOP_TAG: YS:i (makeStopTag :1316-1319) */
+       BBMAP_SAM_MAKE_LENGTH = 256,      /* MAKE_LENGTH_TAG: YL:Z:a,b (makeLengthTag :1321-1324) */
+       BBMAP_SAM_MAKE_IDENTITY = 512,    /* MAKE_IDENTITY_TAG: YI:f (makeIdentityTag :1326-1330) */
+       BBMAP_SAM_MAKE_SCORE = 1024,      /* MAKE_SCORE_TAG: YR:i:<mapScore> (:1613) */
+       BBMAP_SAM_MAKE_INSERT = 2048,     /* MAKE_INSERT_TAG: X8:Z:<insertSizeMapped(false)> for a read with a mate (:1615-1619) */
+       BBMAP_SAM_MAKE_BOUNDS = 4096,     /* MAKE_BOUNDS_TAG: XB:Z (:1673-1681) */
+       BBMAP_SAM_NO_TAGS = 8192 };       /* NO_TAGS */
+typedef struct bbmap_sam_config {
+    int32_t flags;                 /* BBMAP_SAM_CIGAR13 | BBMAP_SAM_MD */
+    int32_t intronLimit;           /* INT32_MAX = none */
+    int32_t tags;                  /* BBMAP_SAM_MAKE_* | BBMAP_SAM_XS_SECONDSTRAND | BBMAP_SAM_NO_TAGS */
+    int32_t reserved[5];           /* 0 */
+} bbmap_sam_config;                /* 32 bytes */
+/* flags 0, no intron limit, NM and AM: what bbmap_get_sam_records does. */
+int bbmap_sam_default_config(bbmap_sam_config *cfg);
+/* The further tags of one line, as values (the host prints them); parallel to bbmap_samrec.  All 0 for an unmapped line (:1483-1484). */
+typedef struct bbmap_samtags {
+    int32_t present;               /* BBMAP_SAM_MAKE_* bits of SM XM XS NH STOP LENGTH IDENTITY SCORE INSERT BOUNDS: tags this line carries */
+    int32_t xs;                    /* +1 / -1 */
+    int32_t nh, sm, xm;
+    int32_t ys;
+    int32_t yl_query, yl_ref;      /* YL:Z:yl_query,yl_ref */
+    int32_t yi_good, yi_bad;       /* identityFlat's good / bad after the `n` folding (Read.java:1586-1588): f = good / (float)max(good + bad, 1) */
+    int32_t yi_perfect;            /* 1: the line prints YI:f:100 (:1327), good / bad are 0 */
+    int32_t yr;
+    int32_t x8;
+    int32_t xb;                    /* this read's letter I / O / U, and in bits 8-15 the mate's (0 without a mate) */
+    int32_t introns;               /* N operators in this line's CIGAR */
+    int32_t splices;               /* Read.countErrors(INTRON_LIMIT)[5] (Read.java:2189-2240) of a mapped record with a match string,
+                                    * whatever the tag switches: splices > 0 is what readCountSplice1 / 2 count
+                                    * (AbstractMapThread.java:1528, :1679), the table's "Splice Rate" line.  Handed out here because
+                                    * bbmap_runstats has no room for it. */
+} bbmap_samtags;                   /* 64 bytes */
+/* bbmap_get_sam_records under a configuration: the same kernels, *tags = a second device array of n_reads records (tags may be NULL:
+ * not made).  With bbmap_sam_default_config's values *recs and *text are bbmap_get_sam_records', byte for byte.  BBMAP_E_ARG as there,
+ * or intronLimit < 0, or unknown flag / tag bits. */
+int bbmap_get_sam_records_cfg(bbmap_ctx *ctx, void *stream, const bbmap_sam_config *cfg, const bbmap_samrec **recs,
+                              const bbmap_samtags **tags, const uint8_t **text, int64_t *text_bytes);
+/* Host form, mirroring bbmap_get_sam; tags_out may be NULL. */
+int bbmap_get_sam_cfg(bbmap_ctx *ctx, int64_t n_reads, const bbmap_sam_config *cfg, bbmap_samrec *out, bbmap_samtags *tags_out,
+                      uint8_t *text_out, int64_t text_cap, int64_t *text_bytes);
+/* The raw form over device arrays the caller owns: reads (len, bases_off) and `bases` (the reads as they came in), one final record per
+ * read with its string in `pool` at match_off, one bbmap_scafrec per read (bbmap_get_scaffold_records' layout; the caller may write it
+ * by hand), sites = n_reads x cap records with nsites[r] in use (read for XM only: both may be NULL without BBMAP_SAM_MAKE_XM),
+ * chrom_arr[c] / chrom_arr_len[c] = chromosome c's array as ChromosomeArray holds it (device array of device pointers; read for MD only).
+ * paired: reads 2p and 2p + 1 are mates.  max_read_len bounds reads[].len (<= 6016).  Outputs: recs, tags (may be NULL), `text` of
+ * text_cap bytes, *text_bytes_dev (a device word) = the bytes the blob needs.  When the blob does not fit nothing is written at or behind
+ * text_cap, and the records still carry the true lengths and offsets.  workspace: bbpipe_sam_records_workspace_bytes(n_reads,
+ * max_read_len) bytes of device memory.  Enqueues the sizing pass, the scan and the emit pass on `stream` and does not wait. */
+int64_t bbpipe_sam_records_workspace_bytes(int64_t n_reads, int32_t max_read_len);
+int bbpipe_sam_records_device(void *stream, int64_t n_reads, int32_t paired, const bbmap_sam_config *cfg, int32_t max_read_len,
+                              const bbidx_read *reads, const uint8_t *bases, const bbmap_final *finals, const uint8_t *pool,
+                              const bbmap_scafrec *scaf, const bbmap_msite *sites, const int32_t *nsites, int32_t cap,
+                              const uint8_t *const *chrom_arr, const int32_t *chrom_arr_len, bbmap_samrec *recs, bbmap_samtags *tags,
+                              uint8_t *text, int64_t text_cap, int64_t *text_bytes_dev, void *workspace, int64_t workspace_bytes);
 int bbmap_last_stats(bbmap_ctx *ctx, bbmap_stats *out);
 
 /* =====================================================================================
