@@ -11,6 +11,7 @@ from bbmap_amd import workload as W
 from bbmap_amd.index import DeviceIndex
 from bbmap_amd.mapper import Mapper
 from oracle import oracle as O
+from tests.config_problems import oracle_params
 from tests.mapper_check import DP_ROUTES, compare, gpu_fills, set_route as _set_route  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +28,7 @@ def _run(ref, reads, L, k, paired, max_sites=32, cap=64, **cfg):
     out = mp.fetch()
     st = mp.stats()
     oi = O.OracleIndex([ref], k=k)
-    params = O.map_default_params(**{k_: v for k_, v in cfg.items() if k_ in ("tipSearchDist", "trimList", "doRescue", "averagePairDist")})
+    params = oracle_params(cfg)         # every setting the oracle has goes to it; one that is neither its nor device-only raises
     if paired:
         oi.s.p.quitAfterTwoPerfects = 0
         r = reads.reshape(-1, L)

@@ -15,7 +15,7 @@ from bbmap_amd import keys as K
 from bbmap_amd import reference as R
 from bbmap_amd import runstats as RS
 from bbmap_amd.index import DeviceIndex, PROFILE_PACBIO, READ_DTYPE
-from bbmap_amd.mapper import FINAL_DTYPE, MSITE_DTYPE, Mapper, _copy, bbmap_overflow_output
+from bbmap_amd.mapper import FINAL_DTYPE, MSITE_DTYPE, Mapper
 from tests import runstats_check as RC
 from tests.test_scaffolds_gpu import ACGT, KL, _mutate, _rc
 
@@ -223,52 +223,7 @@ def _pairs(n_pairs, seed):
     return reads, np.array(truth, RS.TRUTH_DTYPE)
 
 
-def _restate(mp, reads, paired, truth, scheme=0):
-    out = mp.fetch(with_match=False)
-    fin, blob = mp.final()
-    matches = [blob[int(f["match_off"]): int(f["match_off"]) + int(f["match_len"])].tobytes() if int(f["match_len"]) > 0 else None for f in fin]
-    lists = RC.merged_site_lists(out)
-    lens = [len(r) for r in reads]
-    # a read the tier mapped (nsites == -3 in the main list) takes the tier's own record and string, read from the tier's output
-    ov = bbmap_overflow_output()
-    assert mp.L.bbmap_get_overflow_output(mp.h, C.byref(ov)) == 0
-    if ov.n_reads > 0:
-        nt = int(ov.n_reads)
-        tf = _copy(ov.out.final, nt * FINAL_DTYPE.itemsize).view(FINAL_DTYPE)
-        tpool = _copy(ov.out.final_match, int(ov.out.final_match_bytes))
-        ids = _copy(ov.read_ids, nt * 4).view(np.int32)
-        fin = fin.copy()
-        for i, r in enumerate(ids):
-            if int(out["nsites"][int(r)]) == -3:
-                fin[int(r)] = tf[i]
-                o, ml = int(tf[i]["match_off"]), int(tf[i]["match_len"])
-                matches[int(r)] = tpool[o: o + ml].tobytes() if ml > 0 else None
-    return fin, matches, lists, lens
-
-
-def _check_mapped(mp, reads, paired, truth, scheme=0):
-    fin, matches, lists, lens = _restate(mp, reads, paired, truth, scheme)
-    want, whist = RC.run_stats(fin, matches, lists, lens, paired, truth, scheme, 0, mp.cfg.maxPairDist)
-    mp.reset_run_stats()
-    mp.add_run_stats(truth)
-    got, hist = mp.run_stats()
-    assert not RC.differences(got, want), RC.differences(got, want)
-    assert np.array_equal(hist, whist)
-    # ---- independent of the restatement
-    withstr = sum(lens[r] for r in range(len(fin)) if len(lists[r]) > 0 and matches[r] is not None)
-    assert sum(int(got["matchCount%s%d" % (c, m)]) for c in "MSIN" for m in (1, 2)) == withstr
-    for m in ("1", "2"):
-        assert sum(int(got[k + m]) for k in ("firstSiteCorrectP", "firstSiteCorrectM", "firstSiteIncorrect")) == int(got["mappedRetained" + m])
-    if paired:
-        pos = 0
-        for r in range(0, len(fin), 2):
-            a, b = fin[r], fin[r + 1]
-            if a["paired"] and a["mapped"] and b["mapped"]:
-                pos += RC.insert_size_mapped(RC._R(a, lens[r]), RC._R(b, lens[r + 1])) > 0
-        assert int(hist.sum()) == pos
-    else:
-        assert hist.sum() == 0
-    return got, want
+_restate, _check_mapped = RC.restate, RC.check_mapped           # (other test modules take them from tests/runstats_check.py)
 
 
 def _mapper(reads, paired, profile=0, **kw):
