@@ -9,17 +9,14 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import bbband_config
+from ._lib import bbband_config, bbband_job, bbband_result
 
 FORWARD, FORWARD_RC, REVERSE, REVERSE_RC = 0, 1, 2, 3
 EXACT = 1 << 2
 SEMANTICS_JNI_C, SEMANTICS_JAVA = 0, 1
 
-JOB_DTYPE = np.dtype([("query_off", "<i8"), ("ref_off", "<i8"), ("query_len", "<i4"), ("ref_len", "<i4"),
-                      ("qstart", "<i4"), ("rstart", "<i4"), ("maxEdits", "<i4"), ("flags", "<i4")])
-PAIR_DTYPE = np.dtype([("query_off", "<i8"), ("ref_off", "<i8"), ("query_len", "<i4"), ("ref_len", "<i4")])
-RESULT_DTYPE = np.dtype([("edits", "<i4"), ("lastQueryLoc", "<i4"), ("lastRefLoc", "<i4"), ("lastRow", "<i4"),
-                         ("lastEdits", "<i4"), ("lastOffset", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
+JOB_DTYPE, RESULT_DTYPE = np.dtype(bbband_job), np.dtype(bbband_result)
+PAIR_DTYPE = np.dtype([("query_off", "<i8"), ("ref_off", "<i8"), ("query_len", "<i4"), ("ref_len", "<i4")])          # bbband_pair
 
 
 class BandedAligner:
@@ -75,7 +72,6 @@ class BandedAligner:
     def alignQuadruple(self, pairs, maxEdits, exact):
         recs, seqs = self._pairs(pairs)
         out = np.zeros(len(pairs), np.int32)
-        self.L.bbband_align_quadruple_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
         _lib.check(self.L.bbband_align_quadruple_batch(self.h, len(pairs), recs.ctypes.data, seqs.ctypes.data, seqs.size, maxEdits,
                                                        1 if exact else 0, out.ctypes.data), "bbband_align_quadruple_batch")
         return out.tolist()
@@ -83,8 +79,6 @@ class BandedAligner:
     def alignQuadrupleProgressive(self, pairs, minEdits, maxEdits, exact):
         recs, seqs = self._pairs(pairs)
         out = np.zeros(len(pairs), np.int32)
-        self.L.bbband_align_quadruple_progressive_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
-                                                                    C.c_int32, C.c_int32, C.c_void_p]
         _lib.check(self.L.bbband_align_quadruple_progressive_batch(self.h, len(pairs), recs.ctypes.data, seqs.ctypes.data, seqs.size,
                                                                    minEdits, maxEdits, 1 if exact else 0, out.ctypes.data),
                    "bbband_align_quadruple_progressive_batch")
@@ -93,7 +87,6 @@ class BandedAligner:
     def alignDouble(self, pairs, maxEdits, exact):
         recs, seqs = self._pairs(pairs)
         out = np.zeros(len(pairs), np.int32)
-        self.L.bbband_align_double_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
         _lib.check(self.L.bbband_align_double_batch(self.h, len(pairs), recs.ctypes.data, seqs.ctypes.data, seqs.size, maxEdits,
                                                     1 if exact else 0, out.ctypes.data), "bbband_align_double_batch")
         return out.tolist()

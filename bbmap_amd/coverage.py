@@ -21,6 +21,9 @@ from fractions import Fraction
 
 import numpy as np
 
+from . import _lib as LL
+from .index import READ_DTYPE
+
 COV_START_ONLY, COV_EXCLUDE_DELETIONS, COV_STRANDED, COV_32BIT = 1, 2, 4, 8
 COV_MAX_WAVES = 8192            # wavefronts of the accumulate kernel's persistent grid
 COV_SCAN_TILE = 2048            # slots per workgroup of the prefix sum
@@ -33,7 +36,6 @@ COVSTRAND_DTYPE = np.dtype([("covered", "<i8"), ("median", "<i8"), ("max", "<i8"
 COVREC_DTYPE = np.dtype([("length", "<i8"), ("basehits", "<i8"), ("readhits", "<i8"), ("readhitsMinus", "<i8"), ("fraghits", "<i8"),
                          ("readBases", "<i8", (4,)), ("refBases", "<i8", (4,)), ("strand", COVSTRAND_DTYPE, (2,))])
 COVTOTALS_DTYPE = np.dtype([("readsProcessed", "<i8"), ("mappedReads", "<i8"), ("mappedBases", "<i8"), ("refBases", "<i8")])
-assert COVREC_DTYPE.itemsize == 200 and COVTOTALS_DTYPE.itemsize == 32
 
 
 class bbmap_cov_view(C.Structure):
@@ -47,26 +49,9 @@ def hist_bins(flags):
     return 1000001 if flags & COV_32BIT else 65536
 
 
-def _lib():
-    from . import _lib as LL
-    L = LL.load()
-    L.bbpipe_coverage_layout.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    L.bbpipe_coverage_layout.restype = C.c_int
-    L.bbpipe_coverage_workspace_bytes.argtypes = [C.c_int32, C.c_int64]
-    L.bbpipe_coverage_workspace_bytes.restype = C.c_int64
-    L.bbpipe_coverage_add_device.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + \
-        [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 5
-    L.bbpipe_coverage_add_device.restype = C.c_int
-    L.bbpipe_coverage_finalize_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 10 + [C.c_int32, C.c_void_p,
-                                                                                                                     C.c_int64] + \
-        [C.c_void_p] * 4 + [C.c_int64]
-    L.bbpipe_coverage_finalize_device.restype = C.c_int
-    return L, LL
-
-
 def layout(lengths, binsize=0):
     """bbpipe_coverage_layout: (covoff int64[n + 1], binoff int64[n + 1] or None)."""
-    L, LL = _lib()
+    L = LL.load()
     lengths = np.ascontiguousarray(lengths, np.int32)
     n = len(lengths)
     covoff = np.zeros(n + 1, np.int64)
@@ -122,10 +107,10 @@ class DeviceState:
     def add(self, reads, bases, finals, pool, paired=False):
         """bbpipe_coverage_add_device: reads / finals uint8 views of READ_DTYPE / FINAL_DTYPE records, bases and pool uint8 (device tensors)."""
         import torch
-        L, LL = _lib()
+        L = LL.load()
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         stream = torch.cuda.current_stream().cuda_stream
-        LL.check(L.bbpipe_coverage_add_device(C.c_void_p(stream), reads.numel() // 24, int(paired), self.flags, ptr(reads), ptr(bases), ptr(finals),
+        LL.check(L.bbpipe_coverage_add_device(C.c_void_p(stream), reads.numel() // READ_DTYPE.itemsize, int(paired), self.flags, ptr(reads), ptr(bases), ptr(finals),
                                               ptr(pool), self.nchroms, self.nscaf, ptr(self.d_off), ptr(self.d_loc), ptr(self.d_len), self.pad,
                                               ptr(self.d_covoff), ptr(self.diff[0]), ptr(self.diff[1]) if self.strands == 2 else None,
                                               ptr(self.recs), ptr(self.totals)), "bbpipe_coverage_add_device")
@@ -134,7 +119,7 @@ class DeviceState:
     def finalize(self, binsize=0, names=None):
         """bbpipe_coverage_finalize_device -> Coverage."""
         import torch
-        L, LL = _lib()
+        L = LL.load()
         dev, f32 = self.dev, bool(self.flags & COV_32BIT)
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         depth = [torch.zeros(self.slots, dtype=torch.int32 if f32 else torch.int16, device=dev) for _ in range(self.strands)]

@@ -281,7 +281,12 @@ READ_DTYPE = np.dtype([("bases_off", "<i8"), ("keys_off", "<i8"), ("len", "<i4")
 SITE_DTYPE = np.dtype([("chrom", "<i4"), ("strand", "<i4"), ("start", "<i4"), ("stop", "<i4"), ("hits", "<i4"),
                        ("score", "<i4"), ("perfect", "<i4"), ("semiperfect", "<i4"), ("ngaps", "<i4"),
                        ("gaps", "<i4", (16,))])
-assert C.sizeof(bbidx_params) == 96 and READ_DTYPE.itemsize == 24 and SITE_DTYPE.itemsize == 100
+
+
+def read_lens(recs):
+    """The `len` field of READ_DTYPE records held in a uint8 torch tensor (as Mapper.reads holds them), as an int32 view."""
+    import torch
+    return recs.view(torch.int32).view(-1, READ_DTYPE.itemsize // 4)[:, READ_DTYPE.fields["len"][1] // 4]
 
 
 class BuiltIndexInfo:
@@ -311,13 +316,9 @@ class DeviceIndex:
         ptrs = (C.c_void_p * (len(arrs) + 1))(*([0] + [a.ctypes.data for a in arrs]))
         lens = np.array([0] + [len(a) for a in arrs], np.int32)
         h = C.c_void_p()
-        self.L.bbidx_build_profile.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p,
-                                               C.POINTER(C.c_void_p)]
-        self.L.bbidx_build_profile.restype = C.c_int
         _lib.check(self.L.bbidx_build_profile(device, profile, k, -1 if chromBits is None else chromBits, len(arrs), ptrs,
                                               lens.ctypes.data, C.byref(h)), "bbidx_build_profile")
         self.h = h
-        self._bind()
         p = bbidx_params()
         _lib.check(self.L.bbidx_get_params(self.h, C.byref(p)), "bbidx_get_params")
         params = {n: int(getattr(p, n)) for n, _ in bbidx_params._fields_}
@@ -335,27 +336,6 @@ class DeviceIndex:
         sites = np.zeros(max(1, int(starts[nkeys])), np.int32)
         _lib.check(self.L.bbidx_export_block(self.h, block, None, sites.ctypes.data, len(sites), None, None), "bbidx_export_block")
         return starts, sites[: int(starts[nkeys])], counts, hist
-
-    def _bind(self):
-        L = self.L
-        L.bbidx_destroy.argtypes = [C.c_void_p]
-        L.bbidx_find_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
-        L.bbidx_find_batch.restype = C.c_int
-        L.bbidx_find_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-        L.bbidx_find_batch_device.restype = C.c_int
-        L.bbidx_find_batch_device_rc.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-        L.bbidx_find_batch_device_rc.restype = C.c_int
-        L.bbidx_set_kernel.argtypes = [C.c_void_p, C.c_int32]
-        L.bbidx_set_kernel.restype = C.c_int
-        L.bbidx_get_params.argtypes = [C.c_void_p, C.POINTER(bbidx_params)]
-        L.bbidx_get_params.restype = C.c_int
-        L.bbidx_export_block.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-        L.bbidx_export_block.restype = C.c_int
-        L.bbidx_last_launch.argtypes = [C.c_void_p, C.c_void_p]
-        L.bbidx_last_launch.restype = C.c_int
 
     def __init__(self, host, device=0):
         self.L = _lib.load()
@@ -376,18 +356,8 @@ class DeviceIndex:
         d.chromArrLen = self._clen.ctypes.data
         d.chromLengths = self._clen.ctypes.data
         h = C.c_void_p()
-        self.L.bbidx_create.argtypes = [C.c_int32, C.POINTER(bbidx_index_desc), C.POINTER(C.c_void_p)]
-        self.L.bbidx_create.restype = C.c_int
-        self.L.bbidx_destroy.argtypes = [C.c_void_p]
-        self.L.bbidx_find_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
-        self.L.bbidx_find_batch.restype = C.c_int
-        self.L.bbidx_find_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                   C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-        self.L.bbidx_find_batch_device.restype = C.c_int
         _lib.check(self.L.bbidx_create(device, C.byref(d), C.byref(h)), "bbidx_create")
         self.h = h
-        self._bind()
 
     def set_kernel(self, kind):
         """kind: "auto" (one read per wavefront, per-lane kernel for the reads that do not fit), "lane", or "long" (the
@@ -399,8 +369,6 @@ class DeviceIndex:
         `lengths`, optional `names` and `inter_scaffold_padding`); None clears it.  Every Mapper over this index uses it from its
         next step on."""
         L = self.L
-        L.bbidx_set_scaffolds.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
-        L.bbidx_set_scaffolds.restype = C.c_int
         if packed is None:
             _lib.check(L.bbidx_set_scaffolds(self.h, self.host.nchroms, None, None, None, 0), "bbidx_set_scaffolds")
             self.scaffold_names = None
@@ -417,8 +385,6 @@ class DeviceIndex:
 
     def set_max_read_len(self, max_len):
         """Sizing hint for the wavefront kernel (reads of at most 160 bases: 8 waves per SIMD instead of 6)."""
-        self.L.bbidx_set_max_read_len.argtypes = [C.c_void_p, C.c_int32]
-        self.L.bbidx_set_max_read_len.restype = C.c_int
         _lib.check(self.L.bbidx_set_max_read_len(self.h, int(max_len)), "bbidx_set_max_read_len")
 
     def close(self):

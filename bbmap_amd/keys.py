@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .index import READ_DTYPE
+from .index import READ_DTYPE, read_lens
 
 PROFILE_BBMAP, PROFILE_PACBIO = 0, 1
 
@@ -19,8 +19,6 @@ class bbkeys_config(C.Structure):
 def default_config(profile=PROFILE_BBMAP, **kw):
     L = _lib.load()
     cfg = bbkeys_config()
-    L.bbkeys_default_config.argtypes = [C.c_int32, C.POINTER(bbkeys_config)]
-    L.bbkeys_default_config.restype = C.c_int
     _lib.check(L.bbkeys_default_config(profile, C.byref(cfg)), "bbkeys_default_config")
     for k, v in kw.items():
         setattr(cfg, k, v)
@@ -37,8 +35,6 @@ def make_keys(bases, quality=None, cfg=None):
     q = None if quality is None else np.ascontiguousarray(np.frombuffer(bytes(quality), np.uint8) if not isinstance(quality, np.ndarray) else quality, np.uint8)
     cap = max(1, n)
     offs, ks, bs = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(max(1, n), np.int8)
-    L.bbkeys_make.argtypes = [C.POINTER(bbkeys_config), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    L.bbkeys_make.restype = C.c_int
     m = L.bbkeys_make(C.byref(cfg), b.ctypes.data, None if q is None else q.ctypes.data, n, offs.ctypes.data, ks.ctypes.data, cap, bs.ctypes.data)
     if m < 0:
         _lib.check(m, "bbkeys_make")
@@ -65,9 +61,6 @@ def make_batch(reads, qualities=None, cfg=None):
     keyinfo = np.zeros(cap, np.int32)
     bs = np.zeros(max(1, len(blob)), np.int8)
     used = C.c_int64(0)
-    L.bbkeys_make_batch.argtypes = [C.POINTER(bbkeys_config), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
-    L.bbkeys_make_batch.restype = C.c_int
     _lib.check(L.bbkeys_make_batch(C.byref(cfg), len(arrs), offs.ctypes.data, lens.ctypes.data, blob.ctypes.data,
                                    None if qblob is None else qblob.ctypes.data, recs.ctypes.data, keyinfo.ctypes.data, cap, bs.ctypes.data,
                                    C.byref(used)), "bbkeys_make_batch")
@@ -77,17 +70,8 @@ def make_batch(reads, qualities=None, cfg=None):
 _workspace = {}          # torch device -> the uint8 tensor make_batch_device hands to the library, grown on demand
 
 
-def _bind_device(L):
-    L.bbkeys_device_workspace_bytes.argtypes = [C.POINTER(bbkeys_config), C.c_int64, C.c_int64]
-    L.bbkeys_device_workspace_bytes.restype = C.c_int64
-    L.bbkeys_make_batch_device.argtypes = [C.POINTER(bbkeys_config), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-    L.bbkeys_make_batch_device.restype = C.c_int
-
-
 def workspace_bytes(cfg, n_reads, total_bases):
     L = _lib.load()
-    _bind_device(L)
     nb = L.bbkeys_device_workspace_bytes(C.byref(cfg), n_reads, total_bases)
     if nb < 0:
         _lib.check(int(nb), "bbkeys_device_workspace_bytes")
@@ -110,14 +94,13 @@ def make_batch_device(recs, bases, quality=None, cfg=None, keyinfo_cap=None):
     runtime."""
     import torch
     L = _lib.load()
-    _bind_device(L)
     cfg = cfg or default_config()
     dev = bases.device
     assert recs.dtype == torch.uint8 and recs.is_contiguous() and recs.numel() % READ_DTYPE.itemsize == 0 and recs.device == dev
     assert bases.dtype == torch.uint8 and bases.is_contiguous()
     assert quality is None or (quality.dtype == torch.uint8 and quality.is_contiguous() and quality.device == dev and quality.numel() >= bases.numel())
     n = recs.numel() // READ_DTYPE.itemsize
-    total = int(recs.view(torch.int32).view(-1, 6)[:, 4].clamp(min=0).sum(dtype=torch.int64).item()) if n else 0
+    total = int(read_lens(recs).clamp(min=0).sum(dtype=torch.int64).item()) if n else 0
     cap = keyinfo_bound(cfg, n, total) if keyinfo_cap is None else int(keyinfo_cap)
     keyinfo = torch.empty(max(1, cap), dtype=torch.int32, device=dev)
     base_scores = torch.zeros(max(1, bases.numel()), dtype=torch.int8, device=dev)

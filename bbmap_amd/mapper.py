@@ -7,7 +7,7 @@ import torch
 
 from . import _lib
 from . import msa as M
-from .index import READ_DTYPE
+from .index import READ_DTYPE, read_lens
 
 MSITE_DTYPE = np.dtype([("chrom", "<i4"), ("strand", "<i4"), ("start", "<i4"), ("stop", "<i4"), ("hits", "<i4"),
                         ("quickScore", "<i4"), ("score", "<i4"), ("slowScore", "<i4"), ("pairedScore", "<i4"),
@@ -41,8 +41,6 @@ SAM_DEFAULT_TAGS = SAM_MAKE_NM | SAM_MAKE_AM
 SAM_ALL_TAGS = (SAM_DEFAULT_TAGS | SAM_MAKE_SM | SAM_MAKE_XM | SAM_MAKE_XS | SAM_MAKE_NH | SAM_MAKE_STOP | SAM_MAKE_LENGTH |
                 SAM_MAKE_IDENTITY | SAM_MAKE_SCORE | SAM_MAKE_INSERT | SAM_MAKE_BOUNDS)
 SAM_NO_INTRON_LIMIT = 2 ** 31 - 1
-assert MSITE_DTYPE.itemsize == 128 and FINAL_DTYPE.itemsize == 64 and SCAFREC_DTYPE.itemsize == 32 and SAMREC_DTYPE.itemsize == 64
-assert SAMTAGS_DTYPE.itemsize == 64
 GAPPED_BIT = 1 << 30
 
 
@@ -91,63 +89,9 @@ class bbmap_overflow_output(C.Structure):
 NSITES_OVERFLOW, NSITES_MATE_OVERFLOW, NSITES_IN_TIER = -1, -2, -3
 
 
-def _bind(L):
-    L.bbmap_default_config.argtypes = [C.POINTER(bbmap_config)]
-    L.bbmap_default_config_profile.argtypes = [C.c_int32, C.POINTER(bbmap_config)]
-    L.bbmap_default_config_profile.restype = C.c_int
-    L.bbmap_create.argtypes = [C.c_void_p, C.POINTER(bbmap_config), C.POINTER(C.c_void_p)]
-    L.bbmap_destroy.argtypes = [C.c_void_p]
-    L.bbmap_destroy.restype = None
-    L.bbmap_map_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    L.bbmap_get_output.argtypes = [C.c_void_p, C.POINTER(bbmap_output)]
-    L.bbmap_last_stats.argtypes = [C.c_void_p, C.POINTER(bbmap_stats)]
-    L.bbmap_get_overflow_output.argtypes = [C.c_void_p, C.POINTER(bbmap_overflow_output)]
-    L.bbmap_pack_sites_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-    L.bbmap_pack_sites_device.restype = C.c_int
-    L.bbmap_map_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                  C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-    L.bbmap_map_batch.restype = C.c_int
-    L.bbmap_get_final.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-    L.bbmap_get_final.restype = C.c_int
-    L.bbmap_set_average_pair_dist.argtypes = [C.c_void_p, C.c_int32]
-    L.bbmap_set_average_pair_dist.restype = C.c_int
-    L.bbmap_get_scaffold_records.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
-    L.bbmap_get_scaffold_records.restype = C.c_int
-    L.bbmap_get_sam_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-    L.bbmap_get_sam_records.restype = C.c_int
-    L.bbmap_get_sam.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-    L.bbmap_get_sam.restype = C.c_int
-    L.bbmap_sam_default_config.argtypes = [C.POINTER(bbmap_sam_config)]
-    L.bbmap_sam_default_config.restype = C.c_int
-    L.bbmap_get_sam_records_cfg.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(bbmap_sam_config), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                            C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-    L.bbmap_get_sam_records_cfg.restype = C.c_int
-    L.bbmap_get_sam_cfg.argtypes = [C.c_void_p, C.c_int64, C.POINTER(bbmap_sam_config), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                    C.POINTER(C.c_int64)]
-    L.bbmap_get_sam_cfg.restype = C.c_int
-    L.bbpipe_sam_records_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
-    L.bbpipe_sam_records_workspace_bytes.restype = C.c_int64
-    L.bbpipe_sam_records_device.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(bbmap_sam_config), C.c_int32] + [C.c_void_p] * 7 + \
-        [C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
-    L.bbpipe_sam_records_device.restype = C.c_int
-    L.bbmap_add_run_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.bbmap_get_run_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.bbmap_reset_run_stats.argtypes = [C.c_void_p]
-    L.bbmap_set_adaptive.argtypes = [C.c_void_p, C.c_int32]
-    L.bbmap_set_truth.argtypes = [C.c_void_p, C.c_void_p]
-    L.bbmap_get_adaptive_state.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    for f in ("bbmap_add_run_stats", "bbmap_get_run_stats", "bbmap_reset_run_stats", "bbmap_set_adaptive", "bbmap_set_truth",
-              "bbmap_get_adaptive_state"):
-        getattr(L, f).restype = C.c_int
-    for f in ("bbmap_default_config", "bbmap_create", "bbmap_map_batch_device", "bbmap_get_output", "bbmap_last_stats",
-              "bbmap_get_overflow_output"):
-        getattr(L, f).restype = C.c_int
-
-
 def sam_workspace_bytes(n_reads, max_read_len):
     """bbpipe_sam_records_workspace_bytes"""
     L = _lib.load()
-    _bind(L)
     b = L.bbpipe_sam_records_workspace_bytes(int(n_reads), int(max_read_len))
     if b < 0:
         _lib.check(int(b), "bbpipe_sam_records_workspace_bytes")
@@ -163,7 +107,6 @@ def sam_records_device(reads, bases, finals, pool, scaf, recs, text, text_bytes,
     chrom_arr (int64: device addresses by chromosome number) / chrom_arr_len (int32) for MD.  Enqueues on the current stream and does
     not wait."""
     L = _lib.load()
-    _bind(L)
     n = reads.numel() // READ_DTYPE.itemsize
     cfg = sam_config(flags, intron_limit, tags)
     ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
@@ -179,8 +122,6 @@ def _copy(ptr, nbytes, dev=None):
     out = np.empty(max(nbytes, 0), np.uint8)
     if nbytes > 0:
         L = _lib.load()
-        L.bbmap_copy_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-        L.bbmap_copy_to_host.restype = C.c_int
         _lib.check(L.bbmap_copy_to_host(out.ctypes.data, C.c_void_p(ptr), nbytes), "bbmap_copy_to_host")
     return out
 
@@ -190,21 +131,38 @@ class Mapper:
     key scores.  from_records / from_reads take reads of any lengths with keys of their own; in paired mode the mates of a pair may
     differ in length (each stage uses the length of the mate it works on, as BBMapThread.processReadPair does)."""
 
-    def __init__(self, di, n_reads, read_len, offsets, key_scores, paired=False, device=0, max_sites=32, **cfg_kw):
+    def _open(self, di, n, read_len, paired, device, max_sites, cfg_kw, profile=None):
+        """What the three entry points share: the default bbmap_config (profile None: Mapper(...)'s, bbmap.sh's defaults with the
+        read length as given and always announced to the index; otherwise the profile's, a length of at least 1, announced for
+        profile 0 only), the five sizing fields, cfg_kw on top, and the context."""
         self.L = _lib.load()
-        _bind(self.L)
-        self.di, self.n, self.read_len, self.paired = di, n_reads, read_len, paired
+        self.di, self.n, self.read_len, self.paired = di, n, read_len, paired
         self.dev = torch.device("cuda", device)
-        di.set_max_read_len(read_len)
         cfg = bbmap_config()
-        _lib.check(self.L.bbmap_default_config(C.byref(cfg)), "bbmap_default_config")
-        cfg.device, cfg.paired, cfg.max_reads, cfg.max_read_len, cfg.max_sites = device, int(paired), n_reads, read_len, max_sites
+        if profile is None:
+            max_len = read_len
+            _lib.check(self.L.bbmap_default_config(C.byref(cfg)), "bbmap_default_config")
+        else:
+            max_len = max(1, read_len)
+            _lib.check(self.L.bbmap_default_config_profile(profile, C.byref(cfg)), "bbmap_default_config_profile")
+        if not profile:
+            di.set_max_read_len(max_len)
+        cfg.device, cfg.paired, cfg.max_reads, cfg.max_read_len, cfg.max_sites = device, int(paired), n, max_len, max_sites
         for k, v in cfg_kw.items():
             setattr(cfg, k, v)
         self.cfg = cfg
         h = C.c_void_p()
         _lib.check(self.L.bbmap_create(di.h, C.byref(cfg), C.byref(h)), "bbmap_create")
         self.h = h
+
+    def _upload_bases(self, blob):
+        """A fresh doubled buffer with the blob in its first half: plus strands, then the reverse complements a step writes."""
+        self.total_bytes = int(blob.size)
+        self.bases = torch.zeros(2 * self.total_bytes, dtype=torch.uint8, device=self.dev)
+        self.bases[: self.total_bytes].copy_(torch.from_numpy(blob))
+
+    def __init__(self, di, n_reads, read_len, offsets, key_scores, paired=False, device=0, max_sites=32, **cfg_kw):
+        self._open(di, n_reads, read_len, paired, device, max_sites, cfg_kw)
         self.total_bytes = n_reads * read_len
         self.bases = torch.zeros(2 * self.total_bytes, dtype=torch.uint8, device=self.dev)       # plus strands, then reverse complements
         self.base_scores = torch.zeros(self.total_bytes, dtype=torch.int8, device=self.dev)
@@ -223,28 +181,9 @@ class Mapper:
         1 = mapPacBio.sh's (BBIDX_PROFILE_*; must be the index's).  cfg_kw sets bbmap_config fields, e.g. finalStage = 1 for
         mapPacBio's final records (off by default for that profile; 2 = BBMapThread's tail, for parity tests)."""
         self = cls.__new__(cls)
-        self.L = _lib.load()
-        _bind(self.L)
         recs = np.ascontiguousarray(recs, READ_DTYPE)
-        n = len(recs)
-        self.di, self.n, self.paired = di, n, paired
-        self.read_len = int(recs["len"].max()) if n else 0
-        self.dev = torch.device("cuda", device)
-        if profile == 0:
-            di.set_max_read_len(max(1, self.read_len))
-        cfg = bbmap_config()
-        _lib.check(self.L.bbmap_default_config_profile(profile, C.byref(cfg)), "bbmap_default_config_profile")
-        cfg.device, cfg.paired, cfg.max_reads, cfg.max_read_len, cfg.max_sites = device, int(paired), n, max(1, self.read_len), max_sites
-        for k, v in cfg_kw.items():
-            setattr(cfg, k, v)
-        self.cfg = cfg
-        h = C.c_void_p()
-        _lib.check(self.L.bbmap_create(di.h, C.byref(cfg), C.byref(h)), "bbmap_create")
-        self.h = h
-        blob = np.ascontiguousarray(bases, np.uint8)
-        self.total_bytes = int(blob.size)
-        self.bases = torch.zeros(2 * self.total_bytes, dtype=torch.uint8, device=self.dev)
-        self.bases[: self.total_bytes].copy_(torch.from_numpy(blob))
+        self._open(di, len(recs), int(recs["len"].max()) if len(recs) else 0, paired, device, max_sites, cfg_kw, profile)
+        self._upload_bases(np.ascontiguousarray(bases, np.uint8))
         self.base_scores = torch.from_numpy(np.ascontiguousarray(base_scores, np.int8)).to(self.dev)
         assert self.base_scores.numel() >= self.total_bytes
         self.reads = torch.from_numpy(recs.view(np.uint8).reshape(-1).copy()).to(self.dev)
@@ -264,8 +203,6 @@ class Mapper:
         it and that order is the caller's."""
         from . import keys as K
         self = cls.__new__(cls)
-        self.L = _lib.load()
-        _bind(self.L)
         lens = np.ascontiguousarray(lens, np.int32)
         n = len(lens)
         recs = np.zeros(n, READ_DTYPE)
@@ -274,23 +211,8 @@ class Mapper:
             recs["bases_off"][1:] = np.cumsum(lens[:-1].astype(np.int64))
         blob = np.ascontiguousarray(bases, np.uint8).reshape(-1)
         assert blob.size >= int(lens.astype(np.int64).sum())
-        self.di, self.n, self.paired = di, n, paired
-        self.read_len = int(lens.max()) if n else 0
-        self.dev = torch.device("cuda", device)
-        if profile == 0:
-            di.set_max_read_len(max(1, self.read_len))
-        cfg = bbmap_config()
-        _lib.check(self.L.bbmap_default_config_profile(profile, C.byref(cfg)), "bbmap_default_config_profile")
-        cfg.device, cfg.paired, cfg.max_reads, cfg.max_read_len, cfg.max_sites = device, int(paired), n, max(1, self.read_len), max_sites
-        for k, v in cfg_kw.items():
-            setattr(cfg, k, v)
-        self.cfg = cfg
-        h = C.c_void_p()
-        _lib.check(self.L.bbmap_create(di.h, C.byref(cfg), C.byref(h)), "bbmap_create")
-        self.h = h
-        self.total_bytes = int(blob.size)
-        self.bases = torch.zeros(2 * self.total_bytes, dtype=torch.uint8, device=self.dev)
-        self.bases[: self.total_bytes].copy_(torch.from_numpy(blob))
+        self._open(di, n, int(lens.max()) if n else 0, paired, device, max_sites, cfg_kw, profile)
+        self._upload_bases(blob)
         q = None
         if quality is not None:
             qblob = np.ascontiguousarray(quality, np.uint8).reshape(-1)
@@ -304,7 +226,7 @@ class Mapper:
             from . import trim as T
             self.reads_untrimmed = self.reads
             self.reads, self.trims = T.trim_batch_device(self.reads_untrimmed, self.bases[: self.total_bytes], q, trim)
-            if n and int(self.reads.view(torch.int32).view(-1, 6)[:, 4].min().item()) <= 0:
+            if n and int(read_lens(self.reads).min().item()) <= 0:
                 raise ValueError("Mapper.from_reads: trimming left a read without bases (possible with minLength <= 0 only); "
                                  "the mapper takes no zero-length read")
         _, keyinfo, self.base_scores = K.make_batch_device(self.reads, self.bases[: self.total_bytes], q, kcfg or K.default_config(profile))
@@ -334,11 +256,10 @@ class Mapper:
         recs = np.ascontiguousarray(recs, READ_DTYPE)
         assert 0 < len(recs) <= self.cfg.max_reads and int(recs["len"].max()) <= self.cfg.max_read_len
         blob = np.ascontiguousarray(bases, np.uint8)
-        self.n, self.total_bytes = len(recs), int(blob.size)
+        self.n = len(recs)
         self.quality = None                 # (the qualities from_reads uploaded belong to the reads it was given)
         self.reads_untrimmed = self.trims = None            # (and so do its trims)
-        self.bases = torch.zeros(2 * self.total_bytes, dtype=torch.uint8, device=self.dev)
-        self.bases[: self.total_bytes].copy_(torch.from_numpy(blob))
+        self._upload_bases(blob)
         self.base_scores = torch.from_numpy(np.ascontiguousarray(base_scores, np.int8)).to(self.dev)
         assert self.base_scores.numel() >= self.total_bytes
         self.reads = torch.from_numpy(recs.view(np.uint8).reshape(-1).copy()).to(self.dev)
@@ -380,8 +301,6 @@ class Mapper:
         the trimmed read); a second call for one step raises."""
         if getattr(self, "trims", None) is None:
             raise ValueError("Mapper.untrim: the context was not made by from_reads(trim=...)")
-        self.L.bbmap_untrim_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        self.L.bbmap_untrim_batch_device.restype = C.c_int
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(self.L.bbmap_untrim_batch_device(self.h, C.c_void_p(stream), self.reads_untrimmed.data_ptr(), self.trims.data_ptr()),
                    "bbmap_untrim_batch_device")
@@ -405,8 +324,6 @@ class Mapper:
         d_sites = torch.from_numpy(st.view(np.uint8).reshape(-1).copy()).to(self.dev)
         d_ns = torch.from_numpy(np.ascontiguousarray(nsites, np.int32)).to(self.dev)
         stream = torch.cuda.current_stream().cuda_stream
-        self.L.bbmap_final_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-        self.L.bbmap_final_batch_device.restype = C.c_int
         _lib.check(self.L.bbmap_final_batch_device(self.h, C.c_void_p(stream), self.n, self.reads.data_ptr(), self.bases.data_ptr(),
                                                    self.total_bytes, d_sites.data_ptr(), d_ns.data_ptr()), "bbmap_final_batch_device")
 
@@ -505,22 +422,16 @@ class Mapper:
 
     def enable_coverage(self, flags=0):
         """bbmap_cov_enable: allocates the coverage state for the index's scaffold table (flags: bbmap_amd.coverage.COV_*)."""
-        self.L.bbmap_cov_enable.argtypes = [C.c_void_p, C.c_int32]
-        self.L.bbmap_cov_enable.restype = C.c_int
         _lib.check(self.L.bbmap_cov_enable(self.h, int(flags)), "bbmap_cov_enable")
 
     def add_coverage(self):
         """bbmap_add_coverage: adds the last step, overflow tier included.  A second call for one step raises."""
-        self.L.bbmap_add_coverage.argtypes = [C.c_void_p, C.c_void_p]
-        self.L.bbmap_add_coverage.restype = C.c_int
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(self.L.bbmap_add_coverage(self.h, C.c_void_p(stream)), "bbmap_add_coverage")
 
     def coverage(self, binsize=1000):
         """bbmap_cov_finalize: a snapshot of everything added so far as a bbmap_amd.coverage.Coverage (numpy arrays)."""
         from . import coverage as V
-        self.L.bbmap_cov_finalize.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(V.bbmap_cov_view)]
-        self.L.bbmap_cov_finalize.restype = C.c_int
         w = V.bbmap_cov_view()
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(self.L.bbmap_cov_finalize(self.h, C.c_void_p(stream), int(binsize), C.byref(w)), "bbmap_cov_finalize")
@@ -538,9 +449,6 @@ class Mapper:
         """bbmap_get_coverage, the host-buffer form: sizes first, then everything into buffers that hold it.  Returns a Coverage
         without covoff-independent extras (covoff and binoff are bbmap_amd.coverage.layout's)."""
         from . import coverage as V
-        self.L.bbmap_get_coverage.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                              C.c_int64, C.c_void_p, C.c_int64, C.POINTER(V.bbmap_cov_view)]
-        self.L.bbmap_get_coverage.restype = C.c_int
         nscaf = len(self.di.scaffold_names)
         recs, totals, w = np.zeros(nscaf, V.COVREC_DTYPE), np.zeros(1, V.COVTOTALS_DTYPE), V.bbmap_cov_view()
         _lib.check(self.L.bbmap_get_coverage(self.h, int(binsize), recs.ctypes.data, nscaf, totals.ctypes.data, None, 0, None, 0, None, 0,
@@ -557,17 +465,15 @@ class Mapper:
                           [b[:w.nbins] for b in bins] if binsize > 0 else None, self.di.scaffold_names)
 
     def reset_coverage(self):
-        self.L.bbmap_reset_coverage.argtypes = [C.c_void_p]
-        self.L.bbmap_reset_coverage.restype = C.c_int
         _lib.check(self.L.bbmap_reset_coverage(self.h), "bbmap_reset_coverage")
 
     def pack_sites(self, counts, offsets, packed):
         """The last step's site lists without their empty slots (bbmap_pack_sites_device), enqueued on the current stream:
-        counts int32[n+1], offsets int64[n+1], packed uint8[cap_records * 128] -- device tensors of the caller's."""
+        counts int32[n+1], offsets int64[n+1], packed uint8[cap_records * MSITE_DTYPE.itemsize] -- device tensors of the caller's."""
         stream = torch.cuda.current_stream().cuda_stream
-        assert counts.numel() == self.n + 1 and offsets.numel() == self.n + 1 and packed.numel() % 128 == 0
+        assert counts.numel() == self.n + 1 and offsets.numel() == self.n + 1 and packed.numel() % MSITE_DTYPE.itemsize == 0
         _lib.check(self.L.bbmap_pack_sites_device(self.h, C.c_void_p(stream), self.n, counts.data_ptr(), offsets.data_ptr(),
-                                                  packed.data_ptr(), packed.numel() // 128), "bbmap_pack_sites_device")
+                                                  packed.data_ptr(), packed.numel() // MSITE_DTYPE.itemsize), "bbmap_pack_sites_device")
 
     def output_pointers(self):
         """(bbmap_output of the last step) -- device pointers and counts, for callers that move the logs themselves."""
@@ -587,16 +493,17 @@ class Mapper:
         cap = o.cap
         out = dict(cap=cap)
         ns = n if rows is None else min(rows, n)
-        out["sites"] = _copy(o.sites, ns * cap * 128, self.dev).view(MSITE_DTYPE).reshape(ns, cap)
+        rec = lambda p, count, dt: _copy(p, count * dt.itemsize, self.dev).view(dt)
+        out["sites"] = rec(o.sites, ns * cap, MSITE_DTYPE).reshape(ns, cap)
         out["nsites"] = _copy(o.nsites, n * 4, self.dev).view(np.int32)
         nj, ng = int(o.n_jobs), int(o.n_gapped_jobs)
-        out["jobs"] = _copy(o.jobs, nj * 40, self.dev).view(M.JOB_DTYPE)
-        out["results"] = _copy(o.results, nj * 80, self.dev).view(M.RESULT_DTYPE)
-        out["jobinfo"] = _copy(o.jobinfo, nj * 16, self.dev).view(JOBINFO_DTYPE)
-        out["gjobs"] = _copy(o.gjobs, ng * 40, self.dev).view(M.JOB_DTYPE)
-        out["gresults"] = _copy(o.gresults, ng * 80, self.dev).view(M.RESULT_DTYPE)
-        out["gjobinfo"] = _copy(o.gjobinfo, ng * 16, self.dev).view(JOBINFO_DTYPE)
-        out["ggaps"] = _copy(o.ggaps, ng * 68, self.dev).view(M.GAPS_DTYPE)
+        out["jobs"] = rec(o.jobs, nj, M.JOB_DTYPE)
+        out["results"] = rec(o.results, nj, M.RESULT_DTYPE)
+        out["jobinfo"] = rec(o.jobinfo, nj, JOBINFO_DTYPE)
+        out["gjobs"] = rec(o.gjobs, ng, M.JOB_DTYPE)
+        out["gresults"] = rec(o.gresults, ng, M.RESULT_DTYPE)
+        out["gjobinfo"] = rec(o.gjobinfo, ng, JOBINFO_DTYPE)
+        out["ggaps"] = rec(o.ggaps, ng, M.GAPS_DTYPE)
         out["match_stride"], out["gmatch_stride"] = o.match_stride, o.gmatch_stride
         if with_match:
             out["match"] = _copy(o.match, nj * o.match_stride, self.dev).reshape(nj, o.match_stride)
@@ -622,8 +529,6 @@ class Mapper:
     def enable_read_hist(self, flags=None):
         """bbmap_hist_enable: allocates the zeroed histogram state (flags: bbmap_amd.readstats.RH_*, default all groups)."""
         from . import readstats as R
-        self.L.bbmap_hist_enable.argtypes = [C.c_void_p, C.c_int32]
-        self.L.bbmap_hist_enable.restype = C.c_int
         _lib.check(self.L.bbmap_hist_enable(self.h, int(R.RH_ALL if flags is None else flags)), "bbmap_hist_enable")
 
     def add_read_hist(self, quality=None):
@@ -634,8 +539,6 @@ class Mapper:
         if quality is None and getattr(self, "_stepped_own_bases", True):
             quality = getattr(self, "quality", None)        # (cleared by load_reads / load_records; not used for step(bases=other))
         assert quality is None or (quality.dtype == torch.uint8 and quality.numel() >= self.total_bytes)
-        self.L.bbmap_add_read_hist.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        self.L.bbmap_add_read_hist.restype = C.c_int
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(self.L.bbmap_add_read_hist(self.h, C.c_void_p(stream), None if quality is None else C.c_void_p(quality.data_ptr())),
                    "bbmap_add_read_hist")
@@ -643,8 +546,6 @@ class Mapper:
     def read_hist(self):
         """bbmap_get_read_hist: a host copy of everything added so far as a bbmap_amd.readstats.ReadHist."""
         from . import readstats as R
-        self.L.bbmap_get_read_hist.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(R.bbmap_readhist_view)]
-        self.L.bbmap_get_read_hist.restype = C.c_int
         w = R.bbmap_readhist_view()
         _lib.check(self.L.bbmap_get_read_hist(self.h, None, 0, C.byref(w)), "bbmap_get_read_hist")
         block = np.zeros(w.words, np.int64)
@@ -652,15 +553,12 @@ class Mapper:
         return R.ReadHist(w.flags, block)
 
     def reset_read_hist(self):
-        self.L.bbmap_reset_read_hist.argtypes = [C.c_void_p]
-        self.L.bbmap_reset_read_hist.restype = C.c_int
         _lib.check(self.L.bbmap_reset_read_hist(self.h), "bbmap_reset_read_hist")
 
     def enable_split(self, tables, flags=None, ambiguous2=0, clearzone=0, max_sites=0):
         """bbmap_split_enable: reference-set binning over the index's scaffold table.  tables: bbmap_amd.refsplit.tables(...) of the
         reference's scaffold names; clearzone / max_sites 0 = the context's CLEARZONE1 and the profile's MAX_SITESCORES_TO_PRINT."""
         from . import refsplit as S
-        S._bind()
         cfg = S.config(S.SPLIT_ALL if flags is None else flags, ambiguous2, clearzone, max_sites, tables.nsets, tables.nkeys)
         sets, keys = np.ascontiguousarray(tables.scaf_sets, np.uint64), np.ascontiguousarray(tables.scaf_key, np.int32)
         _lib.check(self.L.bbmap_split_enable(self.h, C.byref(cfg), sets.ctypes.data, keys.ctypes.data), "bbmap_split_enable")
@@ -668,24 +566,19 @@ class Mapper:
 
     def add_split(self):
         """bbmap_add_split: adds the last step, overflow tier included.  A second call for one step raises."""
-        from . import refsplit as S
-        S._bind()
         _lib.check(self.L.bbmap_add_split(self.h, C.c_void_p(torch.cuda.current_stream().cuda_stream)), "bbmap_add_split")
 
     def split_records(self):
         """Host copy of the last added step's per-read records (refsplit.SPLITREC_DTYPE)."""
         from . import refsplit as S
-        S._bind()
         p = C.c_void_p()
         _lib.check(self.L.bbmap_get_split_records(self.h, C.byref(p)), "bbmap_get_split_records")
         torch.cuda.current_stream().synchronize()
-        return _copy(p.value, self.n * 32, self.dev).view(S.SPLITREC_DTYPE)
+        return _copy(p.value, self.n * S.SPLITREC_DTYPE.itemsize, self.dev).view(S.SPLITREC_DTYPE)
 
     def split_lists(self):
         """bbmap_get_split_lists: (set_off int64[2 nsets + 1], units int32[total]) of the last added step, on the host; rows 0 .. nsets - 1
         are the sets' streams, the rest their ambiguous streams (refsplit.lists_of splits them)."""
-        from . import refsplit as S
-        S._bind()
         torch.cuda.current_stream().synchronize()
         set_off = np.zeros(2 * self._split_tables.nsets + 1, np.int64)
         total = C.c_int64()
@@ -698,13 +591,10 @@ class Mapper:
     def split_stats(self):
         """bbmap_get_split_stats: everything added so far as a refsplit.SplitStats."""
         from . import refsplit as S
-        S._bind()
         t = self._split_tables
         words = np.zeros(S.STATE_HEAD + 4 * (t.nkeys + t.nsets), np.int64)
         _lib.check(self.L.bbmap_get_split_stats(self.h, words.ctypes.data, words.size), "bbmap_get_split_stats")
         return S.SplitStats.from_words(words, t.nkeys, t.nsets, t.key_names, t.set_names)
 
     def reset_split(self):
-        from . import refsplit as S
-        S._bind()
         _lib.check(self.L.bbmap_reset_split(self.h), "bbmap_reset_split")

@@ -22,14 +22,8 @@ FILL_AND_SCORE_LIMITED = FILL_LIMITED | CLAMP_WINDOW | DO_SCORE
 
 ST_OK, ST_NULL, ST_BAD_SHAPE = 0, 1, 2
 
-JOB_DTYPE = np.dtype([("read_off", "<i8"), ("ref_off", "<i8"), ("read_len", "<i4"), ("ref_len", "<i4"),
-                      ("refStartLoc", "<i4"), ("refEndLoc", "<i4"), ("minScore", "<i4"), ("flags", "<i4")])
-RESULT_DTYPE = np.dtype([("result", "<i4", (5,)), ("status", "<i4"), ("iterations", "<i8"),
-                         ("score", "<i4", (8,)), ("score_len", "<i4"), ("match_len", "<i4"),
-                         ("fill_kind", "<i4"), ("columns", "<i4")])
-GAPS_DTYPE = np.dtype([("ngaps", "<i4"), ("gaps", "<i4", (16,))])
-assert JOB_DTYPE.itemsize == C.sizeof(bbmsa_job) and RESULT_DTYPE.itemsize == C.sizeof(bbmsa_result)
-assert GAPS_DTYPE.itemsize == 68
+JOB_DTYPE, RESULT_DTYPE = np.dtype(bbmsa_job), np.dtype(bbmsa_result)
+GAPS_DTYPE = np.dtype([("ngaps", "<i4"), ("gaps", "<i4", (16,))])          # bbmsa_gaps
 
 
 class bbmsa_ticket(C.Structure):

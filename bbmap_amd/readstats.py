@@ -18,6 +18,9 @@ from decimal import ROUND_HALF_UP, Decimal
 
 import numpy as np
 
+from . import _lib as LL
+from .index import READ_DTYPE
+
 RH_MATCH, RH_QUALITY, RH_BASE, RH_ACCURACY, RH_INDEL, RH_ERROR, RH_LENGTH, RH_GC, RH_IDENTITY = 1, 2, 4, 8, 16, 32, 64, 128, 256
 RH_ALL = 511
 RH_GROUPS = (RH_MATCH, RH_QUALITY, RH_BASE, RH_ACCURACY, RH_INDEL, RH_ERROR, RH_LENGTH, RH_GC, RH_IDENTITY)
@@ -47,21 +50,9 @@ class bbmap_readhist_view(C.Structure):
         [(name if name != "del" else "del_", C.c_void_p) for name, _ in SHAPES]
 
 
-def _lib():
-    from . import _lib as LL
-    L = LL.load()
-    L.bbpipe_read_hist_bytes.argtypes = [C.c_int32]
-    L.bbpipe_read_hist_bytes.restype = C.c_int64
-    L.bbpipe_read_hist_view.argtypes = [C.c_int32, C.c_void_p, C.POINTER(bbmap_readhist_view)]
-    L.bbpipe_read_hist_view.restype = C.c_int
-    L.bbpipe_read_hist_add_device.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6
-    L.bbpipe_read_hist_add_device.restype = C.c_int
-    return L, LL
-
-
 def state_words(flags):
     """bbpipe_read_hist_bytes / 8"""
-    L, LL = _lib()
+    L = LL.load()
     b = L.bbpipe_read_hist_bytes(int(flags))
     if b < 0:
         LL.check(int(b), "bbpipe_read_hist_bytes")
@@ -156,7 +147,7 @@ class ReadHist:
     bbmap_readhist_view (views of the block; "del" as .del_ too); an array of a group that is not selected is None."""
 
     def __init__(self, flags, block):
-        L, LL = _lib()
+        L = LL.load()
         self.flags = int(flags)
         self.block = np.ascontiguousarray(block, np.int64)
         w = bbmap_readhist_view()
@@ -396,10 +387,10 @@ class DeviceState:
         """bbpipe_read_hist_add_device: reads / finals uint8 views of READ_DTYPE / FINAL_DTYPE records, bases / quality / pool uint8
         (device tensors; quality may be None)."""
         import torch
-        L, LL = _lib()
+        L = LL.load()
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         stream = torch.cuda.current_stream().cuda_stream
-        LL.check(L.bbpipe_read_hist_add_device(C.c_void_p(stream), reads.numel() // 24, int(paired), self.flags, ptr(reads), ptr(bases), ptr(quality),
+        LL.check(L.bbpipe_read_hist_add_device(C.c_void_p(stream), reads.numel() // READ_DTYPE.itemsize, int(paired), self.flags, ptr(reads), ptr(bases), ptr(quality),
                                                ptr(finals), ptr(pool), ptr(self.state)), "bbpipe_read_hist_add_device")
         torch.cuda.current_stream().synchronize()
 

@@ -9,6 +9,7 @@ import numpy as np
 
 from . import _lib as LL
 from .coverage import jfmt
+from .index import READ_DTYPE
 
 SPLIT_SCAF_STATS, SPLIT_SET_STATS, SPLIT_RECORDS, SPLIT_LISTS, SPLIT_ALL = 1, 2, 4, 8, 15
 AMBIG2_UNSET, AMBIG2_FIRST, AMBIG2_SPLIT, AMBIG2_TOSS, AMBIG2_RANDOM, AMBIG2_ALL = 0, 1, 2, 3, 4, 5       # BBSplitter.java:1203-1208
@@ -17,16 +18,12 @@ LDS_SLOTS, MAX_PROBES, CHUNK_READS, MAX_BLOCKS, LIST_BLOCK = 1024, 8, 4096, 1024
 STATE_HEAD = 4
 REC_AMBIG_SETS, REC_AMBIG_READ, REC_MAPPED = 1, 2, 4
 SPLITREC_DTYPE = np.dtype([("primary_mask", "<u8"), ("ambig_mask", "<u8"), ("flags", "<i4"), ("key", "<i4"), ("stats_mask", "<u8")])
-assert SPLITREC_DTYPE.itemsize == 32
 HEADER = "#name\t%unambiguousReads\tunambiguousMB\t%ambiguousReads\tambiguousMB\tunambiguousReads\tambiguousReads"      # :1170
 
 
 class bbmap_split_config(C.Structure):
     _fields_ = [("flags", C.c_int32), ("ambiguous2", C.c_int32), ("clearzone", C.c_int32), ("maxSites", C.c_int32), ("nsets", C.c_int32),
                 ("nkeys", C.c_int32), ("reserved", C.c_int32 * 2)]
-
-
-assert C.sizeof(bbmap_split_config) == 32
 
 
 def slot_of(key):
@@ -141,37 +138,12 @@ def lists_of(set_off, units, nsets):
     return rows[:nsets], rows[nsets:]
 
 
-def _bind():
-    L = LL.load()
-    L.bbpipe_refsplit_state_bytes.argtypes = [C.c_int32, C.c_int32]
-    L.bbpipe_refsplit_state_bytes.restype = C.c_int64
-    L.bbpipe_refsplit_add_device.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(bbmap_split_config)] + [C.c_void_p] * 4 + \
-        [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4
-    L.bbpipe_refsplit_add_device.restype = C.c_int
-    L.bbpipe_refsplit_lists_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
-    L.bbpipe_refsplit_lists_workspace_bytes.restype = C.c_int64
-    L.bbpipe_refsplit_lists_device.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                               C.c_void_p, C.c_int64]
-    L.bbpipe_refsplit_lists_device.restype = C.c_int
-    L.bbmap_split_enable.argtypes = [C.c_void_p, C.POINTER(bbmap_split_config), C.c_void_p, C.c_void_p]
-    L.bbmap_add_split.argtypes = [C.c_void_p, C.c_void_p]
-    L.bbmap_get_split_records.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-    L.bbmap_get_split_lists_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-    L.bbmap_get_split_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-    L.bbmap_get_split_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-    L.bbmap_reset_split.argtypes = [C.c_void_p]
-    for f in ("bbmap_split_enable", "bbmap_add_split", "bbmap_get_split_records", "bbmap_get_split_lists_device", "bbmap_get_split_lists",
-              "bbmap_get_split_stats", "bbmap_reset_split"):
-        getattr(L, f).restype = C.c_int
-    return L
-
-
 def config(flags=SPLIT_ALL, ambiguous2=AMBIG2_UNSET, clearzone=0, max_sites=0, nsets=0, nkeys=0):
     return bbmap_split_config(int(flags), int(ambiguous2), int(clearzone), int(max_sites), int(nsets), int(nkeys), (C.c_int32 * 2)(0, 0))
 
 
 def state_words(nkeys, nsets):
-    b = _bind().bbpipe_refsplit_state_bytes(int(nkeys), int(nsets))
+    b = LL.load().bbpipe_refsplit_state_bytes(int(nkeys), int(nsets))
     if b < 0:
         LL.check(int(b), "bbpipe_refsplit_state_bytes")
     return int(b) // 8
@@ -197,9 +169,9 @@ class DeviceSplit:
 
     def add(self, reads, finals, sites, nsites, cap, paired):
         """reads / finals / sites: uint8 device tensors of READ_DTYPE / FINAL_DTYPE / MSITE_DTYPE records (sites n x cap), nsites int32"""
-        L, torch = _bind(), self.torch
-        n = reads.numel() // 24
-        self.records = torch.zeros(max(n, 1) * 32, dtype=torch.uint8, device=self.dev)
+        L, torch = LL.load(), self.torch
+        n = reads.numel() // READ_DTYPE.itemsize
+        self.records = torch.zeros(max(n, 1) * SPLITREC_DTYPE.itemsize, dtype=torch.uint8, device=self.dev)
         self.n, self.paired = n, bool(paired)
         stream = torch.cuda.current_stream().cuda_stream
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())        # noqa: E731
@@ -216,7 +188,7 @@ class DeviceSplit:
 
     def lists(self):
         """(set_off int64[2 nsets + 1], units int32[total]) of the last add, on the host"""
-        L, torch = _bind(), self.torch
+        L, torch = LL.load(), self.torch
         nsets = self.cfg.nsets
         need = L.bbpipe_refsplit_lists_workspace_bytes(self.n, int(self.paired), nsets)
         if need < 0:

@@ -9,7 +9,6 @@ from . import _lib
 JOB_DTYPE = np.dtype([("read_off", "<i8"), ("read_len", "<i4"), ("chrom", "<i4"), ("loc", "<i4"), ("searchDist", "<i4"),
                       ("idealStart", "<i4"), ("maxAllowedMismatches", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
 RESULT_DTYPE = np.dtype([(n, "<i4") for n in ("found", "start", "stop", "score", "mismatches", "perfect", "semiperfect", "maxContig")])
-assert JOB_DTYPE.itemsize == 40 and RESULT_DTYPE.itemsize == 32
 
 
 def quick_rescue_batch(problems, chroms, min_index=None, points_match=70, points_match2=100, use_affine=True,

@@ -5,6 +5,9 @@ import ctypes as C
 
 import numpy as np
 
+from . import _lib
+from .index import READ_DTYPE
+
 PER_MATE = ("mappedRetained", "mappedRetainedBases", "ambiguousBestAlignment", "ambiguousBestAlignmentBases", "matchCountM", "matchCountS",
             "matchCountD", "matchCountI", "matchCountN", "readCountS", "readCountD", "readCountI", "readCountN", "readCountE", "rescuedP",
             "rescuedM", "perfectMatch", "perfectMatchBases", "perfectHitCount", "semiPerfectHitCount", "semiperfectMatch",
@@ -20,7 +23,6 @@ TRUTH_DTYPE = np.dtype([("chrom", "<i4"), ("strand", "<i4"), ("start", "<i4"), (
 INSERT_HIST_BINS = 40001            # ReadStats.MAXINSERTLEN + 1
 RUNSTATS_MAX_WAVES = 8192           # wavefronts of the kernel's persistent grid
 ADAPT_INSERT_LENGTH, ADAPT_RESCUE_SKIP = 1, 2
-assert RUNSTATS_DTYPE.itemsize == 768 and TRUTH_DTYPE.itemsize == 16
 
 
 def run_stats_device(reads, finals, pool, sites, nsites, cap, paired=False, scheme=0, thresh=0, truth=None, counters=None, ihist=None):
@@ -28,11 +30,8 @@ def run_stats_device(reads, finals, pool, sites, nsites, cap, paired=False, sche
     TRUTH_DTYPE truth or None); counters: int64[96] tensor that is ADDED to (made when None), ihist: int64[INSERT_HIST_BINS] or None.
     Returns (RUNSTATS_DTYPE scalar, the counters tensor)."""
     import torch
-    from . import _lib
     L = _lib.load()
-    L.bbpipe_run_stats_device.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 3
-    L.bbpipe_run_stats_device.restype = C.c_int
-    n = reads.numel() // 24
+    n = reads.numel() // READ_DTYPE.itemsize
     if counters is None:
         counters = torch.zeros(RUNSTATS_DTYPE.itemsize // 8, dtype=torch.int64, device=reads.device)
     stream = torch.cuda.current_stream().cuda_stream

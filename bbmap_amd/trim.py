@@ -18,22 +18,9 @@ class bbtrim_config(C.Structure):
                 ("windowLength", C.c_int32), ("minGoodInterval", C.c_int32), ("optimalBias", C.c_float)]
 
 
-assert C.sizeof(bbtrim_config) == 32 and TRIM_DTYPE.itemsize == 8
-
-
-def _bind(L):
-    L.bbtrim_default_config.argtypes = [C.POINTER(bbtrim_config)]
-    L.bbtrim_default_config.restype = C.c_int
-    L.bbtrim_batch.argtypes = [C.POINTER(bbtrim_config), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.bbtrim_batch.restype = C.c_int
-    L.bbtrim_batch_device.argtypes = [C.POINTER(bbtrim_config), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.bbtrim_batch_device.restype = C.c_int
-    return L
-
-
 def default_config(**kw):
     """BBMap's defaults (optimal mode, both sides off, trimq 6, minLength 60, window 4, interval 2, no bias); kw sets fields."""
-    L = _bind(_lib.load())
+    L = _lib.load()
     cfg = bbtrim_config()
     _lib.check(L.bbtrim_default_config(C.byref(cfg)), "bbtrim_default_config")
     for k, v in kw.items():
@@ -108,7 +95,7 @@ def from_flags(qtrim=None, trimq=None, minlength=None, optitrim=None, trimgoodin
 def trim_batch(recs, bases, quality=None, cfg=None):
     """bbtrim_batch, the host form.  recs: READ_DTYPE (bases_off, len), bases / quality: uint8 blobs (quality numeric phred at the same
     offsets, or None).  Returns (trimmed READ_DTYPE records: bases_off moved, keys_off = nkeys = 0, TRIM_DTYPE[n])."""
-    L = _bind(_lib.load())
+    L = _lib.load()
     cfg = cfg or default_config()
     recs = np.ascontiguousarray(recs, READ_DTYPE)
     b = np.ascontiguousarray(bases, np.uint8).reshape(-1)
@@ -129,7 +116,7 @@ def trim_batch_device(recs, bases, quality=None, cfg=None):
     recs is not written.  Enqueues on the current stream and does not wait.  As with the mapper, torch must have been imported
     before the library is first loaded."""
     import torch
-    L = _bind(_lib.load())
+    L = _lib.load()
     cfg = cfg or default_config()
     dev = bases.device
     assert recs.dtype == torch.uint8 and recs.is_contiguous() and recs.numel() % READ_DTYPE.itemsize == 0 and recs.device == dev

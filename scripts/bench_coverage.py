@@ -78,8 +78,6 @@ def main():
         mp.enable_coverage(flags)
         step, add, stats, fin = [], [], [], []
         view = V.bbmap_cov_view()
-        mp.L.bbmap_cov_finalize.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(V.bbmap_cov_view)]
-        mp.L.bbmap_add_coverage.argtypes = [C.c_void_p, C.c_void_p]
         for i in range(args.warmup + args.reps):
             t_step = timed(mp.step)
             t_add = timed(lambda: _lib.check(mp.L.bbmap_add_coverage(mp.h, C.c_void_p(stream)), "bbmap_add_coverage"))

@@ -81,8 +81,6 @@ def main():
         return spread(ms)
 
     out = dict(workload=args.workload, reads=n, read_len=L, reps=args.reps, ms_step=timed(mp.step))
-    mp.L.bbmap_add_read_hist.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    mp.L.bbmap_add_coverage.argtypes = [C.c_void_p, C.c_void_p]
     qp = C.c_void_p(quality.data_ptr())
     out["ms_add_read_hist_all"] = series(lambda: _lib.check(mp.L.bbmap_add_read_hist(mp.h, C.c_void_p(stream), qp), "bbmap_add_read_hist"),
                                          before=mp.step)
@@ -96,7 +94,7 @@ def main():
     # ---- the raw form over the same records: all groups, each alone, all without qualities
     o = bbmap_output()
     _lib.check(mp.L.bbmap_get_output(mp.h, C.byref(o)), "bbmap_get_output")
-    Lr, _ = R._lib()
+    Lr = _lib.load()
 
     def raw(flags, q):
         state = R.DeviceState(flags)

@@ -36,8 +36,6 @@ d_sites = torch.zeros(n * max_sites * 100, dtype=torch.uint8, device=dev)
 d_nsites = torch.zeros(n, dtype=torch.int32, device=dev)
 Lb = _lib.load()
 f = Lb.bbidx_find_batch_device
-f.restype = C.c_int
-f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.c_int32, C.c_void_p]
 stream = torch.cuda.current_stream().cuda_stream
 for it in range(4):
     torch.cuda.synchronize()

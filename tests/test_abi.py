@@ -2,8 +2,10 @@
 import ctypes as C
 import os
 import re
+import subprocess
 import threading
 
+import numpy as np
 import pytest
 
 from bbmap_amd import _lib, build
@@ -14,17 +16,63 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def declared_symbols():
     hdr = open(os.path.join(ROOT, "include", "bbmap_amd.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return sorted(set(re.findall(r"\b(bb(?:map|msa|band|idx|pipe|keys)_[a-z0-9_]+)\s*\(", hdr)))
+    return sorted(set(re.findall(r"\b(bb[a-z]+_[a-z0-9_]+)\s*\(", hdr)))
 
 
 def test_library_builds_and_exports_every_declared_symbol():
     build.build()
     L = C.CDLL(_lib.SO_PATH)
     syms = declared_symbols()
-    assert syms, "no symbols parsed from include/bbmap_amd.h"
+    assert len(syms) >= 111, "include/bbmap_amd.h declared 111 functions when this test was written; the regex finds %d" % len(syms)
+    for s in ("bbmsa_align_batch", "bbband_align_batch", "bbidx_find_batch", "bbmap_map_batch_device", "bbpipe_revcomp_device", "bbtrim_batch"):
+        assert s in syms, "not found in the header: " + s
     for s in syms:
         assert hasattr(L, s), "missing export: " + s
-    assert sorted(_lib.EXPORTS) == syms
+    assert _lib.EXPORTS == syms                 # the loader's prototype reader and this regex find the same names
+
+
+VP, I32, I64 = C.c_void_p, C.c_int32, C.c_int64
+# (restype, argtypes) as the binding declared them by hand before the loader read the header, every POINTER(x) written as c_void_p
+PINNED = {
+    "bbmap_get_sam": (C.c_int, [VP, I64, I32, VP, VP, I64, VP]),                                     # an int64_t count between pointers
+    "bbidx_export_block": (C.c_int, [VP, I32, VP, VP, I64, VP, VP]),                                 # an int32_t between pointers
+    "bbpipe_sam_records_device": (C.c_int, [VP, I64, I32, VP, I32] + [VP] * 7 + [I32] + [VP] * 5 + [I64, VP, VP, I64]),      # a long mixed tail
+    "bbkeys_device_workspace_bytes": (I64, [VP, I64, I64]),                                          # an int64_t return
+    "bbpipe_sam_records_workspace_bytes": (I64, [I64, I32]),                                         # no pointer at all
+    "bbmap_destroy": (None, [VP]),                                                                   # a void return
+    "bbmap_last_error": (C.c_char_p, []),                                                            # const char *, and (void)
+    "bbmap_abi_version": (C.c_int, []),                                                              # (void)
+    "bbmsa_align_batch": (C.c_int, [VP, I64, VP, VP, I64, VP, I64, VP, VP, I32]),                    # four header lines
+    "bbidx_build_profile": (C.c_int, [I32] * 5 + [VP] * 3),                                          # values first; `const T *const *`
+    "bbmsa_fill_submit": (C.c_int, [VP, VP, I32, VP, I32, I32, I32, I32, I32, VP, VP, VP]),
+    "bbtrim_batch_device": (C.c_int, [VP, VP, I64, VP, VP, VP, VP, VP]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(PINNED))
+def test_derived_signature_equals_the_hand_written_one(name):
+    assert _lib.PROTOTYPES[name] == PINNED[name]
+    fn = getattr(_lib.load(), name)
+    assert (fn.restype, list(fn.argtypes)) == PINNED[name]
+
+
+def test_load_types_every_declared_function():
+    L = _lib.load()
+    for s in declared_symbols():
+        fn = getattr(L, s)
+        assert fn.argtypes is not None and (fn.restype, list(fn.argtypes)) == _lib.PROTOTYPES[s], s
+
+
+@pytest.mark.parametrize("proto, word", [("int bbmap_new_call(bbmap_ctx *ctx, float ratio);", "float ratio"),
+                                         ("int bbmap_new_call(bbmap_ctx *ctx, bbmap_config cfg);", "bbmap_config cfg"),
+                                         ("double bbmap_new_call(bbmap_ctx *ctx);", "double"),
+                                         ("bbmap_ctx *bbmap_new_call(void);", "bbmap_ctx *")])
+def test_a_type_outside_the_table_is_refused_by_name(proto, word):
+    good = "/* c */\ntypedef struct bbx { int32_t a; } bbx;\nint bbmap_ok(const bbx *x,\n             int64_t n);\n"
+    assert _lib.parse_prototypes(good) == {"bbmap_ok": (C.c_int, [VP, I64])}
+    with pytest.raises(_lib.BBMapAmdError) as e:
+        _lib.parse_prototypes(good + proto)
+    assert "bbmap_new_call" in str(e.value) and word in str(e.value)
 
 
 def test_struct_layouts_match_header():
@@ -32,6 +80,57 @@ def test_struct_layouts_match_header():
     assert C.sizeof(_lib.bbmsa_result) == 80
     assert _lib.bbmsa_result.iterations.offset == 24
     assert _lib.bbmsa_result.score.offset == 32
+
+
+def _mirrors():
+    """(struct name in the header, its Python mirror: a ctypes.Structure or a numpy dtype), every record the binding declares"""
+    from bbmap_amd import banded, coverage, index, keys, mapper, msa, readstats, refsplit, rescue, runstats, trim
+    return [("bbmsa_job", _lib.bbmsa_job), ("bbmsa_result", _lib.bbmsa_result), ("bbmsa_config", _lib.bbmsa_config),
+            ("bbband_job", _lib.bbband_job), ("bbband_result", _lib.bbband_result), ("bbband_config", _lib.bbband_config),
+            ("bbmsa_job", msa.JOB_DTYPE), ("bbmsa_result", msa.RESULT_DTYPE), ("bbmsa_gaps", msa.GAPS_DTYPE), ("bbmsa_ticket", msa.bbmsa_ticket),
+            ("bbband_job", banded.JOB_DTYPE), ("bbband_result", banded.RESULT_DTYPE), ("bbband_pair", banded.PAIR_DTYPE),
+            ("bbidx_params", index.bbidx_params), ("bbidx_index_desc", index.bbidx_index_desc), ("bbidx_read", index.READ_DTYPE),
+            ("bbidx_site", index.SITE_DTYPE), ("bbkeys_config", keys.bbkeys_config), ("bbtrim_config", trim.bbtrim_config),
+            ("bbtrim_rec", trim.TRIM_DTYPE), ("bbresc_job", rescue.JOB_DTYPE), ("bbresc_result", rescue.RESULT_DTYPE),
+            ("bbmap_msite", mapper.MSITE_DTYPE), ("bbmap_jobinfo", mapper.JOBINFO_DTYPE), ("bbmap_final", mapper.FINAL_DTYPE),
+            ("bbmap_scafrec", mapper.SCAFREC_DTYPE), ("bbmap_samrec", mapper.SAMREC_DTYPE), ("bbmap_samtags", mapper.SAMTAGS_DTYPE),
+            ("bbmap_config", mapper.bbmap_config), ("bbmap_sam_config", mapper.bbmap_sam_config), ("bbmap_output", mapper.bbmap_output),
+            ("bbmap_stats", mapper.bbmap_stats), ("bbmap_overflow_output", mapper.bbmap_overflow_output),
+            ("bbmap_runstats", runstats.RUNSTATS_DTYPE), ("bbmap_truth", runstats.TRUTH_DTYPE),
+            ("bbmap_covstrand", coverage.COVSTRAND_DTYPE), ("bbmap_covrec", coverage.COVREC_DTYPE), ("bbmap_covtotals", coverage.COVTOTALS_DTYPE),
+            ("bbmap_cov_view", coverage.bbmap_cov_view), ("bbmap_readhist_view", readstats.bbmap_readhist_view),
+            ("bbmap_split_config", refsplit.bbmap_split_config), ("bbmap_splitrec", refsplit.SPLITREC_DTYPE)]
+
+
+def _layout(mirror):
+    """(size, {field: offset}) of a ctypes.Structure or a numpy dtype"""
+    if isinstance(mirror, np.dtype):
+        return mirror.itemsize, {n: mirror.fields[n][1] for n in mirror.names}
+    return C.sizeof(mirror), {n: getattr(mirror, n).offset for n, *_ in mirror._fields_}
+
+
+def test_every_mirrored_record_has_the_compiler_s_layout(tmp_path):
+    """sizeof and every mirrored field's offsetof, as the host C compiler lays the header's structs out, against the Python mirrors:
+    a mirror field the header lacks does not compile, a missing or reordered one shifts an offset or the size."""
+    mirrors = _mirrors()
+    assert len(mirrors) >= 42
+    src = ["#include <stdio.h>", "#include <stddef.h>", '#include "bbmap_amd.h"', "int main(void) {"]
+    for i, (name, mirror) in enumerate(mirrors):
+        src.append('    printf("%d sizeof %%zu\\n", sizeof(%s));' % (i, name))
+        for f in _layout(mirror)[1]:
+            # (a trailing underscore keeps a mirror's field clear of a Python keyword: bbmap_readhist_view.del_)
+            src.append('    printf("%d %s %%zu\\n", offsetof(%s, %s));' % (i, f, name, f.rstrip("_")))
+    src += ["    return 0;", "}", ""]
+    (tmp_path / "layout.c").write_text("\n".join(src))
+    exe = str(tmp_path / "layout")
+    subprocess.run([os.environ.get("CC", "cc"), "-std=c11", "-I", os.path.join(ROOT, "include"), str(tmp_path / "layout.c"), "-o", exe], check=True)
+    got = {}
+    for line in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines():
+        i, f, v = line.split()
+        got.setdefault(int(i), {})[f] = int(v)
+    for i, (name, mirror) in enumerate(mirrors):
+        size, offsets = _layout(mirror)
+        assert dict(offsets, sizeof=size) == got[i], "%s (%s)" % (name, mirror.__name__ if isinstance(mirror, type) else "dtype")
 
 
 def test_abi_version():
@@ -66,7 +165,7 @@ def _idx_desc_k(k):
     return d
 
 
-NULL, I32, I64 = None, C.c_int32, C.c_int64
+NULL = None
 OUT = lambda: C.byref(C.c_void_p())         # noqa: E731
 
 # (entry point, arguments, return code, bbmap_last_error()): every one is refused before the first HIP call, so the same holds

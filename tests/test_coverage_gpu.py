@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from bbmap_amd import _lib
 from bbmap_amd import coverage as V
 from bbmap_amd.index import DeviceIndex, READ_DTYPE
 from bbmap_amd.mapper import FINAL_DTYPE, Mapper
@@ -256,7 +257,7 @@ def test_accumulation_goes_on_after_a_finalize():
 
 
 def test_raw_calls_reject_bad_arguments():
-    L, _ = V._lib()
+    L = _lib.load()
     assert L.bbpipe_coverage_add_device(None, -1, 0, 0, *([None] * 4), 1, 1, None, None, None, 0, *([None] * 5)) == -2
     assert L.bbpipe_coverage_add_device(None, 1, 0, 16, *([None] * 4), 1, 1, None, None, None, 0, *([None] * 5)) == -2
     assert L.bbmap_last_error() == b"bbpipe_coverage_add_device: unknown flag bits"

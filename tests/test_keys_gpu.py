@@ -94,7 +94,6 @@ def test_phix_reads_with_their_qualities(gpu_msa_lib, profile):
 
 def _raw(cfg, recs, bases, quality, keyinfo, cap, base_scores, ws, ws_bytes):
     L = _lib.load()
-    K._bind_device(L)
     used = C.c_int64(-5)
     rc = L.bbkeys_make_batch_device(C.byref(cfg), C.c_void_p(torch.cuda.current_stream().cuda_stream), recs.numel() // 24, recs.data_ptr(),
                                     bases.data_ptr(), quality.data_ptr(), keyinfo.data_ptr(), cap, base_scores.data_ptr(), ws.data_ptr(),

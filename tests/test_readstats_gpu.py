@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from bbmap_amd import _lib
 from bbmap_amd import readstats as R
 from bbmap_amd.index import DeviceIndex, READ_DTYPE
 from bbmap_amd.mapper import FINAL_DTYPE, Mapper
@@ -226,7 +227,7 @@ def test_many_identical_reads_several_workgroups_several_chunks():
 
 
 def test_raw_call_on_nothing():
-    L, _ = R._lib()
+    L = _lib.load()
     assert L.bbpipe_read_hist_add_device(None, 0, 0, R.RH_ALL, *([None] * 6)) == 0
     state = R.DeviceState(R.RH_GC)
     assert state.words == R.RH_GC_BINS + 2
@@ -272,7 +273,6 @@ def test_phix_reads_with_their_qualities(mode):
         assert int(h.gc_hist.sum()) == (len(reads) // 2 if paired else len(reads))
         # the view's pointers are the device's, in the order of the host copy
         w = R.bbmap_readhist_view()
-        mp.L.bbmap_get_read_hist_view.argtypes = [C.c_void_p, C.POINTER(R.bbmap_readhist_view)]
         assert mp.L.bbmap_get_read_hist_view(mp.h, C.byref(w)) == 0 and w.flags == R.RH_ALL and w.words == h.block.size and w.match == w.state
         # the feature only reads: the batch's records and strings are what a run without histograms gives
         di0, mp0, _, _, _ = _phix(mode, hist=False, max_sites=32)

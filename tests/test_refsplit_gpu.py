@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from bbmap_amd import _lib
 from bbmap_amd import reference as REFM
 from bbmap_amd import refsplit as S
 from bbmap_amd.index import DeviceIndex, READ_DTYPE
@@ -401,7 +402,7 @@ def test_two_batches_add_up_and_reset_zeroes():
 
 
 def test_raw_refusals_and_a_call_on_nothing():
-    L = S._bind()
+    L = _lib.load()
     err = lambda: L.bbmap_last_error()         # noqa: E731
     args = lambda cfg, off=None: (None, 2, 0, C.byref(cfg), None, None, None, None, 0, 1, off, None, PAD, None, None, None, None)        # noqa: E731
     assert L.bbpipe_refsplit_add_device(*args(S.config(nsets=65))) == -2 and err() == b"bbpipe_refsplit_add_device: at most 64 reference sets are supported"
@@ -533,7 +534,6 @@ def test_context_refusals():
     reads, quals, paired = fixture_inputs("se1", True)
     p = _two_genomes()
     tab = S.tables(p)
-    S._bind()
     sets, keys = np.ascontiguousarray(tab.scaf_sets), np.ascontiguousarray(tab.scaf_key)
     di = DeviceIndex.build(p.chroms, k=13)
     try:

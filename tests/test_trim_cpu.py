@@ -111,7 +111,9 @@ def test_default_config_is_bbmaps():
     c = T.default_config()
     assert (c.mode, c.trimLeft, c.trimRight, c.trimq, c.minLength, c.windowLength, c.minGoodInterval, c.optimalBias) == (0, 0, 0, 6, 60, 4, 2, -1.0)
     L = _lib.load()
-    assert all(hasattr(L, s) for s in _lib.TRIM_EXPORTS) and hasattr(L, "bbmap_untrim_batch_device")
+    trim_exports = ["bbtrim_default_config", "bbtrim_batch", "bbtrim_batch_device"]
+    assert [s for s in _lib.EXPORTS if s.startswith("bbtrim_")] == sorted(trim_exports)
+    assert all(hasattr(L, s) for s in trim_exports) and hasattr(L, "bbmap_untrim_batch_device")
 
 
 # ------------------------------------------------------------------------------------------------ against the restatement
@@ -234,7 +236,7 @@ def test_from_flags_bias():
 
 
 def test_refusals():
-    L = T._bind(_lib.load())
+    L = _lib.load()
     recs, blob, _ = pack([b"ACGT"])
     out, trims = np.zeros(1, READ_DTYPE), np.zeros(1, T.TRIM_DTYPE)
     args = lambda c, n=1, o=out: (None if c is None else C.byref(c), n, recs.ctypes.data, blob.ctypes.data, None, o.ctypes.data, trims.ctypes.data)  # noqa: E731
@@ -267,9 +269,6 @@ def test_trimmed_records_give_the_keys_of_the_trimmed_reads():
     n = len(out)
     offs, lens = np.ascontiguousarray(out["bases_off"], np.int64), np.ascontiguousarray(out["len"], np.int32)
     grecs, gki, gbs, used = np.zeros(n, READ_DTYPE), np.zeros(2 * int(lens.sum()) + 2, np.int32), np.zeros(len(blob), np.int8), C.c_int64(0)
-    L.bbkeys_make_batch.argtypes = [C.POINTER(K.bbkeys_config), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
-    L.bbkeys_make_batch.restype = C.c_int
     _lib.check(L.bbkeys_make_batch(C.byref(kc), n, offs.ctypes.data, lens.ctypes.data, blob.ctypes.data, qblob.ctypes.data, grecs.ctypes.data,
                                    gki.ctypes.data, gki.size, gbs.ctypes.data, C.byref(used)), "bbkeys_make_batch")
     assert np.array_equal(grecs["nkeys"], wrecs["nkeys"]) and np.array_equal(grecs["keys_off"], wrecs["keys_off"]) and int(wrecs["nkeys"].sum()) > n

@@ -76,7 +76,7 @@ def test_device_on_nothing():
     recs, trims = T.trim_batch_device(torch.zeros(0, dtype=torch.uint8, device=DEV), torch.zeros(0, dtype=torch.uint8, device=DEV), None, cfg())
     assert recs.numel() == 0 and trims.numel() == 0
     d = _dev(np.zeros(1, READ_DTYPE))
-    L = T._bind(_lib.load())
+    L = _lib.load()
     assert L.bbtrim_batch_device(C.byref(cfg()), None, 1, d.data_ptr(), d.data_ptr(), None, d.data_ptr(), d.data_ptr()) == -2
     assert L.bbmap_last_error() == b"bbtrim_batch_device: reads_out must not alias reads_in"
 
