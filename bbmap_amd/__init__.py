@@ -4,5 +4,6 @@ The package holds the HIP kernels + C ABI (csrc/, libbbmap_amd.so) and thin Pyth
 tests and bench.py.  All compute runs in the HIP library; there is no CPU fallback.
 """
 from . import _lib  # noqa: F401
+from . import merge  # noqa: F401
 
-__all__ = ["_lib"]
+__all__ = ["_lib", "merge"]

@@ -534,6 +534,70 @@ int bbtrim_batch_device(const bbtrim_config *cfg, void *stream, int64_t n_reads,
                         const uint8_t *bases, const uint8_t *quality, bbidx_read *reads_out, bbtrim_rec *trims);
 
 /* =====================================================================================
+ * Merging overlapping read pairs: BBMerge's ratio-mode overlap search and the join
+ *   Overlap search is BBMerge.mateByOverlap_ratioMode (current/jgi/BBMerge.java:1615-1639) over the two natives Java calls under
+ *   usejni, mateByOverlapRatioJNI (flat weights) and mateByOverlapRatioJNI_WithQualities (jni/BBMergeOverlapper.c:127-402):
+ *     rvector[4] = 0; the quality form runs when useQuality is set and the batch has qualities; the flat form runs when the quality
+ *     form did not, or when withoutQuality is set and the quality form returned x < 0 or rvector[4] == 1; the record is the return
+ *     value and rvector[2], rvector[4] of the last form that ran.
+ *   The join is the overlapped branch of Read.joinRead(a, b, insert) (current/stream/Read.java:2804-2840), with and without
+ *   qualities.  Mate 2 is handed over as it was sequenced: both stages reverse-complement it (and reverse its qualities) while they
+ *   read it, as BBMerge does before the search (Read.reverseComplement, Read.java:1127-1131); no second copy of the batch is made.
+ *   A read is (bases_off, len) into one blob; keys_off / nkeys are ignored; numeric phred qualities lie at the same offsets in
+ *   `quality`.  Two forms with the same output on every input: host code (bbmerge_*_batch) and kernels over a resident batch
+ *   (bbmerge_*_batch_device).  good and bad are float32 sums taken column by column in the reference's order; the natives' inner
+ *   early exit is not reproduced, because the addends are not negative: a full column sum fails `bad <= badlimit` exactly when the
+ *   truncated one does and equals it otherwise.
+ *   Out of scope: mateByOverlap (normal mode; Java has its native switched off, BBMergeOverlapper.java:68), everything around the
+ *   search in BBMerge.mateByOverlap (:1741-2036: entropy-derived minOverlap, efilter / pfilter, the Tadpole filters, adapter detection,
+ *   extension, the strict / loose presets, trimming retries), the no-overlap branch of joinRead (insert >= alen + blen), and JNI.
+ * ===================================================================================== */
+#define BBMERGE_MAX_READ_LEN 512
+typedef struct bbmerge_config {
+    int32_t minOverlap0, minOverlap, minInsert0, minInsert;   /* as handed to the natives: MIN_OVERLAPPING_BASES_0 - reduction, minOverlap -
+                                                                 reduction, minInsert0, minInsert: 5, 8, 26, 35.  The natives clamp the first two
+                                                                 themselves (minOverlap = max(4, minOverlap0, minOverlap), minOverlap0 = mid(4, ...)) */
+    float   maxRatio, ratioMargin, ratioOffset, gIncr, bIncr; /* .09, 5.5, .55, .95, .95 */
+    int32_t useQuality, withoutQuality;                       /* overlapUsingQuality 0, overlapWithoutQuality 1 */
+    int32_t maxMergeQuality;                                  /* Read.MAX_MERGE_QUALITY, maxq=: 41 */
+} bbmerge_config;              /* 48 bytes */
+enum { BBMERGE_INFO_QUALITY = 1,      /* the quality form ran */
+       BBMERGE_INFO_FLAT = 2,         /* the flat form ran */
+       BBMERGE_INFO_SKIPPED = 256 };  /* not evaluated: a mate longer than BBMERGE_MAX_READ_LEN, or, where the quality form would run,
+                                         a quality outside 0..70 (the domain of probCorrect): insert -1, bad 0, ambig 0 */
+typedef struct bbmerge_rec {
+    int32_t insert;            /* the native's return value: -1 or the insert size */
+    int32_t bad;               /* rvector[2] */
+    int32_t ambig;             /* rvector[4] */
+    int32_t info;              /* BBMERGE_INFO_* */
+} bbmerge_rec;                 /* 16 bytes */
+/* BBMerge's defaults (BBMerge.java:2220-2221, :2278-2279, :2334-2346, :605-611) */
+int bbmerge_default_config(bbmerge_config *cfg);
+/* Host form.  Pair i is reads1[i] and reads2[i]; `quality` may be NULL (only the flat form can run).  BBMAP_E_ARG: a null argument,
+ * n_pairs < 0, a NaN among the floats, ratioMargin < 1 (Java's assert), gIncr or bIncr < 0 (the full sums above need addends that are
+ * not negative), minInsert0 or minInsert < 0 (an insert below 0 has no columns), maxMergeQuality outside 0..127.  minOverlap0 >
+ * minOverlap is no error: the natives clamp. */
+int bbmerge_overlap_batch(const bbmerge_config *cfg, int64_t n_pairs, const bbidx_read *reads1, const bbidx_read *reads2,
+                          const uint8_t *bases, const uint8_t *quality, bbmerge_rec *recs);
+/* Device form: every pointer but cfg is a device pointer on the current device.  Enqueues on `stream` (one wavefront per pair, once
+ * for pairs whose mates fit 192 bases and once for the longer ones), makes no device allocation and does not wait.  n_pairs == 0:
+ * BBMAP_OK, nothing is launched.  BBMAP_E_NODEVICE without a gfx950 device. */
+int bbmerge_overlap_batch_device(const bbmerge_config *cfg, void *stream, int64_t n_pairs, const bbidx_read *reads1,
+                                 const bbidx_read *reads2, const uint8_t *bases, const uint8_t *quality, bbmerge_rec *recs);
+/* The join, host form.  insert[i] is the caller's decision (the usual rule: rec.insert > 0 && !rec.ambig ? rec.insert : 0).
+ * merged[i].bases_off is an input and names a slot of at least alen + blen bytes in out_bases (and out_quality); merged[i].len is an
+ * output: the insert, or 0 for insert <= 0 or insert >= alen + blen, and then nothing of the slot is written; keys_off and nkeys are
+ * left alone.  Bytes of a slot beyond len are not written.  With quality == NULL out_quality may be NULL and joinRead's rules for
+ * reads without qualities apply.  Only maxMergeQuality of cfg is used; BBMAP_E_ARG as above.  No length limit. */
+int bbmerge_join_batch(const bbmerge_config *cfg, int64_t n_pairs, const bbidx_read *reads1, const bbidx_read *reads2,
+                       const uint8_t *bases, const uint8_t *quality, const int32_t *insert, bbidx_read *merged,
+                       uint8_t *out_bases, uint8_t *out_quality);
+/* Device form of the join, one lane per output base: as bbmerge_overlap_batch_device. */
+int bbmerge_join_batch_device(const bbmerge_config *cfg, void *stream, int64_t n_pairs, const bbidx_read *reads1,
+                              const bbidx_read *reads2, const uint8_t *bases, const uint8_t *quality, const int32_t *insert,
+                              bbidx_read *merged, uint8_t *out_bases, uint8_t *out_quality);
+
+/* =====================================================================================
  * Batch helpers (device-resident) used by the mapper below; also callable on their own.
  * ===================================================================================== */
 /* bases_out[read] = reverse complement of bases_in[read] (AminoAcid.reverseComplementBases) */
