@@ -15,6 +15,8 @@
 // Join kernel: one wavefront per pair, one lane per output base; every position of joinRead's right-to-left loop is independent.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstddef>
 #include <mutex>
 #include <vector>
 
@@ -224,7 +226,332 @@ template <bool Q> static void host_search(const std::vector<Col> &a, const std::
     decide<Q>(HostWave(), Triples{g.data(), bd.data(), rt.data()}, p, range, alen, blen, r);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The verdict (merge_shared.h: verdict_of).  Same geometry as the overlap kernel: one wavefront per pair, the mates in LDS, now with
+// their qualities beside them for the filters.  bbmerge_stats is counted from the records by a kernel of its own, below.
+// The entropy scans are one lane's work: under the defaults a scan ends after about a dozen bases, and only a low-complexity mate is
+// walked to its end.  The normal mode's counts go lane per overlap like the ratio sums, into the same LDS arrays (a count is at most
+// 512 and exact as a float).  The filters look at one insert per pair: 64 lanes work out 64 columns' terms, then the terms are folded
+// in column order.
+static const float h_probCorrect2[MAX_FILTER_QUALITY + 1] = {BBMERGE_PROB_CORRECT2};
+__device__ const float d_probCorrect2[MAX_FILTER_QUALITY + 1] = {BBMERGE_PROB_CORRECT2};
+
+// a mate with its qualities, as the filters read it
+struct QCols {
+    const Col *c; const uint8_t *q;
+    __host__ __device__ int base(int i) const { return c[i].base; }
+    __host__ __device__ float prob(int i) const { return c[i].p; }
+    __host__ __device__ int qual(int i) const { return q[i]; }
+};
+// the normal mode's per-overlap counts as normal_decide() reads them
+struct Counts {
+    const float *g, *b;
+    __host__ __device__ float good(int k) const { return g[k]; }
+    __host__ __device__ float bad(int k) const { return b[k]; }
+};
+
+template <int MAXLEN> struct VerdictLds {
+    PairLds<MAXLEN> pair;
+    uint8_t qa[MAXLEN], qb[MAXLEN];
+    // The entropy scans' k-mer counts (4^k of them) live in the per-insert arrays, which nobody needs before the first search: the
+    // short class keeps the overlap kernel's 20 wavefronts per CU.
+    // For k = 5 the 2 KB of counts run from good[] on into bad[]: the three arrays must follow each other in this order.
+    static_assert(offsetof(PairLds<MAXLEN>, bad) == offsetof(PairLds<MAXLEN>, good) + sizeof(float) * 2 * MAXLEN &&
+                  offsetof(PairLds<MAXLEN>, ratio) == offsetof(PairLds<MAXLEN>, bad) + sizeof(float) * 2 * MAXLEN &&
+                  sizeof(PairLds<MAXLEN>) == offsetof(PairLds<MAXLEN>, ratio) + sizeof(float) * 2 * MAXLEN, "good, bad, ratio are one run of floats");
+    static_assert(sizeof(float) * 3 * 2 * MAXLEN >= sizeof(uint16_t) << (2 * MAX_ENTROPY_K), "the counts fit good, bad and ratio");
+    __device__ uint16_t *counts() { return reinterpret_cast<uint16_t *>(pair.good); }
+};
+
+// the pair in LDS; every method is called by the whole wavefront in uniform control flow
+template <int MAXLEN> struct DevicePair {
+    VerdictLds<MAXLEN> &S;
+    const bbmerge_verdict_config &c;
+    int alen, blen;
+    __device__ int entropy(bool tail) {
+        __syncthreads();                        // the mates are in LDS; the scan before this one is over
+        uint16_t *counts = S.counts();
+        for (int i = (int)threadIdx.x; i < (1 << (2 * c.entropyK)); i += 64) counts[i] = 0;
+        __syncthreads();
+        int r = 0;
+        if (threadIdx.x == 0)
+            r = tail ? entropy_scan(FromEnd<Cols>{Cols{S.pair.a}, alen}, alen, c.entropyK, c.minEntropyScore, counts)
+                     : entropy_scan(Cols{S.pair.b}, blen, c.entropyK, c.minEntropyScore, counts);
+        return __shfl(r, 0);
+    }
+    __device__ int entropy_a() { return entropy(true); }
+    __device__ int entropy_b() { return entropy(false); }
+    template <bool Q> __device__ void ratio(const Params &p, bbmerge_rec &r) { search<Q>(S.pair, p, alen, blen, r); }
+    template <bool Q> __device__ int normal(const NormalParams &p, int &bad, int &ambig) {
+        const Cols A{S.pair.a}, B{S.pair.b};
+        const float minprob = d_probCorrect[p.minq];
+        const int n = p.maxOverlap - p.first;
+        __syncthreads();                        // the walks before this pass have read their triples
+        for (int k0 = 0; k0 < n; k0 += 64) {
+            const int k = k0 + (int)threadIdx.x;
+            if (k < n) {
+                int g, b;
+                normal_counts<Q>(A, B, p.first + k, alen, blen, minprob, g, b);
+                S.pair.good[k] = (float)g; S.pair.bad[k] = (float)b;
+            }
+        }
+        __syncthreads();
+        return normal_decide(DeviceWave(), Counts{S.pair.good, S.pair.bad}, p, alen, blen, bad, ambig);
+    }
+    // the filters: 64 lanes work out the terms of 64 columns, then every lane folds them in column order (lane l's term comes
+    // through a scalar register), so the table lookups of a chunk are in flight together and the order of the float operations is
+    // the reference's
+    static __device__ float lane_value(float x, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l)); }
+    __device__ float expected(int insert) {
+        const QCols A{S.pair.a, S.qa}, B{S.pair.b, S.qb};
+        const FilterSpan s = expected_span(alen, blen, __builtin_amdgcn_readfirstlane(insert));
+        float expected = 0;
+        for (int c0 = 0; c0 < s.n; c0 += 64) {
+            const int col = c0 + (int)threadIdx.x;
+            const float t = col < s.n ? expected_term(A, B, s.istart + col, s.jstart + col, d_probCorrect2) : 0.0f;
+            for (int l = 0, cnt = imin(64, s.n - c0); l < cnt; l++) expected += lane_value(t, l);
+        }
+        return expected;
+    }
+    __device__ float probability(int insert) {
+        const QCols A{S.pair.a, S.qa}, B{S.pair.b, S.qb};
+        const FilterSpan s = probability_span(alen, blen, __builtin_amdgcn_readfirstlane(insert));
+        float probActual = 1, probCommon = 1;
+        for (int c0 = 0; c0 < s.n; c0 += 64) {
+            const int col = c0 + (int)threadIdx.x;
+            float common = 1, actual = 1;
+            if (col < s.n) probability_terms(A, B, s.istart + col, s.jstart + col, d_probCorrect2, common, actual);
+            for (int l = 0, cnt = imin(64, s.n - c0); l < cnt; l++) {
+                probCommon *= lane_value(common, l); probActual *= lane_value(actual, l);
+            }
+        }
+        return probability_of(probActual, probCommon);
+    }
+};
+
+// Pairs whose longer mate has MINLEN < length <= MAXLEN; the launch with MAXLEN == BBMERGE_MAX_READ_LEN also reports longer pairs.
+template <int MINLEN, int MAXLEN>
+__global__ void __launch_bounds__(64) bbmerge_verdict_kernel(bbmerge_verdict_config cfg, const bbidx_read *reads1, const bbidx_read *reads2,
+                                                             const uint8_t *bases, const uint8_t *quality, bbmerge_verdict_rec *recs) {
+    __shared__ VerdictLds<MAXLEN> S;
+    const long long pair = blockIdx.x;
+    const int lane = (int)threadIdx.x;
+    const bbidx_read r1 = reads1[pair], r2 = reads2[pair];
+    const int alen = imax(r1.len, 0), blen = imax(r2.len, 0);
+    const int longer = imax(alen, blen);
+    if (longer <= MINLEN || (longer > MAXLEN && MAXLEN != BBMERGE_MAX_READ_LEN)) return;
+    const bool have_quality = cfg.useQuality != 0 && quality != nullptr;
+    const bool prob_read = reads_prob_correct(cfg, have_quality), filtered = filters_on(cfg, have_quality);
+    bbmerge_verdict_rec v;
+    bool outside = longer > MAXLEN;
+    if (!outside) {
+        for (int i = lane; i < alen; i += 64) {
+            Col c;
+            c.base = (int8_t)bases[r1.bases_off + i]; c.p = 0;
+            if (have_quality) {
+                const int q = quality[r1.bases_off + i];
+                outside |= (prob_read && q > MAX_QUALITY) || (filtered && q > MAX_FILTER_QUALITY);
+                if (prob_read) c.p = d_probCorrect[imin(q, MAX_QUALITY)];
+                S.qa[i] = (uint8_t)imin(q, MAX_FILTER_QUALITY);
+            }
+            S.pair.a[i] = c;
+        }
+        for (int i = lane; i < blen; i += 64) {      // Read.reverseComplement: base i of b is the complement of mate 2's base blen - 1 - i
+            Col c;
+            c.base = (int8_t)bbpipe::complement_extended(bases[r2.bases_off + blen - 1 - i]); c.p = 0;
+            if (have_quality) {
+                const int q = quality[r2.bases_off + blen - 1 - i];
+                outside |= (prob_read && q > MAX_QUALITY) || (filtered && q > MAX_FILTER_QUALITY);
+                if (prob_read) c.p = d_probCorrect[imin(q, MAX_QUALITY)];
+                S.qb[i] = (uint8_t)imin(q, MAX_FILTER_QUALITY);
+            }
+            S.pair.b[i] = c;
+        }
+        outside = __any(outside);
+    }
+    if (outside) {
+        skipped_verdict(v);
+    } else {
+        DevicePair<MAXLEN> e{S, cfg, alen, blen};
+        verdict_of(e, cfg, alen, blen, have_quality, v);
+    }
+    if (lane == 0) recs[pair] = v;
+}
+
+// bbmerge_stats from the records.  One pair's wavefront adding its own counts would send a million atomics to the same few
+// addresses (measured: 87 ms for 1 M pairs beside 9 ms for the verdicts themselves), so the counting is a pass of its own over the
+// 48-byte records: a workgroup takes 8192 consecutive records, its threads stride through them by 256 and count in registers, the
+// workgroup sums in LDS (its own histogram included), and one thread per counter or bin adds to memory what the workgroup holds.
+constexpr int STATS_THREADS = 256, STATS_RECORDS_PER_BLOCK = 8192;
+__global__ void __launch_bounds__(STATS_THREADS) bbmerge_stats_kernel(long long n, const bbmerge_verdict_rec *recs, bbmerge_stats *stats) {
+    typedef unsigned long long U;               // (every counter is >= 0)
+    __shared__ unsigned hist[BBMERGE_HIST_LEN];
+    __shared__ U sums[8];                       // pairs, merged, ambiguous, tooShort, tooLong, noSolution, skipped, insertSum
+    __shared__ int lo, hi;
+    for (int i = (int)threadIdx.x; i < BBMERGE_HIST_LEN; i += STATS_THREADS) hist[i] = 0;
+    if (threadIdx.x < 8) sums[threadIdx.x] = 0;
+    if (threadIdx.x == 0) { lo = 999999999; hi = 0; }
+    __syncthreads();
+    StatsDelta d;
+    d.clear();
+    const long long first = (long long)blockIdx.x * STATS_RECORDS_PER_BLOCK;
+    for (long long i = first + threadIdx.x; i < first + STATS_RECORDS_PER_BLOCK && i < n; i += STATS_THREADS) {
+        bbmerge_verdict_rec v;
+        v.code = recs[i].code; v.info = recs[i].info;
+        d.count(v);
+        if (v.code > 0 && !(v.info & BBMERGE_INFO_SKIPPED)) atomicAdd(&hist[imin(v.code, BBMERGE_HIST_LEN - 1)], 1u);
+    }
+    const int part[7] = {d.pairs, d.merged, d.ambiguous, d.tooShort, d.tooLong, d.noSolution, d.skipped};
+    for (int k = 0; k < 7; k++) if (part[k]) atomicAdd(&sums[k], (U)part[k]);
+    if (d.merged) {
+        atomicAdd(&sums[7], (U)d.insertSum);
+        atomicMin(&lo, d.insertMin);
+        atomicMax(&hi, d.insertMax);
+    }
+    __syncthreads();
+    U *const out[8] = {(U *)&stats->pairs, (U *)&stats->merged, (U *)&stats->ambiguous, (U *)&stats->tooShort, (U *)&stats->tooLong,
+                       (U *)&stats->noSolution, (U *)&stats->skipped, (U *)&stats->insertSum};
+    if (threadIdx.x < 8 && sums[threadIdx.x]) atomicAdd(out[threadIdx.x], sums[threadIdx.x]);
+    if (threadIdx.x == 8 && sums[1]) { atomicMin((U *)&stats->insertMin, (U)lo); atomicMax((U *)&stats->insertMax, (U)hi); }
+    for (int i = (int)threadIdx.x; i < BBMERGE_HIST_LEN; i += STATS_THREADS) if (hist[i]) atomicAdd((U *)&stats->hist[i], (U)hist[i]);
+}
+
+// the pair in plain arrays: the same functions, the wavefront a loop
+struct HostPair {
+    const bbmerge_verdict_config &c;
+    int alen, blen;
+    std::vector<Col> &a, &b;
+    std::vector<uint8_t> &qa, &qb;
+    std::vector<uint16_t> &counts;
+    std::vector<float> &g, &bd, &rt;
+    int entropy_a() {
+        std::fill(counts.begin(), counts.end(), (uint16_t)0);
+        return entropy_scan(FromEnd<Cols>{Cols{a.data()}, alen}, alen, c.entropyK, c.minEntropyScore, counts.data());
+    }
+    int entropy_b() {
+        std::fill(counts.begin(), counts.end(), (uint16_t)0);
+        return entropy_scan(Cols{b.data()}, blen, c.entropyK, c.minEntropyScore, counts.data());
+    }
+    template <bool Q> void ratio(const Params &p, bbmerge_rec &r) { host_search<Q>(a, b, p, alen, blen, g, bd, rt, r); }
+    template <bool Q> int normal(const NormalParams &p, int &bad, int &ambig) {
+        const Cols A{a.data()}, B{b.data()};
+        for (int k = 0; k < p.maxOverlap - p.first; k++) {
+            int gk, bk;
+            normal_counts<Q>(A, B, p.first + k, alen, blen, h_probCorrect[p.minq], gk, bk);
+            g[k] = (float)gk; bd[k] = (float)bk;
+        }
+        return normal_decide(HostWave(), Counts{g.data(), bd.data()}, p, alen, blen, bad, ambig);
+    }
+    float expected(int insert) { return expected_mismatches(QCols{a.data(), qa.data()}, QCols{b.data(), qb.data()}, alen, blen, insert, h_probCorrect2); }
+    float probability(int insert) { return merge_probability(QCols{a.data(), qa.data()}, QCols{b.data(), qb.data()}, alen, blen, insert, h_probCorrect2); }
+};
+
+static int check_verdict_args(const char *who, const bbmerge_verdict_config *cfg, int64_t n_pairs, const bbidx_read *reads1, const bbidx_read *reads2,
+                              const uint8_t *bases, const bbmerge_verdict_rec *recs) {
+    if (!cfg) return bbfail(BBMAP_E_ARG, "%s: null config", who);
+    BBTRY(check_config(who, &cfg->ratio, n_pairs));
+    if (!good_verdict_config(*cfg))
+        return bbfail(BBMAP_E_ARG, "%s: bad config (entropyK 1..5, qualIters >= 1, 0 <= maxMismatches0 >= maxMismatches >= margin, a mode on, no NaN)", who);
+    if (n_pairs > 0 && (!reads1 || !reads2 || !bases || !recs)) return bbfail(BBMAP_E_ARG, "%s: null buffer", who);
+    return BBMAP_OK;
+}
+
 }  // namespace bbmerge
+
+extern "C" int bbmerge_default_verdict_config(bbmerge_verdict_config *cfg) {
+    if (!cfg) return bbfail(BBMAP_E_ARG, "bbmerge_default_verdict_config: null argument");
+    BBTRY(bbmerge_default_config(&cfg->ratio));
+    cfg->useEntropy = 1; cfg->entropyK = 3; cfg->minEntropyScore = 39;                       // BBMerge.java: useEntropy, entropyK, minEntropyScore
+    cfg->minOverlapBases = 11; cfg->minOverlapBases0 = 8; cfg->ratioReduction = 3;
+    cfg->useRatioMode = 1; cfg->useNormalMode = 0; cfg->requireRatioMatch = 0; cfg->maxMismatchesR = 20;
+    cfg->margin = 2; cfg->maxMismatches = 3; cfg->maxMismatches0 = 3; cfg->minQuality = 10; cfg->qualIters = 3;
+    cfg->useQuality = 1; cfg->useEfilter = 1;
+    cfg->efilterRatio = 6.0f; cfg->efilterOffset = 0.05f; cfg->pfilterRatio = 0.00004f;
+    cfg->maxLength = 0; cfg->reserved = 0;
+    return BBMAP_OK;
+}
+
+extern "C" int bbmerge_verdict_batch(const bbmerge_verdict_config *cfg, int64_t n_pairs, const bbidx_read *reads1, const bbidx_read *reads2,
+                                     const uint8_t *bases, const uint8_t *quality, bbmerge_verdict_rec *recs, bbmerge_stats *stats) {
+    using namespace bbmerge;
+    BBTRY(check_verdict_args("bbmerge_verdict_batch", cfg, n_pairs, reads1, reads2, bases, recs));
+    const bool have_quality = cfg->useQuality != 0 && quality != nullptr;
+    const bool prob_read = reads_prob_correct(*cfg, have_quality), filtered = filters_on(*cfg, have_quality);
+    std::vector<Col> a(BBMERGE_MAX_READ_LEN), b(BBMERGE_MAX_READ_LEN);
+    std::vector<uint8_t> qa(BBMERGE_MAX_READ_LEN), qb(BBMERGE_MAX_READ_LEN);
+    std::vector<uint16_t> counts(1 << (2 * cfg->entropyK));
+    std::vector<float> g(2 * BBMERGE_MAX_READ_LEN), bd(2 * BBMERGE_MAX_READ_LEN), rt(2 * BBMERGE_MAX_READ_LEN);
+    StatsDelta delta;
+    delta.clear();
+    for (int64_t pair = 0; pair < n_pairs; pair++) {
+        const bbidx_read r1 = reads1[pair], r2 = reads2[pair];
+        const int alen = imax(r1.len, 0), blen = imax(r2.len, 0);
+        bbmerge_verdict_rec v;
+        bool outside = imax(alen, blen) > BBMERGE_MAX_READ_LEN;
+        for (int i = 0; i < alen && !outside; i++) {
+            a[i].base = (int8_t)bases[r1.bases_off + i]; a[i].p = 0;
+            if (have_quality) {
+                const int q = quality[r1.bases_off + i];
+                outside |= (prob_read && q > MAX_QUALITY) || (filtered && q > MAX_FILTER_QUALITY);
+                if (prob_read) a[i].p = h_probCorrect[imin(q, MAX_QUALITY)];
+                qa[i] = (uint8_t)imin(q, MAX_FILTER_QUALITY);
+            }
+        }
+        for (int i = 0; i < blen && !outside; i++) {
+            b[i].base = (int8_t)bbpipe::complement_extended(bases[r2.bases_off + blen - 1 - i]); b[i].p = 0;
+            if (have_quality) {
+                const int q = quality[r2.bases_off + blen - 1 - i];
+                outside |= (prob_read && q > MAX_QUALITY) || (filtered && q > MAX_FILTER_QUALITY);
+                if (prob_read) b[i].p = h_probCorrect[imin(q, MAX_QUALITY)];
+                qb[i] = (uint8_t)imin(q, MAX_FILTER_QUALITY);
+            }
+        }
+        if (outside) {
+            skipped_verdict(v);
+        } else {
+            HostPair e{*cfg, alen, blen, a, b, qa, qb, counts, g, bd, rt};
+            verdict_of(e, *cfg, alen, blen, have_quality, v);
+        }
+        recs[pair] = v;
+        delta.count(v);
+        if (stats && v.code > 0 && !(v.info & BBMERGE_INFO_SKIPPED)) stats->hist[imin(v.code, BBMERGE_HIST_LEN - 1)]++;
+    }
+    if (stats) {
+        stats->pairs += delta.pairs; stats->merged += delta.merged; stats->ambiguous += delta.ambiguous; stats->tooShort += delta.tooShort;
+        stats->tooLong += delta.tooLong; stats->noSolution += delta.noSolution; stats->skipped += delta.skipped;
+        stats->insertSum += delta.insertSum;
+        if (delta.merged) {
+            if (delta.insertMin < stats->insertMin) stats->insertMin = delta.insertMin;
+            if (delta.insertMax > stats->insertMax) stats->insertMax = delta.insertMax;
+        }
+    }
+    return BBMAP_OK;
+}
+
+extern "C" int bbmerge_verdict_batch_device(const bbmerge_verdict_config *cfg, void *stream, int64_t n_pairs, const bbidx_read *reads1,
+                                            const bbidx_read *reads2, const uint8_t *bases, const uint8_t *quality, bbmerge_verdict_rec *recs,
+                                            bbmerge_stats *stats) {
+    using namespace bbmerge;
+    BBTRY(check_verdict_args("bbmerge_verdict_batch_device", cfg, n_pairs, reads1, reads2, bases, recs));
+    if (n_pairs == 0) return BBMAP_OK;
+    BBTRY(prepare_device("bbmerge_verdict_batch_device"));
+    const int64_t chunk = 1 << 24;              // (a grid holds fewer than 2^32 threads)
+    for (int64_t at = 0; at < n_pairs; at += chunk) {
+        const unsigned blocks = (unsigned)(n_pairs - at < chunk ? n_pairs - at : chunk);
+        hipLaunchKernelGGL((bbmerge_verdict_kernel<-1, SHORT_LEN>), dim3(blocks), dim3(64), 0, (hipStream_t)stream, *cfg, reads1 + at, reads2 + at, bases,
+                           quality, recs + at);
+        BBHIP(hipGetLastError());
+        hipLaunchKernelGGL((bbmerge_verdict_kernel<SHORT_LEN, BBMERGE_MAX_READ_LEN>), dim3(blocks), dim3(64), 0, (hipStream_t)stream, *cfg, reads1 + at,
+                           reads2 + at, bases, quality, recs + at);
+        BBHIP(hipGetLastError());
+    }
+    if (stats) {
+        const unsigned blocks = (unsigned)((n_pairs + STATS_RECORDS_PER_BLOCK - 1) / STATS_RECORDS_PER_BLOCK);
+        hipLaunchKernelGGL(bbmerge_stats_kernel, dim3(blocks), dim3(STATS_THREADS), 0, (hipStream_t)stream, (long long)n_pairs, recs, stats);
+        BBHIP(hipGetLastError());
+    }
+    return BBMAP_OK;
+}
 
 extern "C" int bbmerge_default_config(bbmerge_config *cfg) {
     if (!cfg) return bbfail(BBMAP_E_ARG, "bbmerge_default_config: null argument");

@@ -548,9 +548,10 @@ int bbtrim_batch_device(const bbtrim_config *cfg, void *stream, int64_t n_reads,
  *   (bbmerge_*_batch_device).  good and bad are float32 sums taken column by column in the reference's order; the natives' inner
  *   early exit is not reproduced, because the addends are not negative: a full column sum fails `bad <= badlimit` exactly when the
  *   truncated one does and equals it otherwise.
- *   Out of scope: mateByOverlap (normal mode; Java has its native switched off, BBMergeOverlapper.java:68), everything around the
- *   search in BBMerge.mateByOverlap (:1741-2036: entropy-derived minOverlap, efilter / pfilter, the Tadpole filters, adapter detection,
- *   extension, the strict / loose presets, trimming retries), the no-overlap branch of joinRead (insert >= alen + blen), and JNI.
+ *   These two entry points give the record of the natives.  BBMerge's answer for a pair -- the entropy-derived minOverlap, the normal
+ *   mode, the composition of the two modes, efilter / pfilter and the return code -- is bbmerge_verdict_batch, further down.
+ *   Out of scope everywhere: the `loose` branches, trim-on-failure, ecco, the Tadpole filters and extension, adapter detection and
+ *   verification, preprocess and the qtrim retries, the no-overlap branch of joinRead (insert >= alen + blen), and JNI.
  * ===================================================================================== */
 #define BBMERGE_MAX_READ_LEN 512
 typedef struct bbmerge_config {
@@ -596,6 +597,85 @@ int bbmerge_join_batch(const bbmerge_config *cfg, int64_t n_pairs, const bbidx_r
 int bbmerge_join_batch_device(const bbmerge_config *cfg, void *stream, int64_t n_pairs, const bbidx_read *reads1,
                               const bbidx_read *reads2, const uint8_t *bases, const uint8_t *quality, const int32_t *insert,
                               bbidx_read *merged, uint8_t *out_bases, uint8_t *out_quality);
+
+/* -------------------------------------------------------------------------------------
+ * BBMerge's verdict per pair: what bbmerge.sh decides under its defaults, the strict / vstrict / ustrict / xstrict / fast presets
+ * and their flags.  BBMerge.mateByOverlap (current/jgi/BBMerge.java:1741-1837) inside processReadPair_inner (:2044-2068):
+ *   1. minOverlap per pair from entropy (calcMinOverlapFromEntropy :1696-1711, the branch without `loose`):
+ *      max(minOverlapBases, calcMinOverlapByEntropyTail(mate 1), calcMinOverlapByEntropyHead(mate 2 reverse-complemented))
+ *      (BBMergeOverlapper.java:860-934); useEntropy 0 gives minOverlapBases.
+ *   2. Ratio mode (:1615-1639): the search of bbmerge_overlap_batch with minOverlap0 = minOverlapBases0 - ratioReduction and
+ *      minOverlap = (the pair's minOverlap) - ratioReduction.  `ratio.minOverlap0` and `ratio.minOverlap` are NOT read here.
+ *   3. Normal mode (mateByOverlap_normalMode :1641-1661, :1690-1693): up to qualIters passes (one without qualities) of
+ *      BBMergeOverlapper.mateByOverlapJava_unrolled (BBMergeOverlapper.java:543-657) with minOverlap0 - i, minOverlap + i and
+ *      minQuality - 2 i.  That is the form Java runs (its native is switched off, :68), and it differs from the native in one
+ *      index: Java weighs a column by aprob[j] * bprob[i] (:591), jni/BBMergeOverlapper.c:73 by aprob[j] * bprob[j].  The Java is
+ *      followed.  The inner early exit is not reproduced: a truncated column loop ends with bad = bestBad + margin + 1, which fails
+ *      both `bad <= bestBad` and `bad < margin` (bestBad >= 0), so such an overlap never changes state, with full counts either.
+ *   4. The composition of the two modes (:1765-1805) incl. requireRatioMatch, bestBad > maxMismatchesR (:1809), the early
+ *      RET_AMBIG / RET_NO_SOLUTION (:1811-1814), efilter (:1817-1824, expectedMismatches, BBMergeOverlapper.java:667-724) and
+ *      pfilter (:1826-1831, probability, :728-785) -- float32 sums and products in the reference's column order, the quotient in
+ *      float32, the square root in double -- and the return code (:2061-2067).
+ *   With useQuality 0 the pair counts as having no qualities in every stage (:1913-1916); the filters run only with qualities.
+ *   Not built: the `loose` branches (:1664-1672, :1699-1704), trim-on-failure (:1674-1687; the config is trimonfailure=0), ecco,
+ *   the Tadpole filters and extension, adapter verification, preprocess, the qtrim retries, minsecondratio (read by the Java ratio
+ *   forms only).
+ *   Deviation: a pair with a quality above 59 is skipped up front while a filter is on (Java throws once it reaches the filter:
+ *   probCorrect2 has 60 entries), and one with a quality above 70 where the quality form or the normal mode would read probCorrect.
+ * ------------------------------------------------------------------------------------- */
+typedef struct bbmerge_verdict_config {
+    bbmerge_config ratio;                                      /* the ratio search's numbers, minInsert0 / minInsert (also the normal
+                                                                  mode's and the return code's) and maxMergeQuality */
+    int32_t useEntropy, entropyK, minEntropyScore;             /* 1, 3 (1..5), 39 */
+    int32_t minOverlapBases, minOverlapBases0, ratioReduction; /* MIN_OVERLAPPING_BASES 11, MIN_OVERLAPPING_BASES_0 8,
+                                                                  MIN_OVERLAPPING_BASES_RATIO_REDUCTION 3 */
+    int32_t useRatioMode, useNormalMode, requireRatioMatch;    /* 1, 0, 0 */
+    int32_t maxMismatchesR;                                    /* MAX_MISMATCHES_R 20 */
+    int32_t margin, maxMismatches, maxMismatches0;             /* normal mode: MISMATCH_MARGIN 2, MAX_MISMATCHES 3, MAX_MISMATCHES0 3 */
+    int32_t minQuality, qualIters;                             /* normal mode: MIN_QUALITY 10, QUAL_ITERS 3 */
+    int32_t useQuality;                                        /* BBMerge.useQuality 1 (ratio.useQuality is overlapUsingQuality) */
+    int32_t useEfilter;                                        /* 1 */
+    float   efilterRatio, efilterOffset, pfilterRatio;         /* 6, 0.05, 0.00004 */
+    int32_t maxLength;                                         /* maxReadLength; 0 = no limit */
+    int32_t reserved;
+} bbmerge_verdict_config;      /* 136 bytes */
+enum { BBMERGE_INFO_RATIO = 4,        /* the ratio mode ran */
+       BBMERGE_INFO_NORMAL = 8,       /* the normal mode ran */
+       BBMERGE_INFO_EFILTER = 16,     /* expectedMismatches was evaluated; otherwise `expected` is 0 */
+       BBMERGE_INFO_PFILTER = 32 };   /* probability was evaluated; otherwise `probability` is 0 */
+enum { BBMERGE_RET_NO_SOLUTION = -1, BBMERGE_RET_AMBIG = -2, BBMERGE_RET_SHORT = -4, BBMERGE_RET_LONG = -5 };
+typedef struct bbmerge_verdict_rec {
+    int32_t code;                      /* processReadPair_inner's return value: the insert, or BBMERGE_RET_* */
+    int32_t minOverlap;                /* calcMinOverlapFromEntropy */
+    int32_t insertRM, badRM, ambigRM;  /* mateByOverlap's locals; -1, 0, 0 where the ratio mode did not run */
+    int32_t insertNM, badNM, ambigNM;  /* -1, 99999, 0 where the normal mode did not run */
+    int32_t bad;                       /* bestBad as :1789-1805 composes it */
+    float   expected, probability;     /* the filters' values (a NaN is the canonical one, 0x7fc00000) */
+    int32_t info;                      /* BBMERGE_INFO_*; a SKIPPED pair has code -1, minOverlap 0, -1 0 0, -1 99999 0, bad 0 */
+} bbmerge_verdict_rec;         /* 48 bytes */
+#define BBMERGE_HIST_LEN 2000
+typedef struct bbmerge_stats {
+    int64_t pairs, merged, ambiguous, tooShort, tooLong, noSolution, skipped;   /* pairs = the sum of the other six */
+    int64_t insertSum, insertMin, insertMax;                   /* over merged pairs; the caller starts insertMin at 999999999 */
+    int64_t hist[BBMERGE_HIST_LEN];                            /* hist[min(insert, 1999)]++ per merged pair (:1406-1408) */
+} bbmerge_stats;               /* 16080 bytes */
+/* BBMerge's defaults: bbmerge_default_config and the table above */
+int bbmerge_default_verdict_config(bbmerge_verdict_config *cfg);
+/* Host form; arguments as bbmerge_overlap_batch.  `stats` may be NULL; otherwise the call ADDS this batch to it (a skipped pair
+ * counts in pairs and skipped only).  BBMAP_E_ARG: what bbmerge_overlap_batch refuses, entropyK outside 1..5, qualIters < 1,
+ * maxMismatches0 < 0, maxMismatches0 < maxMismatches, margin > maxMismatches, neither mode on, a NaN among the three floats.
+ * minOverlapBases, minOverlapBases0, ratioReduction, minEntropyScore and minQuality take any value and are clamped where the
+ * reference clamps them: the ratio natives raise their two overlaps to at least 4, the normal mode starts at overlap
+ * max(min(max(1, minOverlapBases0 - i), minOverlap + i), 0) and takes minprob from probCorrect[mid(1, minQuality - 2 i, 41)], and
+ * a score the scan never reaches gives len + 1; no value leads outside a pair's alen + blen inserts. */
+int bbmerge_verdict_batch(const bbmerge_verdict_config *cfg, int64_t n_pairs, const bbidx_read *reads1, const bbidx_read *reads2,
+                          const uint8_t *bases, const uint8_t *quality, bbmerge_verdict_rec *recs, bbmerge_stats *stats);
+/* Device form: as bbmerge_overlap_batch_device (one wavefront per pair, two length classes, no allocation, no wait, n_pairs == 0
+ * launches nothing).  `stats` is device memory that the caller has initialised; a third kernel counts the records into it: a
+ * thread counts in registers, a workgroup sums in LDS (its histogram too), then vector atomics add the workgroup's sums. */
+int bbmerge_verdict_batch_device(const bbmerge_verdict_config *cfg, void *stream, int64_t n_pairs, const bbidx_read *reads1,
+                                 const bbidx_read *reads2, const uint8_t *bases, const uint8_t *quality, bbmerge_verdict_rec *recs,
+                                 bbmerge_stats *stats);
 
 /* =====================================================================================
  * Batch helpers (device-resident) used by the mapper below; also callable on their own.
