@@ -349,7 +349,7 @@ static int final_fill(mapper *M, int which, int kind, const uint8_t *bases, int 
     const int64_t it0 = M->msa->iterationsLimited + M->msa->iterationsUnlimited;
     int gcopy[ORC_MAX_GAPS]; memcpy(gcopy, ss->gaps, sizeof gcopy);
     int ok;
-    if (kind == 6) { orc_fill_unlimited(M->msa, bases, L, c, cl, minLoc, maxLoc, ss->ngaps ? gcopy : NULL, ss->ngaps, mx); ok = 1; }
+    if (kind == 6) ok = orc_fill_unlimited(M->msa, bases, L, c, cl, minLoc, maxLoc, ss->ngaps ? gcopy : NULL, ss->ngaps, mx);
     else ok = orc_fill_limited(M->msa, bases, L, c, cl, minLoc, maxLoc, minscore, ss->ngaps ? gcopy : NULL, ss->ngaps, mx);
     const int n = ok ? orc_score(M->msa, bases, c, minLoc, maxLoc, mx[0], mx[1], mx[2], ss->ngaps ? 1 : 0, sc) : 0;
     const int64_t it = M->msa->iterationsLimited + M->msa->iterationsUnlimited - it0;

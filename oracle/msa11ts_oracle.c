@@ -491,17 +491,25 @@ int orc_fill_limited(orc_msa *m, const uint8_t *read, int read_len, const uint8_
     int lim = orc_make_gref(m, ref, ref_len, g, ngaps, refStartLoc, refEndLoc);
     free(g);
     if (lim < 0) return 0;
+    /* fillLimitedX(read, gref, 0, greflimit, minScore) (:127) fills greflimit + 1 columns.  The planes and horizLimit hold
+     * maxColumns + 1 entries (:80, :83), so with more columns the Java throws (horizLimit[columns], :153) and the JNI C would write
+     * past them; makeGref itself only refuses at maxColumns + 2 (:668-757).  "Does not fit" is answered like the overflow above. */
+    if (m->greflimit + 1 > m->maxColumns) return 0;
     return fill_limited_x(m, read, read_len, m->grefbuffer, m->maxColumns + 2, 0, m->greflimit, minScore, out4);
 }
 
-void orc_fill_unlimited(orc_msa *m, const uint8_t *read, int read_len, const uint8_t *ref, int ref_len,
-                        int refStartLoc, int refEndLoc, const int32_t *gaps, int ngaps, int32_t *out4) { /* :166-192 */
-    if (!gaps) { orc_fill_unlimited_raw(m, read, read_len, ref, ref_len, refStartLoc, refEndLoc, out4); return; }
+int orc_fill_unlimited(orc_msa *m, const uint8_t *read, int read_len, const uint8_t *ref, int ref_len,
+                       int refStartLoc, int refEndLoc, const int32_t *gaps, int ngaps, int32_t *out4) { /* :166-192 */
+    if (!gaps) { orc_fill_unlimited_raw(m, read, read_len, ref, ref_len, refStartLoc, refEndLoc, out4); return 1; }
     int32_t *g = (int32_t *)malloc((size_t)ngaps * sizeof(int32_t));
     memcpy(g, gaps, (size_t)ngaps * sizeof(int32_t));
-    orc_make_gref(m, ref, ref_len, g, ngaps, refStartLoc, refEndLoc);
+    const int lim = orc_make_gref(m, ref, ref_len, g, ngaps, refStartLoc, refEndLoc);
     free(g);
+    /* makeGref returned null (the Java's assert(gref!=null), :170), or fillUnlimited(read, gref, 0, greflimit) (:171) would run
+     * greflimit + 1 > maxColumns columns over planes of maxColumns + 1 (:80): refused, as in orc_fill_limited */
+    if (lim < 0 || m->greflimit + 1 > m->maxColumns) { out4[0] = out4[1] = out4[2] = out4[3] = -1; return 0; }
     orc_fill_unlimited_raw(m, read, read_len, m->grefbuffer, m->maxColumns + 2, 0, m->greflimit, out4);
+    return 1;
 }
 
 /* ---- path walk shared by traceback2 and score2 -------------------------------------- */
@@ -561,11 +569,11 @@ int orc_traceback2(orc_msa *m, const uint8_t *read, const uint8_t *ref,
     if (col != row) {
         while (row > 0) { tmp[n++] = 'X'; row--; col--; }
     }
-    const int total = n + gaps * (K_GAPLEN - 1);
+    const int total = m->keepGaps ? n : n + gaps * (K_GAPLEN - 1);
     if (total > cap) { free(tmp); return -1; }
     int j = 0;
     for (int i = n - 1; i >= 0; i--) {
-        if (tmp[i] != K_GAPC) out[j++] = tmp[i];
+        if (tmp[i] != K_GAPC || m->keepGaps) out[j++] = tmp[i];
         else { for (int k = 0; k < K_GAPLEN; k++) out[j++] = 'D'; }
     }
     free(tmp);

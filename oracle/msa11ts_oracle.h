@@ -51,6 +51,8 @@ typedef struct orc_msa {
     int rows, columns;                /* :1662-1663 */
     int bandwidth;                    /* MSA.java:864 (static in the reference) */
     float bandwidthRatio;             /* MSA.java:865 */
+    int keepGaps;                     /* not in the reference: traceback2 returns out2, the string before :481-493 expand
+                                       * each '-' to 128 'D' (what BBMSA_TRACE_KEEP_GAPS asks of the device) */
 } orc_msa;
 
 orc_msa *orc_msa_new(int maxRows, int maxColumns);
@@ -77,15 +79,16 @@ void orc_fill_limited_raw(orc_msa *m, const uint8_t *read, int read_len,
                           int refStartLoc, int refEndLoc, int minScore, int32_t *result);
 
 /* MultiStateAligner11tsJNI.java:116-164 (fillLimited + Java gate + minScore-=120).
- * gaps may be NULL.  Returns 1 and fills out[4] on success, 0 when the Java returns null. */
+ * gaps may be NULL.  Returns 1 and fills out[4] on success, 0 when the Java returns null or when the
+ * gapped reference does not fit maxColumns (the Java throws there). */
 int orc_fill_limited(orc_msa *m, const uint8_t *read, int read_len,
                      const uint8_t *ref, int ref_len, int refStartLoc, int refEndLoc,
                      int minScore, const int32_t *gaps, int ngaps, int32_t *out4);
 
-/* MultiStateAligner11tsJNI.java:166-192 */
-void orc_fill_unlimited(orc_msa *m, const uint8_t *read, int read_len,
-                        const uint8_t *ref, int ref_len, int refStartLoc, int refEndLoc,
-                        const int32_t *gaps, int ngaps, int32_t *out4);
+/* MultiStateAligner11tsJNI.java:166-192.  Returns 1, or 0 when a gapped reference does not fit maxColumns (out4 = -1). */
+int orc_fill_unlimited(orc_msa *m, const uint8_t *read, int read_len,
+                       const uint8_t *ref, int ref_len, int refStartLoc, int refEndLoc,
+                       const int32_t *gaps, int ngaps, int32_t *out4);
 
 /* MultiStateAligner11tsJNI.java:376-495.  Returns match-string length (written to out, cap bytes),
  * or -1 if cap is too small. */

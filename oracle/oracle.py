@@ -77,7 +77,7 @@ class MSAStruct(C.Structure):
                 ("greflimit", C.c_int), ("greflimit2", C.c_int), ("grefRefOrigin", C.c_int),
                 ("iterationsLimited", C.c_int64), ("iterationsUnlimited", C.c_int64),
                 ("rows", C.c_int), ("columns", C.c_int),
-                ("bandwidth", C.c_int), ("bandwidthRatio", C.c_float)]
+                ("bandwidth", C.c_int), ("bandwidthRatio", C.c_float), ("keepGaps", C.c_int)]
 
 
 class OracleMSA:
@@ -134,17 +134,35 @@ class OracleMSA:
         r, f = _u8(read), _u8(ref)
         out = np.zeros(4, np.int32)
         g = None if gaps is None else np.asarray(gaps, np.int32).copy()
-        self.L.orc_fill_unlimited(C.c_void_p(self.h), _p(r, c_u8p), len(read), _p(f, c_u8p), len(ref),
-                                  a, b, None if g is None else _p(g, c_i32p), 0 if g is None else len(g),
-                                  _p(out, c_i32p))
-        return out.tolist()
+        ok = self.L.orc_fill_unlimited(C.c_void_p(self.h), _p(r, c_u8p), len(read), _p(f, c_u8p), len(ref),
+                                       a, b, None if g is None else _p(g, c_i32p), 0 if g is None else len(g),
+                                       _p(out, c_i32p))
+        return out.tolist() if ok else None              # None: the gapped reference does not fit maxColumns
 
-    def traceback(self, read, ref, a, b, row, col, state, gapped=False):
+    def makeGref(self, ref, gaps, a, b):
+        """makeGref alone (:668-757): greflimit, or None where the reference returns null (the copy would pass maxColumns + 2)."""
+        f = _u8(ref)
+        g = np.asarray(gaps, np.int32).copy()
+        lim = self.L.orc_make_gref(C.c_void_p(self.h), _p(f, c_u8p), len(ref), _p(g, c_i32p), len(g), a, b)
+        return None if lim < 0 else lim
+
+    def gref(self):
+        """(grefbuffer[:greflimit2 + 1] as bytes, greflimit, greflimit2, grefRefOrigin) of the last gapped fill."""
+        lim, lim2 = self.s.greflimit, self.s.greflimit2
+        buf = bytes(np.ctypeslib.as_array(self.s.grefbuffer, shape=(self.maxColumns + 2,))[:max(lim, lim2 + 1, 0)])
+        return buf, lim, lim2, self.s.grefRefOrigin
+
+    def traceback(self, read, ref, a, b, row, col, state, gapped=False, keep_gaps=False):
+        """keep_gaps: the string with its '-' symbols, before the reference expands each to 128 'D' (:481-493)."""
         r, f = _u8(read), _u8(ref)
-        cap = row + col + 8 + 128 * 64
+        # every '-' of the gapped reference the walk can cross becomes 128 'D'
+        symbols = self.gref()[0].count(b"-") if gapped else 64
+        cap = row + col + 8 + 128 * symbols
         out = np.zeros(cap, np.uint8)
+        self.s.keepGaps = 1 if keep_gaps else 0
         n = self.L.orc_traceback(C.c_void_p(self.h), _p(r, c_u8p), _p(f, c_u8p), a, b, row, col, state,
                                  1 if gapped else 0, _p(out, c_u8p), cap)
+        self.s.keepGaps = 0
         if n < 0:
             raise RuntimeError("traceback overflow")
         return out[:n].tobytes()

@@ -43,6 +43,93 @@ def oracle_align(om, read, ref, a, b, ms, flags):
     return out
 
 
+def oracle_align_gapped(om, read, ref, a, b, ms, gaps, flags):
+    """What the reference would produce for one job of the gapped entries (bbmsa_align_gapped_batch*): without a gap array the
+    plain job; with one, MSA.fillAndScoreLimited(read, ref, a, b, minScore, gaps) -- or fillUnlimited(read, ref, a, b, gaps) for
+    BBMSA_FILL_UNLIMITED_RAW -- on the clamped window, then score(..., gapped) always and traceback(..., gapped) on request.
+    Beside oracle_align's fields: refused (the gapped reference does not fit maxColumns: the device answers BBMSA_ST_BAD_SHAPE),
+    kept (the string before its '-' are expanded) and gref = (buffer, greflimit, greflimit2, grefRefOrigin)."""
+    if gaps is None:
+        out = oracle_align(om, read, ref, a, b, ms, flags)
+        out.update(refused=False, kept=out["match"], gref=None)
+        return out
+    a, b = max(0, a), min(len(ref) - 1, b)
+    out = {"score": None, "match": None, "kept": None, "status": 0, "refused": False, "gref": None, "result": None,
+           "iterations": 0, "fill_kind": 0}
+    lim = om.makeGref(ref, gaps, a, b)
+    if lim is None or lim + 1 > om.maxColumns:
+        out["refused"] = True
+        out["status"] = M.ST_BAD_SHAPE
+        assert om.fillLimited(read, ref, a, b, ms, gaps) is None and om.fillUnlimited(read, ref, a, b, gaps) is None
+        return out
+    it_l0, it_u0 = om.iterationsLimited, om.iterationsUnlimited
+    if flags & 7 == M.FILL_UNLIMITED_RAW:
+        r4 = om.fillUnlimited(read, ref, a, b, gaps)
+    else:
+        r4 = om.fillLimited(read, ref, a, b, ms, gaps)
+    out["iterations"] = (om.iterationsLimited - it_l0) + (om.iterationsUnlimited - it_u0)
+    out["fill_kind"] = 1 if om.iterationsUnlimited != it_u0 else 0
+    out["gref"] = om.gref()
+    if r4 is None:
+        out["status"] = M.ST_NULL
+        return out
+    out["result"] = r4 + [0]
+    out["score"] = om.score(read, ref, a, b, r4[0], r4[1], r4[2], gapped=True)
+    if flags & M.DO_TRACEBACK:
+        out["match"] = om.traceback(read, ref, a, b, r4[0], r4[1], r4[2], gapped=True)
+        out["kept"] = om.traceback(read, ref, a, b, r4[0], r4[1], r4[2], gapped=True, keep_gaps=True)
+    return out
+
+
+_GAPPED = {}
+
+
+def gapped_set(scheme, name):
+    """One set of tests/gapped_problems.py, built once: (problems, flags, kinds)."""
+    from tests import gapped_problems as G
+    key = ("set", scheme, name)
+    if key not in _GAPPED:
+        _GAPPED[key] = G.SETS[name](scheme)
+    return _GAPPED[key]
+
+
+def gapped_expected(scheme, name, band=(0, 0.0), maxColumns=None, problems=None, flags=None, kinds=None):
+    """The oracle's answers for a set of tests/gapped_problems.py (or for the jobs given), computed once per context shape and
+    shared by the tests; None for the arrays of the `refused` class, which the reference's contract does not cover."""
+    from tests import gapped_problems as G
+    key = ("exp", scheme, name, band, maxColumns)
+    if key not in _GAPPED:
+        if problems is None:
+            problems, flags, kinds = gapped_set(scheme, name)
+        sh = G.SHAPES[scheme]
+        om = OracleMSA(sh["maxRows"], maxColumns or sh["maxColumns"], band[0], band[1], scheme=scheme)
+        _GAPPED[key] = [None if G.is_refused(k) else oracle_align_gapped(om, p[0], p[1], p[2], p[3], p[4], G.gaps_of(p), f)
+                        for p, f, k in zip(problems, flags, kinds)]
+    return _GAPPED[key]
+
+
+def check_gapped_job(g, exp, flags, ctx):
+    """g: one raw record (test_msa_routes_gpu.record) of a job of the gapped entries; exp: oracle_align_gapped's answer.  Status,
+    score[0..score_len), result[0..4] and match_len always; the string where DO_TRACEBACK asked for one (KEEP_GAPS: with its '-');
+    iterations unless BBMSA_NO_ITERATIONS."""
+    if exp["refused"]:
+        assert g["status"] == M.ST_BAD_SHAPE and g["match_len"] == 0 and g["score"] is None, ctx
+        return
+    assert g["status"] == exp["status"], ctx
+    if exp["result"] is not None:
+        assert g["result"] == exp["result"], ctx
+    assert g["score"] == exp["score"], ctx
+    assert g["fill_kind"] == exp["fill_kind"], ctx
+    if not flags & M.NO_ITERATIONS:
+        assert g["iterations"] == exp["iterations"], ctx
+    want = exp["kept"] if flags & M.TRACE_KEEP_GAPS else exp["match"]
+    if flags & M.DO_TRACEBACK and want is not None:
+        assert g["match_len"] == len(want), ctx
+        assert g["match"] == want, ctx
+    else:
+        assert g["match_len"] == 0 and g["match"] is None, ctx
+
+
 def check_job(g, exp, ctx):
     """g: one record as MultiStateAligner11ts.align returns it; exp: oracle_align's answer for the same job."""
     if exp["result"] is not None:
